@@ -4,16 +4,28 @@
 
 A step = zero grads, student train forward (output_qkv), teacher eval forward, DEKD losses, backward with the
 bucketed RCCL gradient all-reduce, global-norm clip + AdamW + EMA + bf16 weight re-cast (engine.py:62-132 of
-the reference).  Inputs are synthetic and already resident in HBM; weights are random-init.
+the reference).  Inputs are synthetic and already resident in HBM; weights are random-init, and every step starts
+from them again (one copy of the fp32 masters and of their bf16 copy per step).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full   (+ roofline, exchange, parity, CPU baseline)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python bench.py --gpus N ...            (no launcher: starts its own N ranks, one per GPU, before touching a GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0).  `roofline` describes the dominant kernel (the forward `gemm_kernel<A_row,B_row>`
-template: teacher + student Linear layers); `cpu_baseline` is the CPU oracle (oracle/, "port") timed on this
-box's host cores on a bounded bs-8 sample of the same step.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`); everything else it can report needs `--full`, and is `null` without it.  With `--full`, `roofline`
+describes the dominant kernel (the forward `gemm_kernel<A_row,B_row>` template: teacher + student Linear layers) from
+extra instrumented steps, `exchange` times one more step's bucket all-reduce (N > 1), `parity` cites the committed
+margins, and `cpu_baseline` is the CPU oracle (oracle/, "port") timed on this box's host cores on a bounded bs-8
+sample of the same step.
+
+`--dump-outputs DIR` writes what the last timed step computed as float32 DIR/<name>.npy (rank 0): the DEKD losses and
+logits that engine.distill_forward returned, and -- after that step's optimizer update -- a fixed sample (seed 0) of
+the student's fp32 master weights, their EMA and the gradient the step applied.  Inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output: every step starts from the same weights (see
+`step`), so two runs differ only by the rounding of the fp32 atomics that sum the weight gradients.
 """
 import argparse
 import json
@@ -42,7 +54,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch-size", type=int, default=256)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: host cost at an idle queue, the "
+                         "gradient exchange (N > 1), the dominant-kernel roofline / per-family / HBM-bound figures (extra "
+                         "instrumented steps), the parity statement and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as float32 DIR/<name>.npy (rank 0; at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-baseline leg")
     ap.add_argument("--teacher-lookahead", type=int, default=1,
                     help="1: teacher forward of batch k+1 runs beside the student step of batch k (default); 0: inside the step")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
@@ -66,7 +84,10 @@ def parse():
     ap.add_argument("--host-input", action="store_true",
                     help="PCIe-inclusive variant (DESIGN.md section 6, never the headline value): every step's batch starts "
                          "in pinned host memory and crosses to the GPU through the training loop's prefetcher")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def usable_cores():
@@ -124,6 +145,40 @@ def cpu_baseline(seconds):
             "sample": f"{n} fp32 DEKD steps (student fwd+bwd, DeiT-B teacher fwd, losses) at bs 8, no optimizer",
             "config1_forward": {"value": round(8 * m / fdt, 2), "unit": "images/sec",
                                 "sample": f"{m} fp32 `dedeit` eval forwards at bs 8 (BASELINE configs[0])"}}
+
+
+DUMP_SAMPLE = 1 << 20            # elements sampled from each flat fp32 buffer (4 MB each)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(out, flat, opt):
+    """Host float32 copies of what one step handed its caller: distill_forward's losses and logits (`out`) and, after the
+    optimizer update, the same fixed sample (seed 0) of the flat fp32 master weights, their EMA and the applied gradient."""
+    import numpy as np
+    arrays = {}
+    for k, v in out.items():
+        if isinstance(v, (tuple, list)):         # a distilled model in train mode: (class head, distillation head)
+            for i, t in enumerate(v):
+                arrays[f"{k}_{i}"] = torch.as_tensor(t).detach().float().cpu().numpy()
+        else:
+            arrays[k] = torch.as_tensor(v).detach().float().cpu().numpy()
+    idx = np.sort(np.random.default_rng(0).choice(flat.numel, size=min(DUMP_SAMPLE, flat.numel), replace=False))
+    bufs = {"student_master_weights_sample": flat.flat, "student_grad_sample": flat.flat_grad}
+    if opt.ema is not None:
+        bufs["student_ema_weights_sample"] = opt.ema
+    for k, t in bufs.items():
+        arrays[k] = t.detach().cpu().numpy()[idx]
+    return arrays
+
+
+def dump_outputs(arrays, path):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def kernel_sources_hash():
@@ -382,9 +437,19 @@ def main():
         feed = iter(feed_batches)
 
     opt_events = None        # instrumented step: events around the optimizer tail (clip + AdamW + EMA + bf16 re-cast)
+    kept = {}                # --dump-outputs: distill_forward's dict of the last timed step
 
-    def step():
+    # Every step starts from the same weights: the fp32 masters and their bf16 copy (with the k-major copies derived from it) are put back to
+    # the state after set-up, so each timed step is the same optimisation step on the same inputs.  The weight gradients are summed with fp32
+    # atomics (bitwise different from run to run), and AdamW's early updates turn that rounding into different weights within a few steps:
+    # chained, the steps would compute different things every run.  Adam's moments, the EMA and the step count still advance.
+    start_flat, start_flat16 = flat.flat.clone(), flat.flat16.clone()
+
+    def step(keep=False):
         nonlocal cur
+        flat.flat.copy_(start_flat)
+        flat.flat16.copy_(start_flat16)
+        flat.refresh_kmajor()
         opt.zero_grad()
         t_out = None
         if feed is not None:
@@ -407,6 +472,8 @@ def main():
         if opt_events is not None:
             opt_events.append(torch.cuda.Event(enable_timing=True))
             opt_events[-1].record()
+        if keep:
+            kept["out"] = out
         return out["loss"]
 
     def fence():
@@ -419,19 +486,27 @@ def main():
         step()
     fence()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    dump = args.dump_outputs is not None
+    for i in range(args.steps):
+        loss = step(keep=dump and i == args.steps - 1)
     t_enqueue = time.perf_counter() - t0          # host time to enqueue the K steps (no device wait inside)
     fence()
     dt = time.perf_counter() - t0
-    # host cost of one step with nothing in the way: the device idle and its queue empty when the enqueue starts
-    # (`host_enqueue_ms_per_step` above also contains the time the host sits blocked on a full launch queue once it is
-    # several steps ahead of the GPU)
-    t1 = time.perf_counter()
-    step()
-    step()
-    host_step_ms = (time.perf_counter() - t1) / 2 * 1e3
-    fence()
+    if dump:          # before any further step moves the weights
+        out_last = kept.pop("out")
+        if rank == 0:
+            dump_outputs(step_outputs(out_last, flat, opt), args.dump_outputs)
+        del out_last
+    host_step_ms = None
+    if args.full:
+        # host cost of one step with nothing in the way: the device idle and its queue empty when the enqueue starts
+        # (`host_enqueue_ms_per_step` above also contains the time the host sits blocked on a full launch queue once it is
+        # several steps ahead of the GPU)
+        t1 = time.perf_counter()
+        step()
+        step()
+        host_step_ms = (time.perf_counter() - t1) / 2 * 1e3
+        fence()
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -441,120 +516,124 @@ def main():
     img_per_s = B * world * args.steps / dt
     hbm_peak_gb = torch.cuda.max_memory_allocated(dev) / 1e9     # this rank, warm-up + timed steps (torch's allocator: arenas, masters, gradients)
 
-    # ---- gradient exchange of one more step: summed bucket all-reduce time and the share of it that ran under backward
-    exchange = None
-    if reducer.world > 1:
-        reducer.timing = True
-        step()
-        reducer.timing = False
-        ar_ms, ov = reducer.timing_summary()
-        t = torch.tensor([ar_ms, -ov], dtype=torch.float64, device=dev)
-        if world > 1:
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)              # worst rank, like the step time: longest exchange, least overlap
-        exchange = {"allreduce_ms": round(float(t[0]), 3), "overlap_frac": round(-float(t[1]), 3),
-                    "buckets": len(reducer.buckets), "bytes": flat.numel * 4,
-                    "over_ranks": "max allreduce_ms, min overlap_frac"}
-
-    # ---- dominant-kernel roofline: extra instrumented steps, events on the launch stream ---------------------
-    # (a) as in the timed region: the teacher's launches share the GPU with the student's (two streams), so an event
-    #     bracket there also contains the other model's workgroups -- this is what a rocprofv3 average over the run sees
-    two_stream = None
-    if look is not None and feed is None:
-        ops.PROFILE = []
-        step()
-        torch.cuda.synchronize()
-        recs, ops.PROFILE = ops.PROFILE, None
-        sel = [(2.0 * M * N * K * batch, e0.elapsed_time(e1) * 1e-3) for t, M, N, K, batch, e0, e1 in recs if t == "A_row/B_row"]
-        fl2, tm2 = sum(f for f, _ in sel), sum(t for _, t in sel)
-        two_stream = {"achieved": round(fl2 / tm2 / 1e12, 2), "avg_launch_us": round(tm2 / len(sel) * 1e6, 2),
-                      "launches_per_step": len(sel)}
-    # (b) one launch at a time (`achieved` below): the kernel's own rate
-    os.environ["DEVIT_TEACHER_STREAM"] = "0"      # serialise the two forwards so that event brackets time ONE kernel
-    os.environ["DEVIT_WGRAD_STREAM"] = "0"        # ... and the weight gradients back on the launch stream (csrc/encoder.hip)
-    if feed is not None:
-        assert next(feed, None) is None       # the prefetcher is drained (its last batch submits no look-ahead)
-        feed = None
-    elif look is not None:
-        look.take(cur)
-    look = None
-    step()
-    torch.cuda.synchronize()
-    # per-family split of the serialized step (events on the launch stream): the frozen teacher's forward alone, the rest is the
-    # student's half (forward, losses, backward, optimizer tail) -- tracked because the two halves sit at very different fractions
-    def timed(fn, reps=3):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / reps
-    serial_ms = timed(step)
-    teacher_ms = timed(lambda: engine._teacher_forward(teacher, img))
-    student_ms = serial_ms - teacher_ms
-    families = {"serialized_step_ms": round(serial_ms, 3),
-                "teacher_forward_ms": round(teacher_ms, 3), "teacher_gflop_per_img_algorithmic": 35.311,
-                "teacher_frac": round(B * 35.311e9 / (teacher_ms * 1e-3) / BF16_DENSE_PEAK, 4),
-                "student_ms_per_step": round(student_ms, 3), "student_gflop_per_img_algorithmic": round(GFLOP_PER_IMG_STEP - 35.311, 3),
-                "student_frac": round(B * (GFLOP_PER_IMG_STEP - 35.311) * 1e9 / (student_ms * 1e-3) / BF16_DENSE_PEAK, 4),
-                "counts": "ALGORITHMIC FLOPs (teacher forward 35.311, student forward + backward + relation losses 28.192 GFLOP per image) / "
-                          "event time of the serialized step's halves / 2.5 PFLOP/s"}
-    ops.PROFILE, ops.PROFILE_HBM, ops.PROFILE_WGRAD = [], [], []
-    opt_events = []
-    step()
-    torch.cuda.synchronize()
-    opt_tail_ms = opt_events[0].elapsed_time(opt_events[1])
-    opt_events = None
-    recs, ops.PROFILE = ops.PROFILE, None
-    hbm_recs, ops.PROFILE_HBM = ops.PROFILE_HBM, None
-    wg_recs, ops.PROFILE_WGRAD = ops.PROFILE_WGRAD, None
-    # the bandwidth-bound kernels of the same serialized step: algorithmic bytes / event time (HBM peak 8 TB/s)
-    hbm = {}
-    for name, nbytes, e0, e1 in hbm_recs:
-        d = hbm.setdefault(name, [0.0, 0.0, 0])
-        d[0] += nbytes
-        d[1] += e0.elapsed_time(e1) * 1e-3
-        d[2] += 1
-    hbm = {k: {"GB/s": round(v[0] / v[1] / 1e9, 1), "frac_of_8TB/s": round(v[0] / v[1] / 8e12, 3), "launches": v[2],
-               "ms_per_step": round(v[1] * 1e3, 3)} for k, v in hbm.items()}
-    by_t = {}
-    for tmpl, M, N, K, batch, e0, e1 in recs:
-        d = by_t.setdefault(tmpl, [0.0, 0.0, 0])
-        d[0] += 2.0 * M * N * K * batch
-        d[1] += e0.elapsed_time(e1) * 1e-3
-        d[2] += 1
-    # the grouped weight-gradient launches (devit_wgrad_grouped: a block's four products in one launch of the full-row k-major x k-major kernel)
-    if wg_recs:
-        wt = sum(e0.elapsed_time(e1) * 1e-3 for _, _, e0, e1 in wg_recs)
-        by_t["A_km/B_km grouped (wgradfr_kernel)"] = [sum(f for f, _, _, _ in wg_recs), wt, len(wg_recs)]
-        hbm["wgrad_grouped"] = {"GB/s": round(sum(b for _, b, _, _ in wg_recs) / wt / 1e9, 1),
-                                "frac_of_8TB/s": round(sum(b for _, b, _, _ in wg_recs) / wt / 8e12, 3), "launches": len(wg_recs),
-                                "ms_per_step": round(wt * 1e3, 3)}
-    dom = "A_row/B_row"
-    fl, tm, cnt = by_t[dom]
-    traffic, traffic_src = committed_counter("*_pmc_traffic.json", "traffic_bytes_per_launch")
-    busy, busy_src = committed_counter("*_pmc_mfma.json", "mfma_busy")
     from devit_amd import de_vit
     executed = GFLOP_PER_IMG_EXECUTED if de_vit.LEAN_TAIL else GFLOP_PER_IMG_STEP
-    roof = {"bound": "mfma", "kernel": "gemm_kernel<*, A_row, B_row, *> (persistent 128x128 / 256x256 x64 bf16 MFMA tiles; fwd Linear layers of teacher + student; "
-                      "the student's fc2 on the full-row 256x384 kernel through a k-major copy of its weight counts here too)",
-            "achieved": round(fl / tm / 1e12, 2), "peak": BF16_DENSE_PEAK / 1e12, "unit": "TFLOP/s",
-            "frac": round(fl / tm / BF16_DENSE_PEAK, 4),
-            "achieved_counts": "FLOPs the launches execute (2 M N K of each launch, padded rows included) / their event time",
-            "traffic": traffic, "traffic_source": traffic_src, "mfma_busy": busy, "mfma_busy_source": busy_src,
-            "launches_per_step": cnt, "avg_launch_us": round(tm / cnt * 1e6, 2),
-            "gflop_per_launch_avg": round(fl / cnt / 1e9, 3),
-            "step_frac": round(img_per_s / world * GFLOP_PER_IMG_STEP * 1e9 / BF16_DENSE_PEAK, 4),
-            "step_frac_counts": "ALGORITHMIC FLOPs of the reference's step (63.503 GFLOP per image) x images/sec / peak",
-            "step_frac_executed": round(img_per_s / world * executed * 1e9 / BF16_DENSE_PEAK, 4),
-            "other_templates": {k: {"tflops": round(v[0] / v[1] / 1e12, 2), "launches": v[2],
-                                    "ms_per_step": round(v[1] * 1e3, 3)} for k, v in by_t.items() if k != dom},
-            "gemm_ms_per_step": round(sum(v[1] for v in by_t.values()) * 1e3, 3),
-            "in_two_stream_timed_region": two_stream, "families": families, "hbm_bound_kernels": hbm,
-            "optimizer_tail_ms_per_step": round(opt_tail_ms, 3)}
+
+    # ---- --full: what the headline does not need, each from steps of its own after the timed ones
+    exchange = roof = None
+    if args.full:
+        # ---- gradient exchange of one more step: summed bucket all-reduce time and the share of it that ran under backward
+        exchange = None
+        if reducer.world > 1:
+            reducer.timing = True
+            step()
+            reducer.timing = False
+            ar_ms, ov = reducer.timing_summary()
+            t = torch.tensor([ar_ms, -ov], dtype=torch.float64, device=dev)
+            if world > 1:
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)              # worst rank, like the step time: longest exchange, least overlap
+            exchange = {"allreduce_ms": round(float(t[0]), 3), "overlap_frac": round(-float(t[1]), 3),
+                        "buckets": len(reducer.buckets), "bytes": flat.numel * 4,
+                        "over_ranks": "max allreduce_ms, min overlap_frac"}
+
+        # ---- dominant-kernel roofline: extra instrumented steps, events on the launch stream ---------------------
+        # (a) as in the timed region: the teacher's launches share the GPU with the student's (two streams), so an event
+        #     bracket there also contains the other model's workgroups -- this is what a rocprofv3 average over the run sees
+        two_stream = None
+        if look is not None and feed is None:
+            ops.PROFILE = []
+            step()
+            torch.cuda.synchronize()
+            recs, ops.PROFILE = ops.PROFILE, None
+            sel = [(2.0 * M * N * K * batch, e0.elapsed_time(e1) * 1e-3) for t, M, N, K, batch, e0, e1 in recs if t == "A_row/B_row"]
+            fl2, tm2 = sum(f for f, _ in sel), sum(t for _, t in sel)
+            two_stream = {"achieved": round(fl2 / tm2 / 1e12, 2), "avg_launch_us": round(tm2 / len(sel) * 1e6, 2),
+                          "launches_per_step": len(sel)}
+        # (b) one launch at a time (`achieved` below): the kernel's own rate
+        os.environ["DEVIT_TEACHER_STREAM"] = "0"      # serialise the two forwards so that event brackets time ONE kernel
+        os.environ["DEVIT_WGRAD_STREAM"] = "0"        # ... and the weight gradients back on the launch stream (csrc/encoder.hip)
+        if feed is not None:
+            assert next(feed, None) is None       # the prefetcher is drained (its last batch submits no look-ahead)
+            feed = None
+        elif look is not None:
+            look.take(cur)
+        look = None
+        step()
+        torch.cuda.synchronize()
+        # per-family split of the serialized step (events on the launch stream): the frozen teacher's forward alone, the rest is the
+        # student's half (forward, losses, backward, optimizer tail) -- tracked because the two halves sit at very different fractions
+        def timed(fn, reps=3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / reps
+        serial_ms = timed(step)
+        teacher_ms = timed(lambda: engine._teacher_forward(teacher, img))
+        student_ms = serial_ms - teacher_ms
+        families = {"serialized_step_ms": round(serial_ms, 3),
+                    "teacher_forward_ms": round(teacher_ms, 3), "teacher_gflop_per_img_algorithmic": 35.311,
+                    "teacher_frac": round(B * 35.311e9 / (teacher_ms * 1e-3) / BF16_DENSE_PEAK, 4),
+                    "student_ms_per_step": round(student_ms, 3), "student_gflop_per_img_algorithmic": round(GFLOP_PER_IMG_STEP - 35.311, 3),
+                    "student_frac": round(B * (GFLOP_PER_IMG_STEP - 35.311) * 1e9 / (student_ms * 1e-3) / BF16_DENSE_PEAK, 4),
+                    "counts": "ALGORITHMIC FLOPs (teacher forward 35.311, student forward + backward + relation losses 28.192 GFLOP per image) / "
+                              "event time of the serialized step's halves / 2.5 PFLOP/s"}
+        ops.PROFILE, ops.PROFILE_HBM, ops.PROFILE_WGRAD = [], [], []
+        opt_events = []
+        step()
+        torch.cuda.synchronize()
+        opt_tail_ms = opt_events[0].elapsed_time(opt_events[1])
+        opt_events = None
+        recs, ops.PROFILE = ops.PROFILE, None
+        hbm_recs, ops.PROFILE_HBM = ops.PROFILE_HBM, None
+        wg_recs, ops.PROFILE_WGRAD = ops.PROFILE_WGRAD, None
+        # the bandwidth-bound kernels of the same serialized step: algorithmic bytes / event time (HBM peak 8 TB/s)
+        hbm = {}
+        for name, nbytes, e0, e1 in hbm_recs:
+            d = hbm.setdefault(name, [0.0, 0.0, 0])
+            d[0] += nbytes
+            d[1] += e0.elapsed_time(e1) * 1e-3
+            d[2] += 1
+        hbm = {k: {"GB/s": round(v[0] / v[1] / 1e9, 1), "frac_of_8TB/s": round(v[0] / v[1] / 8e12, 3), "launches": v[2],
+                   "ms_per_step": round(v[1] * 1e3, 3)} for k, v in hbm.items()}
+        by_t = {}
+        for tmpl, M, N, K, batch, e0, e1 in recs:
+            d = by_t.setdefault(tmpl, [0.0, 0.0, 0])
+            d[0] += 2.0 * M * N * K * batch
+            d[1] += e0.elapsed_time(e1) * 1e-3
+            d[2] += 1
+        # the grouped weight-gradient launches (devit_wgrad_grouped: a block's four products in one launch of the full-row k-major x k-major kernel)
+        if wg_recs:
+            wt = sum(e0.elapsed_time(e1) * 1e-3 for _, _, e0, e1 in wg_recs)
+            by_t["A_km/B_km grouped (wgradfr_kernel)"] = [sum(f for f, _, _, _ in wg_recs), wt, len(wg_recs)]
+            hbm["wgrad_grouped"] = {"GB/s": round(sum(b for _, b, _, _ in wg_recs) / wt / 1e9, 1),
+                                    "frac_of_8TB/s": round(sum(b for _, b, _, _ in wg_recs) / wt / 8e12, 3), "launches": len(wg_recs),
+                                    "ms_per_step": round(wt * 1e3, 3)}
+        dom = "A_row/B_row"
+        fl, tm, cnt = by_t[dom]
+        traffic, traffic_src = committed_counter("*_pmc_traffic.json", "traffic_bytes_per_launch")
+        busy, busy_src = committed_counter("*_pmc_mfma.json", "mfma_busy")
+        roof = {"bound": "mfma", "kernel": "gemm_kernel<*, A_row, B_row, *> (persistent 128x128 / 256x256 x64 bf16 MFMA tiles; fwd Linear layers of teacher + student; "
+                          "the student's fc2 on the full-row 256x384 kernel through a k-major copy of its weight counts here too)",
+                "achieved": round(fl / tm / 1e12, 2), "peak": BF16_DENSE_PEAK / 1e12, "unit": "TFLOP/s",
+                "frac": round(fl / tm / BF16_DENSE_PEAK, 4),
+                "achieved_counts": "FLOPs the launches execute (2 M N K of each launch, padded rows included) / their event time",
+                "traffic": traffic, "traffic_source": traffic_src, "mfma_busy": busy, "mfma_busy_source": busy_src,
+                "launches_per_step": cnt, "avg_launch_us": round(tm / cnt * 1e6, 2),
+                "gflop_per_launch_avg": round(fl / cnt / 1e9, 3),
+                "step_frac": round(img_per_s / world * GFLOP_PER_IMG_STEP * 1e9 / BF16_DENSE_PEAK, 4),
+                "step_frac_counts": "ALGORITHMIC FLOPs of the reference's step (63.503 GFLOP per image) x images/sec / peak",
+                "step_frac_executed": round(img_per_s / world * executed * 1e9 / BF16_DENSE_PEAK, 4),
+                "other_templates": {k: {"tflops": round(v[0] / v[1] / 1e12, 2), "launches": v[2],
+                                        "ms_per_step": round(v[1] * 1e3, 3)} for k, v in by_t.items() if k != dom},
+                "gemm_ms_per_step": round(sum(v[1] for v in by_t.values()) * 1e3, 3),
+                "in_two_stream_timed_region": two_stream, "families": families, "hbm_bound_kernels": hbm,
+                "optimizer_tail_ms_per_step": round(opt_tail_ms, 3)}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds)
 
     if rank == 0:
@@ -562,16 +641,16 @@ def main():
             "metric": "images/sec distill_sub step (DeiT-B->dedeit, bs256, 224^2)", "value": round(img_per_s, 2),
             "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 3), "host_enqueue_ms_per_step": round(t_enqueue / args.steps * 1e3, 3),
-            "host_ms_per_step_idle_queue": round(host_step_ms, 3),
+            "host_ms_per_step_idle_queue": round(host_step_ms, 3) if host_step_ms is not None else None,
             "cpu_cores": len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else None,   # (what this rank may run on: --cpu-cores)
             "hbm_peak_allocated_gb": round(hbm_peak_gb, 2),
             "higher_is_better": True, "scaling": "weak",
             "algorithmic_gflop_per_img": GFLOP_PER_IMG_STEP, "executed_gflop_per_img": executed,
             "timing_protocol": f"{args.warmup} untimed steps, then {args.steps} steps wall-clocked between barrier + "
                                "torch.cuda.synchronize() on both sides, max over ranks, mean per step (SURVEY 8d's median-of-50 "
-                               "protocol is not what the driver runs); roofline / hbm_bound_kernels from one extra instrumented "
-                               "serialized step (HIP events on the launch stream)",
-            "parity": parity_statement(),
+                               "protocol is not what the driver runs)" + ("; roofline / hbm_bound_kernels from one extra instrumented "
+                               "serialized step (HIP events on the launch stream)" if args.full else ""),
+            "full": args.full, "parity": parity_statement() if args.full else None,
             "vs_baseline": None, "dtype": "bf16", "teacher_dtype": args.teacher_precision, "data": "synthetic, pinned host batches through PCIe every step" if args.host_input else "synthetic",
             "config": {"workload": f"distill_sub step dedeit<-deit_base_distilled_patch16_224, num_division=4 "
                                    f"(C={C}), bs={B}/GPU, 224x224, hard distillation, drop_path 0.1, AdamW+EMA",

@@ -6,5 +6,5 @@ for i in 1 2; do
   for v in 0 1; do echo "== DEVIT_GEMM4=$v"; DEVIT_GEMM4=$v COLD=1 timeout -k 10 300 python tools/gemm_bench.py 2>&1 | grep -E "$F" || exit 1; done
 done
 for i in 1 2; do
-  for v in 0 1; do echo "== bench DEVIT_GEMM4=$v"; DEVIT_GEMM4=$v timeout -k 10 600 python bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline 2>&1 | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], d['ms_per_step'], 'dominant', r['achieved'], 'gemm_ms', r['gemm_ms_per_step'])" || exit 1; done
+  for v in 0 1; do echo "== bench DEVIT_GEMM4=$v"; DEVIT_GEMM4=$v timeout -k 10 600 python bench.py --steps ${STEPS:-10} --warmup 3 --full --no-cpu-baseline 2>&1 | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], d['ms_per_step'], 'dominant', r['achieved'], 'gemm_ms', r['gemm_ms_per_step'])" || exit 1; done
 done
