@@ -92,6 +92,8 @@ SIGNATURES = {
     "devit_layernorm_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _I, _P]),
     "devit_layernorm_bwd_workspace": (_Z, [_I, _I]),
     "devit_layernorm_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _Z, _P]),
+    "devit_dgrad_layernorm_bwd_fused": (_I, [_I, _I, _I]),
+    "devit_dgrad_layernorm_bwd": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _Z, _P]),
     "devit_block_acts_sizes": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]),
     "devit_block_bwd_sizes": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]),
     "devit_encoder_fwd": (_I, [_I, C.POINTER(BlockWeights), C.POINTER(BlockActs), _I, _I, _I, _F, _P]),

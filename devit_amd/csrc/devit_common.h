@@ -35,6 +35,11 @@ void devit_set_error(const char* fmt, ...);
   } while (0)
 
 
+// ---- internal entry points shared between translation units (not exported) -----------------
+// layernorm.hip: the column-sum pass behind a LayerNorm backward, partial[nparts][3][D] -> dgamma, dbeta, colsum(dx_bf16)
+int devit_layernorm_bwd_finish(const float* partial, int nparts, int D, float* dgamma, float* dbeta, float* dx_bf16_colsum,
+                               int accumulate, void* stream);
+
 // ---- scalar helpers ---------------------------------------------------------------------
 __device__ __forceinline__ float bf2f(__bf16 v) { return (float)v; }
 __device__ __forceinline__ __bf16 f2bf(float v) { return (__bf16)v; }

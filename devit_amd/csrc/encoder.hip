@@ -339,24 +339,42 @@ extern "C" int devit_block_bwd(const devit_block_weights* wp, const devit_block_
     ep.aux_in = b[DEVIT_ACT_H_PRE];
     TRY(linear_dgrad(c, io->g2, w.fc2_w16, D, Hd, ep));
   }
-  TRY(linear_dgrad(c, dh_pre, w.fc1_w16, Hd, D, make_ep(DEVIT_EPI_STORE_BF16, dln2, D, c.M)));
-  TRY(wgrad(1, dh_pre, b[DEVIT_ACT_LN2], g.fc1_w, g.fc1_b, Hd, D));
-  // LN2 backward: dx1 = dx + LN'(dln2); g1 = bf16(dp1 * dx1); its column sums = the proj bias gradient
-  TRY(devit_layernorm_bwd(dln2, 0, (const float*)b[DEVIT_ACT_X1], c.M, D, 0, 0, (const float*)b[DEVIT_ACT_MEAN2],
-                          (const float*)b[DEVIT_ACT_RSTD2], w.n2w, io->dx, dx1, g1, a.dp1, N, g.n2w, g.n2b, g.proj_b, 1,
-                          io->ws[DEVIT_BWD_LNWS], io->lnws_bytes, stream));
+  // fc1's dgrad and the LN2 backward behind it: dln2 = dh_pre @ fc1_w; dx1 = dx + LN'(dln2); g1 = bf16(dp1 * dx1); its column sums = the proj bias
+  // gradient.  One kernel where the full-row GEMM holds whole rows of dln2 (devit_dgrad_layernorm_bwd_fused; dln2 then never goes to memory),
+  // else the two launches with the weight gradient's fork between them, as before.
+  if (devit_dgrad_layernorm_bwd_fused(c.Mp, D, Hd)) {
+    TRY(devit_dgrad_layernorm_bwd(dh_pre, w.fc1_w16, c.Mp, Hd, dln2, (const float*)b[DEVIT_ACT_X1], c.M, D, (const float*)b[DEVIT_ACT_MEAN2],
+                                  (const float*)b[DEVIT_ACT_RSTD2], w.n2w, io->dx, dx1, g1, a.dp1, N, g.n2w, g.n2b, g.proj_b, 1,
+                                  io->ws[DEVIT_BWD_LNWS], io->lnws_bytes, stream));
+    TRY(wgrad(1, dh_pre, b[DEVIT_ACT_LN2], g.fc1_w, g.fc1_b, Hd, D));
+  } else {
+    TRY(linear_dgrad(c, dh_pre, w.fc1_w16, Hd, D, make_ep(DEVIT_EPI_STORE_BF16, dln2, D, c.M)));
+    TRY(wgrad(1, dh_pre, b[DEVIT_ACT_LN2], g.fc1_w, g.fc1_b, Hd, D));
+    TRY(devit_layernorm_bwd(dln2, 0, (const float*)b[DEVIT_ACT_X1], c.M, D, 0, 0, (const float*)b[DEVIT_ACT_MEAN2],
+                            (const float*)b[DEVIT_ACT_RSTD2], w.n2w, io->dx, dx1, g1, a.dp1, N, g.n2w, g.n2b, g.proj_b, 1,
+                            io->ws[DEVIT_BWD_LNWS], io->lnws_bytes, stream));
+  }
   // ---- attention branch: x1 = x + dp1 * proj(gate * attn(qkv(ln1)))
   TRY(linear_dgrad(c, g1, w.proj_w16, D, Da, make_ep(DEVIT_EPI_STORE_BF16, dattn, Da, c.M)));
   TRY(wgrad(2, g1, b[DEVIT_ACT_ATTN_O], g.proj_w, nullptr, D, Da));
   TRY(devit_attn_bwd(b[DEVIT_ACT_QKV], b[DEVIT_ACT_ATTN_O], dattn, (const float*)b[DEVIT_ACT_LSE], w.head_gate, io->dqkv_add,
                      dqkv, B, N, H, 64, 0.125f, stream));
-  TRY(linear_dgrad(c, dqkv, w.qkv_w16, 3 * Da, D, make_ep(DEVIT_EPI_STORE_BF16, dln1, D, c.M)));
-  TRY(wgrad(3, dqkv, b[DEVIT_ACT_LN1], g.qkv_w, g.qkv_b, 3 * Da, D));
-  TRY(flush(3));
-  // LN1 backward: dx_in = dx1 + LN'(dln1); g_prev = bf16(prev_dp2 * dx_in) (+ the block below's fc2 bias gradient)
-  TRY(devit_layernorm_bwd(dln1, 0, a.x, c.M, D, 0, 0, (const float*)b[DEVIT_ACT_MEAN1], (const float*)b[DEVIT_ACT_RSTD1],
-                          w.n1w, dx1, io->dx_in, io->g_prev, io->prev_dp2, N, g.n1w, g.n1b,
-                          io->g_prev ? io->prev_fc2_b_grad : nullptr, 1, io->ws[DEVIT_BWD_LNWS], io->lnws_bytes, stream));
+  // qkv's dgrad and the LN1 backward behind it, fused under the same rule: dln1 = dqkv @ qkv_w; dx_in = dx1 + LN'(dln1);
+  // g_prev = bf16(prev_dp2 * dx_in) (+ the block below's fc2 bias gradient)
+  if (devit_dgrad_layernorm_bwd_fused(c.Mp, D, 3 * Da)) {
+    TRY(devit_dgrad_layernorm_bwd(dqkv, w.qkv_w16, c.Mp, 3 * Da, dln1, a.x, c.M, D, (const float*)b[DEVIT_ACT_MEAN1],
+                                  (const float*)b[DEVIT_ACT_RSTD1], w.n1w, dx1, io->dx_in, io->g_prev, io->prev_dp2, N, g.n1w, g.n1b,
+                                  io->g_prev ? io->prev_fc2_b_grad : nullptr, 1, io->ws[DEVIT_BWD_LNWS], io->lnws_bytes, stream));
+    TRY(wgrad(3, dqkv, b[DEVIT_ACT_LN1], g.qkv_w, g.qkv_b, 3 * Da, D));
+    TRY(flush(3));
+  } else {
+    TRY(linear_dgrad(c, dqkv, w.qkv_w16, 3 * Da, D, make_ep(DEVIT_EPI_STORE_BF16, dln1, D, c.M)));
+    TRY(wgrad(3, dqkv, b[DEVIT_ACT_LN1], g.qkv_w, g.qkv_b, 3 * Da, D));
+    TRY(flush(3));
+    TRY(devit_layernorm_bwd(dln1, 0, a.x, c.M, D, 0, 0, (const float*)b[DEVIT_ACT_MEAN1], (const float*)b[DEVIT_ACT_RSTD1],
+                            w.n1w, dx1, io->dx_in, io->g_prev, io->prev_dp2, N, g.n1w, g.n1b,
+                            io->g_prev ? io->prev_fc2_b_grad : nullptr, 1, io->ws[DEVIT_BWD_LNWS], io->lnws_bytes, stream));
+  }
   return DEVIT_OK;
   }();
   if (sd && forked) {

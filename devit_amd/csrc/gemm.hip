@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "devit_common.h"
+#include "ln_rows.h"
 
 namespace {
 
@@ -1167,13 +1168,32 @@ __device__ __forceinline__ int fr_b_row(int u, int wave, int K) {
   return r < 0 ? r + K : (r >= K ? r - K : r);
 }
 
+// Internal epilogue kind of gemmfr_kernel (not a devit_epilogue kind): the bf16 store of DEVIT_EPI_STORE_BF16 goes to LDS instead of memory and the
+// LayerNorm backward of those rows runs in the same workgroup (see the epilogue below).  One tile per workgroup only.
+constexpr int DEVIT_EPI_LNBWD = 64;
+template <int KIND>
+struct FrArgs {
+  GemmArgs g;
+};
+template <>
+struct FrArgs<DEVIT_EPI_LNBWD> {
+  GemmArgs g;
+  LnBwdArgs ln;
+};
+constexpr int LNF_PITCH = 832;                  // bytes of a staged bf16 row: 768 + 64, so that the sixteen rows of an m-tile start in different banks
+constexpr int LNF_ROWS = 128;                   // rows staged per pass (two passes per tile)
+constexpr int LNF_RED = LNF_ROWS * LNF_PITCH;   // byte offset of the column sums' reduction buffer [4][3][384] floats
+constexpr int LNF_SIDE = LNF_RED + 4 * 3 * 384 * 4, LNF_SIDE_PITCH = 272;   // the second pass's VGPR-resident columns: [128][2 x 64] bf16, rows 256 + 16 bytes
+static_assert(LNF_SIDE + LNF_ROWS * LNF_SIDE_PITCH <= (256 + 384) * 128 * 2, "the fused epilogue lives in the operand ring's LDS");
+
 template <int KIND>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void gemmfr_kernel(const GemmArgs g) {
-  static_assert(KIND == DEVIT_EPI_RESIDUAL_F32 || KIND == DEVIT_EPI_STORE_BF16, "the student's N = 384 launches");
+void gemmfr_kernel(const FrArgs<KIND> fa) {
+  static_assert(KIND == DEVIT_EPI_RESIDUAL_F32 || KIND == DEVIT_EPI_STORE_BF16 || KIND == DEVIT_EPI_LNBWD, "the student's N = 384 launches");
+  const GemmArgs& g = fa.g;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int BM = 256, BN = 384, NWAVES = 4;
-  constexpr bool PAIRED = KIND == DEVIT_EPI_STORE_BF16;   // column order of the n-tiles, tile_row<PAIRED>()
+  constexpr bool PAIRED = KIND != DEVIT_EPI_RESIDUAL_F32;   // column order of the n-tiles, tile_row<PAIRED>()
   constexpr int A_SLOT = BM * BK * 2, B_SLOT = BN * BK * 2, B_RING = 2 * A_SLOT;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1300,12 +1320,156 @@ void gemmfr_kernel(const GemmArgs g) {
     const unsigned long long ts1 = __builtin_amdgcn_s_memtime();
     st_sum[0] += 1; st_sum[1] += ts1 - ts0; st_sum[3] += d1; st_sum[4] += d2;
 #endif
-    // epilogue: the eight-wave kernels' register epilogue on chunks of two m-tiles x four n-tiles; the column group that lives in
-    // VGPRs (n-tiles 8..11) first -- it frees the registers the other chunks' values are read out into
     int lane_e;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
     const size_t ob = (size_t)ct.bz * ep.out_batch_stride;
     const int m_lim = ep.m_valid > 0 ? ep.m_valid : g.M;
+    if constexpr (KIND == DEVIT_EPI_LNBWD) {
+      // ---- fused epilogue: dgrad + LayerNorm backward.  The tile's rows are whole 384-wide rows of exactly the matrix ln_bwd_kernel would read
+      // next, so they never go to memory: the accumulators are rounded to bf16 as DEVIT_EPI_STORE_BF16 rounds them and staged in LDS in true
+      // column order, 128 rows per pass (m-tiles 4 P .. 4 P + 3 of both wm halves; the ring is dead: this workgroup has no next tile, the host
+      // guarantees it), and ln_rows.h's row body runs on them in ln_bwd_kernel's own lane layout -- half a wave per row, the same additions in the
+      // same order -- so dx / dx_bf16 are bit for bit what the two launches gave.  The three column sums stay in registers across the tile's 256 rows
+      // and leave as partial[tile] (colsum_partials_kernel finishes them: no atomics).  Measured in the serialized step (profiles/r07_a_*): 102 us per
+      // launch against 56 (dgrad) + 57 (ln_bwd_kernel) us: the row stage's 273 MB (x, dres, dx, the bf16 copy) cost ~47 us behind the K loop.
+      const LnBwdArgs& la = fa.ln;
+      const int gq = lane_e >> 4, c = lane_e & 15, hl = lane_e & 31, half = lane_e >> 5;
+      f32x4 cs[4];
+      float zf;                    // (a zero made here: constants of the epilogue must not live in VGPRs across the K loop, whose statement owns most of them)
+      asm volatile("v_mov_b32 %0, 0" : "=v"(zf));
+      const f32x4 z4 = {zf, zf, zf, zf};
+      LnBwdCols<3> cols;
+      ln_bwd_cols_init<3, false>(la, hl, cols, z4);
+      float invD = 1.0f / 384.0f;   // (= the standalone kernel's correctly rounded 1.0f / D)
+      asm volatile("" : "+v"(invD));
+      const size_t zhi = (size_t)__builtin_bit_cast(unsigned, zf) << 32;
+      // staged row of (wm, pass-local m-tile pair kk, m-tile u of the pair, row c): wm * 64 + kk * 32 + 16 u + c; columns: the lane's eight at
+      // wn * 192 + 64 H + 32 q + 8 gq (tile_row<true>)
+      char* const srow = smem + (wm * 64 + c) * LNF_PITCH + (wn * 192 + 8 * gq) * 2;
+      // The column group that lives in VGPRs (n-tiles 8..11 of each wn) leaves the registers at once, all four m-tile pairs of it: the second
+      // pass's share waits in a side region [128 rows][2 x 64 columns] (nothing of the accumulators stays pinned in VGPRs across the row loop).
+      char* const siderow = smem + LNF_SIDE + (wm * 64 + c) * LNF_SIDE_PITCH + (wn * 64 + 8 * gq) * 2;
+      auto put_v = [&](const f32x32& cv, int k) {
+        int noff[4];
+        f32x4 bias[4];
+        load_cols<DEVIT_EPI_STORE_BF16>(ep, lane_e, ct.n0 + wn * 192 + 128, noff, bias, cs);
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+          for (int q = 0; q < 2; ++q) {
+            float x[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[e] = cv[16 * u + 4 * (2 * q + (e >> 2)) + (e & 3)] + bias[2 * q + (e >> 2)][e & 3];
+            char* const dst = k < 2 ? srow + ((k & 1) * 32 + 16 * u) * LNF_PITCH + (128 + 32 * q) * 2
+                                    : siderow + ((k & 1) * 32 + 16 * u) * LNF_SIDE_PITCH + (32 * q) * 2;
+            *(bf16x8*)dst = pack8<false>(x);
+          }
+      };
+      auto put_a = [&](auto hc, auto ic) {
+        constexpr int H = decltype(hc)::value, I0 = decltype(ic)::value;
+        int noff[4];
+        f32x4 bias[4];
+        load_cols<DEVIT_EPI_STORE_BF16>(ep, lane_e, ct.n0 + wn * 192 + H * 64, noff, bias, cs);
+        f32x4 acc[2][4];
+        gemmfr_read_acc<H, I0>(acc);
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+          for (int q = 0; q < 2; ++q) {
+            float x[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[e] = acc[u][2 * q + (e >> 2)][e & 3] + bias[2 * q + (e >> 2)][e & 3];
+            *(bf16x8*)(srow + (((I0 >> 1) & 1) * 32 + 16 * u) * LNF_PITCH + (H * 64 + 32 * q) * 2) = pack8<false>(x);
+          }
+      };
+      // The half-wave's 32 rows of the tile, q = 16 P + t: pass P, staged row t * 8 + (its index among the eight half-waves).  The global inputs of
+      // rows q + R .. q + 2 R - 1 are requested before rows q .. q + R - 1 are worked on (the first R before the staging, the second pass's first
+      // R across the barriers between the passes): the kernel streams at the rate of its requests in flight.
+      constexpr int R = 2;
+      struct Pre {
+        f32x4 xv[3], dr[3];
+        float mu, rs, rsc;
+        int m;                                   // the row, -1: a pad row
+      };
+      auto fetch = [&](int q, Pre& p) {
+        const int lr = (q & 15) * 8 + wave * 2 + half;
+        const int m = ct.m0 + (lr >> 6) * 128 + 64 * (q >> 4) + (lr & 63);
+        const bool live = m < m_lim;
+        p.m = live ? m : -1;
+        p.rsc = (live && la.dx_bf16 && la.rowscale) ? la.rowscale[(unsigned)m / (unsigned)la.rows_per_scale] : 1.0f;
+        p.mu = live ? la.mean[m] : zf;
+        p.rs = live ? la.rstd[m] : zf;
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+          const size_t o = (zhi | (unsigned)(live ? m : 0)) * 384 + v * 128 + hl * 4;
+          p.xv[v] = z4;
+          p.dr[v] = z4;
+          if (live) {
+            p.xv[v] = load_stream((const f32x4*)(la.x + o));
+            if (la.dres) p.dr[v] = load_stream((const f32x4*)(la.dres + o));
+          }
+        }
+      };
+      Pre cur[R], nxt[R];
+      auto ln_pass = [&](int P) {
+#pragma unroll 1
+        for (int t0 = 0; t0 < LNF_ROWS / 8; t0 += R) {
+          if (16 * P + t0 + R < 32) {
+#pragma unroll
+            for (int i = 0; i < R; ++i) fetch(16 * P + t0 + R + i, nxt[i]);
+          }
+#pragma unroll
+          for (int i = 0; i < R; ++i) {
+            const int lr = (t0 + i) * 8 + wave * 2 + half;
+            const bool live = cur[i].m >= 0;
+            LnBwdRow<3> in;
+            in.mu = cur[i].mu;
+            in.rs = cur[i].rs;
+#pragma unroll
+            for (int v = 0; v < 3; ++v) {
+              const int col = v * 128 + hl * 4;
+              in.xv[v] = cur[i].xv[v];
+              in.dyv[v] = z4;
+              if (live) {                        // (a pad row's staged line holds what its accumulators held: never read)
+                // (second pass: columns 128..191 and 320..383, the VGPR group of wn = 0 / 1, wait in the side region)
+                const bool side = P == 1 && ((v == 1 && (col & 127) < 64) || (v == 2 && (col & 127) >= 64));
+                const char* src = side ? smem + LNF_SIDE + lr * LNF_SIDE_PITCH + ((v - 1) * 64 + (col & 63)) * 2 : smem + lr * LNF_PITCH + col * 2;
+                const bf16x4 t = *(const bf16x4*)src;
+                in.dyv[v] = (f32x4){bf2f(t[0]), bf2f(t[1]), bf2f(t[2]), bf2f(t[3])};
+              }
+            }
+            ln_bwd_row<3, false>(la, cols, in, live, zhi | (unsigned)(live ? cur[i].m : 0), lane_e, 384, invD, cur[i].rsc,
+                                 [&](int v, size_t) { return cur[i].dr[v]; });
+          }
+#pragma unroll
+          for (int i = 0; i < R; ++i) cur[i] = nxt[i];
+        }
+      };
+      wait_vmcnt<0>();
+      __syncthreads();             // every wave's last fragment reads are done: the ring is free
+#pragma unroll
+      for (int i = 0; i < R; ++i) fetch(i, cur[i]);
+      put_v(c0, 0);
+      put_v(c1, 1);
+      put_v(c2, 2);
+      put_v(c3, 3);
+      put_a(std::integral_constant<int, 0>(), std::integral_constant<int, 0>());
+      put_a(std::integral_constant<int, 1>(), std::integral_constant<int, 0>());
+      put_a(std::integral_constant<int, 0>(), std::integral_constant<int, 2>());
+      put_a(std::integral_constant<int, 1>(), std::integral_constant<int, 2>());
+      __syncthreads();             // both wn waves of every row have written it
+      ln_pass(0);
+      __syncthreads();             // every half-wave has read its rows: the region is rewritten
+      put_a(std::integral_constant<int, 0>(), std::integral_constant<int, 4>());
+      put_a(std::integral_constant<int, 1>(), std::integral_constant<int, 4>());
+      put_a(std::integral_constant<int, 0>(), std::integral_constant<int, 6>());
+      put_a(std::integral_constant<int, 1>(), std::integral_constant<int, 6>());
+      __syncthreads();
+      ln_pass(1);
+      ln_bwd_cols_store<3>(la, cols, (float (*)[3][384])(smem + LNF_RED), wave, lane_e, 384, (size_t)tile);
+    } else {
+    // epilogue: the eight-wave kernels' register epilogue on chunks of two m-tiles x four n-tiles; the column group that lives in
+    // VGPRs (n-tiles 8..11) first -- it frees the registers the other chunks' values are read out into
     const bool full = ct.m0 + BM <= m_lim;
     f32x4 cs[4];   // (no column scale in these kinds)
     auto run = [&](f32x4 (&acc)[2][4], const int (&noff)[4], const f32x4 (&bias)[4], int i0) {
@@ -1349,6 +1513,7 @@ void gemmfr_kernel(const GemmArgs g) {
     };
     group(std::integral_constant<int, 0>());
     group(std::integral_constant<int, 1>());
+    }
 #ifdef DEVIT_GEMMFR_STAMP
     st_sum[2] += __builtin_amdgcn_s_memtime() - ts1;
 #endif
@@ -1602,6 +1767,27 @@ int reserved_cus() {
   return g_reserved_cus;
 }
 
+int cu_count() {      // 0: the query failed
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8) cus = n;
+  }
+  return cus;
+}
+// workgroups of a persistent grid with `occ` of them per CU: a multiple of 8 (every XCD gets the same number), the reserved CUs left free
+long long persistent_grid(int cus, int occ) {
+  const int avail = cus - reserved_cus() >= 8 ? cus - reserved_cus() : 8;
+  return ((long long)avail * occ) / 8 * 8;
+}
+int gemm_force() {    // DEVIT_GEMM_FORCE (tools/gpu_tiles.sh): 1 = 128x128 tiles for everything, 3 = 256x256 wherever built
+  static const int exact = getenv("DEVIT_GEMM_FORCE") ? atoi(getenv("DEVIT_GEMM_FORCE")) : 0;
+  return exact;
+}
+
+int gemm_launch(const devit_operand* Aop, const devit_operand* Bop, int M, int N, int K, int batch, int split_k, const devit_epilogue* ep,
+                const LnBwdArgs* ln, void* stream);
+
 }  // namespace
 
 // The full-row 256x384 kernel (gemmfr_kernel): N == 384 exactly (one n-tile: its B stream is cyclic over the tiles), whole 256-row tiles and
@@ -1695,6 +1881,14 @@ extern "C" int devit_get_reserved_cus(void) { return reserved_cus(); }
 
 extern "C" int devit_gemm_bf16(const devit_operand* Aop, const devit_operand* Bop, int M, int N, int K, int batch,
                                int split_k, const devit_epilogue* ep, void* stream) {
+  return gemm_launch(Aop, Bop, M, N, K, batch, split_k, ep, nullptr, stream);
+}
+
+namespace {
+// devit_gemm_bf16; with `ln`, the launch whose bf16 output feeds the LayerNorm backward `ln` in the same kernel (devit_dgrad_layernorm_bwd: the
+// caller has checked devit_dgrad_layernorm_bwd_fused, anything else is an error here, never a silent other path)
+int gemm_launch(const devit_operand* Aop, const devit_operand* Bop, int M, int N, int K, int batch, int split_k, const devit_epilogue* ep,
+                const LnBwdArgs* ln, void* stream) {
   DEVIT_CHECK(Aop && Bop && Aop->ptr && Bop->ptr && ep && ep->out, DEVIT_ERR_ARG, "devit_gemm_bf16: null pointer");
   const void* A = Aop->ptr;
   const void* B = Bop->ptr;
@@ -1765,7 +1959,7 @@ extern "C" int devit_gemm_bf16(const devit_operand* Aop, const devit_operand* Bo
   // too few 256x256 tiles to give every CU one (the token-row GEMMs of the lean last block, M = 512): 128x128 tiles
   // quarter the time of the longest workgroup; same accumulation order per output element either way
   if (cfg == 3 && (long long)(M / 256) * ((N + 255) / 256) * batch < 64) cfg = 1;
-  static const int exact = getenv("DEVIT_GEMM_FORCE") ? atoi(getenv("DEVIT_GEMM_FORCE")) : 0;   // tools/gpu_tiles.sh
+  const int exact = gemm_force();
   if (exact == 1 || (exact == 3 && M % 256 == 0 && (N % 256 == 0 || ragged_ok) && variant != 3)) cfg = exact;
   // the full-row 256x384 kernel: the student's N = 384 launches (round 5; per-shape times inside the step: profiles/r05_*).  DEVIT_GEMMFR=0 / 1
   // forces it off / on for everything it is built for (read per call: tests switch it).
@@ -1807,22 +2001,17 @@ extern "C" int devit_gemm_bf16(const devit_operand* Aop, const devit_operand* Bo
   g.d_split = make_fastdiv(split_k);
   // persistent grid: as many workgroups as stay resident (LDS: two 128x128 rings or one 256-wide ring per CU), a
   // multiple of 8 so that every XCD gets the same number
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    DEVIT_CHECK(hipGetDevice(&dev) == hipSuccess &&
-                    hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8,
-                DEVIT_ERR_DEVICE, "devit_gemm_bf16: cannot query the CU count");
-    cus = n;
-  }
+  const int cus = cu_count();
+  DEVIT_CHECK(cus >= 8, DEVIT_ERR_DEVICE, "devit_gemm_bf16: cannot query the CU count");
   static const int occ_env = getenv("DEVIT_GEMM_OCC") ? atoi(getenv("DEVIT_GEMM_OCC")) : 0;
   const int occ = cfg == 4 ? 1 : occ_env > 0 ? occ_env : (cfg == 1 ? 2 : 1);
   // A persistent grid holds every CU it starts on (the 256x256 workgroup owns the CU's whole LDS and register file) until
   // its last tile: a collective's kernels launched meanwhile (RCCL on the exchange stream) wait for a GEMM to END, and once
   // they hold CUs the next 256-workgroup grid runs a second, nearly empty round.  With `reserved` CUs left free the grid
   // is smaller and its tiles are dealt over the workgroups that do run (devit_set_reserved_cus; 0 at world size 1).
-  const int avail = cus - reserved_cus() >= 8 ? cus - reserved_cus() : 8;
-  long long nwg = ((long long)avail * occ) / 8 * 8;
+  long long nwg = persistent_grid(cus, occ);
+  DEVIT_CHECK(!ln || (cfg == 4 && ep->kind == DEVIT_EPI_STORE_BF16 && tiles <= nwg), DEVIT_ERR_ARG,
+              "the fused dgrad + LayerNorm-backward launch needs the full-row kernel and one tile per workgroup: M=%d K=%d", M, K);
   if (nwg > (tiles + 7) / 8 * 8) nwg = (tiles + 7) / 8 * 8;
   hipStream_t s = (hipStream_t)stream;
 #define DEVIT_LAUNCH_ONE_T(BM_, BN_, WMM_, WNN_, NS_, AKM_, BKM_, KIND_, F16_)                                   \
@@ -1909,11 +2098,19 @@ extern "C" int devit_gemm_bf16(const devit_operand* Aop, const devit_operand* Bo
       DEVIT_CHECK(e == hipSuccess, DEVIT_ERR_LAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));         \
       attr = true;                                                                                             \
     }                                                                                                          \
-    hipLaunchKernelGGL((gemmfr_kernel<KIND_>), dim3((unsigned)nwg), dim3(256), lds, s, g);                     \
+    hipLaunchKernelGGL((gemmfr_kernel<KIND_>), dim3((unsigned)nwg), dim3(256), lds, s, fa);                    \
   } while (0)
   if (cfg == 4) {
-    if (ep->kind == DEVIT_EPI_STORE_BF16) DEVIT_LAUNCH_GEMMFR(DEVIT_EPI_STORE_BF16);
-    else DEVIT_LAUNCH_GEMMFR(DEVIT_EPI_RESIDUAL_F32);
+    if (ln) {
+      FrArgs<DEVIT_EPI_LNBWD> fa{g, *ln};
+      DEVIT_LAUNCH_GEMMFR(DEVIT_EPI_LNBWD);
+    } else if (ep->kind == DEVIT_EPI_STORE_BF16) {
+      FrArgs<DEVIT_EPI_STORE_BF16> fa{g};
+      DEVIT_LAUNCH_GEMMFR(DEVIT_EPI_STORE_BF16);
+    } else {
+      FrArgs<DEVIT_EPI_RESIDUAL_F32> fa{g};
+      DEVIT_LAUNCH_GEMMFR(DEVIT_EPI_RESIDUAL_F32);
+    }
   } else if (use4) {
     switch (ep->kind) {
       case DEVIT_EPI_STORE_BF16: DEVIT_LAUNCH_GEMM4(DEVIT_EPI_STORE_BF16); break;
@@ -1933,4 +2130,48 @@ extern "C" int devit_gemm_bf16(const devit_operand* Aop, const devit_operand* Bo
 #undef DEVIT_LAUNCH_GEMM
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
+}
+}  // namespace
+
+// Would devit_dgrad_layernorm_bwd take the fused launch?  The rule, in one place: the full-row kernel would run the product (N = D = 384, whole
+// 256-row tiles and enough of them, DEVIT_GEMMFR / DEVIT_GEMM_FORCE not against it) AND every workgroup of its grid gets at most one tile -- with a
+// next tile the operand ring holds that tile's prefetched stages and there is no LDS to stage rows in.  DEVIT_LNFUSE=0 (read per call: tests switch
+// it) forces the two unfused launches.
+extern "C" int devit_dgrad_layernorm_bwd_fused(int M_pad, int D, int K) {
+  const char* e = getenv("DEVIT_LNFUSE");
+  if (e && *e && atoi(e) == 0) return 0;
+  if (D != 384 || gemm_force() == 1 || !devit_gemm_full_row_selected(M_pad, D, K, DEVIT_EPI_STORE_BF16)) return 0;
+  const int cus = cu_count();
+  return cus >= 8 && M_pad / 256 <= persistent_grid(cus, 1);
+}
+
+extern "C" int devit_dgrad_layernorm_bwd(const void* dy, const void* w, int M_pad, int K, void* dln, const float* x, int rows, int D,
+                                         const float* mean, const float* rstd, const float* gamma, const float* dres, float* dx,
+                                         void* dx_bf16, const float* rowscale, int rows_per_scale, float* dgamma, float* dbeta,
+                                         float* dx_bf16_colsum, int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  DEVIT_CHECK(dy && w && dln && rows > 0 && rows <= M_pad, DEVIT_ERR_ARG, "devit_dgrad_layernorm_bwd: bad argument");
+  devit_operand A = {dy, K, 0, 0, 0, 0}, Bo = {w, D, 1, 0, 0, 0};
+  devit_epilogue ep = {};
+  ep.kind = DEVIT_EPI_STORE_BF16;
+  ep.out = dln;
+  ep.ldc = D;
+  ep.m_valid = rows;
+  if (!devit_dgrad_layernorm_bwd_fused(M_pad, D, K)) {
+    int rc = devit_gemm_bf16(&A, &Bo, M_pad, D, K, 1, 1, &ep, stream);
+    if (rc != DEVIT_OK) return rc;
+    return devit_layernorm_bwd(dln, 0, x, rows, D, 0, 0, mean, rstd, gamma, dres, dx, dx_bf16, rowscale, rows_per_scale, dgamma, dbeta,
+                               dx_bf16_colsum, accumulate, workspace, workspace_bytes, stream);
+  }
+  // (devit_layernorm_bwd's argument checks)
+  DEVIT_CHECK(x && mean && rstd && gamma && dx && dgamma && dbeta && workspace, DEVIT_ERR_ARG, "devit_dgrad_layernorm_bwd: null pointer");
+  DEVIT_CHECK(workspace_bytes >= devit_layernorm_bwd_workspace(rows, D), DEVIT_ERR_ARG, "devit_dgrad_layernorm_bwd: workspace too small");
+  DEVIT_CHECK(!rowscale || rows_per_scale > 0, DEVIT_ERR_ARG, "devit_dgrad_layernorm_bwd: rows_per_scale");
+  DEVIT_CHECK(!dx_bf16_colsum || dx_bf16, DEVIT_ERR_ARG, "devit_dgrad_layernorm_bwd: dx_bf16_colsum needs dx_bf16");
+  DEVIT_CHECK(aligned16(x) && aligned16(dx) && (!dres || aligned16(dres)) && (!dx_bf16 || aligned16(dx_bf16)), DEVIT_ERR_ARG,
+              "devit_dgrad_layernorm_bwd: x / dres / dx / dx_bf16 must be 16-byte aligned");
+  const int tiles = M_pad / 256;      // one partial per tile: <= CUs <= the rows / 8 (or 1024) parts the workspace is sized for
+  LnBwdArgs ln{nullptr, x, mean, rstd, gamma, dres, dx, (__bf16*)dx_bf16, rowscale, rows_per_scale, (float*)workspace, rows, D, 0, 0, 0};
+  int rc = gemm_launch(&A, &Bo, M_pad, D, K, 1, 1, &ep, &ln, stream);
+  if (rc != DEVIT_OK) return rc;
+  return devit_layernorm_bwd_finish((const float*)workspace, tiles, D, dgamma, dbeta, dx_bf16_colsum, accumulate, stream);
 }

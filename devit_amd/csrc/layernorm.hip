@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "devit_common.h"
+#include "ln_rows.h"
 
 namespace {
 
@@ -21,10 +22,6 @@ struct LnFwdArgs {
   float eps;
   int f16;              // y_bf16 holds IEEE f16 instead of bf16 (frozen-teacher forward)
 };
-
-__device__ __forceinline__ size_t ln_in_row(int r, int group, int stride) {
-  return group > 0 ? (size_t)(r / group) * stride + (r % group) : (size_t)r;
-}
 
 // Half a wave (32 lanes) per row, 16-byte loads: lane l holds float4 v of the row at columns (v * 32 + l) * 4,
 // NV = D / 128 of them; bf16 output leaves as 8-byte stores.  (The first version read float2 per lane with one wave
@@ -92,39 +89,17 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwdArgs a) {
   }
 }
 
-struct LnBwdArgs {
-  const void* dy;       // [rows][D] bf16 or f32 (dense, row r)
-  const float* x;       // forward input, physical row map as in fwd
-  const float* mean;
-  const float* rstd;
-  const float* gamma;
-  const float* dres;    // [phys rows][D] f32 upstream residual-stream gradient or NULL
-  float* dx;            // [phys rows][D] f32 = dres + LN'(dy)
-  __bf16* dx_bf16;      // optional bf16 copy of rowscale * dx (branch gradient for the next GEMMs)
-  const float* rowscale;
-  int rows_per_scale;
-  float* partial;       // [grid][3][D] column partial sums (dgamma, dbeta, colsum of dx_bf16)
-  int rows, D, in_group, in_stride, dy_is_f32;
-};
-
 // Half a wave (32 lanes x 4*NV columns) per token row, two rows per wave pass: 16-byte loads of x / dres and 8-byte
-// loads of the bf16 dy keep ~2.5 KB per wave in flight (HBM-bound kernel).
+// loads of the bf16 dy keep ~2.5 KB per wave in flight (HBM-bound kernel).  The row arithmetic is ln_rows.h's (shared with
+// the full-row GEMM's fused epilogue).
 template <int NV, bool RAG = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwdArgs a) {
   __shared__ float red[4][3][NV * 128];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, hl = lane & 31, half = lane >> 5;
   const int slot = (blockIdx.x * 4 + wv) * 2 + half;       // half-wave id
   const int nslots = gridDim.x * 8;
-  f32x4 gm[NV], dg[NV], db[NV], dsum[NV];
-  bool ok[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    ok[v] = !RAG || v * 128 + hl * 4 < a.D;
-    gm[v] = ok[v] ? *(const f32x4*)(a.gamma + v * 128 + hl * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    dg[v] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    db[v] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    dsum[v] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
+  LnBwdCols<NV> s;
+  ln_bwd_cols_init<NV, RAG>(a, hl, s);
   const float invD = 1.0f / (float)a.D;
   const int nit = (a.rows + nslots - 1) / nslots;           // wave-uniform trip count (shuffles need all lanes)
   for (int it = 0; it < nit; ++it) {
@@ -132,77 +107,29 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwdArgs a) {
     const bool live = r < a.rows;
     const size_t pr = ln_in_row(live ? r : 0, a.in_group, a.in_stride);
     const float* xr = a.x + pr * a.D;
-    const float mu = live ? a.mean[r] : 0.f, rs = live ? a.rstd[r] : 0.f;
-    f32x4 xh[NV], g[NV], dyv[NV];
-    float s1 = 0.f, s2 = 0.f;
+    LnBwdRow<NV> in;
+    in.mu = live ? a.mean[r] : 0.f;
+    in.rs = live ? a.rstd[r] : 0.f;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int c = v * 128 + hl * 4;
-      f32x4 xv = {0.f, 0.f, 0.f, 0.f};
-      dyv[v] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (live && ok[v]) {
-        xv = load_stream((const f32x4*)(xr + c));
+      in.xv[v] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      in.dyv[v] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (live && s.ok[v]) {
+        in.xv[v] = load_stream((const f32x4*)(xr + c));
         if (a.dy_is_f32) {
-          dyv[v] = load_stream((const f32x4*)((const float*)a.dy + (size_t)r * a.D + c));
+          in.dyv[v] = load_stream((const f32x4*)((const float*)a.dy + (size_t)r * a.D + c));
         } else {
           const bf16x4 t = load_stream((const bf16x4*)((const __bf16*)a.dy + (size_t)r * a.D + c));
-          dyv[v] = (f32x4){bf2f(t[0]), bf2f(t[1]), bf2f(t[2]), bf2f(t[3])};
-        }
-      }
-      xh[v] = ok[v] ? (xv - mu) * rs : (f32x4){0.f, 0.f, 0.f, 0.f};
-      g[v] = dyv[v] * gm[v];
-      dg[v] += dyv[v] * xh[v];
-      db[v] += dyv[v];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        s1 += g[v][e];
-        s2 += g[v][e] * xh[v][e];
-      }
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-      s1 += __shfl_xor(s1, o, 64);
-      s2 += __shfl_xor(s2, o, 64);
-    }
-    const float m1 = s1 * invD, m2 = s2 * invD;
-    if (live) {
-      const float rsc = (a.dx_bf16 && a.rowscale) ? a.rowscale[pr / a.rows_per_scale] : 1.0f;
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        const size_t o = pr * a.D + v * 128 + hl * 4;
-        if (RAG && !ok[v]) continue;
-        f32x4 d = rs * (g[v] - m1 - xh[v] * m2);
-        if (a.dres) d += load_stream((const f32x4*)(a.dres + o));
-        *(f32x4*)(a.dx + o) = d;
-        if (a.dx_bf16) {
-          const bf16x4 ob = {f2bf(d[0] * rsc), f2bf(d[1] * rsc), f2bf(d[2] * rsc), f2bf(d[3] * rsc)};
-          *(bf16x4*)(a.dx_bf16 + o) = ob;
-          dsum[v] += (f32x4){bf2f(ob[0]), bf2f(ob[1]), bf2f(ob[2]), bf2f(ob[3])};
+          in.dyv[v] = (f32x4){bf2f(t[0]), bf2f(t[1]), bf2f(t[2]), bf2f(t[3])};
         }
       }
     }
+    const float rsc = (live && a.dx_bf16 && a.rowscale) ? a.rowscale[pr / a.rows_per_scale] : 1.0f;
+    ln_bwd_row<NV, RAG>(a, s, in, live, pr, lane, a.D, invD, rsc, [&](int, size_t o) { return load_stream((const f32x4*)(a.dres + o)); });
   }
   // block reduction of the column sums -> partial[block][{dgamma, dbeta, colsum(dx_bf16)}][D]
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {      // the two half-waves hold the same columns
-      dg[v][e] += __shfl_xor(dg[v][e], 32, 64);
-      db[v][e] += __shfl_xor(db[v][e], 32, 64);
-      dsum[v][e] += __shfl_xor(dsum[v][e], 32, 64);
-    }
-    if (half == 0 && ok[v]) {
-      *(f32x4*)&red[wv][0][v * 128 + hl * 4] = dg[v];
-      *(f32x4*)&red[wv][1][v * 128 + hl * 4] = db[v];
-      *(f32x4*)&red[wv][2][v * 128 + hl * 4] = dsum[v];
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 3 * a.D; i += 256) {
-    const int which = i / a.D, c = i - which * a.D;
-    a.partial[((size_t)blockIdx.x * 3 + which) * a.D + c] =
-        red[0][which][c] + red[1][which][c] + red[2][which][c] + red[3][which][c];
-  }
+  ln_bwd_cols_store<NV>(a, s, red, wv, lane, a.D, blockIdx.x);
 }
 
 // out_k[c] (+)= sum_p partial[p][k][c], k = 0..2  (deterministic order; 32 columns x 32 part-groups per block)
@@ -294,8 +221,14 @@ extern "C" int devit_layernorm_bwd(const void* dy, int dy_is_f32, const float* x
   });
   DEVIT_CHECK(rc == 0, DEVIT_ERR_SHAPE, "devit_layernorm_bwd: unsupported D=%d", D);
   DEVIT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(colsum_partials_kernel, dim3((3 * D + 31) / 32), dim3(1024), 0, (hipStream_t)stream,
-                     (const float*)workspace, grid, D, dgamma, dbeta, dx_bf16_colsum, accumulate);
+  return devit_layernorm_bwd_finish((const float*)workspace, grid, D, dgamma, dbeta, dx_bf16_colsum, accumulate, stream);
+}
+
+// partial[nparts][3][D] -> dgamma / dbeta / the optional column sums of dx_bf16 (internal: also behind the full-row GEMM's fused epilogue)
+int devit_layernorm_bwd_finish(const float* partial, int nparts, int D, float* dgamma, float* dbeta, float* dx_bf16_colsum,
+                               int accumulate, void* stream) {
+  hipLaunchKernelGGL(colsum_partials_kernel, dim3((3 * D + 31) / 32), dim3(1024), 0, (hipStream_t)stream, partial, nparts, D, dgamma,
+                     dbeta, dx_bf16_colsum, accumulate);
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
 }

@@ -172,6 +172,22 @@ DEVIT_API int devit_layernorm_bwd(const void* dy, int dy_is_f32, const float* x,
                         void* dx_bf16, const float* rowscale, int rows_per_scale, float* dgamma, float* dbeta,
                         float* dx_bf16_colsum, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
+/* A Linear layer's input gradient and the LayerNorm backward behind it as one call:
+ *     dln[M_pad][D] = dy[M_pad][K] @ w[K][D]     (w = the layer's [out_features K][in_features D] weight, read k-major; bf16)
+ *     devit_layernorm_bwd(dln, 0, x, rows, D, 0, 0, mean, ..., stream)
+ * i.e. autograd through `fc1(norm2(x))` / `qkv(norm1(x))` of models/de_vit.py:113-116 back to the residual stream.  Where
+ * devit_dgrad_layernorm_bwd_fused(M_pad, D, K) says so -- D == 384, the full-row 256x384 kernel would run the product
+ * (devit_gemm_full_row_selected) and every workgroup of its grid gets at most one tile (M_pad / 256 <= CUs - reserved CUs) --
+ * both run in ONE kernel: the tile's rows go through LDS instead of memory and dln is not written.  dx and dx_bf16 are bit for
+ * bit what the two launches give; dgamma / dbeta / dx_bf16_colsum are summed in another (fixed) order.  Otherwise, and with
+ * DEVIT_LNFUSE=0 in the environment (read per call), the two launches run.  dln: [M_pad][D] bf16 scratch either way;
+ * rows <= M_pad; everything else as in devit_layernorm_bwd. */
+DEVIT_API int devit_dgrad_layernorm_bwd_fused(int M_pad, int D, int K);
+DEVIT_API int devit_dgrad_layernorm_bwd(const void* dy, const void* w, int M_pad, int K, void* dln, const float* x, int rows, int D,
+                        const float* mean, const float* rstd, const float* gamma, const float* dres, float* dx, void* dx_bf16,
+                        const float* rowscale, int rows_per_scale, float* dgamma, float* dbeta, float* dx_bf16_colsum,
+                        int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fused attention core.  Replaces models/de_vit.py:68-79 (unbind q,k,v; q k^T * scale; softmax;
  * @ v; transpose; head-gate mul_) and its backward.
