@@ -175,6 +175,8 @@ def test_attention_backward_full_size(dev, H, with_add):
     inputs; the relation-loss gradient that the student's middle block adds in is checked on the student shape."""
     from devit_amd import ops
     from devit_amd._lib import call, ptr, stream_ptr
+    from _attn_model import check_packed
+    from conftest import chk
     D = H * 64
     g = torch.Generator(device=dev).manual_seed(11 + H)
     qkv = ops.rows_alloc(M, 3 * D, BF16, dev)
@@ -205,6 +207,9 @@ def test_attention_backward_full_size(dev, H, with_add):
         ref = x.grad + (add[r0:r1].float() if add is not None else 0)
         e = relmax(dqkv[r0:r1], ref)
         assert e < 2e-2, f"images {b0}..{b0 + 16}: dqkv rel-to-max err {e:.3e}"
+        # ... and every element of O, lse, dQ, dK, dV of the slice against its own bound (tests/_attn_model.py)
+        check_packed(chk, f"full_size/H{H}/images{b0}", qkv[r0:r1], 16, N, H, gate, 0.125, out[r0:r1], lse[b0:b0 + 16], dout[r0:r1], dqkv[r0:r1],
+                     None if add is None else add[r0:r1])
 
 
 @pytest.mark.parametrize("D", [384, 768])

@@ -471,6 +471,10 @@ def test_attention_fwd_bwd(dev, B, N, H):
          stream_ptr())
     err = relerr(dqkv[:M], q32.grad)
     assert err < 2e-2, f"dqkv rel-to-max err {err:.3e}"    # bf16 P / dS operands: ~2^-8 relative
+    # ... and O, lse, dQ, dK, dV each against its own elementwise bound (tests/_attn_model.py)
+    from _attn_model import check_packed
+    from conftest import chk
+    check_packed(chk, f"fwd_bwd/B{B}-N{N}-H{H}", qkv, B, N, H, gate, 0.125, out, lse, dout, dqkv)
     # extra gradient added into dqkv (relation loss on the middle block): one rounding, after the fp32 add
     add = ops.rows_alloc(M, 3 * D, BF16, dev)
     add[:M] = rnd((M, 3 * D), dev, 0.5, seed=11, dtype=BF16)
@@ -480,6 +484,7 @@ def test_attention_fwd_bwd(dev, B, N, H):
     err2 = relerr(dqkv2[:M], q32.grad + add[:M].float())
     assert err2 < 2e-2, f"dqkv + add rel-to-max err {err2:.3e}"
     bf16_ulp_ok(dqkv2[:M], dqkv[:M].float() + add[:M].float(), extra=2e-3)
+    check_packed(chk, f"fwd_bwd/B{B}-N{N}-H{H}/add", qkv, B, N, H, gate, 0.125, out, lse, dout, dqkv2, add)
 
 
 # ------------------------------------------------------------------------------------------ elementwise
@@ -531,30 +536,43 @@ def test_sgemm_small_and_cls_loss(dev):
 
 
 def test_relation_loss(dev):
+    """Pooled bar as before, plus per column block j (weighted 0.2 / 0.1 / 0.3) the elementwise bound of _attn_model.relation_bounds, at the
+    flat (std 0.25) and the unit scale: at unit scale both softmaxes sit on the diagonal and S is a small difference of terms near 1."""
     from devit_amd import ops
+    from _attn_model import relation_bounds, ratio
+    from conftest import chk
     B, N, Hs, Ht = 3, 198, 2, 4
     Ds, Dt = Hs * 64, Ht * 64
     M = B * N
-    s_buf = ops.rows_alloc(M, 3 * Ds, BF16, dev, extra=128)
-    t_buf = ops.rows_alloc(M, 3 * Dt, BF16, dev, extra=128)
-    s_buf[:M] = rnd((M, 3 * Ds), dev, 0.25, 1, BF16)
-    t_buf[:M] = rnd((M, 3 * Dt), dev, 0.25, 2, BF16)
-    s_buf.requires_grad_(True)
-    losses = ops.RelationLossFn.apply(s_buf, t_buf, B, N, 64, 64)
-    wts = torch.tensor([0.2, 0.1, 0.3], device=dev) / 12
-    (losses * wts).sum().backward()
-    s32 = s_buf.detach()[:M].float().requires_grad_(True)
-    ref = []
-    for j in range(3):
-        fs, ft = s32[:, j * Ds:(j + 1) * Ds].view(B, N, Ds), t_buf[:M, j * Dt:(j + 1) * Dt].float().view(B, N, Dt)
-        t = torch.log_softmax(ft @ ft.transpose(1, 2) / 8, -1)
-        s = torch.log_softmax(fs @ fs.transpose(1, 2) / 8, -1)
-        ref.append(torch.sum(t.exp() * (t - s)) / B)
-    ref = torch.stack(ref)
-    (ref * wts).sum().backward()
-    assert relerr(losses, ref) < 1e-4, (losses, ref)
-    err = relerr(s_buf.grad[:M], s32.grad)
-    assert err < 2e-2, f"relation grad rel-to-max err {err:.3e}"
+    for std in (0.25, 1.0):
+        s_buf = ops.rows_alloc(M, 3 * Ds, BF16, dev, extra=128)
+        t_buf = ops.rows_alloc(M, 3 * Dt, BF16, dev, extra=128)
+        s_buf[:M] = rnd((M, 3 * Ds), dev, std, 1, BF16)
+        t_buf[:M] = rnd((M, 3 * Dt), dev, std, 2, BF16)
+        s_buf.requires_grad_(True)
+        losses = ops.RelationLossFn.apply(s_buf, t_buf, B, N, 64, 64)
+        wts = torch.tensor([0.2, 0.1, 0.3], device=dev) / 12
+        (losses * wts).sum().backward()
+        s32 = s_buf.detach()[:M].float().requires_grad_(True)
+        ref = []
+        for j in range(3):
+            fs, ft = s32[:, j * Ds:(j + 1) * Ds].view(B, N, Ds), t_buf[:M, j * Dt:(j + 1) * Dt].float().view(B, N, Dt)
+            t = torch.log_softmax(ft @ ft.transpose(1, 2) / 8, -1)
+            s = torch.log_softmax(fs @ fs.transpose(1, 2) / 8, -1)
+            ref.append(torch.sum(t.exp() * (t - s)) / B)
+        ref = torch.stack(ref)
+        (ref * wts).sum().backward()
+        if std == 0.25:        # at unit scale a row's KL (~3e-4) is a difference of log-probabilities of magnitude 16 and 32, each good to an fp32
+            assert relerr(losses, ref) < 1e-4, (losses, ref)     # ulp of that: neither the kernel nor this fp32 reference resolves it to 1e-4
+        err = relerr(s_buf.grad[:M], s32.grad)
+        assert err < 2e-2, f"relation grad rel-to-max err {err:.3e}"
+        for j in range(3):
+            fs = s_buf.detach()[:M, j * Ds:(j + 1) * Ds].double().view(B, N, Ds)
+            ft = t_buf[:M, j * Dt:(j + 1) * Dt].double().view(B, N, Dt)
+            want, bound, _ = relation_bounds(fs, ft, float(wts[j]), 64, 64)
+            r = ratio(s_buf.grad[:M, j * Ds:(j + 1) * Ds].double().view(B, N, Ds), want, bound)
+            print(f"relation std {std} block {j}: worst |err| / bound {r:.3f}")
+            assert chk(r, 1.0, name=f"relation/std{std}/block{j}"), (std, j, r)
 
 
 def test_adamw_and_sumsq(dev):
