@@ -6,8 +6,9 @@
      compiler is told they are clobbered, not that they are LIVE between the loop and the read-out asm statements), nothing but an MFMA writes an
      a-register: no v_accvgpr_write, no load into an AGPR (advisor r04: a compiler that used AGPRs as spill space there would corrupt the tile).
 A missing tool or an object that cannot be taken apart is an ERROR, never a pass; an object is skipped only when it holds no device code at all
-(no .hip_fatbin section: api / comm / encoder today -- found by looking, not by name, so device code added to one of them later is gated too).
+(no .hip_fatbin section: api / comm / encoder / gemm today -- found by looking, not by name, so device code added to one of them later is gated too).
 usage: check_objects.py BUILD_DIR obj..."""
+import contextlib
 import os
 import re
 import subprocess
@@ -46,21 +47,40 @@ def scan_agpr_writes(disassembly):
     return bad, seen
 
 
-def main(build, names):
+def tools_present():
     for tool in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf", "llvm-objdump"):
         if not os.access(os.path.join(LLVM, tool), os.X_OK):
             sys.exit(f"check_objects: {LLVM}/{tool} is missing: the no-spill / AGPR gates cannot run (set DEVIT_LLVM_BIN)")
+
+
+@contextlib.contextmanager
+def code_object(build, f):
+    """the gfx950 code object of BUILD/f.o as a file (removed on exit); None for an object that holds host code only (tools/kernel_digest.py reads
+    the objects through this too)"""
+    obj, fat, co = (os.path.join(build, f + e) for e in (".o", ".fatbin", ".gfx950.co"))
+    if not re.search(r"\s\.hip_fatbin\s", run(os.path.join(LLVM, "llvm-readelf"), "-S", "-W", obj)):
+        yield None
+        return
+    try:
+        run(os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", obj)
+        run(os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}",
+            f"--output={co}", "--unbundle")
+        yield co
+    finally:
+        for p in (fat, co):
+            if os.path.exists(p):
+                os.remove(p)
+
+
+def main(build, names):
+    tools_present()
     bad = []
     checked = 0
     for f in names:
-        obj, fat, co = (os.path.join(build, f + e) for e in (".o", ".fatbin", ".gfx950.co"))
-        if not re.search(r"\s\.hip_fatbin\s", run(os.path.join(LLVM, "llvm-readelf"), "-S", "-W", obj)):
-            continue                                  # host code only
-        checked += 1
-        try:
-            run(os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", obj)
-            run(os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}",
-                f"--output={co}", "--unbundle")
+        with code_object(build, f) as co:
+            if co is None:
+                continue                                  # host code only
+            checked += 1
             notes = run(os.path.join(LLVM, "llvm-readelf"), "--notes", co)
             kernels = re.findall(r"\.name:\s+(\S+)", notes)
             if not kernels:
@@ -81,10 +101,6 @@ def main(build, names):
                 bad += [f"{f}.hip: {x}" for x in found]
                 if seen == 0:
                     sys.exit(f"check_objects: {f}.o: the disassembly of the asm-accumulator kernels shows no MFMA: the gate is not seeing them")
-        finally:
-            for p in (fat, co):
-                if os.path.exists(p):
-                    os.remove(p)
     if checked == 0:
         sys.exit("check_objects: none of the objects holds device code: the gate is not seeing the build")
     if bad:

@@ -63,7 +63,7 @@ int linear_wgrad(const Ctx& c, const void* dy, const void* x, float* w_grad, flo
   return devit_gemm_bf16(&A, &Bo, Nw, K, c.Mp, 1, split_k_for(Nw, K, c.Mp / 64), &ep, c.stream);
 }
 
-// The block's weight gradients as jobs of ONE devit_wgrad_grouped launch (the full-row weight-gradient kernel, gemm.hip): possible when
+// The block's weight gradients as jobs of ONE devit_wgrad_grouped launch (the full-row weight-gradient kernel, wgradfr.hip): possible when
 // one side of every product is exactly 384 features wide (D == 384: the student) and the other a multiple of 128.
 //   dW[Nw][K] += dy^T x:   K == 384 -> tiles over dy's features (column sums of dy = the bias gradient from the same launch);
 //                          Nw == 384 -> the product transposed, tiles over x's features (no bias gradient: the caller has it from elsewhere)
@@ -186,7 +186,7 @@ int block_fwd(const Ctx& c, const devit_block_weights& w, const devit_block_acts
     ep.res = (const float*)b[DEVIT_ACT_X1];
     ep.rowscale = a.dp2;
     ep.rows_per_scale = c.N;
-    // with a k-major copy of the weight the launch can take the full-row 256x384 kernel (gemm.hip: bit-identical, 126 -> ~95 us in the step)
+    // with a k-major copy of the weight the launch can take the full-row 256x384 kernel (gemmfr.hip: bit-identical, 126 -> ~95 us in the step)
     if (w.fc2_w16t && !t16 && devit_gemm_full_row_selected(c.Mp, D, Hd, DEVIT_EPI_RESIDUAL_F32)) {
       devit_operand A = {b[DEVIT_ACT_H], Hd, 0, 0, 0, 0}, Bo = {w.fc2_w16t, D, 1, 0, 0, 0};
       TRY(devit_gemm_bf16(&A, &Bo, c.Mp, D, Hd, 1, 1, &ep, c.stream));

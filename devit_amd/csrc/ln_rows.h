@@ -1,5 +1,5 @@
 // The per-row arithmetic of the LayerNorm backward, in ONE place: layernorm.hip's standalone kernel and the full-row GEMM's fused epilogue
-// (gemm.hip) both run these bodies in the same lane layout -- half a wave (32 lanes) per token row, lane l holds float4 v of the row at columns
+// (gemmfr.hip) both run these bodies in the same lane layout -- half a wave (32 lanes) per token row, lane l holds float4 v of the row at columns
 // (v * 32 + l) * 4 -- with the same order of additions and the same xor-shuffle tree, so a row comes out bit for bit the same whichever
 // kernel handled it (tests/test_gpu_lnfuse.py; tests/test_gpu_fullsize.py switches the full-row kernel, and with it the fusion, on and off).
 #pragma once

@@ -11,7 +11,7 @@ namespace {
 // master's row / column, or -1 for a padding unit (compacted widths are padded to the GEMM granules with all-zero units).
 __global__ __launch_bounds__(256) void index_copy_kernel(const devit_index_job* jobs) {
   const devit_index_job j = jobs[blockIdx.y];
-  if (j.mode == 4) {   // 16-bit transpose dst[c][r] = src[r][c]: the k-major copy of a Linear weight (full-row GEMM, gemm.hip); 64 x 64 tiles through LDS
+  if (j.mode == 4) {   // 16-bit transpose dst[c][r] = src[r][c]: the k-major copy of a Linear weight (full-row GEMM, gemmfr.hip); 64 x 64 tiles through LDS
     __shared__ unsigned short tile[64][66];
     const int tr = (j.rows + 63) / 64, tc = (j.cols + 63) / 64;
     const unsigned short* src = (const unsigned short*)j.src;

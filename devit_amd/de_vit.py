@@ -40,7 +40,7 @@ def _w16(lin, f16=False):
 
 
 def _w16t(lin, w16):
-    """K-major bf16 copy [in][out] of an nn.Linear's bf16 GEMM copy `w16` ([out][in]) for the full-row 256x384 GEMM (csrc/gemm.hip: N == 384
+    """K-major bf16 copy [in][out] of an nn.Linear's bf16 GEMM copy `w16` ([out][in]) for the full-row 256x384 GEMM (csrc/gemmfr.hip: N == 384
     outputs), re-derived whenever `w16` was re-made; in-place rewrites of `w16` (fused optimizer, FlatParams.refresh_bf16) re-derive it through
     ddp.FlatParams.refresh_kmajor()."""
     c = lin.__dict__.get("_w16t")
@@ -565,7 +565,7 @@ def check_geometry(name, embed_dim, num_heads, mlp_ratio=4.):
     """Refuse, at construction and with the reason, a geometry the gfx950 kernels are not built for -- instead of registering a
     name whose first forward fails deep inside a launch.  Heads are 64 wide everywhere (csrc/attention.hip and the reference's own
     registered names).  The MFMA GEMM tiles, the fused attention kernels and the block calls want every width in multiples of 128
-    (csrc/gemm.hip, encoder.hip): geometries that are multiples of 64 only -- the three D = 192 names of models/deit_vit.py:457-525
+    (csrc/gemm*.hip, encoder.hip): geometries that are multiples of 64 only -- the three D = 192 names of models/deit_vit.py:457-525
     (`deit_tiny_patch16_224`, `deit_tiny_distilled_patch16_224`, `vit_tiny_patch16_224`; none of them is on the DeViT path: student
     `dedeit` is 384 / 6, teachers are DeiT-B 768 / 12 or ViT-L 1024 / 16, README.md:50-68 of the reference) -- run on the exact-fp32
     kernels instead (csrc/sgemm.hip, ops_f32.py: forward, backward, every loss; a few TFLOP/s, which a 1.3-GFLOP model does not notice):

@@ -113,7 +113,7 @@ def compact(model, trainable=False):
         # uncompact() makes it again
         blk.mlp.fc2.__dict__.pop("_w16t", None)
         c = blk._compact
-        if c["fc2_w16"].is_cuda and c["fc2_w16"].shape[0] == 384:      # fc2's forward on the full-row GEMM (csrc/gemm.hip): k-major copy
+        if c["fc2_w16"].is_cuda and c["fc2_w16"].shape[0] == 384:      # fc2's forward on the full-row GEMM (csrc/gemmfr.hip): k-major copy
             c["fc2_w16t"] = torch.empty((c["fc2_w16"].shape[1], 384), dtype=c["fc2_w16"].dtype, device=dev)
             ops.transpose16(c["fc2_w16"], c["fc2_w16t"])
         report.append((len(w["kept_heads"]), w["num_heads"], len(w["kept_neurons"]), w["fc1_w"].shape[0]))

@@ -135,7 +135,8 @@ DEVIT_API int devit_get_reserved_cus(void);
  * exactly 384 columns wide (the student's D; fc2's gradient is taken transposed, a = the GELU output, b = dY); a_cols % 128 == 0.
  * Kernel: 256 x 384 output tiles on the full-row tile of devit_gemm_bf16 (k-major x k-major variant, one tile and one K slice per
  * workgroup, fp32 atomics through LDS in whole 256-byte rows); every workgroup of the table runs at once, so split_k slices x tiles
- * should fill the device: split_k == 0 picks floor(CUs / tiles).  K % 64 == 0, K / 64 / split_k >= 3, njobs <= 48 (the four products of
+ * should fill the device: split_k == 0 picks the slice count by a two-term cost model (K-steps per workgroup x rounds of workgroups + the
+ * atomics of every (tile, slice): csrc/wgradfr.hip).  K % 64 == 0, K / 64 / split_k >= 3, njobs <= 48 (the four products of
  * up to twelve blocks: devit_block_bwd_io.defer_jobs collects them).
  * jobs is a HOST array (copied into the kernel arguments).
  * ---------------------------------------------------------------------------------------- */

@@ -159,6 +159,23 @@ def test_gemmfr_inc_is_current(lib, tmp_path):
     assert out.read_bytes() == open(os.path.join(ROOT, "devit_amd", "csrc", "gemmfr_kloop.inc"), "rb").read()
 
 
+def test_build_generates_with_experiment_switches_stripped(tmp_path):
+    """build.sh's generation step ignores the generators' experiment switches in the caller's environment, every GEMM4_* / GEMMFR_* one (it used
+    to unset four names: GEMM4_NODMA=1 in the shell baked a wrong-result kernel into the library).  The switches are live in the generators
+    themselves -- the comparison would mean nothing otherwise."""
+    clean_env = {k: v for k, v in os.environ.items() if not k.startswith(("GEMM4_", "GEMMFR_"))}
+    dirty_env = dict(clean_env, GEMM4_NODMA="1", GEMMFR_NOREQ="1")
+    (tmp_path / "clean").mkdir()
+    for g in ("gemm4", "gemmfr"):
+        gen = ["python3", os.path.join(ROOT, "tools", f"gen_{g}.py")]
+        subprocess.check_call(gen + [str(tmp_path / "clean" / f"{g}_kloop.inc")], env=clean_env, stdout=subprocess.DEVNULL)
+        subprocess.check_call(gen + [str(tmp_path / f"{g}_switched.inc")], env=dirty_env, stdout=subprocess.DEVNULL)
+        assert (tmp_path / f"{g}_switched.inc").read_bytes() != (tmp_path / "clean" / f"{g}_kloop.inc").read_bytes(), g
+    subprocess.check_call([os.path.join(ROOT, "devit_amd", "csrc", "build.sh"), "-g", str(tmp_path / "built")], env=dirty_env)
+    for g in ("gemm4", "gemmfr"):
+        assert (tmp_path / "built" / f"{g}_kloop.inc").read_bytes() == (tmp_path / "clean" / f"{g}_kloop.inc").read_bytes(), g
+
+
 def test_full_row_rule_is_the_library_s(lib, monkeypatch):
     """ops.full_row_selected() CALLS csrc/gemm.hip's devit_gemm_full_row_selected() (the host decides with it whether to hand the GEMM a
     k-major weight): one rule, one parser of DEVIT_GEMMFR (advisor r05: the Python restatement read "" and non-numeric values differently)."""
@@ -213,3 +230,33 @@ def test_build_gate_sees_agpr_writes():
         assert len(bad) == 1 and "gemm4_kernel" in bad[0], line
     bad, _ = mod.scan_agpr_writes(ok.replace("gemm4_kernelILi0ELb0EEE", "gemmfr_kernelILi2EEE").replace("\tv_accvgpr_read_b32 v5, a17", "\tv_accvgpr_write_b32 a17, v5"))
     assert len(bad) == 1 and "gemmfr_kernel" in bad[0]
+
+
+def test_kernel_digest_covers_every_instruction():
+    """tools/kernel_digest.py (the check that a move of kernel code left the machine code alone) hashes the encoding of EVERY instruction, the
+    branches too, whose lines carry a `<label+off>` annotation behind the hex words: on synthetic `llvm-objdump -d` text a changed branch
+    condition or target changes the digest, a changed annotation or asm-label id does not, and a line whose encoding cannot be read ends the run."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("kernel_digest", os.path.join(ROOT, "tools", "kernel_digest.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    k = "_ZN12_GLOBAL__N_112gemm4_kernelILi0ELb0EEEvNS_8GemmArgsE"
+    text = f"""
+0000000000001000 <{k}>:
+\ts_load_dword s3, s[0:1], 0xa90                             // 000000001000: C00200C0 00000A90
+\ts_cbranch_scc1 8559                                        // 000000001008: BF85216F <L_gemm4_done_0+0x2cfc>
+000000000000100c <L_gemm4_w1_7>:
+\tv_mfma_f32_16x16x32_bf16 a[4:7], v[164:167], v[128:131], a[4:7] // 00000000100C: D3B58004 04030144
+\ts_endpgm                                                   // 000000001014: BF810000
+"""
+    base = mod.encodings(text)
+    assert list(base) == [k] and base[k][1] == 6                                   # words: 2 + 1 + 2 + 1, the label opens no kernel
+    same = mod.encodings(text.replace("L_gemm4_done_0+0x2cfc", "L_gemm4_done_4+0x2d00").replace("L_gemm4_w1_7", "L_gemm4_w1_3"))
+    assert same == base                                                            # annotations and label ids are not code
+    for old, new in (("BF85216F", "BF84216F"),      # scc1 -> scc0
+                     ("BF85216F", "BF852170"),      # another target
+                     ("04030144", "04030145"),      # second word of a two-word instruction
+                     ("BF810000", "BF800000")):
+        assert mod.encodings(text.replace(old, new))[k][0] != base[k][0], (old, new)
+    with pytest.raises(SystemExit):
+        mod.encodings(text.replace("BF85216F <", "BF85216F ; <"))

@@ -309,7 +309,7 @@ def test_distill_step_bf16_vs_f32_full_size(dev):
 
 
 def test_full_row_gemm_inside_the_model_full_size(dev, monkeypatch):
-    """The student's fc2 forward and its qkv / proj / fc1 dgrads run on the full-row 256x384 GEMM (csrc/gemm.hip, default at >= 64 row tiles);
+    """The student's fc2 forward and its qkv / proj / fc1 dgrads run on the full-row 256x384 GEMM (csrc/gemmfr.hip, default at >= 64 row tiles);
     fc2 reads a K-MAJOR copy of its weight that must follow every rewrite of the bf16 copy.  At bs 256: the training forward + backward with the
     kernel switched off (DEVIT_GEMMFR=0) and on -- logits and q / k / v of the middle block bit-identical, the gradient of pos_embed (behind every
     dgrad) to fp32 round-off (the weight gradients go through fp32 atomics: not compared) -- and again after an optimizer step of the fused flat AdamW, which rewrites the bf16 copies

@@ -1,4 +1,4 @@
-"""The student's dgrad + LayerNorm backward as ONE launch of the full-row GEMM (csrc/gemm.hip, epilogue kind LNBWD; devit_dgrad_layernorm_bwd):
+"""The student's dgrad + LayerNorm backward as ONE launch of the full-row GEMM (csrc/gemmfr.hip, epilogue kind LNBWD; devit_dgrad_layernorm_bwd):
 the fused launch against the two launches it replaces, on the same inputs, at the step's shapes.
 
 dx and dx_bf16 must be the SAME BITS: the epilogue stages the tile's rows in LDS and runs ln_bwd_kernel's own row body on them (csrc/ln_rows.h).

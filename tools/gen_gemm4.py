@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generator of devit_amd/csrc/gemm4_kloop.inc: the hand-scheduled K loop of the FOUR-wave 256x256x64 bf16 GEMM
-(csrc/gemm.hip, gemm4_kernel) as one inline-asm string, plus the accumulator read-out helpers.
+(csrc/gemm4.hip, gemm4_kernel) as one inline-asm string, plus the accumulator read-out helpers.
 
 Why generated asm: a wave that has its SIMD to itself issues about one instruction per four cycles, MFMAs included, so the
 64 MFMAs of a phase (1024 cycles of matrix pipe) leave room for ~2 other instructions per MFMA; hipcc's schedule of the
@@ -13,7 +13,7 @@ sub-tile rows 128 wm.., columns 128 wn.. of a 256 x 256 output tile):
     is on the MFMA's row side, as in the eight-wave kernel, so lane (g, c) register r holds C[m = 16 i + c][n = ncol(q, 4 g + r)]
   * fragments: two buffers of (8 A + 8 B) x 4 VGPRs: buf0 v[128:191] (k-half 0), buf1 v[192:255] (k-half 1)
   * LDS ring as the eight-wave kernel: three A slots (32 KB each, at 0) and two B slots (at 96 KB), lane-linear images
-    with the bank swizzle on the DMA source address / the fragment read address (swz_row in gemm.hip)
+    with the bank swizzle on the DMA source address / the fragment read address (swz_row in gemm_device.h)
   * one K-step (stage t) = two phases of 64 MFMAs:
       phase 1: MFMAs on buf0 = (t, kk 0) | ds_read (t, kk 1) -> buf1 | LDS-DMA request A(t + 2)
       middle : s_waitcnt vmcnt(8) (everything but that A request has landed: stage t + 1 is in LDS), lgkmcnt(0), s_barrier

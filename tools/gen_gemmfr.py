@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generator of devit_amd/csrc/gemmfr_kloop.inc: the hand-scheduled K loop of the FULL-ROW 256 x 384 x 64 bf16 GEMM
-(csrc/gemm.hip, gemmfr_kernel; activation operand row-major, weight operand k-major, N = 384 = the student's whole output row)
+(csrc/gemmfr.hip, gemmfr_kernel; activation operand row-major, weight operand k-major, N = 384 = the student's whole output row)
 as one inline-asm string, plus the accumulator read-out helper.
 
 Why this tile (verdict r04 #1): every K loop on this chip runs at the rate a CU's LDS-DMA requests are served (DESIGN.md section
@@ -12,7 +12,7 @@ columns 192 wn.. of the tile: 8 m-tiles x 12 n-tiles of 16 x 16):
   * accumulators: 96 tiles = 384 registers.  n-tiles q < 8 in a[4 (8 i + q) : +4] (the four-wave kernel's plan), n-tiles 8..11 in
     v[128 + 4 (4 i + q - 8) : +4] -- declared to the compiler as four pinned 32-register outputs ([c0]..[c3] = v[128:159], ...),
     so the epilogue reads them as ordinary values.  The weight operand is on the MFMA's row side (lane (g, c), register r holds
-    C[m = 16 i + c][n = ncol(q, 4 g + r)]), as in every kernel of gemm.hip: same epilogue code, same accumulation order per element.
+    C[m = 16 i + c][n = ncol(q, 4 g + r)]), as in every kernel of the GEMM family (gemm_device.h): same epilogue code, same accumulation order per element.
   * fragments: ONE buffer, A tiles v[48 + 4 i : +4] (8), B tiles v[80 + 4 q : +4] (12).  The 96 MFMAs of a phase (one k-half of 32)
     run row by row (i outer, q inner); A[i] is dead after MFMA (i, 11) and B[q] after MFMA (7, q), so the next phase's A[i] is read
     right behind row i and its B tiles (two ds_read_b64_tr_b16 each) behind the MFMAs of the last row.  LDS returns in order, so every
@@ -52,7 +52,7 @@ Operands of the asm statement (named; declared in gemmfr_kernel):
   [dmaa0..3] v per-lane source byte offsets of A slabs 0..3 (4..7 = + lda64)
   [dmab0..11] v of this wave's twelve B slabs, relative to its first k row (16 k rows per wave)
 
-The WEIGHT-GRADIENT variant (round 6: DEVIT_WGRADFR_KLOOP_ASM, wgradfr_kernel in gemm.hip; KMA = True below): the A operand is K-MAJOR as
+The WEIGHT-GRADIENT variant (round 6: DEVIT_WGRADFR_KLOOP_ASM, wgradfr_kernel in wgradfr.hip; KMA = True below): the A operand is K-MAJOR as
 well (dW = dY^T X: both operands are [K token rows][features]), one tile and one K slice per workgroup (no next tile), column sums of A
 on the side.  What changes against the PAIRED variant above, and nothing else does (same ring protocol, phases, waits, request gaps):
   * A slot image [64 k][256 cols] (512-byte rows, swz_krow); the wave requests its 16 k rows as eight 1-KiB slabs of two k rows
@@ -115,13 +115,13 @@ def a_reads_per_tile():
     return 2 if KMA else 1
 
 
-PAIRED = True      # column order of the n-tiles: tile_row<PAIRED>() in gemm.hip (bf16 store: PAIRED, fp32 residual: natural)
+PAIRED = True      # column order of the n-tiles: tile_row<PAIRED>() in gemm_device.h (bf16 store: PAIRED, fp32 residual: natural)
 KMA = False        # the weight-gradient variant: A k-major too, column sums of A, no next tile (see the docstring)
 TB = 2             # first [t] register of the B read addresses (KMA: 4 -- A takes t0..t3)
 
 
 def b_reads(q, half, wave):
-    """the two transposed reads of n-tile q, k rows 32 half .. + 31 of the slot (addresses: read_frag<true, W = 384, PAIRED> in gemm.hip).
+    """the two transposed reads of n-tile q, k rows 32 half .. + 31 of the slot (addresses: read_frag<true, W = 384, PAIRED> in gemm_device.h).
     Lane (G, q4, p) reads k row 8 G + q4 (+ 32 half, + 4 for the second read); with x = 6 wn + q / 2 the 64-byte chunk group of the
     n-tile pair in the 768-byte k row, its address inside the slot is
       PAIRED : 768 krow + 64 (x ^ q4) + 16 (p ^ 2 (G & 1)) + 8 (q & 1)                        -> base register by x & 3

@@ -1,7 +1,7 @@
 // Diagnostic (round 5): how fast does a GEMM-like operand stream come out of HBM as a function of the contiguous bytes per row a request
 // touches?  Every CU (one 256-thread workgroup) streams its own 256-row panel of a [M][K] bf16 matrix far larger than the Infinity Cache
 // by LDS-DMA (1 KiB per wave-instruction), a fixed number of requests in flight per wave, in the order a tiled GEMM would: PIECE bytes of each
-// of 1024 / PIECE rows per request, K-steps of PIECE bytes.  PIECE = 128 is what every BK = 64 kernel of gemm.hip does.
+// of 1024 / PIECE rows per request, K-steps of PIECE bytes.  PIECE = 128 is what every BK = 64 kernel of the GEMM family (gemm_device.h) does.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 // (the 16-requests-in-flight rows of the first version, profiles/r05_a_gemm_full_row.txt, measured the same as 8)
