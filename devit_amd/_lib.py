@@ -66,10 +66,23 @@ class WgradJob(C.Structure):
                 ("ldc", C.c_int), ("transposed", C.c_int), ("a_colsum", C.c_void_p)]
 
 
+# devit_launch_info.has
+HAS_Y_BF16, HAS_Y_F32, HAS_DY_F32, HAS_DRES, HAS_DX, HAS_DX_BF16, HAS_DQKV_ADD = 1, 2, 4, 8, 16, 32, 64
+
+
+class LaunchInfo(C.Structure):
+    _fields_ = [("name", C.c_char_p)] + [(n, C.c_int) for n in ("a_kmajor", "b_kmajor", "kind", "M", "N", "K", "batch", "split_k", "rows",
+                                                                "width", "q_rows", "has", "njobs", "a_cols")] + \
+               [("flops", C.c_double), ("bytes", C.c_double)]
+
+
+# devit_launch_observer: fn(user, phase, stream, info)
+LAUNCH_OBSERVER = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(LaunchInfo))
+
 WGRAD_MAX_JOBS = 48
-ABI_VERSION = 2
+ABI_VERSION = 3
 # devit_abi_struct_size(which) -> the mirror it must equal (checked at load time: an array of stale mirrors is misread silently)
-ABI_STRUCTS = {0: Epilogue, 1: Operand, 2: BlockWeights, 3: BlockWgrads, 4: BlockActs, 5: BlockBwdIO, 6: IndexJob, 7: WgradJob}
+ABI_STRUCTS = {0: Epilogue, 1: Operand, 2: BlockWeights, 3: BlockWgrads, 4: BlockActs, 5: BlockBwdIO, 6: IndexJob, 7: WgradJob, 8: LaunchInfo}
 
 
 class DevitError(RuntimeError):
@@ -84,6 +97,7 @@ SIGNATURES = {
     "devit_last_error": (C.c_char_p, []),
     "devit_check_device": (_I, [_I]),
     "devit_abi_struct_size": (_Z, [_I]),
+    "devit_set_launch_observer": (_I, [LAUNCH_OBSERVER, _P]),
     "devit_gemm_full_row_selected": (_I, [_I, _I, _I, _I]),
     "devit_wgrad_grouped": (_I, [C.POINTER(WgradJob), _I, _I, _I, _P]),
     "devit_gemm_bf16": (_I, [C.POINTER(Operand), C.POINTER(Operand), _I, _I, _I, _I, _I, C.POINTER(Epilogue), _P]),

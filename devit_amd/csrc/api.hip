@@ -1,4 +1,4 @@
-// Error plumbing, version and device check for libdevit_hip.so.
+// Error plumbing, launch observer, version and device check for libdevit_hip.so.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -14,6 +14,13 @@ void devit_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+thread_local DevitObserver devit_observer = {nullptr, nullptr};
+
+extern "C" int devit_set_launch_observer(devit_launch_observer fn, void* user) {
+  devit_observer = DevitObserver{fn, fn ? user : nullptr};
+  return DEVIT_OK;
+}
+
 extern "C" int devit_version(void) { return DEVIT_ABI_VERSION; }
 extern "C" const char* devit_last_error(void) { return g_err; }
 
@@ -27,6 +34,7 @@ extern "C" size_t devit_abi_struct_size(int which) {
     case 5: return sizeof(devit_block_bwd_io);
     case 6: return sizeof(devit_index_job);
     case 7: return sizeof(devit_wgrad_job);
+    case 8: return sizeof(devit_launch_info);
     default: return 0;
   }
 }

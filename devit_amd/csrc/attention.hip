@@ -651,6 +651,14 @@ int launch_attn_bwd(const AttnBwdArgs& a, void* stream) {
 
 bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
+// what the launch observer is told about an attention call: B * N token rows, B * NQ query rows (0: the packed-qkv entry points), H * 64 features
+devit_launch_info attn_info(const char* name, int B, int N, int NQ, int H, bool dqkv_add = false) {
+  devit_launch_info i = {name};
+  i.rows = B * N; i.q_rows = B * NQ; i.width = H * HD;
+  i.has = dqkv_add ? DEVIT_HAS_DQKV_ADD : 0;
+  return i;
+}
+
 }  // namespace
 
 extern "C" int devit_attn_fwd(const void* qkv, void* out, float* lse, const float* head_gate, int B, int N, int H,
@@ -661,7 +669,7 @@ extern "C" int devit_attn_fwd(const void* qkv, void* out, float* lse, const floa
   const int D = H * HD;
   const __bf16* p = (const __bf16*)qkv;
   AttnFwdArgs a{p, p + D, p + 2 * D, (__bf16*)out, lse, head_gate, B, N, N, H, 3 * D, 3 * D, scale};
-  return launch_attn_fwd(a, dtype16, stream);
+  return devit_observed(stream, [&] { return attn_info("devit_attn_fwd", B, N, 0, H); }, [&] { return launch_attn_fwd(a, dtype16, stream); });
 }
 
 extern "C" int devit_attn_fwd_rows(const void* q, int q_ld, const void* kv, int kv_ld, void* out, float* lse,
@@ -675,7 +683,7 @@ extern "C" int devit_attn_fwd_rows(const void* q, int q_ld, const void* kv, int 
               DEVIT_ERR_ARG, "devit_attn_fwd_rows: q_ld=%d kv_ld=%d / pointers must be 16-byte aligned and hold H*64 (2*H*64) features", q_ld, kv_ld);
   const __bf16* p = (const __bf16*)kv;
   AttnFwdArgs a{(const __bf16*)q, p, p + D, (__bf16*)out, lse, head_gate, B, N, NQ, H, q_ld, kv_ld, scale};
-  return launch_attn_fwd(a, dtype16, stream);
+  return devit_observed(stream, [&] { return attn_info("devit_attn_fwd_rows", B, N, NQ, H); }, [&] { return launch_attn_fwd(a, dtype16, stream); });
 }
 
 extern "C" int devit_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
@@ -691,7 +699,7 @@ extern "C" int devit_attn_bwd(const void* qkv, const void* out, const void* dout
   AttnBwdArgs a{p, p + D, p + 2 * D, (const __bf16*)out, (const __bf16*)dout, lse, head_gate,
                 ad, ad ? ad + D : nullptr, ad ? ad + 2 * D : nullptr, d, d + D, d + 2 * D,
                 B, N, N, H, 3 * D, 3 * D, 3 * D, 3 * D, scale};
-  return launch_attn_bwd(a, stream);
+  return devit_observed(stream, [&] { return attn_info("devit_attn_bwd", B, N, 0, H, dqkv_add != nullptr); }, [&] { return launch_attn_bwd(a, stream); });
 }
 
 extern "C" int devit_attn_bwd_rows(const void* q, int q_ld, const void* kv, int kv_ld, const void* out, const void* dout,
@@ -708,5 +716,5 @@ extern "C" int devit_attn_bwd_rows(const void* q, int q_ld, const void* kv, int 
   __bf16* d = (__bf16*)dkv;
   AttnBwdArgs a{(const __bf16*)q, p, p + D, (const __bf16*)out, (const __bf16*)dout, lse, head_gate,
                 nullptr, nullptr, nullptr, (__bf16*)dq, d, d + D, B, N, NQ, H, q_ld, kv_ld, dq_ld, dkv_ld, scale};
-  return launch_attn_bwd(a, stream);
+  return devit_observed(stream, [&] { return attn_info("devit_attn_bwd_rows", B, N, NQ, H); }, [&] { return launch_attn_bwd(a, stream); });
 }

@@ -34,6 +34,25 @@ void devit_set_error(const char* fmt, ...);
     }                                                                   \
   } while (0)
 
+// ---- launch observer (host; api.hip: devit_set_launch_observer) -------------------------------
+struct DevitObserver {
+  devit_launch_observer fn;
+  void* user;
+};
+extern thread_local DevitObserver devit_observer;
+// An observed entry point ends, behind its argument checks, in devit_observed(stream, info, launch): `launch` enqueues its kernels, `info`
+// makes the devit_launch_info (built only when this thread has an observer: one thread-local load and one branch otherwise).
+template <class Info, class Launch>
+inline int devit_observed(void* stream, Info&& info, Launch&& launch) {
+  const devit_launch_observer fn = devit_observer.fn;
+  if (!fn) return launch();
+  void* const user = devit_observer.user;
+  const devit_launch_info i = info();
+  fn(user, 0, stream, &i);
+  const int rc = launch();
+  fn(user, 1, stream, &i);
+  return rc;
+}
 
 // ---- internal entry points shared between translation units (not exported) -----------------
 // layernorm.hip: the column-sum pass behind a LayerNorm backward, partial[nparts][3][D] -> dgamma, dbeta, colsum(dx_bf16)

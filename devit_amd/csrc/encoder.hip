@@ -1,8 +1,9 @@
 // Whole encoder blocks per host call (devit_encoder_fwd / devit_block_bwd): the block's kernels are enqueued here, in C++,
-// through the same single-kernel entry points the granular path uses -- identical kernels, arguments and order, so the
-// two paths agree bit for bit (tests/test_gpu_model.py::test_block_calls_match_granular_path; the weight gradients are
-// split-K atomics either way).  devit_block_bwd puts its four weight-gradient launches on a side stream of its own and joins
-// it before it returns (round 4, see there).  Host code only.
+// through the single-kernel entry points of the C ABI.  This is the ONE host sequence of the 16-bit block: the Python side
+// (devit_amd/ops.py) holds no restatement of it, and what instruments need to see of it -- which GEMM, LayerNorm, attention and
+// weight-gradient launches, on which stream -- those entry points report to the launch observer (devit_set_launch_observer).
+// devit_block_bwd puts its four weight-gradient launches on a side stream of its own and joins it before it returns (round 4,
+// see there).  Host code only.
 #include <mutex>
 
 #include "devit_common.h"

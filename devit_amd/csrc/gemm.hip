@@ -41,8 +41,14 @@ int devit_gemm::gemm_force() {    // DEVIT_GEMM_FORCE (tools/gpu_tiles.sh): 1 = 
 }
 
 namespace {
+// the LayerNorm backward fused into a launch (devit_dgrad_layernorm_bwd): the kernel's arguments and those of the column-sum pass behind it
+struct FusedLnBwd {
+  LnBwdArgs ln;
+  float *dgamma, *dbeta, *dx_bf16_colsum;
+  int accumulate;
+};
 int gemm_launch(const devit_operand* Aop, const devit_operand* Bop, int M, int N, int K, int batch, int split_k, const devit_epilogue* ep,
-                const LnBwdArgs* ln, void* stream);
+                const FusedLnBwd* ln, void* stream);
 }  // namespace
 
 // The full-row 256x384 kernel (gemmfr_kernel, gemmfr.hip): N == 384 exactly (one n-tile: its B stream is cyclic over the tiles), whole 256-row tiles and
@@ -75,7 +81,7 @@ namespace {
 // devit_gemm_bf16; with `ln`, the launch whose bf16 output feeds the LayerNorm backward `ln` in the same kernel (devit_dgrad_layernorm_bwd: the
 // caller has checked devit_dgrad_layernorm_bwd_fused, anything else is an error here, never a silent other path)
 int gemm_launch(const devit_operand* Aop, const devit_operand* Bop, int M, int N, int K, int batch, int split_k, const devit_epilogue* ep,
-                const LnBwdArgs* ln, void* stream) {
+                const FusedLnBwd* ln, void* stream) {
   DEVIT_CHECK(Aop && Bop && Aop->ptr && Bop->ptr && ep && ep->out, DEVIT_ERR_ARG, "devit_gemm_bf16: null pointer");
   const void* A = Aop->ptr;
   const void* B = Bop->ptr;
@@ -214,9 +220,22 @@ int gemm_launch(const devit_operand* Aop, const devit_operand* Bop, int M, int N
                         ep->kind != DEVIT_EPI_DGELU_BF16 && ep->kind != DEVIT_EPI_ATOMIC_F32;
   const bool gemm4_pays = (ep->kind == DEVIT_EPI_STORE_BF16 || ep->kind == DEVIT_EPI_RESIDUAL_F32) && K >= 768 && batch == 1;
   const bool use4 = gemm4_ok && (gemm4_env ? atoi(gemm4_env) != 0 : gemm4_pays);
-  if (cfg == 4) return launch_gemmfr(g, ln, (unsigned)nwg, s);
-  if (use4) return launch_gemm4(g, (unsigned)nwg, s);
-  return cfg == 3 ? launch_gemm_tile256(g, variant, (unsigned)nwg, s) : launch_gemm_tile128(g, variant, (unsigned)nwg, s);
+  auto info = [&] {
+    devit_launch_info i = {ln ? "devit_dgrad_layernorm_bwd" : "devit_gemm_bf16"};
+    i.a_kmajor = a_kmajor != 0; i.b_kmajor = b_kmajor != 0; i.kind = ep->kind;
+    i.M = M; i.N = N; i.K = K; i.batch = batch; i.split_k = split_k;
+    return i;
+  };
+  return devit_observed(stream, info, [&]() -> int {
+    if (cfg == 4) {
+      const int rc = launch_gemmfr(g, ln ? &ln->ln : nullptr, (unsigned)nwg, s);
+      if (rc != DEVIT_OK || !ln) return rc;
+      // (one partial per tile: <= CUs <= the rows / 8 (or 1024) parts the workspace is sized for)
+      return devit_layernorm_bwd_finish(ln->ln.partial, g.tiles_m, N, ln->dgamma, ln->dbeta, ln->dx_bf16_colsum, ln->accumulate, stream);
+    }
+    if (use4) return launch_gemm4(g, (unsigned)nwg, s);
+    return cfg == 3 ? launch_gemm_tile256(g, variant, (unsigned)nwg, s) : launch_gemm_tile128(g, variant, (unsigned)nwg, s);
+  });
 }
 }  // namespace
 
@@ -256,9 +275,7 @@ extern "C" int devit_dgrad_layernorm_bwd(const void* dy, const void* w, int M_pa
   DEVIT_CHECK(!dx_bf16_colsum || dx_bf16, DEVIT_ERR_ARG, "devit_dgrad_layernorm_bwd: dx_bf16_colsum needs dx_bf16");
   DEVIT_CHECK(aligned16(x) && aligned16(dx) && (!dres || aligned16(dres)) && (!dx_bf16 || aligned16(dx_bf16)), DEVIT_ERR_ARG,
               "devit_dgrad_layernorm_bwd: x / dres / dx / dx_bf16 must be 16-byte aligned");
-  const int tiles = M_pad / 256;      // one partial per tile: <= CUs <= the rows / 8 (or 1024) parts the workspace is sized for
-  LnBwdArgs ln{nullptr, x, mean, rstd, gamma, dres, dx, (__bf16*)dx_bf16, rowscale, rows_per_scale, (float*)workspace, rows, D, 0, 0, 0};
-  int rc = gemm_launch(&A, &Bo, M_pad, D, K, 1, 1, &ep, &ln, stream);
-  if (rc != DEVIT_OK) return rc;
-  return devit_layernorm_bwd_finish((const float*)workspace, tiles, D, dgamma, dbeta, dx_bf16_colsum, accumulate, stream);
+  const FusedLnBwd ln{{nullptr, x, mean, rstd, gamma, dres, dx, (__bf16*)dx_bf16, rowscale, rows_per_scale, (float*)workspace, rows, D, 0, 0, 0},
+                      dgamma, dbeta, dx_bf16_colsum, accumulate};
+  return gemm_launch(&A, &Bo, M_pad, D, K, 1, 1, &ep, &ln, stream);
 }

@@ -187,12 +187,20 @@ extern "C" int devit_layernorm_fwd(const float* x, int rows, int D, int in_group
               "devit_layernorm_fwd: D=%d must be a multiple of 64 (of 128 above 384), <= 1024", D);
   LnFwdArgs a{x, gamma, beta, (__bf16*)y_bf16, y_f32, mean, rstd, rows, D, in_group, in_stride, eps, dtype16};
   const int grid = rows < 8 * 2048 ? (rows + 7) / 8 : 2048;   // 8 half-waves (rows in flight) per 256-thread block
-  int rc = dispatch_nv<LnFwdArgs>(D, [&](auto nv, auto rag) {
-    hipLaunchKernelGGL((ln_fwd_kernel<decltype(nv)::value, decltype(rag)::value>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  auto info = [&] {
+    devit_launch_info i = {"devit_layernorm_fwd"};
+    i.rows = rows; i.width = D;
+    i.has = (y_bf16 ? DEVIT_HAS_Y_BF16 : 0) | (y_f32 ? DEVIT_HAS_Y_F32 : 0);
+    return i;
+  };
+  return devit_observed(stream, info, [&]() -> int {
+    int rc = dispatch_nv<LnFwdArgs>(D, [&](auto nv, auto rag) {
+      hipLaunchKernelGGL((ln_fwd_kernel<decltype(nv)::value, decltype(rag)::value>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    });
+    DEVIT_CHECK(rc == 0, DEVIT_ERR_SHAPE, "devit_layernorm_fwd: unsupported D=%d", D);
+    DEVIT_LAUNCH_CHECK();
+    return DEVIT_OK;
   });
-  DEVIT_CHECK(rc == 0, DEVIT_ERR_SHAPE, "devit_layernorm_fwd: unsupported D=%d", D);
-  DEVIT_LAUNCH_CHECK();
-  return DEVIT_OK;
 }
 
 static int ln_bwd_grid(int rows) { return rows < 8 * 1024 ? (rows + 7) / 8 : 1024; }
@@ -216,12 +224,20 @@ extern "C" int devit_layernorm_bwd(const void* dy, int dy_is_f32, const float* x
   const int grid = ln_bwd_grid(rows);
   LnBwdArgs a{dy, x, mean, rstd, gamma, dres, dx, (__bf16*)dx_bf16, rowscale, rows_per_scale,
               (float*)workspace, rows, D, in_group, in_stride, dy_is_f32};
-  int rc = dispatch_nv<LnBwdArgs>(D, [&](auto nv, auto rag) {
-    hipLaunchKernelGGL((ln_bwd_kernel<decltype(nv)::value, decltype(rag)::value>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  auto info = [&] {
+    devit_launch_info i = {"devit_layernorm_bwd"};
+    i.rows = rows; i.width = D;
+    i.has = (dy_is_f32 ? DEVIT_HAS_DY_F32 : 0) | (dres ? DEVIT_HAS_DRES : 0) | DEVIT_HAS_DX | (dx_bf16 ? DEVIT_HAS_DX_BF16 : 0);
+    return i;
+  };
+  return devit_observed(stream, info, [&]() -> int {
+    int rc = dispatch_nv<LnBwdArgs>(D, [&](auto nv, auto rag) {
+      hipLaunchKernelGGL((ln_bwd_kernel<decltype(nv)::value, decltype(rag)::value>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+    });
+    DEVIT_CHECK(rc == 0, DEVIT_ERR_SHAPE, "devit_layernorm_bwd: unsupported D=%d", D);
+    DEVIT_LAUNCH_CHECK();
+    return devit_layernorm_bwd_finish((const float*)workspace, grid, D, dgamma, dbeta, dx_bf16_colsum, accumulate, stream);
   });
-  DEVIT_CHECK(rc == 0, DEVIT_ERR_SHAPE, "devit_layernorm_bwd: unsupported D=%d", D);
-  DEVIT_LAUNCH_CHECK();
-  return devit_layernorm_bwd_finish((const float*)workspace, grid, D, dgamma, dbeta, dx_bf16_colsum, accumulate, stream);
 }
 
 // partial[nparts][3][D] -> dgamma / dbeta / the optional column sums of dx_bf16 (internal: also behind the full-row GEMM's fused epilogue)

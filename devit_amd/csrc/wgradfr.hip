@@ -284,5 +284,15 @@ extern "C" int devit_wgrad_grouped(const devit_wgrad_job* jobs, int njobs, int K
   g.dbg = nullptr;
 #endif
   constexpr int lds = (256 + 384) * 128 * 2;
-  return launch_kernel<wgradfr_kernel, lds>((unsigned)((g.total + 7) / 8 * 8), 256, (hipStream_t)stream, g);
+  auto info = [&] {
+    devit_launch_info i = {"devit_wgrad_grouped"};
+    i.a_kmajor = i.b_kmajor = 1; i.kind = DEVIT_EPI_ATOMIC_F32; i.K = K; i.split_k = split_k; i.njobs = njobs;
+    for (int j = 0; j < njobs; ++j) i.a_cols += jobs[j].a_cols;
+    i.flops = 2.0 * K * i.a_cols * 384;
+    i.bytes = (double)K * (i.a_cols + 384 * njobs) * 2 + (double)i.a_cols * 384 * 4;
+    return i;
+  };
+  return devit_observed(stream, info, [&] {
+    return launch_kernel<wgradfr_kernel, lds>((unsigned)((g.total + 7) / 8 * 8), 256, (hipStream_t)stream, g);
+  });
 }

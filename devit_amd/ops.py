@@ -12,21 +12,132 @@ Layout conventions
     padded to a multiple of 128 with ZERO pad rows (`rows_alloc`): the GEMM tiles are 128 rows tall and
     the weight-gradient GEMMs reduce over the padded row count.
   * residual stream: fp32 [B, N, D]; branch activations / branch gradients: bf16.
+  * the encoder blocks' launch sequence lives in C (csrc/encoder.hip: devit_encoder_fwd / devit_block_bwd) and nowhere else; EncoderFn is
+    that call, the lean tail of the last block and the grouping of the weight gradients.  bench.py's instruments see the launches
+    through the library's launch observer (`observing`), so the instrumented step is the step that runs.
   * weight gradients are ACCUMULATED straight into `param.grad` (fp32, allocated zero on first use), the
     way DDP "main_grad" fusions do; `backward` returns None for parameters and reports finished blocks
     through `grad_ready` callbacks (devit_amd/ddp.py hooks its bucket all-reduce there).
 """
+import contextlib
 import ctypes as C
-import math
-
 import os
+
 import torch
 
 from . import _lib as L
-from ._lib import call, ptr, stream_ptr
+from ._lib import ptr, stream_ptr
 
 BF16, F16, F32 = torch.bfloat16, torch.float16, torch.float32
 ROW_TILE = 256
+
+
+# ----------------------------------------------------------------------------------------------
+# instruments: the library reports its launches (devit_set_launch_observer, include/devit_hip.h) to whoever observes this thread
+# ----------------------------------------------------------------------------------------------
+# bench.py's three instruments: each is None or a list, set by plain assignment and read back after the step.  While one is a list, every
+# launch the library reports from a call made here is bracketed by events on the stream the kernels really go to:
+PROFILE = None          # GEMM launches: (template, M, N, K, batch, start_event, end_event)
+PROFILE_HBM = None      # the bandwidth-bound kernels (LayerNorm, attention): (name, algorithmic bytes, start_event, end_event)
+PROFILE_WGRAD = None    # grouped weight-gradient launches: (algorithmic flops, algorithmic bytes, start_event, end_event)
+
+
+def gemm_template(a_kmajor, b_kmajor, kind, fused_ln_bwd=False):
+    """PROFILE's label of a GEMM launch.  The student's fc2 forward reads a k-major COPY of its weight on the full-row kernel (k-major B with the
+    fp32 residual epilogue): still a forward Linear layer of the dominant template."""
+    b_row = not b_kmajor or kind == L.EPI_RESIDUAL_F32
+    return ("A_km" if a_kmajor else "A_row") + "/" + ("B_row" if b_row else "B_km") + ("+ln_bwd" if fused_ln_bwd else "")
+
+
+def hbm_record(i):
+    """(name, algorithmic bytes) of a reported LayerNorm / attention launch, None for anything else.  i: L.LaunchInfo."""
+    def has(bit):
+        return 1 if i.has & bit else 0
+    name = i.name.decode()
+    if name == "devit_layernorm_fwd":       # the fp32 rows in, the normalised rows out (bf16 and / or fp32)
+        return "layernorm_fwd", i.rows * i.width * (4 + 2 * has(L.HAS_Y_BF16) + 4 * has(L.HAS_Y_F32))
+    if name == "devit_layernorm_bwd":       # dy, x and the incoming residual gradient in; the fp32 gradient (and its bf16 copy) out
+        return "layernorm_bwd", i.rows * i.width * ((4 if has(L.HAS_DY_F32) else 2) + 4 + 4 * has(L.HAS_DRES) + 4 * has(L.HAS_DX) +
+                                                    2 * has(L.HAS_DX_BF16))
+    if name == "devit_attn_fwd":            # q, k, v in, the head outputs out (bf16)
+        return "attention_fwd", i.rows * i.width * 2 * 4
+    if name == "devit_attn_bwd":            # q, k, v, o, do in; dq, dk, dv out (+ the relation-loss gradient that is added in)
+        return "attention_bwd", i.rows * i.width * 2 * (8 + 3 * has(L.HAS_DQKV_ADD))
+    if name == "devit_attn_fwd_rows":
+        return "attention_fwd_rows", (i.rows * 2 * i.width + 2 * i.q_rows * i.width) * 2
+    if name == "devit_attn_bwd_rows":
+        return "attention_bwd_rows", (i.rows * 4 * i.width + 4 * i.q_rows * i.width) * 2
+    return None
+
+
+_observer = None        # the callback of the innermost observing() block
+_observer_error = None
+
+
+@L.LAUNCH_OBSERVER
+def _on_launch(user, phase, stream, info):
+    global _observer_error
+    try:
+        _observer(phase, stream, info.contents)
+    except BaseException as e:       # (ctypes would print and swallow it: observing() re-raises it once the library call has returned)
+        if _observer_error is None:
+            _observer_error = e
+
+
+@contextlib.contextmanager
+def observing(callback):
+    """Inside the block, callback(phase, stream, info) runs for every launch the library reports from THIS thread: phase 0 just before the entry
+    point's first kernel, 1 just after its last; stream: the hipStream_t (int or None) the kernels go to; info: L.LaunchInfo, valid during the
+    callback only.  An exception raised by the callback leaves the block once the library call it interrupted has returned."""
+    global _observer, _observer_error
+    prev, _observer = _observer, callback
+    L.call("devit_set_launch_observer", _on_launch, None)
+    try:
+        yield
+    finally:
+        _observer = prev
+        if prev is None:
+            L.call("devit_set_launch_observer", L.LAUNCH_OBSERVER(0), None)
+        err, _observer_error = _observer_error, None
+    if err is not None:
+        raise err
+
+
+def torch_stream(stream):
+    """The hipStream_t a launch was reported on, as the torch stream to record events on.  torch's own object where it is the current stream: an
+    ExternalStream made from the default stream's handle (0) does not bracket the kernels -- measured: 6-15 us around every launch, some negative."""
+    cur = torch.cuda.current_stream()
+    return cur if cur.cuda_stream == (stream or 0) else torch.cuda.ExternalStream(stream)
+
+
+_start = None           # the start event of the launch being reported (reports do not nest)
+
+
+def _record(phase, stream, i):
+    """The observer behind PROFILE / PROFILE_HBM / PROFILE_WGRAD: events on the stream the launch goes to, not on the current one."""
+    global _start
+    name = i.name.decode()
+    rec = PROFILE_WGRAD if name == "devit_wgrad_grouped" else PROFILE if name in ("devit_gemm_bf16", "devit_dgrad_layernorm_bwd") else PROFILE_HBM
+    if rec is None:
+        return
+    ev = torch.cuda.Event(enable_timing=True)
+    ev.record(torch_stream(stream))
+    if phase == 0:
+        _start = ev
+    elif name == "devit_wgrad_grouped":
+        rec.append((i.flops, i.bytes, _start, ev))
+    elif rec is PROFILE:
+        rec.append((gemm_template(i.a_kmajor, i.b_kmajor, i.kind, name == "devit_dgrad_layernorm_bwd"), i.M, i.N, i.K, i.batch, _start, ev))
+    else:
+        rec.append(hbm_record(i) + (_start, ev))
+
+
+def call(name, *args):
+    """_lib.call; while an instrument is set, with its observer around the call."""
+    if (PROFILE is None and PROFILE_HBM is None and PROFILE_WGRAD is None) or _observer is not None:
+        return L.call(name, *args)
+    with observing(_record):
+        return L.call(name, *args)
 
 
 def pad_rows(m):
@@ -60,8 +171,6 @@ def workspace(device, nbytes):
 def gemm(a, lda, a_km, b, ldb, b_km, M, N, K, *, kind, out, ldc, bias=None, colscale=None, aux=None, aux_in=None,
          res=None, rowscale=None, rows_per_scale=0, pos=None, patch_tokens=0, extra_tokens=0, exact_gelu=0, batch=1,
          a_bs=0, b_bs=0, out_bs=0, m_valid=0, split_k=1, a_group=0, a_skip=0, b_group=0, b_skip=0, dtype16=0):
-    if PROFILE is not None:
-        return _profiled_gemm(locals())
     A = L.Operand(a.data_ptr(), lda, a_km, a_group, a_skip, a_bs)
     Bo = L.Operand(b.data_ptr(), ldb, b_km, b_group, b_skip, b_bs)
     ep = L.Epilogue(kind, out.data_ptr(), ldc, _p(bias), _p(colscale), _p(aux), _p(aux_in), _p(res), _p(rowscale),
@@ -100,43 +209,6 @@ class _Transposes:
 
     def run(self):
         call("devit_index_copy", ptr(self.table), self.n, self.blocks, stream_ptr())
-
-
-# bench.py instrumentation: when PROFILE is a list, every GEMM launch is bracketed by events on the current stream
-# (the stream the kernel is launched on) and recorded as (template, M, N, K, batch, start_event, end_event).
-PROFILE = None
-
-
-def _profiled_gemm(kw):
-    global PROFILE
-    rec, PROFILE = PROFILE, None
-    try:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        gemm(**kw)
-        e1.record()
-        # (the student's fc2 forward reads a k-major COPY of its weight on the full-row kernel: still a forward Linear layer of the dominant template)
-        fwd_kmajor_copy = kw["b_km"] and kw["kind"] == L.EPI_RESIDUAL_F32
-        rec.append((("A_km" if kw["a_km"] else "A_row") + "/" + ("B_km" if kw["b_km"] and not fwd_kmajor_copy else "B_row"), kw["M"], kw["N"],
-                    kw["K"], kw["batch"], e0, e1))
-    finally:
-        PROFILE = rec
-
-
-# Second instrument of bench.py: the bandwidth-bound kernels.  When PROFILE_HBM is a list, each LayerNorm / attention launch
-# is bracketed by events on its stream and recorded as (name, algorithmic bytes, start_event, end_event).
-PROFILE_HBM = None
-
-
-def _bracketed(name, nbytes, fn):
-    rec = PROFILE_HBM
-    if rec is None:
-        return fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    rec.append((name, nbytes, e0, e1))
 
 
 def split_k_for(out_rows, out_cols, ksteps):
@@ -183,27 +255,19 @@ def linear_wgrads(jobs, M, split_k=0):
     w_grad += dy^T x; b_grad += colsum(dy).  K == 384: tiles over dy's features; N == 384 (fc2): the product is taken transposed (tiles over x's
     features) and its bias gradient, if asked for, comes from a column-sum pass."""
     mp = pad_rows(M)
-    arr = (L.WgradJob * len(jobs))()
-    late = []
-    for i, (dy, x, w_grad, b_grad) in enumerate(jobs):
-        N, K = w_grad.shape
-        j = arr[i]
-        if K == 384:
-            j.a, j.lda, j.a_cols, j.b, j.ldb = dy.data_ptr(), dy.stride(0), N, x.data_ptr(), x.stride(0)
-            j.out, j.ldc, j.transposed, j.a_colsum = w_grad.data_ptr(), K, 0, _p(b_grad)
-        else:
-            j.a, j.lda, j.a_cols, j.b, j.ldb = x.data_ptr(), x.stride(0), K, dy.data_ptr(), dy.stride(0)
-            j.out, j.ldc, j.transposed, j.a_colsum = w_grad.data_ptr(), K, 1, None
-            if b_grad is not None:
-                late.append((dy, N, b_grad))
+    structs, late = [], []
+    for dy, x, w_grad, b_grad in jobs:
+        if w_grad.shape[1] != 384 and b_grad is not None:     # (the transposed product has no bias-gradient side: a column-sum pass behind the launch)
+            late.append((dy, b_grad))
+            b_grad = None
+        j = wgrad_job_struct(dy, x, w_grad, b_grad)
+        if j is None:
+            raise L.DevitError(f"linear_wgrads: a {tuple(w_grad.shape)} weight gradient does not fit the full-row kernel (wgrad_jobs_ok)")
+        structs.append(j)
+    arr = (L.WgradJob * len(jobs))(*structs)
     call("devit_wgrad_grouped", arr, len(jobs), mp, split_k, stream_ptr())
-    for dy, N, b_grad in late:
-        colsum(dy, mp, N, b_grad, True)
-
-
-# bench.py's third instrument: when PROFILE_WGRAD is a list, each grouped weight-gradient launch (DeferredWgrads.flush) is bracketed by events on
-# its stream and recorded as (algorithmic flops, algorithmic bytes, start_event, end_event)
-PROFILE_WGRAD = None
+    for dy, b_grad in late:
+        colsum(dy, mp, b_grad.shape[0], b_grad, True)
 
 
 def wgrad_enabled(mp):
@@ -221,24 +285,16 @@ def colsum(y, M, N, out, accumulate, row_group=0, row_skip=0):
 
 def layernorm_fwd(x2d, rows, D, gamma, beta, eps, *, y_bf16=None, y_f32=None, mean=None, rstd=None, in_group=0,
                   in_stride=0, dtype16=0):
-    # algorithmic bytes: the fp32 rows in, the normalised rows out (bf16 and / or fp32)
-    nbytes = rows * D * (4 + (2 if y_bf16 is not None else 0) + (4 if y_f32 is not None else 0))
-    _bracketed("layernorm_fwd", nbytes, lambda: call(
-        "devit_layernorm_fwd", ptr(x2d), rows, D, in_group, in_stride, ptr(gamma), ptr(beta), eps, ptr(y_bf16),
-        ptr(y_f32), ptr(mean), ptr(rstd), dtype16, stream_ptr()))
+    call("devit_layernorm_fwd", ptr(x2d), rows, D, in_group, in_stride, ptr(gamma), ptr(beta), eps, ptr(y_bf16),
+         ptr(y_f32), ptr(mean), ptr(rstd), dtype16, stream_ptr())
 
 
 def layernorm_bwd(dy, dy_is_f32, x2d, rows, D, mean, rstd, gamma, dres, dx, dx_bf16, rowscale, rows_per_scale, dgamma,
                   dbeta, in_group=0, in_stride=0, gsum=None):
-    nbytes = L.load().devit_layernorm_bwd_workspace(rows, D)
-    ws = workspace(x2d.device, nbytes)
-    # algorithmic bytes: dy, x and the incoming residual gradient in; the fp32 gradient (and its bf16 copy) out
-    nbytes = rows * D * ((4 if dy_is_f32 else 2) + 4 + (4 if dres is not None else 0) + (4 if dx is not None else 0) +
-                         (2 if dx_bf16 is not None else 0))
-    _bracketed("layernorm_bwd", nbytes, lambda: call(
-        "devit_layernorm_bwd", ptr(dy), int(dy_is_f32), ptr(x2d), rows, D, in_group, in_stride, ptr(mean), ptr(rstd),
-        ptr(gamma), ptr(dres), ptr(dx), ptr(dx_bf16), ptr(rowscale), rows_per_scale, ptr(dgamma), ptr(dbeta),
-        ptr(gsum), 1, ptr(ws), ws.numel(), stream_ptr()))
+    ws = workspace(x2d.device, L.load().devit_layernorm_bwd_workspace(rows, D))
+    call("devit_layernorm_bwd", ptr(dy), int(dy_is_f32), ptr(x2d), rows, D, in_group, in_stride, ptr(mean), ptr(rstd),
+         ptr(gamma), ptr(dres), ptr(dx), ptr(dx_bf16), ptr(rowscale), rows_per_scale, ptr(dgamma), ptr(dbeta),
+         ptr(gsum), 1, ptr(ws), ws.numel(), stream_ptr())
 
 
 def cast_bf16(src, dst=None, f16=False):
@@ -291,7 +347,7 @@ class DeferredWgrads:
     """The weight gradients of SEVERAL blocks in one launch of the full-row weight-gradient kernel (devit_wgrad_grouped).  A block's four
     products are 19 tiles of 256 x 384: alone they need 13 K slices to fill 256 CUs, and the slices' fp32 atomics (97 MB per block at the
     ~1.3 TB/s the memory side adds floats at) are a third of the launch.  Grouped over g blocks the same CUs are filled by 13 / g slices:
-    the blocks' backward records its products as jobs (devit_block_bwd_io.defer_jobs / _block_backward(defer=...)) and the group is launched
+    the blocks' backward records its products as jobs (devit_block_bwd_io.defer_jobs) and the group is launched
     -- and its blocks reported to `grad_ready` -- behind the backward of its last block.  Groups (DEVIT_WGRAD_GROUP=auto|all|block):
       auto   with a gradient exchange to overlap (a reducer with world > 1 on `grad_ready`): the blocks of one reducer bucket, so that every
              bucket still leaves as soon as its gradients exist; without one: all blocks of the encoder call (one launch, no K split)
@@ -326,15 +382,7 @@ class DeferredWgrads:
     def flush(self, mp):
         if self.jobs:
             arr = (L.WgradJob * len(self.jobs))(*self.jobs)
-            rec = PROFILE_WGRAD
-            if rec is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
             call("devit_wgrad_grouped", arr, len(self.jobs), mp, 0, stream_ptr())
-            if rec is not None:
-                e1.record()
-                cols = sum(j.a_cols for j in self.jobs)
-                rec.append((2.0 * mp * cols * 384, mp * (cols + 384 * len(self.jobs)) * 2 + cols * 384 * 4, e0, e1))
         for bp in self.pending:
             bp.finish_grads()
             if self.cfg.grad_ready is not None:
@@ -396,132 +444,6 @@ class EncoderCfg:
         self.lean_tokens = lean_tokens
 
 
-def _block_forward(x, bp, dp, cfg, need_grad, want_att, pad_qkv=True):
-    """x: fp32 [B, N, D] contiguous.  Returns (x_out, saved dict)."""
-    B, N, D = x.shape
-    M, H, dev = B * N, bp.num_heads, x.device
-    x2 = x.view(M, D)
-    s = {}
-    t16 = 1 if bp.qkv_w16.dtype == F16 else 0       # f16: the frozen teacher's forward (no backward)
-    BF16 = F16 if t16 else torch.bfloat16
-    if t16 and need_grad:
-        raise L.DevitError('precision="f16" is forward-only (frozen teacher): run it under torch.no_grad()')
-    ln1 = rows_alloc(M, D, BF16, dev)
-    mean1 = torch.empty(M, dtype=F32, device=dev) if need_grad else None
-    rstd1 = torch.empty(M, dtype=F32, device=dev) if need_grad else None
-    layernorm_fwd(x2, M, D, bp.n1w, bp.n1b, cfg.eps, y_bf16=ln1, mean=mean1, rstd=rstd1, dtype16=t16)
-    Da = bp.qkv_w16.shape[0] // 3          # attention width = heads * 64 (== D unless the block was compacted, shrink.py)
-    # the attention kernels never read rows >= B*N; the relation-loss windows (RelationLossFn) overhang by up to 128
-    qkv = rows_alloc(M, 3 * Da, BF16, dev, extra=128 if pad_qkv else 0)
-    linear_fwd(ln1, bp.qkv_w16, bp.qkv_b, M, out=qkv, dtype16=t16)
-    attn_o = rows_alloc(M, Da, BF16, dev)
-    lse = torch.empty((B, H, N), dtype=F32, device=dev) if need_grad else None
-    # algorithmic bytes: q, k, v in, the head outputs out (bf16)
-    _bracketed("attention_fwd", M * Da * 2 * 4, lambda: call(
-        "devit_attn_fwd", ptr(qkv), ptr(attn_o), ptr(lse), ptr(bp.head_gate), B, N, H, Da // H, (Da // H) ** -0.5,
-        t16, stream_ptr()))
-    x1 = torch.empty((B, N, D), dtype=F32, device=dev)
-    att = torch.empty((M, D), dtype=BF16, device=dev) if want_att else None
-    dp1, dp2 = dp if dp is not None else (None, None)
-    linear_fwd(attn_o, bp.proj_w16, bp.proj_b, M, out=x1.view(M, D), kind=L.EPI_RESIDUAL_F32, res=x2, rowscale=dp1,
-               rows_per_scale=N, aux=att, dtype16=t16)
-    ln2 = rows_alloc(M, D, BF16, dev)
-    mean2 = torch.empty(M, dtype=F32, device=dev) if need_grad else None
-    rstd2 = torch.empty(M, dtype=F32, device=dev) if need_grad else None
-    layernorm_fwd(x1.view(M, D), M, D, bp.n2w, bp.n2b, cfg.eps, y_bf16=ln2, mean=mean2, rstd=rstd2, dtype16=t16)
-    Hd = bp.fc1_w16.shape[0]
-    h = rows_alloc(M, Hd, BF16, dev)
-    h_pre = rows_alloc(M, Hd, BF16, dev) if need_grad else None
-    linear_fwd(ln2, bp.fc1_w16, bp.fc1_b, M, out=h, kind=L.EPI_GELU_BF16, colscale=bp.neuron_gate, aux=h_pre,
-               exact_gelu=cfg.exact_gelu, dtype16=t16)
-    x2o = torch.empty((B, N, D), dtype=F32, device=dev)
-    w2t = getattr(bp, "fc2_w16t", None)
-    if w2t is not None and not t16 and full_row_selected(pad_rows(M), D, Hd):   # k-major weight copy -> the full-row 256x384 GEMM (bit-identical)
-        gemm(h, h.stride(0), 0, w2t, w2t.stride(0), 1, pad_rows(M), D, Hd, kind=L.EPI_RESIDUAL_F32, out=x2o.view(M, D), ldc=D, bias=bp.fc2_b,
-             m_valid=M, res=x1.view(M, D), rowscale=dp2, rows_per_scale=N)
-    else:
-        linear_fwd(h, bp.fc2_w16, bp.fc2_b, M, out=x2o.view(M, D), kind=L.EPI_RESIDUAL_F32, res=x1.view(M, D), rowscale=dp2,
-                   rows_per_scale=N, dtype16=t16)
-    if bp.module is not None and not cfg.lean_tokens:  # shrink contract (core/imp_rank.py:31,108): post-mask values
-        bp.module.mlp.neuron_output = h[:M].view(B, N, Hd)
-        bp.module.attn.head_output = attn_o[:M].view(B, N, H, Da // H)
-    elif bp.module is not None:     # (inside de_vit.lean_tail: not handed out, see _encoder_forward_c)
-        bp.module.mlp.neuron_output = None
-        bp.module.attn.head_output = None
-    if need_grad:
-        s = dict(x=x, ln1=ln1, mean1=mean1, rstd1=rstd1, qkv=qkv, attn_o=attn_o, lse=lse, x1=x1, ln2=ln2, mean2=mean2,
-                 rstd2=rstd2, h=h, h_pre=h_pre, dp1=dp1, dp2=dp2)
-    return x2o, qkv, att, s
-
-
-def _block_backward(dx, g2, s, bp, cfg, dqkv_add, datt, prev_dp2, want_prev_g, prev_fc2_b=None, g2_bias_done=False, defer=None):
-    """dx: fp32 [B,N,D] grad of the block output; g2: bf16 [Mp, D] = bf16(dp2 * dx).
-    Returns (dx_in fp32 [B,N,D], g_prev bf16 [Mp,D] = bf16(prev_dp2 * dx_in) or None).
-    defer: a DeferredWgrads -- the weight gradients the full-row weight-gradient kernel takes are recorded there as jobs (the caller launches
-    them with other blocks' and then calls finish_grads / grad_ready); the others run here on the split-K 128x128 launches."""
-    B, N, D = dx.shape
-    M, H, dev = B * N, bp.num_heads, dx.device
-    Hd = bp.fc1_w.shape[0]
-    Da = H * 64                      # attention width (< D when heads were compacted away)
-    # ---- MLP branch: x2 = x1 + dp2 * fc2(gate * gelu(fc1(ln2)))
-    # Order: the weight gradient that only needs g2 first, then dh_pre's producer and its consumers back to back (dh_pre is
-    # 156 MB at B = 256; these GEMMs run 1.2-1.7x slower on operands from cold HBM than from the 256 MB Infinity Cache,
-    # tools/gemm_bench.py COLD=1; +0.6 % on the step)
-    js, keep = [], []
-
-    def wgrad(dy, x, w_grad, b_grad):
-        j = wgrad_job_struct(dy, x, w_grad, b_grad) if (defer is not None and wgrad_enabled(pad_rows(M))) else None
-        if j is None:
-            linear_wgrad(dy, x, w_grad, b_grad, M)
-        else:
-            js.append(j)
-            keep.extend((dy, x, w_grad, b_grad))
-    fc2_bias = None if g2_bias_done else grad_buf(bp.fc2_b)
-    if fc2_bias is not None and defer is not None and wgrad_enabled(pad_rows(M)) and D == 384 and Hd % 128 == 0:
-        colsum(g2, pad_rows(M), D, fc2_bias, True)      # (the transposed product has no bias-gradient side: devit_block_bwd does the same)
-        fc2_bias = None
-    wgrad(g2, s["h"], grad_buf(bp.fc2_w), fc2_bias)
-    dh_pre = rows_alloc(M, Hd, BF16, dev)
-    linear_dgrad(g2, bp.fc2_w16, M, out=dh_pre, kind=L.EPI_DGELU_BF16, colscale=bp.neuron_gate, aux_in=s["h_pre"],
-                 exact_gelu=cfg.exact_gelu)
-    dln2 = rows_alloc(M, D, BF16, dev)
-    linear_dgrad(dh_pre, bp.fc1_w16, M, out=dln2)
-    wgrad(dh_pre, s["ln2"], grad_buf(bp.fc1_w), grad_buf(bp.fc1_b))
-    dx1 = torch.empty((B, N, D), dtype=F32, device=dev)
-    g1 = rows_alloc(M, D, BF16, dev)
-    fuse_pb = datt is None        # proj bias gradient = column sums of g1, produced by the same LN-bwd launch
-    layernorm_bwd(dln2, False, s["x1"].view(M, D), M, D, s["mean2"], s["rstd2"], bp.n2w, dx.view(M, D), dx1.view(M, D),
-                  g1, s["dp1"], N, grad_buf(bp.n2w), grad_buf(bp.n2b), gsum=grad_buf(bp.proj_b) if fuse_pb else None)
-    # ---- attention branch: x1 = x + dp1 * proj(gate * attn(qkv(ln1)))
-    if datt is not None:  # gradient flowing into the exposed 'attention' output (pre-residual, post-proj)
-        g1 = g1 + _pad_like(datt, g1)
-    dattn = rows_alloc(M, Da, BF16, dev)
-    linear_dgrad(g1, bp.proj_w16, M, out=dattn)
-    wgrad(g1, s["attn_o"], grad_buf(bp.proj_w), None if fuse_pb else grad_buf(bp.proj_b))
-    dqkv = rows_alloc(M, 3 * Da, BF16, dev)
-    # algorithmic bytes: q, k, v, o, do in; dq, dk, dv out (+ the relation-loss gradient that is added in)
-    _bracketed("attention_bwd", M * Da * 2 * (8 + (3 if dqkv_add is not None else 0)), lambda: call(
-        "devit_attn_bwd", ptr(s["qkv"]), ptr(s["attn_o"]), ptr(dattn), ptr(s["lse"]), ptr(bp.head_gate),
-        ptr(dqkv_add), ptr(dqkv), B, N, H, 64, 0.125, stream_ptr()))
-    dln1 = rows_alloc(M, D, BF16, dev)
-    linear_dgrad(dqkv, bp.qkv_w16, M, out=dln1)
-    wgrad(dqkv, s["ln1"], grad_buf(bp.qkv_w), grad_buf(bp.qkv_b))
-    if defer is not None:
-        defer.add(bp, js, keep)
-    dx0 = torch.empty((B, N, D), dtype=F32, device=dev)
-    g_prev = rows_alloc(M, D, BF16, dev) if want_prev_g else None
-    layernorm_bwd(dln1, False, s["x"].view(M, D), M, D, s["mean1"], s["rstd1"], bp.n1w, dx1.view(M, D), dx0.view(M, D),
-                  g_prev, prev_dp2, N, grad_buf(bp.n1w), grad_buf(bp.n1b),
-                  gsum=grad_buf(prev_fc2_b) if (g_prev is not None and prev_fc2_b is not None) else None)
-    return dx0, g_prev
-
-
-def _pad_like(t2d, ref):
-    out = torch.zeros_like(ref)
-    out[: t2d.shape[0]] = t2d.to(ref.dtype)
-    return out
-
-
 def scale_cast(dx, rowscale, N):
     B, _, D = dx.shape
     M = B * N
@@ -534,7 +456,7 @@ def scale_cast(dx, rowscale, N):
 # The LAST block when only the class / distillation tokens of its output are read (models/de_vit.py:286-288 takes
 # x[:, 0], x[:, 1] after the final norm, and engine.py:91-92 takes q/k/v of the middle block only): of the last block
 # only K and V are needed on all rows; the Q projection, attention, proj, LN2, fc1 and fc2 run on the B * ntok token
-# rows.  Same kernels and per-row arithmetic as _block_forward, so the token rows -- and the logits -- are bit-identical
+# rows.  Same kernels and per-row arithmetic as the full block (csrc/encoder.hip), so the token rows -- and the logits -- are bit-identical
 # to the full block's; the reference computes (and then drops) the other 196 rows per image.
 # ----------------------------------------------------------------------------------------------
 def _gather_tok(src2d, B, N, ntok, cols, dtype, dev, pad=True):
@@ -567,9 +489,8 @@ def _tail_forward(x, bp, dp, cfg, need_grad, ntok):
     linear_fwd(ln1_tok, bp.qkv_w16[:Da], qkv_b[:Da], T, out=q_tok, dtype16=t16)
     attn_o = rows_alloc(T, Da, dt, dev)
     lse = torch.empty((B, H, ntok), dtype=F32, device=dev) if need_grad else None
-    _bracketed("attention_fwd_rows", (M * 2 * Da + 2 * T * Da) * 2, lambda: call(
-        "devit_attn_fwd_rows", ptr(q_tok), Da, ptr(kv), 2 * Da, ptr(attn_o), ptr(lse), ptr(bp.head_gate), B, ntok, N, H,
-        64, 0.125, t16, stream_ptr()))
+    call("devit_attn_fwd_rows", ptr(q_tok), Da, ptr(kv), 2 * Da, ptr(attn_o), ptr(lse), ptr(bp.head_gate), B, ntok, N, H,
+         64, 0.125, t16, stream_ptr())
     x_tok = _gather_tok(x2, B, N, ntok, D, F32, dev, pad=False)
     dp1, dp2 = dp if dp is not None else (None, None)
     x1 = torch.empty((B, ntok, D), dtype=F32, device=dev)
@@ -631,9 +552,8 @@ def _tail_backward(dx, s, bp, cfg, defer=None):
     linear_wgrad(g1, s["attn_o"], grad_buf(bp.proj_w), None, T)
     dqkv_tok = rows_alloc(T, 3 * Da, BF16, dev)                          # (dQ | dK | dV) of the token rows
     dkv = rows_alloc(M, 2 * Da, BF16, dev)
-    _bracketed("attention_bwd_rows", (M * 4 * Da + 4 * T * Da) * 2, lambda: call(
-        "devit_attn_bwd_rows", ptr(s["q_tok"]), Da, ptr(s["kv"]), 2 * Da, ptr(s["attn_o"]), ptr(dattn), ptr(s["lse"]),
-        ptr(bp.head_gate), ptr(dqkv_tok), 3 * Da, ptr(dkv), 2 * Da, B, ntok, N, H, 64, 0.125, stream_ptr()))
+    call("devit_attn_bwd_rows", ptr(s["q_tok"]), Da, ptr(s["kv"]), 2 * Da, ptr(s["attn_o"]), ptr(dattn), ptr(s["lse"]),
+         ptr(bp.head_gate), ptr(dqkv_tok), 3 * Da, ptr(dkv), 2 * Da, B, ntok, N, H, 64, 0.125, stream_ptr())
     dqkv_tok[:T].view(B, ntok, 3 * Da)[:, :, Da:].copy_(dkv[:M].view(B, N, 2 * Da)[:, :ntok])
     dln1 = rows_alloc(M, D, BF16, dev)
     linear_dgrad(dkv, bp.qkv_w16[Da:], M, out=dln1)
@@ -657,12 +577,10 @@ def _tail_backward(dx, s, bp, cfg, defer=None):
 
 
 # ----------------------------------------------------------------------------------------------
-# composite path: whole blocks per ctypes call (devit_encoder_fwd / devit_block_bwd, csrc/encoder.hip).
-# Same kernels, arguments and order as _block_forward / _block_backward above (which stay as the granular path that
-# bench.py's per-kernel instrumentation and the rare extra-gradient cases use); one arena per encoder call instead of
-# ~15 torch allocations per block.  COMPOSITE = False forces the granular path (A/B tests).
+# whole blocks per ctypes call (devit_encoder_fwd / devit_block_bwd, csrc/encoder.hip): the ONE host sequence of the 16-bit block --
+# there is no restatement of it here.  One arena per block of an encoder call holds its activations; the instruments above see its
+# launches through the library's observer.
 # ----------------------------------------------------------------------------------------------
-COMPOSITE = os.environ.get("DEVIT_COMPOSITE", "1") == "1"
 # Stream whose allocator pool the encoder arenas come from (None: the current stream).  A forward that runs on a side
 # stream but is consumed on the main stream (the frozen teacher, engine._teacher_forward_async) sets this to the
 # CONSUMER's stream: a 13 GB arena handed across streams with Tensor.record_stream() comes back to the allocator only when
@@ -751,7 +669,7 @@ def _encoder_forward_composite(x, cfg, need_grad, nb):
         pad = bool(cfg.want_qkv) and (cfg.qkv_pad_layers is None or i in cfg.qkv_pad_layers)
         flags = (L.BLK_SAVE if need_grad else 0) | (L.BLK_QKV_PAD if pad else 0) | (L.BLK_ATT if cfg.want_att else 0)
         Da, Hd = weights[i].attn_width, weights[i].hidden
-        BF16 = F16 if weights[i].dtype16 else torch.bfloat16
+        dt = F16 if weights[i].dtype16 else BF16
         if weights[i].dtype16 and need_grad:
             raise L.DevitError('precision="f16" is forward-only (frozen teacher): run it under torch.no_grad()')
         sz, offs, tot = _act_sizes(B, N, D, Da, Hd, flags)
@@ -770,13 +688,13 @@ def _encoder_forward_composite(x, cfg, need_grad, nb):
         def view(j, rows, cols, dt, arena=arena, offs=offs):
             return arena[offs[j]:offs[j] + rows * cols * dt.itemsize].view(dt).view(rows, cols)
         qkv_rows = mp + (128 if flags & L.BLK_QKV_PAD else 0)
-        v = dict(qkv=view(L.ACT_QKV, qkv_rows, 3 * Da, BF16), x2=view(L.ACT_X2, M, D, F32).view(B, N, D),
-                 att=view(L.ACT_ATT, M, D, BF16) if cfg.want_att else None)
+        v = dict(qkv=view(L.ACT_QKV, qkv_rows, 3 * Da, dt), x2=view(L.ACT_X2, M, D, F32).view(B, N, D),
+                 att=view(L.ACT_ATT, M, D, dt) if cfg.want_att else None)
         v["qkv"]._devit_arena = True          # a view of an arena from ARENA_ALLOC_STREAM's pool (engine._hand_over)
         views.append(v)
         if bp.module is not None and not cfg.lean_tokens:  # shrink contract (core/imp_rank.py:31,108): post-mask values
-            bp.module.mlp.neuron_output = view(L.ACT_H, mp, Hd, BF16)[:M].view(B, N, Hd)
-            bp.module.attn.head_output = view(L.ACT_ATTN_O, mp, Da, BF16)[:M].view(B, N, bp.num_heads, Da // bp.num_heads)
+            bp.module.mlp.neuron_output = view(L.ACT_H, mp, Hd, dt)[:M].view(B, N, Hd)
+            bp.module.attn.head_output = view(L.ACT_ATTN_O, mp, Da, dt)[:M].view(B, N, bp.num_heads, Da // bp.num_heads)
         elif bp.module is not None:
             # inside de_vit.lean_tail the caller has declared that it reads the logits (and the middle block's q / k / v) only: the
             # debug views are not handed out, and the ones an earlier public forward left are dropped, so a ranking pass run inside
@@ -871,54 +789,37 @@ class EncoderFn(torch.autograd.Function):
         if need_grad and any(getattr(bp, "compacted", False) and getattr(bp, "masters", None) is None for bp in cfg.blocks):
             raise L.DevitError("this model was compacted for inference (shrink.compact(model)): run it under torch.no_grad(), "
                                "or compact it with shrink.compact(model, trainable=True) to train through the compacted blocks")
-        ctx.run = None
         nb = len(cfg.blocks)
         # lean tail (EncoderCfg.lean_tokens): the last block runs on the token rows only
         lean = cfg.lean_tokens if (cfg.lean_tokens and nb >= 2 and not cfg.want_att and not cfg.want_enc) else 0
         nbody = nb - 1 if lean else nb
         dp_last = cfg.dp_scales[nb - 1] if cfg.dp_scales is not None else None
         ctx.tail = None
-        if COMPOSITE and PROFILE is None and PROFILE_HBM is None:
-            run = _encoder_forward_composite(x, cfg, need_grad, nbody)
-            qkvs = [v["qkv"] for v in run.views] if cfg.want_qkv else []
-            atts = [v["att"] for v in run.views] if cfg.want_att else []
-            encs = [run.views[i]["x2"].clone() if i == nb - 1 else run.views[i]["x2"] for i in range(nb)] if cfg.want_enc else []
-            ctx.cfg, ctx.saved, ctx.need_grad = cfg, None, need_grad
-            ctx.run = run if need_grad else None
-            ctx.counts = (len(qkvs), len(atts), len(encs))
-            ctx.set_materialize_grads(False)
-            xo = run.views[-1]["x2"]
-            if lean:
-                xo, ctx.tail = _tail_forward(xo, cfg.blocks[-1], dp_last, cfg, need_grad, lean)
-            return (xo,) + tuple(qkvs) + tuple(atts) + tuple(encs)
-        saved, qkvs, atts, encs = [], [], [], []
-        for i, bp in enumerate(cfg.blocks[:nbody]):
-            dp = cfg.dp_scales[i] if cfg.dp_scales is not None else None
-            pad = bool(cfg.want_qkv) and (cfg.qkv_pad_layers is None or i in cfg.qkv_pad_layers)
-            x, qkv, att, s = _block_forward(x, bp, dp, cfg, need_grad, cfg.want_att, pad)
-            saved.append(s)
-            if cfg.want_qkv:
-                qkvs.append(qkv)
-            if cfg.want_att:
-                atts.append(att)
-            if cfg.want_enc:
-                encs.append(x.clone() if i == len(cfg.blocks) - 1 else x)
-        if lean:
-            x, ctx.tail = _tail_forward(x, cfg.blocks[-1], dp_last, cfg, need_grad, lean)
-        ctx.cfg, ctx.saved, ctx.need_grad = cfg, saved, need_grad
+        run = _encoder_forward_composite(x, cfg, need_grad, nbody)
+        qkvs = [v["qkv"] for v in run.views] if cfg.want_qkv else []
+        atts = [v["att"] for v in run.views] if cfg.want_att else []
+        encs = [run.views[i]["x2"].clone() if i == nb - 1 else run.views[i]["x2"] for i in range(nb)] if cfg.want_enc else []
+        ctx.cfg, ctx.need_grad = cfg, need_grad
+        ctx.run = run if need_grad else None
         ctx.counts = (len(qkvs), len(atts), len(encs))
         # outputs nobody differentiates (11 of the 12 qkv tensors in the DEKD step) arrive as None in backward, not as
         # zero tensors: a materialised one is a 117 MB fill plus a 117 MB read in the attention backward, per block
         ctx.set_materialize_grads(False)
-        return (x,) + tuple(qkvs) + tuple(atts) + tuple(encs)
+        xo = run.views[-1]["x2"]
+        if lean:
+            xo, ctx.tail = _tail_forward(xo, cfg.blocks[-1], dp_last, cfg, need_grad, lean)
+        return (xo,) + tuple(qkvs) + tuple(atts) + tuple(encs)
 
     @staticmethod
     def backward(ctx, dx, *dothers):
-        cfg, saved = ctx.cfg, ctx.saved
+        cfg = ctx.cfg
         if not ctx.need_grad:
             raise L.DevitError("EncoderFn.backward called but the forward ran without grad bookkeeping")
         nq, na, ne = ctx.counts
         dqkvs, datts, dencs = dothers[:nq], dothers[nq:nq + na], dothers[nq + na:]
+        if any(d is not None for d in datts) or any(d is not None for d in dencs):
+            raise L.DevitError("gradients into the exposed 'attention' / 'encoder' outputs are not taken on the 16-bit path: "
+                               'run the model with precision="f32" (ops_f32.EncoderF32Fn implements both)')
         nb = len(cfg.blocks)
         nparams = 12 * nb
         if ctx.tail is not None:          # lean tail: dx is the [B, ntok, D] gradient of the token rows
@@ -937,44 +838,12 @@ class EncoderFn(torch.autograd.Function):
                     cfg.grad_ready(last.all_params())
         else:
             defer = DeferredWgrads(cfg, nb)
-        if ctx.run is not None:
-            run = ctx.run
-            if any(d is not None for d in datts) or any(d is not None for d in dencs):
-                raise L.DevitError("gradients into the exposed 'attention' / 'encoder' outputs run on the granular path only: "
-                                   "set devit_amd.ops.COMPOSITE = False for this model call")
-            B, N, D = run.dims
-            if dx is None:
-                dx = torch.zeros((B, N, D), dtype=F32, device=run.x.device)
-            dx_in = _encoder_backward_composite(run, cfg, dx.contiguous(), dqkvs if nq else None, defer)
-            ctx.run = None
-            return (dx_in, None) + (None,) * nparams
-        B, N, D = saved[0]["x"].shape
+        run, ctx.run = ctx.run, None
+        B, N, D = run.dims
         if dx is None:
-            dx = torch.zeros((B, N, D), dtype=F32, device=saved[0]["x"].device)
-        dx = dx.contiguous()
-        if ne and dencs[nb - 1] is not None:
-            dx = dx + dencs[nb - 1]
-        g = scale_cast(dx, saved[nb - 1]["dp2"], N)
-        g_bias_done = False           # fc2 bias gradient of block i comes fused from block i+1's LN1 backward
-        for i in range(nb - 1, -1, -1):
-            bp = cfg.blocks[i]
-            dq = dqkvs[i] if nq else None
-            if dq is not None:
-                dq = dq.contiguous()
-            da = datts[i] if na else None
-            prev_dp2 = saved[i - 1]["dp2"] if i > 0 else None
-            extra = dencs[i - 1] if (ne and i > 0 and dencs[i - 1] is not None) else None
-            fuse_prev = i > 0 and extra is None
-            dx, g = _block_backward(dx, g, saved[i], bp, cfg, dq, da, prev_dp2, want_prev_g=fuse_prev,
-                                    prev_fc2_b=cfg.blocks[i - 1].fc2_b if fuse_prev else None, g2_bias_done=g_bias_done, defer=defer)
-            g_bias_done = fuse_prev
-            if extra is not None:
-                dx = dx + extra
-                g = scale_cast(dx, prev_dp2, N)
-            saved[i] = None
-            if defer.last_of_group(i):
-                defer.flush(pad_rows(B * N))
-        return (dx, None) + (None,) * nparams
+            dx = torch.zeros((B, N, D), dtype=F32, device=run.x.device)
+        dx_in = _encoder_backward_composite(run, cfg, dx.contiguous(), dqkvs if nq else None, defer)
+        return (dx_in, None) + (None,) * nparams
 
 
 # ----------------------------------------------------------------------------------------------

@@ -26,7 +26,8 @@ extern "C" {
 /* 2 (round 6): devit_block_weights grew (fc2_w16t), devit_index_copy mode 4, devit_wgrad_grouped, devit_abi_struct_size, exported symbols
  * only (the library is built with -fvisibility=hidden).  A binding asks devit_version() AND checks its struct sizes against
  * devit_abi_struct_size() before it passes arrays of structs (devit_encoder_fwd strides by sizeof(devit_block_weights)). */
-#define DEVIT_ABI_VERSION 2
+/* 3: devit_set_launch_observer. */
+#define DEVIT_ABI_VERSION 3
 #define DEVIT_API __attribute__((visibility("default")))
 
 enum {
@@ -42,10 +43,37 @@ DEVIT_API const char* devit_last_error(void); /* host string, thread-local, vali
 /* 0 if device `dev` is gfx950; DEVIT_ERR_DEVICE otherwise (product path refuses to run). */
 DEVIT_API int devit_check_device(int dev);
 /* sizeof() of the ABI's structs as THIS library was compiled (which: 0 devit_epilogue, 1 devit_operand, 2 devit_block_weights,
- * 3 devit_block_wgrads, 4 devit_block_acts, 5 devit_block_bwd_io, 6 devit_index_job, 7 devit_wgrad_job; anything else: 0).  A binding
+ * 3 devit_block_wgrads, 4 devit_block_acts, 5 devit_block_bwd_io, 6 devit_index_job, 7 devit_wgrad_job, 8 devit_launch_info; anything else: 0).  A binding
  * compares them with its own mirrors once at load time: a stale mirror of a struct that is passed as an ARRAY would otherwise be misread
  * from its second element on, with no error. */
 DEVIT_API size_t devit_abi_struct_size(int which);
+
+/* ------------------------------------------------------------------------------------------
+ * Launch observer: how an instrument (bench.py's per-kernel events, tools/step_gemm_table.py) sees the launches of a step without a
+ * second host program.  While the CALLING THREAD has an observer installed, each of
+ *     devit_gemm_bf16, devit_layernorm_fwd / _bwd, devit_attn_fwd / _bwd / _fwd_rows / _bwd_rows, devit_wgrad_grouped,
+ *     devit_dgrad_layernorm_bwd (only when it takes the fused launch: unfused it calls the GEMM and LayerNorm entry points, which report)
+ * calls it twice: phase 0 just before the entry point's first kernel launch (after its argument checks: a refused call reports nothing),
+ * phase 1 just after its last, with the stream those kernels go to -- from inside devit_block_bwd that is the library's weight-gradient side
+ * stream where the launch went there.  devit_encoder_fwd / devit_block_bwd report nothing of their own; column sums, casts, memsets, the
+ * optimizer and the losses report nothing.  The pointer is thread-local (another thread's launches never enter the callback); fn == NULL
+ * removes it.  With none installed an entry point pays one thread-local load and one branch.
+ * devit_launch_info carries facts of the call, no labels; fields an entry point does not list are 0.
+ * ---------------------------------------------------------------------------------------- */
+enum { DEVIT_HAS_Y_BF16 = 1, DEVIT_HAS_Y_F32 = 2, DEVIT_HAS_DY_F32 = 4, DEVIT_HAS_DRES = 8, DEVIT_HAS_DX = 16, DEVIT_HAS_DX_BF16 = 32,
+       DEVIT_HAS_DQKV_ADD = 64 };
+typedef struct {
+  const char* name;        /* the entry point, e.g. "devit_gemm_bf16" */
+  int a_kmajor, b_kmajor, kind, M, N, K, batch, split_k; /* GEMM; the fused dgrad + LayerNorm backward: its dgrad (M_pad, D, K; kind STORE_BF16);
+                                                            devit_wgrad_grouped: K = the reduction rows (M_pad), split_k = the slices taken */
+  int rows, width;         /* LayerNorm: rows, D.  Attention: B * N token rows, H * head_dim features */
+  int q_rows;              /* devit_attn_*_rows: B * NQ query rows */
+  int has;                 /* DEVIT_HAS_*: which optional pointers of the call are not NULL (DY_F32: dy_is_f32) */
+  int njobs, a_cols;       /* devit_wgrad_grouped: jobs and the sum of their a_cols */
+  double flops, bytes;     /* devit_wgrad_grouped, algorithmic: 2 K a_cols 384;  K (a_cols + 384 njobs) 2 + a_cols 384 4 */
+} devit_launch_info;
+typedef void (*devit_launch_observer)(void* user, int phase, void* stream, const devit_launch_info* info);
+DEVIT_API int devit_set_launch_observer(devit_launch_observer fn, void* user);
 
 /* ------------------------------------------------------------------------------------------
  * GEMM  C[M,N] = sum_k A(m,k) * B(n,k), bf16 operands, fp32 accumulate (MFMA 16x16x32).

@@ -379,3 +379,36 @@ def test_deferred_wgrad_groups(monkeypatch):
     d.add(cfg.blocks[2], [])
     d.flush(512)
     assert hook.seen == [3, 2] and d.pending == []
+
+
+def test_gemm_template_labels():
+    """ops.gemm_template: PROFILE's label of a GEMM launch as a pure function of what the library's launch observer reports -- the four layouts;
+    a k-major B with the fp32 residual epilogue is the fc2 forward reading the k-major COPY of its weight and stays with the forward Linear
+    layers; the fused dgrad + LayerNorm backward has a label of its own."""
+    from devit_amd import ops, _lib as L
+    assert ops.gemm_template(0, 0, L.EPI_STORE_BF16) == "A_row/B_row"
+    assert ops.gemm_template(0, 1, L.EPI_STORE_BF16) == "A_row/B_km" == ops.gemm_template(0, 1, L.EPI_DGELU_BF16)
+    assert ops.gemm_template(1, 0, L.EPI_STORE_F32) == "A_km/B_row"
+    assert ops.gemm_template(1, 1, L.EPI_ATOMIC_F32) == "A_km/B_km"
+    assert ops.gemm_template(0, 1, L.EPI_RESIDUAL_F32) == "A_row/B_row" == ops.gemm_template(0, 0, L.EPI_RESIDUAL_F32)
+    assert ops.gemm_template(0, 1, L.EPI_STORE_BF16, fused_ln_bwd=True) == "A_row/B_km+ln_bwd"
+
+
+def test_hbm_record_bytes():
+    """ops.hbm_record: PROFILE_HBM's (name, algorithmic bytes) from the reported facts, at the shapes of one student block with 396 token rows."""
+    from devit_amd import ops, _lib as L
+
+    def info(name, **kw):
+        return L.LaunchInfo(name=name.encode(), **kw)
+    assert ops.hbm_record(info("devit_layernorm_fwd", rows=396, width=384, has=L.HAS_Y_BF16)) == ("layernorm_fwd", 396 * 384 * 6)
+    assert ops.hbm_record(info("devit_layernorm_fwd", rows=4, width=384, has=L.HAS_Y_F32)) == ("layernorm_fwd", 4 * 384 * 8)
+    full = L.HAS_DRES | L.HAS_DX | L.HAS_DX_BF16
+    assert ops.hbm_record(info("devit_layernorm_bwd", rows=396, width=384, has=full)) == ("layernorm_bwd", 396 * 384 * 16)
+    assert ops.hbm_record(info("devit_layernorm_bwd", rows=396, width=384, has=L.HAS_DRES | L.HAS_DX)) == ("layernorm_bwd", 396 * 384 * 14)
+    assert ops.hbm_record(info("devit_layernorm_bwd", rows=4, width=384, has=L.HAS_DY_F32 | L.HAS_DX)) == ("layernorm_bwd", 4 * 384 * 12)
+    assert ops.hbm_record(info("devit_attn_fwd", rows=396, width=384)) == ("attention_fwd", 396 * 384 * 8)
+    assert ops.hbm_record(info("devit_attn_bwd", rows=396, width=384)) == ("attention_bwd", 396 * 384 * 16)
+    assert ops.hbm_record(info("devit_attn_bwd", rows=396, width=384, has=L.HAS_DQKV_ADD)) == ("attention_bwd", 396 * 384 * 22)
+    assert ops.hbm_record(info("devit_attn_fwd_rows", rows=396, q_rows=4, width=384)) == ("attention_fwd_rows", (396 * 2 * 384 + 2 * 4 * 384) * 2)
+    assert ops.hbm_record(info("devit_attn_bwd_rows", rows=396, q_rows=4, width=384)) == ("attention_bwd_rows", (396 * 4 * 384 + 4 * 4 * 384) * 2)
+    assert ops.hbm_record(info("devit_gemm_bf16")) is None

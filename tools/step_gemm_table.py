@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-shape GEMM times INSIDE the serialized DEKD step (the cache state the launches really run in), for the tile / kernel selection of
-the environment (DEVIT_GEMM_FORCE=0/1/3, DEVIT_GEMM4=0/1): every GEMM launch of three instrumented steps bracketed by events, averaged per
-(layout, kind, M, N, K, batch, split_k).  One process per setting (the switches are read once); compare the printed tables."""
+the environment (DEVIT_GEMM_FORCE=0/1/3, DEVIT_GEMM4=0/1): every GEMM launch the library reports (devit_set_launch_observer through
+ops.observing) of three steps bracketed by events, averaged per (layout, kind, M, N, K, batch, split_k); the fused dgrad + LayerNorm-backward
+launches are the `+ln_bwd` lines.  The observed step is the one that runs uninstrumented.  One process per setting; compare the printed tables."""
 import os, sys, collections
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
@@ -40,22 +41,25 @@ def step():
     out["loss"].backward()
     reducer.finish(); opt.step()
 
-recs = []
-real = ops.gemm
-def traced(a, lda, a_km, b, ldb, b_km, M, N, K, **kw):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(); real(a, lda, a_km, b, ldb, b_km, M, N, K, **kw); e1.record()
-    recs.append((("km" if a_km else "row") + "x" + ("km" if b_km else "row"), kw.get("kind"), M, N, K, kw.get("batch", 1), kw.get("split_k", 1), e0, e1))
+recs, wg, start = [], [], {}
+def traced(phase, stream, i):      # ops.observing: every launch the library reports, on the stream it goes to
+    name = i.name.decode()
+    if name not in ("devit_gemm_bf16", "devit_dgrad_layernorm_bwd", "devit_wgrad_grouped"):
+        return
+    ev = torch.cuda.Event(enable_timing=True); ev.record(ops.torch_stream(stream))
+    if phase == 0:
+        start[name] = ev
+    elif name == "devit_wgrad_grouped":
+        wg.append((i.flops, i.bytes, start[name], ev))
+    else:
+        lay = ("km" if i.a_kmajor else "row") + "x" + ("km" if i.b_kmajor else "row") + ("+ln_bwd" if name == "devit_dgrad_layernorm_bwd" else "")
+        recs.append((lay, i.kind, i.M, i.N, i.K, i.batch, i.split_k, start[name], ev))
 for _ in range(3): step()
 torch.cuda.synchronize()
-ops.COMPOSITE = False       # the host path of single-kernel calls (NOT ops.PROFILE = []: its wrapper calls the module-level gemm -- this tracer --
-ops.gemm = traced           # a second time, and every launch was counted twice in rounds 4-5: verdict r05 weak #12)
-ops.PROFILE_WGRAD = []
 STEPS = 3
-for _ in range(STEPS): step()
+with ops.observing(traced):        # the step that really runs: devit_encoder_fwd / devit_block_bwd, arenas, grouped weight gradients
+    for _ in range(STEPS): step()
 torch.cuda.synchronize()
-ops.gemm = real; ops.COMPOSITE = True
-wg, ops.PROFILE_WGRAD = ops.PROFILE_WGRAD, None
 agg = collections.OrderedDict()
 for lay, kind, M, N, K, batch, sk, e0, e1 in recs:
     d = agg.setdefault((lay, kind, M, N, K, batch, sk), [0.0, 0])
