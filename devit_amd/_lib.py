@@ -79,6 +79,9 @@ class LaunchInfo(C.Structure):
 # devit_launch_observer: fn(user, phase, stream, info)
 LAUNCH_OBSERVER = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(LaunchInfo))
 
+# devit_hsic_scores element types
+HSIC_BF16, HSIC_F16, HSIC_F32 = range(3)
+
 WGRAD_MAX_JOBS = 48
 ABI_VERSION = 3
 # devit_abi_struct_size(which) -> the mirror it must equal (checked at load time: an array of stale mirrors is misread silently)
@@ -118,6 +121,10 @@ SIGNATURES = {
     "devit_attn_fwd_rows": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P]),
     "devit_attn_bwd_rows": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "devit_index_copy": (_I, [_P, _I, _I, _P]),
+    "devit_hsic_target": (_I, [_P, _I, _I, _I, _P, _P, _Z, _P]),
+    "devit_hsic_scores_workspace": (_Z, [_I, _I, _I]),
+    "devit_hsic_scores": (_I, [_P, _I, _I, _I, _I, _I, _LL, _LL, _P, _P, _P, _P, _P, _Z, _P]),
+    "devit_hsic_head_pairs": (_I, [_P, _I, _I, _P, _P]),
     "devit_im2row_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "devit_mix_im2row_bf16": (_I, [_P, _P, _P, _I, _I, C.c_double, _I, _I, _I, _I, _P]),
     "devit_mix_targets": (_I, [_P, _P, _I, _I, C.c_double, C.c_double, _P]),

@@ -22,7 +22,8 @@ import torch
 from . import ops
 
 __all__ = ["compact", "uncompact", "compact_block_weights", "compacted_gflops", "masks_from_sparsity", "load_policy",
-           "get_policy", "save_gates", "load_gates", "read_shrink_checkpoint", "rank_units", "apply_shrink", "neuron_scores", "head_scores"]
+           "get_policy", "save_gates", "load_gates", "read_shrink_checkpoint", "rank_units", "apply_shrink", "neuron_scores", "head_scores", "hsic_target", "hsic_unit_scores",
+           "screen", "search_policy", "macs_target", "dense_gflops", "model_geometry"]
 
 
 def _round_up(n, m):
@@ -395,10 +396,69 @@ def _hsic(x, y, y_kernel, mean_sub):
     return (gx * gy.transpose(-1, -2)).sum((-2, -1))         # trace(G_X G_Y)
 
 
-@torch.no_grad()
-def neuron_scores(neuron_output, prob):
-    """core/imp_rank.py:31-41 for one Mlp: 0.1 * min-max(HSIC(activation of neuron j over [B, N], softmax(logits))) +
-    0.9 * min-max(sum |activation|).  neuron_output [B, N, hidden], prob [B, C] -> [hidden]."""
+# ---- the ranking on the device (csrc/hsic.hip): no [units, B, B] tensor, no vendor BLAS --------------------------------
+def _hsic_elem(dtype):
+    from . import _lib
+    return {torch.bfloat16: _lib.HSIC_BF16, torch.float16: _lib.HSIC_F16, torch.float32: _lib.HSIC_F32}.get(dtype)
+
+
+def hsic_target(y, softmax=False):
+    """W [B, B] = center(y~ y~^T), y~ = p - mean over the batch, p = softmax(y) (softmax=True: y are logits) or y itself:
+    the target kernel of the relevance HSIC, computed once per batch (devit_hsic_target)."""
+    from ._lib import call, ptr, require_device, stream_ptr
+    require_device(y)
+    y = y.detach().float().contiguous()
+    B, C = y.shape
+    W = torch.empty((B, B), dtype=torch.float32, device=y.device)
+    ws = torch.empty((B, C), dtype=torch.float32, device=y.device)
+    call("devit_hsic_target", ptr(y), B, C, int(bool(softmax)), ptr(W), ptr(ws), ws.numel() * 4, stream_ptr())
+    return W
+
+
+def hsic_unit_scores(X, W, group=1, want_act=False, want_kmix=False):
+    """devit_hsic_scores on X [B, N, units * group] (bf16 / f16 / f32, channels contiguous, any batch / token strides: the
+    forward's `neuron_output` / `head_output` are views of padded row buffers and are read in place).
+    Returns (rel [units], act [units] or None, Kmix - 1 [units, B, B] or None), fp32 -- the kernel minus one, zero on the diagonal:
+    what devit_hsic_head_pairs takes (the sums it feeds are against centred kernels; include/devit_hip.h says why)."""
+    from ._lib import call, load, ptr, require_device, stream_ptr
+    require_device(X)
+    if _hsic_elem(X.dtype) is None:
+        X = X.float()
+    if X.stride(2) != 1:
+        X = X.contiguous()
+    B, N, ch = X.shape
+    units = ch // group
+    dev = X.device
+    rel = torch.empty((units,), dtype=torch.float32, device=dev)
+    act = torch.empty((units,), dtype=torch.float32, device=dev) if want_act else None
+    kmix = torch.empty((units, B, B), dtype=torch.float32, device=dev) if want_kmix else None
+    need = load().devit_hsic_scores_workspace(B, N, units)
+    ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    call("devit_hsic_scores", ptr(X), _hsic_elem(X.dtype), B, N, units, group, X.stride(0), X.stride(1), ptr(W), ptr(rel), ptr(act),
+         ptr(kmix), ptr(ws), need, stream_ptr())
+    return rel, act, kmix
+
+
+def _neuron_scores_device(neuron_output, W):
+    hs, act, _ = hsic_unit_scores(neuron_output, W, 1, want_act=True)
+    hs = (hs - hs.min()) / (hs.max() - hs.min())
+    act = (act - act.min()) / (act.max() - act.min())
+    return 0.1 * hs + 0.9 * act
+
+
+def _head_scores_device(head_output, W):
+    from ._lib import call, ptr, stream_ptr
+    B, N, H, hd = head_output.shape
+    if head_output.stride(3) != 1 or head_output.stride(2) != hd:
+        head_output = head_output.contiguous()
+    X = head_output.as_strided((B, N, H * hd), (head_output.stride(0), head_output.stride(1), 1))
+    relv, _, kmix = hsic_unit_scores(X, W, hd, want_kmix=True)
+    red = torch.empty((H,), dtype=torch.float32, device=X.device)
+    call("devit_hsic_head_pairs", ptr(kmix), H, B, ptr(red), stream_ptr())
+    return relv - 0.1 * red
+
+
+def _neuron_scores_torch(neuron_output, prob):
     X = neuron_output.float()
     hs = _hsic(X.permute(2, 0, 1), prob, 'linear', True)
     hs = (hs - hs.min()) / (hs.max() - hs.min())
@@ -407,10 +467,7 @@ def neuron_scores(neuron_output, prob):
     return 0.1 * hs + 0.9 * act
 
 
-@torch.no_grad()
-def head_scores(head_output, prob):
-    """core/imp_rank.py:108-123 for one Attention: relevance(head) - 0.1 * mean redundancy against the other heads, on
-    the head's channel mean.  head_output [B, N, H, hd], prob [B, C] -> [H]."""
+def _head_scores_torch(head_output, prob):
     Hh = head_output.float().mean(-1).permute(2, 0, 1)              # [H, B, N]
     relv = _hsic(Hh, prob, 'linear', True)
     nH = Hh.shape[0]
@@ -419,28 +476,154 @@ def head_scores(head_output, prob):
 
 
 @torch.no_grad()
-def rank_units(model, data_loader, device=None):
-    """One-batch importance ranking of every block's MLP neurons and attention heads (core/imp_rank.py:16-47 and
-    :93-129).  Reads the `neuron_output` / `head_output` the forward leaves on the modules (post-gate values, SURVEY
-    App. D Q3).  Returns (neuron_rank, head_rank): per block an ascending argsort (numpy), the input of
-    masks_from_sparsity.  The reference calls the model in whatever mode it is in (train at that point of
-    distill_sub.py, where a distilled model returns a tuple that F.softmax cannot take); here: eval mode, averaged heads.
-    Host-side torch arithmetic on a single batch: a one-off setup step, not the hot path."""
+def neuron_scores(neuron_output, prob):
+    """core/imp_rank.py:31-41 for one Mlp: 0.1 * min-max(HSIC(activation of neuron j over [B, N], softmax(logits))) +
+    0.9 * min-max(sum |activation|).  neuron_output [B, N, hidden], prob [B, C] -> [hidden].
+    Device tensors run csrc/hsic.hip (2 <= B <= 256); CPU tensors the torch statement of the same formula, which is what the
+    golden ranks pin.  One deviation on the device: a feature column (one neuron at one token) that is constant and NON-zero
+    over the batch has std = 0, the reference shifts it by mean * 1e12 and its HSIC is cancellation noise; the kernel takes
+    pairwise differences of the raw values, which no per-column shift changes, and returns the translation-invariant
+    value.  All-zero columns (masked units) agree."""
+    if neuron_output.is_cuda:
+        return _neuron_scores_device(neuron_output, hsic_target(prob.to(neuron_output.device)))
+    return _neuron_scores_torch(neuron_output, prob)
+
+
+@torch.no_grad()
+def head_scores(head_output, prob):
+    """core/imp_rank.py:108-123 for one Attention: relevance(head) - 0.1 * mean redundancy against the other heads, on
+    the head's channel mean.  head_output [B, N, H, hd], prob [B, C] -> [H].  Device tensors run csrc/hsic.hip (the
+    deviation of neuron_scores applies to the relevance term), CPU tensors the torch statement."""
+    if head_output.is_cuda:
+        return _head_scores_device(head_output, hsic_target(prob.to(head_output.device)))
+    return _head_scores_torch(head_output, prob)
+
+
+@torch.no_grad()
+def rank_units(model, data_loader, device=None, batches=1):
+    """Importance ranking of every block's MLP neurons and attention heads (core/imp_rank.py:16-47 and :93-129).  Reads the
+    `neuron_output` / `head_output` the forward leaves on the modules (post-gate values).  Returns
+    (neuron_rank, head_rank): per block an ascending argsort (numpy), the input of masks_from_sparsity.  The reference
+    calls the model in whatever mode it is in (train at that point of distill_sub.py, where a distilled model returns a
+    tuple that F.softmax cannot take); here: eval mode, averaged heads.  `batches`: the scores of that many batches are
+    summed before the argsort -- the reference's loop is written for it and breaks after the first, so the default is 1.
+    Three launches for the batch's target kernel, two per Mlp and three per Attention (csrc/hsic.hip); the min-max, the
+    0.1 / 0.9 and -0.1 mixes and the argsort are torch ops on [units] vectors."""
+    import itertools
     import numpy as np
-    data, _ = next(iter(data_loader))
-    if device is not None:
-        data = data.to(device)
     was_training = model.training
     model.eval()
-    out = model(data)
-    out = (out[0] + out[1]) / 2 if isinstance(out, tuple) else out
-    prob = torch.softmax(out.float(), dim=-1)
-    neuron_rank, head_rank = [], []
-    for blk in _blocks(model):
-        neuron_rank.append(np.argsort(neuron_scores(blk.mlp.neuron_output, prob).cpu().numpy()))
-        head_rank.append(np.argsort(head_scores(blk.attn.head_output, prob).cpu().numpy()))
+    blocks = _blocks(model)
+    nsum, hsum, seen = [None] * len(blocks), [None] * len(blocks), 0
+    for data, _ in itertools.islice(iter(data_loader), max(1, int(batches))):
+        if device is not None:
+            data = data.to(device)
+        out = model(data)
+        out = (out[0] + out[1]) / 2 if isinstance(out, tuple) else out
+        W = hsic_target(out, softmax=True)
+        for i, blk in enumerate(blocks):
+            ns, hs = _neuron_scores_device(blk.mlp.neuron_output, W), _head_scores_device(blk.attn.head_output, W)
+            nsum[i] = ns if nsum[i] is None else nsum[i] + ns
+            hsum[i] = hs if hsum[i] is None else hsum[i] + hs
+        seen += 1
     model.train(was_training)
-    return neuron_rank, head_rank
+    if seen == 0:
+        raise ValueError("rank_units: the data loader gave no batch")
+    return [np.argsort(s.cpu().numpy()) for s in nsum], [np.argsort(s.cpu().numpy()) for s in hsum]
+
+
+# ------------------------------------------------------------------------------------------------------
+# the policy search (core/shrink_imp.py:66-82 `screen`, :138-179 `model_shrink`; shrink.py:406-418)
+# ------------------------------------------------------------------------------------------------------
+def model_geometry(model):
+    """emb / head / layer / mlp_ratio of the model for flops.macs_g (the reference hard-codes 384 / 6 / 12 / 4)."""
+    blocks = _blocks(model)
+    emb = blocks[0].attn.qkv.weight.shape[1]
+    return dict(emb=emb, head=blocks[0].attn.num_heads, layer=len(blocks), mlp_ratio=blocks[0].mlp.hidden_features // emb)
+
+
+def dense_gflops(**geometry):
+    """Dense forward GFLOPs of the reference's accounting (N = 197, 1000 classes): 9.197764608 for `dedeit`."""
+    from . import flops
+    return flops.forward_gflops(**geometry)
+
+
+def macs_target(shrink_ratio, **geometry):
+    # core/shrink_imp.py:144 `shrink_ratio * 9.19`: a figure in GFLOPs that screen() compares against MACs (half of it); kept
+    return shrink_ratio * dense_gflops(**geometry)
+
+
+def _macs_g_rows(x, layer, emb=768, seq_length=197, mlp_ratio=4, head=12, num_class=1000):
+    """flops.macs_g for every row of x [n, 2 * layer] at once (same operations in the same order, so the same doubles)."""
+    import numpy as np
+    head_dim = emb / head
+    sa = 3 * 2 * seq_length * emb * head_dim + 2 * head_dim * seq_length ** 2 + 2 * head_dim * seq_length ** 2
+    kept_heads = ((1 - x[:, layer:]) * head).astype(np.int64)
+    hidden = (mlp_ratio * (1 - x[:, :layer]) * emb).astype(np.int64)
+    per_block = sa * kept_heads + seq_length * 2 * head_dim * kept_heads * emb + (seq_length * hidden * 2 * emb + seq_length * emb * 2 * hidden)
+    return (2 * 3 * emb * 224 ** 2 + per_block.sum(1) + 2 * emb * num_class) / 1e9 / 2
+
+
+def screen(macs_target, population, lb, ub, layer, rng, max_draws=1 << 26, **geometry):
+    """core/shrink_imp.py:66-82: `population` distinct uniform ratio vectors [neuron ratios (layer), head ratios (layer)]
+    in [lb, ub) whose MACs (flops.macs_g at the given emb / head / mlp_ratio) lie within 2 % of macs_target.  `rng` is a
+    seeded numpy Generator; draws come in chunks that are evaluated at once (for `dedeit` with ub = 0.5 the reference's
+    default ratio 0.3 accepts about one draw in 10^4), every accepted row is then confirmed with flops.macs_g itself.
+    Returns [population, 2 * layer] float64.  Raises after max_draws draws instead of spinning on a target nothing meets."""
+    import numpy as np
+    from . import flops
+    geometry = {k: v for k, v in geometry.items() if k != "layer"}
+    rows, seen, drawn, chunk = [], set(), 0, max(256, 4 * population)
+    while len(rows) < population:
+        if drawn >= max_draws:
+            raise RuntimeError(f"screen: {len(rows)} of {population} candidates within 2 % of {macs_target:.4f} G after {drawn} draws "
+                               f"in [{lb}, {ub}): no such policy is likely (raise --bound or --shrink_ratio)")
+        x = rng.uniform(lb, ub, size=(chunk, 2 * layer))
+        drawn += chunk
+        ok = np.abs(_macs_g_rows(x, layer, **geometry) - macs_target) <= 0.02 * macs_target
+        for r in x[ok]:
+            macs = flops.macs_g(neuron_sparsity=r[:layer], head_sparsity=r[layer:], layer=layer, **geometry)
+            key = r.tobytes()
+            if abs(macs - macs_target) <= 0.02 * macs_target and key not in seen:
+                seen.add(key)
+                rows.append(r)
+                if len(rows) == population:
+                    break
+        chunk = min(chunk * 4, 1 << 16)
+    return np.stack(rows)
+
+
+def search_policy(model, val_loader, neuron_rank, head_rank, shrink_ratio, population, lb, ub, device, seed, log=None, physical=True):
+    """core/shrink_imp.py:138-179 (`model_shrink`): screen `population` candidate policies at shrink_ratio of the dense cost,
+    and score each by the top-1 accuracy of the model masked with it on val_loader.  physical=True evaluates the
+    physically compacted model (compact(): the masked model's function at the shrunk model's FLOPs).  Returns
+    (xp [population, 2 * layer], yp [population]), the content of shrinked_policy.npy / shrinked_accuracy.npy.  The model
+    comes back as it went in: its gates restored, no compacted weights, the same forward bit for bit."""
+    import numpy as np
+    from . import engine, flops
+    geo = model_geometry(model)
+    layer = geo["layer"]
+    target = macs_target(shrink_ratio, **geo)
+    say = log if log is not None else (lambda msg: None)
+    xp = screen(target, population, lb, ub, rng=np.random.default_rng(seed), **geo)
+    before, was_training = get_policy(model), model.training
+    yp = []
+    try:
+        for ratio in xp:
+            load_policy(model, masks_from_sparsity(model, ratio[:layer], ratio[layer:], neuron_rank, head_rank))
+            if physical:
+                compact(model)
+            acc = float(engine.evaluate(val_loader, model, device)['acc1'])
+            uncompact(model)
+            kw = dict(neuron_sparsity=ratio[:layer], head_sparsity=ratio[layer:], **geo)
+            say(f"neuron sparsity {np.round(ratio[:layer], 3).tolist()} head sparsity {np.round(ratio[layer:], 3).tolist()} "
+                f"accuracy {acc:.4f} MACs {flops.macs_g(**kw):.4f} G parameters {flops.params_m(**kw):.4f} M")
+            yp.append(acc)
+    finally:
+        uncompact(model)
+        load_policy(model, before)
+        model.train(was_training)
+    return xp, np.array(yp)
 
 
 def apply_shrink(model, data_loader, shrink_checkpoint, neuron_shrinking, head_shrinking, device=None):

@@ -359,6 +359,36 @@ typedef struct {
 DEVIT_API int devit_index_copy(const devit_index_job* jobs_device, int njobs, int blocks_per_job, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Unit ranking of the shrink stage (csrc/hsic.hip; core/imp_rank.py:16-47 mlp_neuron_rank, :93-129 attn_head_rank,
+ * :175-239 HSICLoss).  For unit u the feature of sample a is x_a[n], n < N tokens: the mean of `group` consecutive
+ * channels X[a][n][u * group ...] (group = 1: an MLP neuron of neuron_output [B][N][hidden]; group = head_dim: a head
+ * of head_output [B][N][H][hd]).
+ *   Kmix_u[a][b] = 1/5 sum_{s = 1, 2, 4, 8, 16} exp(-d2 / (2 s^2)),  d2 = sum_n (x_a[n] - x_b[n])^2   (fp32 differences)
+ *   devit_hsic_target:     W [B][B] = center(y y^T), y = p - mean_a p, p = softmax of the rows (softmax != 0) or the rows
+ *                          themselves (softmax == 0: already probabilities); workspace >= B * C floats
+ *   devit_hsic_scores:     rel[u] = sum_ab Kmix_u[a][b] W[a][b];  act[u] = sum_{a, n} |X[a][n][u]| (optional, group == 1);
+ *                          kmix1 [units][B][B] (optional) receives Kmix_u - 1 (zero diagonal): the sums this kernel feeds are
+ *                          against centred kernels, which a constant does not enter, and on a real model Kmix lies within 1e-3
+ *                          of 1 -- in fp32 the signal is kept only in this form; rel is computed from it, too (W is centred).
+ *                          X: element type DEVIT_HSIC_*, channels
+ *                          contiguous, batch / token strides in elements (the forward's activations are views of padded
+ *                          row buffers).  workspace >= devit_hsic_scores_workspace(B, N, units) bytes, 16-byte aligned.
+ *   devit_hsic_head_pairs: red[h] = 1/(H - 1) sum_{g != h} sum_ab Kmix_h[a][b] center(Kmix_g)[a][b], from kmix1 [H][B][B], H <= 16.
+ * The reference's mean_sub step shifts a feature column by one constant for every sample, which the pairwise distances do
+ * not see; a column that is constant and non-zero over the batch (std = 0: the reference's shift is mean * 1e12 and its
+ * value cancellation noise) gets the translation-invariant value here.  2 <= B <= 256; anything else is DEVIT_ERR_ARG.
+ * One workgroup owns a unit's sums: results do not depend on the launch's timing.
+ * ---------------------------------------------------------------------------------------- */
+enum { DEVIT_HSIC_BF16 = 0, DEVIT_HSIC_F16 = 1, DEVIT_HSIC_F32 = 2 };
+DEVIT_API int devit_hsic_target(const float* y, int B, int C, int softmax, float* W, void* workspace, size_t workspace_bytes,
+                      void* stream);
+DEVIT_API size_t devit_hsic_scores_workspace(int B, int N, int units);
+DEVIT_API int devit_hsic_scores(const void* X, int elem, int B, int N, int units, int group, long long batch_stride,
+                      long long token_stride, const float* W, float* rel, float* act, float* kmix1, void* workspace,
+                      size_t workspace_bytes, void* stream);
+DEVIT_API int devit_hsic_head_pairs(const float* kmix1, int H, int B, float* red, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Patch embedding helpers (timm PatchEmbed used at models/de_vit.py:166-168,258 and token assembly
  * :259-264).  im2row: f32 [B,3,224,224] -> bf16 [B*196][768] with k = c*256 + kh*16 + kw; the
  * projection itself is devit_gemm_bf16 with DEVIT_EPI_PATCH_F32.  embed_tokens writes
