@@ -56,6 +56,11 @@ class BlockBwdIO(C.Structure):
                 ("defer_jobs", C.c_void_p), ("defer_count", C.c_void_p)]
 
 
+class BlockDropout(C.Structure):
+    _fields_ = [("seed", C.c_ulonglong), ("block", C.c_int), ("thr", C.c_uint), ("thr_attn", C.c_uint), ("scale_keep", C.c_float),
+                ("scale_keep_attn", C.c_float), ("tmp", C.c_void_p)]
+
+
 class IndexJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("idx", C.c_void_p), ("rows", C.c_int), ("cols", C.c_int),
                 ("src_ld", C.c_int), ("dst_ld", C.c_int), ("mode", C.c_int), ("elem", C.c_int)]
@@ -82,10 +87,13 @@ LAUNCH_OBSERVER = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(L
 # devit_hsic_scores element types
 HSIC_BF16, HSIC_F16, HSIC_F32 = range(3)
 
+# dropout sites (include/devit_hip.h, "Dropout"): which nn.Dropout of the model a mask belongs to
+DROP_POS, DROP_ATTN, DROP_PROJ, DROP_HIDDEN, DROP_FC2 = range(5)
+
 WGRAD_MAX_JOBS = 48
 ABI_VERSION = 3
 # devit_abi_struct_size(which) -> the mirror it must equal (checked at load time: an array of stale mirrors is misread silently)
-ABI_STRUCTS = {0: Epilogue, 1: Operand, 2: BlockWeights, 3: BlockWgrads, 4: BlockActs, 5: BlockBwdIO, 6: IndexJob, 7: WgradJob, 8: LaunchInfo}
+ABI_STRUCTS = {0: Epilogue, 1: Operand, 2: BlockWeights, 3: BlockWgrads, 4: BlockActs, 5: BlockBwdIO, 6: IndexJob, 7: WgradJob, 8: LaunchInfo, 9: BlockDropout}
 
 
 class DevitError(RuntimeError):
@@ -93,6 +101,7 @@ class DevitError(RuntimeError):
 
 
 _P, _I, _F, _Z, _LL = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_longlong
+_U64, _U32 = C.c_ulonglong, C.c_uint
 
 # name -> (restype, argtypes); must list every symbol of include/devit_hip.h (tests check this)
 SIGNATURES = {
@@ -116,10 +125,18 @@ SIGNATURES = {
     "devit_encoder_fwd": (_I, [_I, C.POINTER(BlockWeights), C.POINTER(BlockActs), _I, _I, _I, _F, _P]),
     "devit_block_bwd": (_I, [C.POINTER(BlockWeights), C.POINTER(BlockActs), C.POINTER(BlockWgrads), C.POINTER(BlockBwdIO),
                              _I, _I, _I, _F, _P]),
+    "devit_encoder_fwd_drop": (_I, [_I, C.POINTER(BlockWeights), C.POINTER(BlockActs), C.POINTER(BlockDropout), _I, _I, _I, _F, _P]),
+    "devit_block_bwd_drop": (_I, [C.POINTER(BlockWeights), C.POINTER(BlockActs), C.POINTER(BlockWgrads), C.POINTER(BlockBwdIO),
+                                  C.POINTER(BlockDropout), _I, _I, _I, _F, _P]),
     "devit_attn_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
     "devit_attn_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "devit_attn_fwd_rows": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P]),
     "devit_attn_bwd_rows": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "devit_dropout_mask": (_I, [_U64, _I, _I, _U32, _I, _I, _LL, _P, _P]),
+    "devit_dropout_apply": (_I, [_P, _I, _I, _I, _I, _LL, _U64, _I, _I, _U32, _F, _P, _P]),
+    "devit_dropout_residual": (_I, [_P, _P, _P, _P, _I, _I, _I, _U64, _I, _I, _U32, _F, _P]),
+    "devit_attn_fwd_drop": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _U32, _F, _P]),
+    "devit_attn_bwd_drop": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _U32, _F, _P]),
     "devit_index_copy": (_I, [_P, _I, _I, _P]),
     "devit_hsic_target": (_I, [_P, _I, _I, _I, _P, _P, _Z, _P]),
     "devit_hsic_scores_workspace": (_Z, [_I, _I, _I]),

@@ -35,6 +35,7 @@ extern "C" size_t devit_abi_struct_size(int which) {
     case 6: return sizeof(devit_index_job);
     case 7: return sizeof(devit_wgrad_job);
     case 8: return sizeof(devit_launch_info);
+    case 9: return sizeof(devit_block_dropout);
     default: return 0;
   }
 }

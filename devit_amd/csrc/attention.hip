@@ -11,6 +11,7 @@
 #include <stdlib.h>
 
 #include "devit_common.h"
+#include "dropout.h"
 
 namespace {
 
@@ -132,147 +133,22 @@ constexpr int OSLAB_ROW = 144;       // bytes per slab row: 128 + 16 (16 rows of
 constexpr int FWD_ROWS = FWD_WAVES == 8 ? KROWS : MAXT * 16;           // rows of the K / V images
 constexpr int FWD_IMG = FWD_ROWS * HD * 2;
 
+// DROP (attn_fwd_drop_kernel; nn.Dropout on the softmax, models/de_vit.py:72): P is normalised, then masked and scaled by 1 / (1 - p) -- here
+// the dropped e^{s - max} are zeroed before they become the MFMA operand and the row's 1 / sum carries the scale; sum and lse are of the
+// undropped row.  A lane's four score registers of a key tile are four consecutive keys of its query row: one Philox call (dropout.h).
+// The kernel body is csrc/attention_fwd.inc, included once per kernel: the preprocessor (ATTN_DROP), not a template flag, takes the dropout lines
+// out, so that attn_fwd_kernel is compiled from the very tokens it had before dropout existed (tools/kernel_digest.py: same machine code).
 template <bool F16>
 __global__ __launch_bounds__(FWD_WAVES * 64, FWD_WAVES == 8 ? 4 : 3) void attn_fwd_kernel(const AttnFwdArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* k_img = smem;
-  char* v_img = smem + FWD_IMG;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
-  const int D = a.H * HD, N = a.N, NQ = a.NQ;
-  const size_t rs = (size_t)a.q_rs, krs = (size_t)a.kv_rs;
-  const __bf16* qbase = a.q + (size_t)b * NQ * rs + h * HD;
-  const float c2 = a.scale * 1.4426950408889634f;  // scores in log2 domain
-#ifdef DEVIT_ATTN_STAMP    // diagnostic build (tools/attn_stamps.py): head_gate carries a u64 stamp buffer, 8 per workgroup
-  unsigned long long* stamps = (unsigned long long*)a.head_gate + (size_t)blockIdx.x * 8;
-  const float gate = 1.0f;
-  if (tid == 0) { stamps[0] = __builtin_amdgcn_s_memrealtime(); stamps[1] = __builtin_amdgcn_s_memtime(); }
-#else
-  const float gate = a.head_gate ? a.head_gate[h] : 1.0f;
-#endif
-  const int ntile = (NQ + 15) >> 4;                  // query tiles
-  const int g = lane >> 4, lc = lane & 15;
-  const int tq = (lane >> 2) & 3, tp = lane & 3;     // transposed-read row / column-quad of this lane
-  constexpr int QT = (MAXT + FWD_WAVES - 1) / FWD_WAVES;   // query tiles per wave
-  // Q fragments of ALL this wave's query tiles first, then the K / V images: one exposed HBM latency per workgroup
-  // (fetched in MFMA layout, 16 rows x 64 bytes per instruction; whole 128-byte rows + a lane trade afterwards measured 0.04 ms
-  // per step SLOWER, profiles/r03_B_attention_rows.txt)
-  bf16x8 qall[QT][2];
-#pragma unroll
-  for (int it = 0; it < QT; ++it) {
-    const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-    const int q_ = (wave + it * FWD_WAVES) * 16 + lc;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-      qall[it][kk] = (wave + it * FWD_WAVES < ntile && q_ < NQ) ? *(const bf16x8*)(qbase + (size_t)q_ * rs + kk * 32 + g * 8) : z;
-  }
-  // K and V images by LDS-DMA: no register round trip, no ds_write pass (forward -6 ... -10 % against register staging, same
-  // box, profiles/r02_l_attention_dma_prologue.txt); the Q fragments above go straight to registers in MFMA layout
-  dma_image<FWD_WAVES, FWD_ROWS>(k_img, a.k + (size_t)b * N * krs + h * HD, krs, N, wave, lane);
-  dma_image<FWD_WAVES, FWD_ROWS>(v_img, a.v + (size_t)b * N * krs + h * HD, krs, N, wave, lane);
-#ifdef DEVIT_ATTN_STAMP
-  if (tid == 0) stamps[6] = __builtin_amdgcn_s_memtime();      // loads issued
-#endif
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share has landed; the barrier covers the others'
-#ifdef DEVIT_ATTN_STAMP
-  if (tid == 0) stamps[7] = __builtin_amdgcn_s_memtime();      // ... landed (wave 0)
-#endif
-  __syncthreads();
-#ifdef DEVIT_ATTN_STAMP
-  if (tid == 0) stamps[2] = __builtin_amdgcn_s_memtime();      // images complete
-#endif
-  const int tmask = N >> 4;                          // first key tile that contains a key >= N
-
-#pragma unroll
-  for (int it = 0; it < QT; ++it) {
-    const int qt = wave + it * FWD_WAVES;
-    if (qt >= ntile) break;
-    const int q = qt * 16 + lc;                      // this lane's query
-    f32x4 s[MAXT + 1];
-#pragma unroll
-    for (int t = 0; t < MAXT; ++t) {
-      s[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) s[t] = mfma16t<F16>(img_row_frag(k_img, t * 16, kk, lane), qall[it][kk], s[t]);
-    }
-    // raw-score row max (scale > 0); only tiles >= tmask can hold padded keys
-    float mx = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < MAXT; ++t) {
-      if (t >= tmask) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (t * 16 + g * 4 + r >= N) s[t][r] = -INFINITY;
-      }
-      mx = fmaxf(fmaxf(fmaxf(s[t][0], s[t][1]), fmaxf(s[t][2], s[t][3])), mx);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float mxs = mx * c2;
-    float sum = 0.f;
-#pragma unroll
-    for (int t = 0; t < MAXT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        s[t][r] = __builtin_amdgcn_exp2f(fmaf(s[t][r], c2, -mxs));   // exp2(-inf) = 0 for padded keys
-        sum += s[t][r];
-      }
-    s[MAXT] = (f32x4){0.f, 0.f, 0.f, 0.f};           // keys 208..223
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    if (a.lse && g == 0 && q < NQ) a.lse[((size_t)b * a.H + h) * NQ + q] = (mxs + log2f(sum)) * 0.6931471805599453f;
-
-    f32x4 o[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 7; ++ks) {
-      const f32x4 p0 = s[2 * ks], p1 = s[2 * ks + 1];
-      const bf16x8 pf = cvt8<F16>(p0, p1);
-      // keys of tile 2ks / 2ks+1 for this lane group; tile 13 (keys 208..223) has P = 0 and, in the 208-row image, no rows:
-      // its operand is read from tile 12's rows (any finite values do)
-      const int r0 = ks * 32 + g * 4 + tq, r1 = (FWD_ROWS < KROWS && ks == 6) ? r0 : r0 + 16;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const int ch = dt * 2 + (tp >> 1), sub = (tp & 1) * 8;
-        const bf16x8 vf = cat8(lds_tr_read(v_img + img_off(r0, ch) + sub), lds_tr_read(v_img + img_off(r1, ch) + sub));
-        o[dt] = mfma16t<F16>(vf, pf, o[dt]);         // O^T[d][q] += V^T[d][key] P^T[key][q]
-      }
-    }
-#if DEVIT_ATTN_OUT_ROWS
-    {
-      // Lane (g, lc) holds O[q = lc][d = 16 dt + 4 g + r]: stored from here, an instruction covers 16 rows x 32 bytes -- quarter
-      // cache lines, four times the transactions of the bytes (ablation: the output stores cost 10 / 25 us of a 62 / 111 us
-      // launch for a quarter of the bytes it reads).  Through this wave's private [16][64] LDS slab instead: two
-      // instructions of eight whole 128-byte rows.
-      const float sc = gate / sum;
-      char* slab = smem + 2 * FWD_IMG + wave * (16 * OSLAB_ROW);
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) *(bf16x4*)(slab + lc * OSLAB_ROW + (dt * 16 + g * 4) * 2) = cvt4<F16>(o[dt] * sc);
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const int row = half * 8 + (lane >> 3), c8 = lane & 7, qr = qt * 16 + row;
-        const bf16x8 v = *(const bf16x8*)(slab + row * OSLAB_ROW + c8 * 16);     // (same wave wrote it: ordered by lgkmcnt)
-        if (qr < NQ) *(bf16x8*)(a.out + ((size_t)b * NQ + qr) * D + h * HD + c8 * 8) = v;
-      }
-    }
-#else
-    if (q < NQ) {
-      const float sc = gate / sum;
-      __bf16* orow = a.out + ((size_t)b * NQ + q) * D + h * HD + g * 4;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        *(bf16x4*)(orow + dt * 16) = cvt4<F16>(o[dt] * sc);
-      }
-    }
-#endif
-  }
-#ifdef DEVIT_ATTN_STAMP
-  if (tid == 0) stamps[3] = __builtin_amdgcn_s_memtime();      // wave 0's compute + store issue done
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (tid == 0) { stamps[4] = __builtin_amdgcn_s_memtime(); stamps[5] = __builtin_amdgcn_s_memrealtime(); }
-#endif
+#define ATTN_DROP 0
+#include "attention_fwd.inc"
+#undef ATTN_DROP
+}
+template <bool F16>
+__global__ __launch_bounds__(FWD_WAVES * 64, FWD_WAVES == 8 ? 4 : 3) void attn_fwd_drop_kernel(const AttnFwdArgs a, const DropKey dk) {
+#define ATTN_DROP 1
+#include "attention_fwd.inc"
+#undef ATTN_DROP
 }
 
 // ------------------------------------------------------------------------------------------
@@ -357,261 +233,20 @@ __device__ __forceinline__ void dma_block(char* blk, const __bf16* src, size_t r
   dma1(g, (unsigned)(size_t)LDS_PTR(blk) + (unsigned)wave * 1024u);
 }
 
+// DROP (attn_bwd4_drop_kernel): with m = keep / (1 - p) regenerated from the forward's counters, dV = (P m)^T dO and dS = P (dP m - delta);
+// delta = rowsum(dO O) as before, O having been formed from the dropped P.  Here the KEY is on the lane and a lane's four registers are four
+// QUERY rows, i.e. four counters; the four lanes of a quad hold four consecutive keys of those same rows, so lane p of the quad runs the
+// one Philox call of row p and the quad trades words (three DPP quad permutes): one call per lane for four elements, as in the forward.
+// (body: csrc/attention_bwd.inc, included once per kernel like the forward's)
 __global__ __launch_bounds__(B4_WAVES * 64, 2) void attn_bwd4_kernel(const AttnBwdArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* k_img = smem;
-  char* qd = smem + IMG_BYTES;                       // QD_NST stages x {Q block [32][64], dO block [32][64]}
-  char* dst = qd + QD_NST * QD_STAGE;                // dS^T of the current block: [224 keys][DST4_STRIDE]
-  float* lse2 = (float*)(dst + DST4_BYTES);
-  float* delta = lse2 + KROWS;
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
-  const int D = a.H * HD, N = a.N, NQ = a.NQ;
-  const size_t rs = (size_t)a.q_rs, krs = (size_t)a.kv_rs;
-  const __bf16* qbase = a.q + (size_t)b * NQ * rs + h * HD;
-  const __bf16* kbase = a.k + (size_t)b * N * krs + h * HD;
-  const __bf16* vbase = a.v + (size_t)b * N * krs + h * HD;
-#ifdef DEVIT_ATTN_STAMP    // diagnostic build (tools/attn_stamps.py): head_gate carries a u64 stamp buffer, 8 per workgroup
-  unsigned long long* stamps = (unsigned long long*)a.head_gate + (size_t)blockIdx.x * 8;
-  const float gate = 1.0f;
-  if (tid == 0) { stamps[0] = __builtin_amdgcn_s_memrealtime(); stamps[1] = __builtin_amdgcn_s_memtime(); }
-#define ATTN_STAMP(i) do { if (tid == 0) stamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-  const float gate = a.head_gate ? a.head_gate[h] : 1.0f;
-#define ATTN_STAMP(i) do { } while (0)
-#endif
-  const __bf16* dobase = a.dout + (size_t)b * NQ * D + h * HD;
-  const __bf16* obase = a.out + (size_t)b * NQ * D + h * HD;
-  const int g = lane >> 4, lc = lane & 15;
-  const int tq = (lane >> 2) & 3, tp = lane & 3;
-  const int ntile = (N + 15) >> 4;
-  const int nblk = (NQ + 31) >> 5;
-
-  // ---- prologue: K image and the first Q / dO block by LDS-DMA; V fragments of this wave's key tiles straight to registers;
-  // delta[q] = sum_d dO[q][d] O[q][d] and lse from global rows
-  dma_image<B4_WAVES>(k_img, kbase, krs, N, wave, lane);
-#pragma unroll
-  for (int pb = 0; pb < QD_NST - 1; ++pb)
-    if (pb < nblk) {
-      dma_block(qd + pb * QD_STAGE, qbase, rs, pb * 32, NQ, wave, lane);
-      dma_block(qd + pb * QD_STAGE + 32 * HD * 2, dobase, (size_t)D, pb * 32, NQ, wave, lane);
-    }
-  bf16x8 vf[B4_KT][2];
-#pragma unroll
-  for (int t = 0; t < B4_KT; ++t) {
-    const int key = min((wave + t * B4_WAVES) * 16 + lc, N - 1);
-#pragma unroll
-#ifdef DEVIT_ATTN_ABL_NOV       // ablation build (round 6): no V loads
-    for (int kk = 0; kk < 2; ++kk) asm volatile("" : "=v"(vf[t][kk]));
-#else
-    for (int kk = 0; kk < 2; ++kk) vf[t][kk] = *(const bf16x8*)(vbase + (size_t)key * krs + kk * 32 + g * 8);
-#endif
-  }
-  {
-    constexpr int NT = B4_WAVES * 64;
-    RowRegs<NT> dr, orr;
-#ifdef DEVIT_ATTN_ABL_NODELTA   // ablation build (round 6): no dO / O rows for delta
-#pragma unroll
-    for (int it = 0; it < RowRegs<NT>::ITERS; ++it) { asm volatile("" : "=v"(dr.v[it])); asm volatile("" : "=v"(orr.v[it])); }
-#else
-    fetch_rows(dr, dobase, (size_t)D, NQ, tid);
-    fetch_rows(orr, obase, (size_t)D, NQ, tid);
-#endif
-    ATTN_STAMP(6);                                     // every prologue load is issued
-#ifdef DEVIT_ATTN_STAMP
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ATTN_STAMP(7);                                     // ... and has landed
-#endif
-    for (int i = tid; i < DST4_BYTES / 16; i += NT) ((f32x4*)dst)[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int it = 0; it < RowRegs<NT>::ITERS; ++it) {
-      const int idx = tid + it * NT, row = idx >> 3, c = idx & 7;
-      float dl = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) dl += bf2f(dr.v[it][e]) * bf2f(orr.v[it][e]);
-      dl += __shfl_xor(dl, 1, 64);
-      dl += __shfl_xor(dl, 2, 64);
-      dl += __shfl_xor(dl, 4, 64);
-      if (c == 0 && row < KROWS) {
-        delta[row] = dl * a.scale;                   // pre-scaled: dS = P * (dP * gate * scale - delta * scale)
-        lse2[row] = row < NQ ? a.lse[((size_t)b * a.H + h) * NQ + row] * 1.4426950408889634f : 0.f;
-      }
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  ATTN_STAMP(2);
-
-  const float c2 = a.scale * 1.4426950408889634f;
-  const float gs = gate * a.scale;
-  f32x4 dv[B4_KT][4], dk[B4_KT][4];  // [key tile of this wave][d tile]: rows d = 4g + r, col key = lc
-#pragma unroll
-  for (int i = 0; i < B4_KT; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      dv[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      dk[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-
-#ifdef DEVIT_ATTN_ABL_NOMAIN    // ablation build (round 6): prologue + final stores only
-  for (int qb = 0; qb < (a.N < 0 ? nblk : 0); ++qb) {
-#else
-  for (int qb = 0; qb < nblk; ++qb) {
-#endif
-    const char* q_blk = qd + (qb & (QD_NST - 1)) * QD_STAGE;
-    const char* do_blk = q_blk + 32 * HD * 2;
-    // Q / dO of block qb + 3 into the stage block qb - 1 was read from (every wave is past that block's barriers).  Exactly
-    // two LDS-DMA instructions per wave and block: the counted wait below relies on it.
-    if (qb + QD_NST - 1 < nblk) {
-      char* nq = qd + ((qb + QD_NST - 1) & (QD_NST - 1)) * QD_STAGE;
-      dma_block(nq, qbase, rs, (qb + QD_NST - 1) * 32, NQ, wave, lane);
-      dma_block(nq + 32 * HD * 2, dobase, (size_t)D, (qb + QD_NST - 1) * 32, NQ, wave, lane);
-    }
-    // ---- per key tile of this wave: S and dP against the block's two query tiles -> P, dS (registers = MFMA operands, dS^T also
-    // to LDS), then dV^T += dO^T P and dK^T += Q^T dS.  The block's Q / dO fragments are read from LDS per tile, not held
-    // across tiles: with 128 accumulator and 32 V-fragment registers there is no room for them (256 per wave at two
-    // workgroups per CU), and LDS has the bandwidth (~70 KB per wave and block).
-#pragma unroll
-    for (int t = 0; t < B4_KT; ++t) {
-      const int kt = wave + t * B4_WAVES;
-      if (kt < ntile) {
-        asm volatile("" ::: "memory");                 // keep hipcc from hoisting (and keeping alive) the loop-invariant LDS reads
-        bf16x8 kf[2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) kf[kk] = img_row_frag(k_img, kt * 16, kk, lane);
-        f32x4 pp[2], ds[2];
-        const bool kok = kt * 16 + lc < N;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          f32x4 sv = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int kk = 0; kk < 2; ++kk) {
-            sv = mfma16(img_row_frag(q_blk, i * 16, kk, lane), kf[kk], sv);       // S[q][key], key on the lane
-            dp = mfma16(img_row_frag(do_blk, i * 16, kk, lane), vf[t][kk], dp);   // dP[q][key] (before the head gate)
-          }
-          const f32x4 l2 = *(const f32x4*)(lse2 + qb * 32 + i * 16 + g * 4), dl = *(const f32x4*)(delta + qb * 32 + i * 16 + g * 4);
-          // The kernel is bound by vector-instruction issue (~1150 per wave and block before this form), not by MFMA or
-          // memory: four instructions per element on the interior (fma, v_exp, fma, mul), the masks only where padded keys
-          // (last key tile) or padded queries (last block) exist -- wave-uniform branch.
-          if (kt * 16 + 16 <= N && qb * 32 + i * 16 + 16 <= NQ) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const float p = __builtin_amdgcn_exp2f(fmaf(sv[r], c2, -l2[r]));
-              pp[i][r] = p;
-              ds[i][r] = p * fmaf(dp[r], gs, -dl[r]);
-            }
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const bool ok = kok && (qb * 32 + i * 16 + g * 4 + r < NQ);
-              const float p = ok ? __builtin_amdgcn_exp2f(fmaf(sv[r], c2, -l2[r])) : 0.f;
-              pp[i][r] = p;
-              ds[i][r] = p * fmaf(dp[r], gs, -dl[r]);
-            }
-          }
-          // dS^T[key][q = 16 i + 4 g + r], 4 consecutive queries = one 8-byte store
-          const bf16x4 dsb = {f2bf(ds[i][0]), f2bf(ds[i][1]), f2bf(ds[i][2]), f2bf(ds[i][3])};
-          *(bf16x4*)(dst + (kt * 16 + lc) * (DST4_STRIDE * 2) + (i * 16 + g * 4) * 2) = dsb;
-        }
-        const bf16x8 pf = {f2bf(pp[0][0]), f2bf(pp[0][1]), f2bf(pp[0][2]), f2bf(pp[0][3]),
-                           f2bf(pp[1][0]), f2bf(pp[1][1]), f2bf(pp[1][2]), f2bf(pp[1][3])};
-        const bf16x8 dsf = {f2bf(ds[0][0]), f2bf(ds[0][1]), f2bf(ds[0][2]), f2bf(ds[0][3]),
-                            f2bf(ds[1][0]), f2bf(ds[1][1]), f2bf(ds[1][2]), f2bf(ds[1][3])};
-        // A operands dO^T, Q^T: k-slot (g, j) = query 16 (j>>2) + 4g + (j&3), transposed reads of the block images
-        const int r0 = g * 4 + tq, r1 = r0 + 16;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          const int ch = dt * 2 + (tp >> 1), sub = (tp & 1) * 8;
-          const bf16x8 dot = cat8(lds_tr_read(do_blk + img_off(r0, ch) + sub), lds_tr_read(do_blk + img_off(r1, ch) + sub));
-          const bf16x8 qtt = cat8(lds_tr_read(q_blk + img_off(r0, ch) + sub), lds_tr_read(q_blk + img_off(r1, ch) + sub));
-          dv[t][dt] = mfma16(dot, pf, dv[t][dt]);      // dV^T[d][key] += dO^T[d][q] P[q][key]
-          dk[t][dt] = mfma16(qtt, dsf, dk[t][dt]);     // dK^T[d][key] += Q^T[d][q] dS[q][key]
-        }
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                       // Y1: dS^T of this block complete
-    asm volatile("" ::: "memory");                      // (s_barrier is IntrNoMem: no LDS access may be moved across it)
-    // This wave's share of block qb + 1 must have landed before Y2.  vmcnt retires in order; DMA(qb + 1) was issued at the top of
-    // iteration qb - 2, and newer than its two instructions are EIGHT operations: the two dq stores of block qb - 2, DMA(qb + 2)
-    // x 2, the two dq stores of block qb - 1, DMA(qb + 3) x 2.  vmcnt(6) is therefore stricter than necessary by the two oldest
-    // stores (issued two blocks ago: free); do NOT read the 6 as the exact count and trim the wait by it.  All of these exist for
-    // every block that has a successor (a block with a successor is full: both of its dq stores are issued by every wave),
-    // and without them the wait is only stricter.
-    if (qb + 1 < nblk) {
-      if (qb + QD_NST - 1 < nblk) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    {
-      // dQ^T[d][q] = sum_key K^T[d][key] dS^T[key][q]: wave -> d tile, both query tiles of the block
-      f32x4 dq[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-      for (int ks = 0; ks < 7; ++ks) {
-        const int kr = ks * 32 + g * 8 + tq;
-        const bf16x8 kfr = img_tr_frag(k_img, ks * 32, wave * 16, lane);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const char* pb = dst + kr * (DST4_STRIDE * 2) + (i * 16 + tp * 4) * 2;
-          const bf16x8 bfr = cat8(lds_tr_read(pb), lds_tr_read(pb + 4 * DST4_STRIDE * 2));
-          dq[i] = mfma16(kfr, bfr, dq[i]);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int q = qb * 32 + i * 16 + lc;
-        if (q < NQ) {
-          const size_t o = ((size_t)b * NQ + q) * a.dq_rs + h * HD + wave * 16 + g * 4;
-          store_grad4(a.dq + o, a.dq_add ? a.dq_add + o : nullptr, dq[i]);
-        }
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                       // Y2: dS^T free again; every wave's share of block qb + 1 is in LDS
-    asm volatile("" ::: "memory");
-  }
-  ATTN_STAMP(3);
-  // ---- dK, dV of this wave's key tiles through a private fp32 LDS slab: whole 128-byte rows, 16 bytes per lane
-  __syncthreads();                                   // every wave has finished reading the images / dS^T
-  {
-    constexpr int SROW = 272;
-    char* slab = smem + wave * (2 * 16 * SROW);
-#pragma unroll
-    for (int t = 0; t < B4_KT; ++t) {
-      const int kt = wave + t * B4_WAVES;
-      if (kt >= ntile) break;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        *(f32x4*)(slab + lc * SROW + (dt * 16 + g * 4) * 4) = dk[t][dt];
-        *(f32x4*)(slab + 16 * SROW + lc * SROW + (dt * 16 + g * 4) * 4) = dv[t][dt] * gate;
-      }
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const int row = half * 8 + (lane >> 3), c8 = lane & 7, key = kt * 16 + row;
-        if (key < N) {
-          const size_t oo = ((size_t)b * N + key) * a.dkv_rs + h * HD + c8 * 8;
-#pragma unroll
-          for (int which = 0; which < 2; ++which) {            // 0: dK, 1: dV
-            const char* src = slab + which * 16 * SROW + row * SROW + c8 * 32;
-            f32x4 lo = *(const f32x4*)src, hi = *(const f32x4*)(src + 16);
-            const __bf16* add = which ? a.dv_add : a.dk_add;
-            if (add) {
-              const bf16x8 e = *(const bf16x8*)(add + oo);
-              lo += (f32x4){bf2f(e[0]), bf2f(e[1]), bf2f(e[2]), bf2f(e[3])};
-              hi += (f32x4){bf2f(e[4]), bf2f(e[5]), bf2f(e[6]), bf2f(e[7])};
-            }
-            const bf16x8 v = {f2bf(lo[0]), f2bf(lo[1]), f2bf(lo[2]), f2bf(lo[3]), f2bf(hi[0]), f2bf(hi[1]), f2bf(hi[2]), f2bf(hi[3])};
-            *(bf16x8*)((which ? a.dv : a.dk) + oo) = v;
-          }
-        }
-      }
-    }
-  }
-#ifdef DEVIT_ATTN_STAMP
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (tid == 0) { stamps[4] = __builtin_amdgcn_s_memtime(); stamps[5] = __builtin_amdgcn_s_memrealtime(); }
-#endif
+#define ATTN_DROP 0
+#include "attention_bwd.inc"
+#undef ATTN_DROP
+}
+__global__ __launch_bounds__(B4_WAVES * 64, 2) void attn_bwd4_drop_kernel(const AttnBwdArgs a, const DropKey dkey) {
+#define ATTN_DROP 1
+#include "attention_bwd.inc"
+#undef ATTN_DROP
 }
 
 constexpr int FWD_LDS = 2 * FWD_IMG + (DEVIT_ATTN_OUT_ROWS ? FWD_WAVES * 16 * OSLAB_ROW : 0);   // 57344 + 18432: two workgroups per CU
@@ -633,6 +268,30 @@ int launch_attn_fwd(const AttnFwdArgs& a, int dtype16, void* stream) {
     hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3(a.B * a.H), dim3(FWD_WAVES * 64), FWD_LDS, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(attn_fwd_kernel<false>, dim3(a.B * a.H), dim3(FWD_WAVES * 64), FWD_LDS, (hipStream_t)stream, a);
+  DEVIT_LAUNCH_CHECK();
+  return DEVIT_OK;
+}
+
+int launch_attn_fwd_drop(const AttnFwdArgs& a, const DropKey& dk, void* stream) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_drop_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FWD_LDS);
+    DEVIT_CHECK(e == hipSuccess, DEVIT_ERR_LAUNCH, "devit_attn_fwd_drop: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(attn_fwd_drop_kernel<false>, dim3(a.B * a.H), dim3(FWD_WAVES * 64), FWD_LDS, (hipStream_t)stream, a, dk);
+  DEVIT_LAUNCH_CHECK();
+  return DEVIT_OK;
+}
+
+int launch_attn_bwd_drop(const AttnBwdArgs& a, const DropKey& dk, void* stream) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute((const void*)attn_bwd4_drop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BWD4_LDS);
+    DEVIT_CHECK(e == hipSuccess, DEVIT_ERR_LAUNCH, "devit_attn_bwd_drop: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(attn_bwd4_drop_kernel, dim3(a.B * a.H), dim3(B4_WAVES * 64), BWD4_LDS, (hipStream_t)stream, a, dk);
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
 }
@@ -700,6 +359,37 @@ extern "C" int devit_attn_bwd(const void* qkv, const void* out, const void* dout
                 ad, ad ? ad + D : nullptr, ad ? ad + 2 * D : nullptr, d, d + D, d + 2 * D,
                 B, N, N, H, 3 * D, 3 * D, 3 * D, 3 * D, scale};
   return devit_observed(stream, [&] { return attn_info("devit_attn_bwd", B, N, 0, H, dqkv_add != nullptr); }, [&] { return launch_attn_bwd(a, stream); });
+}
+
+// The packed entry points with nn.Dropout on the softmax (site 1 of dropout.h, block = the encoder block's index): bf16 only (training).
+extern "C" int devit_attn_fwd_drop(const void* qkv, void* out, float* lse, const float* head_gate, int B, int N, int H, int head_dim,
+                                   float scale, unsigned long long seed, int block, unsigned thr, float scale_keep, void* stream) {
+  DEVIT_CHECK(qkv && out && block >= 0, DEVIT_ERR_ARG, "devit_attn_fwd_drop: bad argument");
+  DEVIT_CHECK(head_dim == HD && N > 0 && N <= MAXT * 16 && B > 0 && H > 0, DEVIT_ERR_SHAPE,
+              "devit_attn_fwd_drop: needs head_dim == 64 and N <= 208 (got hd=%d N=%d)", head_dim, N);
+  const int D = H * HD;
+  const __bf16* p = (const __bf16*)qkv;
+  AttnFwdArgs a{p, p + D, p + 2 * D, (__bf16*)out, lse, head_gate, B, N, N, H, 3 * D, 3 * D, scale};
+  const DropKey dk = drop_key(seed, DROP_SITE_ATTN, block, thr, scale_keep);
+  return devit_observed(stream, [&] { return attn_info("devit_attn_fwd_drop", B, N, 0, H); }, [&] { return launch_attn_fwd_drop(a, dk, stream); });
+}
+
+extern "C" int devit_attn_bwd_drop(const void* qkv, const void* out, const void* dout, const float* lse, const float* head_gate,
+                                   const void* dqkv_add, void* dqkv, int B, int N, int H, int head_dim, float scale,
+                                   unsigned long long seed, int block, unsigned thr, float scale_keep, void* stream) {
+  DEVIT_CHECK(qkv && out && dout && lse && dqkv && block >= 0, DEVIT_ERR_ARG, "devit_attn_bwd_drop: bad argument");
+  DEVIT_CHECK(head_dim == HD && N > 0 && N <= MAXT * 16 && B > 0 && H > 0, DEVIT_ERR_SHAPE,
+              "devit_attn_bwd_drop: needs head_dim == 64 and N <= 208 (got hd=%d N=%d)", head_dim, N);
+  const int D = H * HD;
+  const __bf16* p = (const __bf16*)qkv;
+  const __bf16* ad = (const __bf16*)dqkv_add;
+  __bf16* d = (__bf16*)dqkv;
+  AttnBwdArgs a{p, p + D, p + 2 * D, (const __bf16*)out, (const __bf16*)dout, lse, head_gate,
+                ad, ad ? ad + D : nullptr, ad ? ad + 2 * D : nullptr, d, d + D, d + 2 * D,
+                B, N, N, H, 3 * D, 3 * D, 3 * D, 3 * D, scale};
+  const DropKey dk = drop_key(seed, DROP_SITE_ATTN, block, thr, scale_keep);
+  return devit_observed(stream, [&] { return attn_info("devit_attn_bwd_drop", B, N, 0, H, dqkv_add != nullptr); },
+                        [&] { return launch_attn_bwd_drop(a, dk, stream); });
 }
 
 extern "C" int devit_attn_bwd_rows(const void* q, int q_ld, const void* kv, int kv_ld, const void* out, const void* dout,

@@ -130,12 +130,17 @@ int check_dims(int B, int N, int D, int Da, int Hd) {
   return DEVIT_OK;
 }
 
-int block_fwd(const Ctx& c, const devit_block_weights& w, const devit_block_acts& a) {
+// d: NULL, or the block's dropout (devit_block_dropout).  thr == 0 and thr_attn == 0 (or d == NULL) is today's sequence, launch for launch.
+int block_fwd(const Ctx& c, const devit_block_weights& w, const devit_block_acts& a, const devit_block_dropout* d = nullptr) {
   const int D = c.D, Da = w.attn_width, Hd = w.hidden, H = w.num_heads;
   TRY(check_dims(c.B, c.N, D, Da, Hd));
   DEVIT_CHECK(H > 0 && Da == H * 64, DEVIT_ERR_SHAPE, "block: attn_width %d != heads %d * 64", Da, H);
   const bool save = a.flags & DEVIT_BLK_SAVE;
   const int t16 = w.dtype16;
+  const bool drop = d && d->thr > 0, drop_attn = d && d->thr_attn > 0;
+  DEVIT_CHECK(!(drop || drop_attn) || (t16 == 0 && d->block >= 0), DEVIT_ERR_ARG, "devit_encoder_fwd_drop: dropout runs on bf16 blocks (training)");
+  DEVIT_CHECK(!drop || (d->tmp && !(a.flags & DEVIT_BLK_ATT)), DEVIT_ERR_ARG,
+              "devit_encoder_fwd_drop: p > 0 needs the fp32 temporary and cannot also store the attention-branch output (DEVIT_BLK_ATT)");
   DEVIT_CHECK(t16 == 0 || (t16 == 1 && !save), DEVIT_ERR_ARG,
               "devit_encoder_fwd: dtype16 = %d; f16 is the frozen-teacher forward (no DEVIT_BLK_SAVE: the backward kernels are bf16)", t16);
   void* const* b = a.buf;
@@ -160,9 +165,18 @@ int block_fwd(const Ctx& c, const devit_block_weights& w, const devit_block_acts
     ep.bias = w.qkv_b;
     TRY(linear_fwd(c, b[DEVIT_ACT_LN1], w.qkv_w16, 3 * Da, D, ep));
   }
+  if (drop_attn)
+    TRY(devit_attn_fwd_drop(b[DEVIT_ACT_QKV], b[DEVIT_ACT_ATTN_O], save ? (float*)b[DEVIT_ACT_LSE] : nullptr, w.head_gate, c.B, c.N, H, 64, 0.125f,
+                            d->seed, d->block, d->thr_attn, d->scale_keep_attn, c.stream));
+  else
   TRY(devit_attn_fwd(b[DEVIT_ACT_QKV], b[DEVIT_ACT_ATTN_O], save ? (float*)b[DEVIT_ACT_LSE] : nullptr, w.head_gate, c.B, c.N, H,
                      64, 0.125f, t16, c.stream));
-  {
+  if (drop) {      // proj stores fp32 into the temporary; the residual + DropPath statement runs with the mask in it (site 2)
+    devit_epilogue ep = make_ep(DEVIT_EPI_STORE_F32, d->tmp, D, c.M);
+    ep.bias = w.proj_b;
+    TRY(linear_fwd(c, b[DEVIT_ACT_ATTN_O], w.proj_w16, D, Da, ep));
+    TRY(devit_dropout_residual(a.x, d->tmp, (float*)b[DEVIT_ACT_X1], a.dp1, c.N, c.M, D, d->seed, 2, d->block, d->thr, d->scale_keep, c.stream));
+  } else {
     devit_epilogue ep = make_ep(DEVIT_EPI_RESIDUAL_F32, b[DEVIT_ACT_X1], D, c.M, t16);
     ep.bias = w.proj_b;
     ep.res = a.x;
@@ -181,7 +195,14 @@ int block_fwd(const Ctx& c, const devit_block_weights& w, const devit_block_acts
     ep.aux = save ? b[DEVIT_ACT_H_PRE] : nullptr;
     TRY(linear_fwd(c, b[DEVIT_ACT_LN2], w.fc1_w16, Hd, D, ep));
   }
-  {
+  if (drop) {      // Mlp.drop after GELU (site 3; commutes with the neuron gate), fc2 like proj (site 4)
+    TRY(devit_dropout_apply(b[DEVIT_ACT_H], 0, c.M, Hd, Hd, Hd, d->seed, 3, d->block, d->thr, d->scale_keep, nullptr, c.stream));
+    devit_epilogue ep = make_ep(DEVIT_EPI_STORE_F32, d->tmp, D, c.M);
+    ep.bias = w.fc2_b;
+    TRY(linear_fwd(c, b[DEVIT_ACT_H], w.fc2_w16, D, Hd, ep));
+    TRY(devit_dropout_residual((const float*)b[DEVIT_ACT_X1], d->tmp, (float*)b[DEVIT_ACT_X2], a.dp2, c.N, c.M, D, d->seed, 4, d->block, d->thr,
+                               d->scale_keep, c.stream));
+  } else {
     devit_epilogue ep = make_ep(DEVIT_EPI_RESIDUAL_F32, b[DEVIT_ACT_X2], D, c.M, t16);
     ep.bias = w.fc2_b;
     ep.res = (const float*)b[DEVIT_ACT_X1];
@@ -234,21 +255,37 @@ extern "C" int devit_block_bwd_sizes(int B, int N, int D, int Da, int Hd, size_t
   return DEVIT_OK;
 }
 
-extern "C" int devit_encoder_fwd(int nblocks, const devit_block_weights* w, const devit_block_acts* acts, int B, int N, int D,
-                                 float eps, void* stream) {
+namespace {
+int encoder_fwd(int nblocks, const devit_block_weights* w, const devit_block_acts* acts, const devit_block_dropout* drop, int B, int N, int D,
+                float eps, void* stream) {
   DEVIT_CHECK(nblocks > 0 && w && acts, DEVIT_ERR_ARG, "devit_encoder_fwd: bad argument");
   Ctx c{B * N, pad_rows(B * N), B, N, D, eps, stream};
   for (int i = 0; i < nblocks; ++i) {
     DEVIT_CHECK(i == 0 || acts[i].x == (const float*)acts[i - 1].buf[DEVIT_ACT_X2], DEVIT_ERR_ARG,
                 "devit_encoder_fwd: block %d does not read block %d's output", i, i - 1);
-    TRY(block_fwd(c, w[i], acts[i]));
+    TRY(block_fwd(c, w[i], acts[i], drop ? drop + i : nullptr));
   }
   return DEVIT_OK;
 }
+}  // namespace
 
-extern "C" int devit_block_bwd(const devit_block_weights* wp, const devit_block_acts* ap, const devit_block_wgrads* gp,
-                               const devit_block_bwd_io* io, int B, int N, int D, float eps, void* stream) {
+extern "C" int devit_encoder_fwd(int nblocks, const devit_block_weights* w, const devit_block_acts* acts, int B, int N, int D,
+                                 float eps, void* stream) {
+  return encoder_fwd(nblocks, w, acts, nullptr, B, N, D, eps, stream);
+}
+extern "C" int devit_encoder_fwd_drop(int nblocks, const devit_block_weights* w, const devit_block_acts* acts, const devit_block_dropout* drop,
+                                      int B, int N, int D, float eps, void* stream) {
+  DEVIT_CHECK(drop != nullptr, DEVIT_ERR_ARG, "devit_encoder_fwd_drop: null dropout array");
+  return encoder_fwd(nblocks, w, acts, drop, B, N, D, eps, stream);
+}
+
+namespace {
+int block_bwd(const devit_block_weights* wp, const devit_block_acts* ap, const devit_block_wgrads* gp, const devit_block_bwd_io* io,
+              const devit_block_dropout* d, int B, int N, int D, float eps, void* stream) {
   DEVIT_CHECK(wp && ap && gp && io, DEVIT_ERR_ARG, "devit_block_bwd: null argument");
+  const bool drop = d && d->thr > 0, drop_attn = d && d->thr_attn > 0;
+  DEVIT_CHECK(!drop || !io->g2_bias_done, DEVIT_ERR_ARG,
+              "devit_block_bwd_drop: with p > 0 a block forms its own fc2 bias gradient from its masked g2 (g2_bias_done must be 0)");
   const devit_block_weights& w = *wp;
   const devit_block_acts& a = *ap;
   const devit_block_wgrads& g = *gp;
@@ -329,6 +366,10 @@ extern "C" int devit_block_bwd(const devit_block_weights* wp, const devit_block_
   // fc2's product is taken transposed (its 384 outputs are the B side): its bias gradient cannot come out of the grouped kernel.  Every block but the
   // topmost got it from the LN1 backward of the block above; the topmost takes a column-sum pass over g2 (the LayerNorm workspace is idle here).
   bool fc2_bias_here = !io->g2_bias_done;
+  if (drop) {    // site 4: the incoming branch gradient is masked in place; its column sums are fc2's bias gradient
+    TRY(devit_dropout_apply(const_cast<void*>(io->g2), 0, c.M, D, D, D, d->seed, 4, d->block, d->thr, d->scale_keep, g.fc2_b, stream));
+    fc2_bias_here = false;
+  }
   if (fc2_bias_here && wmode && Hd % 128 == 0 && io->lnws_bytes >= devit_colsum_workspace(c.Mp, D)) {
     TRY(devit_colsum_bf16(io->g2, c.Mp, D, D, 0, 0, g.fc2_b, 1, io->ws[DEVIT_BWD_LNWS], io->lnws_bytes, stream));
     fc2_bias_here = false;
@@ -340,24 +381,31 @@ extern "C" int devit_block_bwd(const devit_block_weights* wp, const devit_block_
     ep.aux_in = b[DEVIT_ACT_H_PRE];
     TRY(linear_dgrad(c, io->g2, w.fc2_w16, D, Hd, ep));
   }
+  if (drop) TRY(devit_dropout_apply(dh_pre, 0, c.M, Hd, Hd, Hd, d->seed, 3, d->block, d->thr, d->scale_keep, nullptr, stream));   // site 3
+  float* const g1_colsum = drop ? nullptr : g.proj_b;      // p > 0: proj's bias gradient comes from the MASKED g1 below
   // fc1's dgrad and the LN2 backward behind it: dln2 = dh_pre @ fc1_w; dx1 = dx + LN'(dln2); g1 = bf16(dp1 * dx1); its column sums = the proj bias
   // gradient.  One kernel where the full-row GEMM holds whole rows of dln2 (devit_dgrad_layernorm_bwd_fused; dln2 then never goes to memory),
   // else the two launches with the weight gradient's fork between them, as before.
   if (devit_dgrad_layernorm_bwd_fused(c.Mp, D, Hd)) {
     TRY(devit_dgrad_layernorm_bwd(dh_pre, w.fc1_w16, c.Mp, Hd, dln2, (const float*)b[DEVIT_ACT_X1], c.M, D, (const float*)b[DEVIT_ACT_MEAN2],
-                                  (const float*)b[DEVIT_ACT_RSTD2], w.n2w, io->dx, dx1, g1, a.dp1, N, g.n2w, g.n2b, g.proj_b, 1,
+                                  (const float*)b[DEVIT_ACT_RSTD2], w.n2w, io->dx, dx1, g1, a.dp1, N, g.n2w, g.n2b, g1_colsum, 1,
                                   io->ws[DEVIT_BWD_LNWS], io->lnws_bytes, stream));
     TRY(wgrad(1, dh_pre, b[DEVIT_ACT_LN2], g.fc1_w, g.fc1_b, Hd, D));
   } else {
     TRY(linear_dgrad(c, dh_pre, w.fc1_w16, Hd, D, make_ep(DEVIT_EPI_STORE_BF16, dln2, D, c.M)));
     TRY(wgrad(1, dh_pre, b[DEVIT_ACT_LN2], g.fc1_w, g.fc1_b, Hd, D));
     TRY(devit_layernorm_bwd(dln2, 0, (const float*)b[DEVIT_ACT_X1], c.M, D, 0, 0, (const float*)b[DEVIT_ACT_MEAN2],
-                            (const float*)b[DEVIT_ACT_RSTD2], w.n2w, io->dx, dx1, g1, a.dp1, N, g.n2w, g.n2b, g.proj_b, 1,
+                            (const float*)b[DEVIT_ACT_RSTD2], w.n2w, io->dx, dx1, g1, a.dp1, N, g.n2w, g.n2b, g1_colsum, 1,
                             io->ws[DEVIT_BWD_LNWS], io->lnws_bytes, stream));
   }
+  if (drop) TRY(devit_dropout_apply(g1, 0, c.M, D, D, D, d->seed, 2, d->block, d->thr, d->scale_keep, g.proj_b, stream));          // site 2
   // ---- attention branch: x1 = x + dp1 * proj(gate * attn(qkv(ln1)))
   TRY(linear_dgrad(c, g1, w.proj_w16, D, Da, make_ep(DEVIT_EPI_STORE_BF16, dattn, Da, c.M)));
   TRY(wgrad(2, g1, b[DEVIT_ACT_ATTN_O], g.proj_w, nullptr, D, Da));
+  if (drop_attn)
+    TRY(devit_attn_bwd_drop(b[DEVIT_ACT_QKV], b[DEVIT_ACT_ATTN_O], dattn, (const float*)b[DEVIT_ACT_LSE], w.head_gate, io->dqkv_add, dqkv, B, N, H, 64,
+                            0.125f, d->seed, d->block, d->thr_attn, d->scale_keep_attn, stream));
+  else
   TRY(devit_attn_bwd(b[DEVIT_ACT_QKV], b[DEVIT_ACT_ATTN_O], dattn, (const float*)b[DEVIT_ACT_LSE], w.head_gate, io->dqkv_add,
                      dqkv, B, N, H, 64, 0.125f, stream));
   // qkv's dgrad and the LN1 backward behind it, fused under the same rule: dln1 = dqkv @ qkv_w; dx_in = dx1 + LN'(dln1);
@@ -383,4 +431,15 @@ extern "C" int devit_block_bwd(const devit_block_weights* wp, const devit_block_
     if (rc == DEVIT_OK) DEVIT_CHECK(joined, DEVIT_ERR_LAUNCH, "devit_block_bwd: cannot join the weight-gradient stream");
   }
   return rc;
+}
+}  // namespace
+
+extern "C" int devit_block_bwd(const devit_block_weights* wp, const devit_block_acts* ap, const devit_block_wgrads* gp,
+                               const devit_block_bwd_io* io, int B, int N, int D, float eps, void* stream) {
+  return block_bwd(wp, ap, gp, io, nullptr, B, N, D, eps, stream);
+}
+extern "C" int devit_block_bwd_drop(const devit_block_weights* wp, const devit_block_acts* ap, const devit_block_wgrads* gp,
+                                    const devit_block_bwd_io* io, const devit_block_dropout* drop, int B, int N, int D, float eps, void* stream) {
+  DEVIT_CHECK(drop != nullptr, DEVIT_ERR_ARG, "devit_block_bwd_drop: null dropout");
+  return block_bwd(wp, ap, gp, io, drop, B, N, D, eps, stream);
 }

@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from .dropout import check_p
 from .registry import register_model
 
 __all__ = ["Mlp", "Attention", "Block", "PatchEmbed", "VisionTransformer", "model_config", "dedeit", "devit"]
@@ -104,12 +105,13 @@ class Mlp(nn.Module, _Gated):
         self.fc1 = nn.Linear(in_features, hidden_features)
         self.act = act_layer()
         self.fc2 = nn.Linear(hidden_features, out_features)
-        self.drop = nn.Dropout(drop)
-        if drop != 0.:
-            raise NotImplementedError("dropout p > 0 is not on the DeViT hot path (distill_sub.py --drop 0.0)")
+        self.drop = nn.Dropout(check_p(drop, "Mlp drop"))
         self._init_gate(hidden_features)
 
     def forward(self, x):
+        if self.training and self.drop.p > 0.:
+            raise NotImplementedError("dropout p > 0 runs inside a Block / VisionTransformer forward (the masks are keyed by the model's seed "
+                                      "and the block's index): a standalone Mlp in train() mode has neither")
         return _standalone_mlp(self, x)
 
 
@@ -122,16 +124,17 @@ class Attention(nn.Module, _Gated):
         head_dim = dim // num_heads
         self.scale = head_dim ** -0.5
         self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
-        self.attn_drop = nn.Dropout(attn_drop)
+        self.attn_drop = nn.Dropout(check_p(attn_drop, "Attention attn_drop"))
         self.proj = nn.Linear(dim, dim)
-        self.proj_drop = nn.Dropout(proj_drop)
-        if attn_drop != 0. or proj_drop != 0.:
-            raise NotImplementedError("dropout p > 0 is not on the DeViT hot path")
+        self.proj_drop = nn.Dropout(check_p(proj_drop, "Attention proj_drop"))
         if head_dim != 64:
             raise NotImplementedError("the fused attention kernel is built for head_dim == 64 (all DeiT/ViT-16 models)")
         self._init_gate(num_heads)
 
     def forward(self, x, output_qkv=False):
+        if self.training and (self.attn_drop.p > 0. or self.proj_drop.p > 0.):
+            raise NotImplementedError("dropout p > 0 runs inside a Block / VisionTransformer forward (the masks are keyed by the model's seed "
+                                      "and the block's index): a standalone Attention in train() mode has neither")
         return _standalone_attention(self, x, output_qkv)
 
 
@@ -222,7 +225,7 @@ class Block(nn.Module):
         return bp
 
     def forward(self, x, output_qkv=False, output_att=False):
-        x_out, qkvs, atts, _ = run_blocks([self], x, self.training, output_qkv, output_att, False)
+        x_out, qkvs, atts, _ = run_blocks([self], x, self.training, output_qkv, output_att, False, dropout_seed=getattr(self, "dropout_seed", None))
         outputs = {'output': x_out}
         outputs['qkv'] = qkvs[0] if output_qkv else None
         outputs['attention'] = atts[0] if output_att else None
@@ -280,8 +283,26 @@ def lean_tail(*models):
             v._lean_tail = p
 
 
+def draw_dropout_seed(pinned=None):
+    """The 64-bit seed of one training forward's dropout masks: `pinned`, or a fresh draw from torch's default CPU generator."""
+    if pinned is not None:
+        return int(pinned) & 0xFFFFFFFFFFFFFFFF
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+
+
+def block_drop_rates(blocks, training):
+    """[(p, p_attn) per block] (Mlp.drop / proj_drop share `drop`, models/de_vit.py:96,101) when a training forward has any p > 0, else None"""
+    if not training:
+        return None
+    rates = [(float(b.mlp.drop.p), float(b.attn.attn_drop.p)) for b in blocks]
+    for b, (p, _) in zip(blocks, rates):
+        if float(b.attn.proj_drop.p) != p:
+            raise NotImplementedError("proj_drop != Mlp.drop in one block: Block builds both from `drop`; the kernels take one threshold")
+    return rates if any(p > 0. or pa > 0. for p, pa in rates) else None
+
+
 def run_blocks(blocks, x, training, want_qkv, want_att, want_enc, grad_ready=None, dp_scales="draw", exact_gelu=0,
-               precision="bf16", qkv_pad_layers=None, lean_tokens=0):
+               precision="bf16", qkv_pad_layers=None, lean_tokens=0, dropout_seed=None):
     """Run a list of Blocks as one EncoderFn node.  Returns (x, qkv tuples, att tensors, enc tensors).
     lean_tokens > 0 (see lean_tail): x comes back as [B, lean_tokens, D] and the last block's qkv entry is None."""
     L.require_device(x)
@@ -298,11 +319,16 @@ def run_blocks(blocks, x, training, want_qkv, want_att, want_enc, grad_ready=Non
     if dp_scales == "draw":
         dp_scales = draw_dp_scales(bps, B, x.device, training)
     nb = len(blocks)
-    lean = lean_tokens if (lean_tokens and nb >= 2 and precision != "f32" and not want_att and not want_enc and
+    rates = block_drop_rates(blocks, training)
+    if rates is not None and precision == "f16":
+        raise L.DevitError('precision="f16" is the frozen-teacher forward: it has no dropout; put the model in eval() mode')
+    lean = lean_tokens if (lean_tokens and nb >= 2 and precision != "f32" and not want_att and not want_enc and rates is None and
                            (not want_qkv or (qkv_pad_layers is not None and nb - 1 not in qkv_pad_layers))) else 0
     cfg = ops.EncoderCfg(bps, training, dp_scales, want_qkv, want_att, want_enc, exact_gelu=exact_gelu,
                          grad_ready=grad_ready, qkv_pad_layers=qkv_pad_layers, lean_tokens=lean)
     cfg.grad_enabled = torch.is_grad_enabled()
+    if rates is not None:
+        cfg.drop = (draw_dropout_seed(dropout_seed), rates)
     flat = [p for bp in bps for p in bp.all_params()]
     if precision == "f32":
         from . import ops_f32
@@ -379,9 +405,11 @@ class VisionTransformer(nn.Module):
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.dist_token = nn.Parameter(torch.zeros(1, 1, embed_dim)) if distilled else None
         self.pos_embed = nn.Parameter(torch.zeros(1, num_patches + self.num_tokens, embed_dim))
-        self.pos_drop = nn.Dropout(p=drop_rate)
-        if drop_rate != 0.:
-            raise NotImplementedError("dropout p > 0 is not on the DeViT hot path (distill_sub.py --drop 0.0)")
+        self.pos_drop = nn.Dropout(p=check_p(drop_rate, "drop_rate"))
+        check_p(attn_drop_rate, "attn_drop_rate")
+        # seed of a training forward's dropout masks (dropout.py): None draws a fresh 63-bit value per forward from torch's default CPU generator
+        # (torch.manual_seed reproduces a run; ranks differ as their DropPath draws do); an int pins it
+        self.dropout_seed = None
 
         dpr = [x.item() for x in torch.linspace(0, drop_path_rate, depth)]      # de_vit.py:175
         self.blocks = nn.Sequential(*[
@@ -499,12 +527,17 @@ class VisionTransformer(nn.Module):
                                       "(models/de_vit.py:276 applies resize_att_mlp to None unless output_att, :313-314 to the distilled "
                                       "(cls, dist) tuple; train_subdata.py:253 unpacks the returned dict as a pair) -- DESIGN.md section 9")
         x = self.embed(x)
+        seed = None
+        if self.training and (self.pos_drop.p > 0. or block_drop_rates(self.blocks, True) is not None):
+            seed = draw_dropout_seed(self.dropout_seed)             # ONE seed per forward: pos_drop and every block's sites share it
+            if self.pos_drop.p > 0.:
+                x = ops.PosDropFn.apply(x, seed, float(self.pos_drop.p))
         emb = x
         xo, qkvs, atts, encs = run_blocks(list(self.blocks), x, self.training, output_qkv, output_att, output_encoders,
                                           grad_ready=self.grad_ready, exact_gelu=self.exact_gelu,
                                           precision=self.precision,
                                           qkv_pad_layers=getattr(self, "qkv_pad_layers", None),
-                                          lean_tokens=self.num_tokens if getattr(self, "_lean_tail", False) else 0)
+                                          lean_tokens=self.num_tokens if getattr(self, "_lean_tail", False) else 0, dropout_seed=seed)
         depth = len(self.blocks)
         encoder_outputs = [emb] if output_emb else []
         encoder_outputs += encs if output_encoders else [None] * depth

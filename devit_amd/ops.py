@@ -442,6 +442,9 @@ class EncoderCfg:
         # distillation tokens, models/de_vit.py:286-288) and nothing of the last block besides: that block then runs as
         # _tail_forward / _tail_backward and the output is [B, lean_tokens, D]
         self.lean_tokens = lean_tokens
+        # dropout p > 0 of a TRAINING forward: None, or (seed, [(p, p_attn) per block]) -- the masks are functions of the seed (dropout.py), so
+        # this is all a backward needs to regenerate them
+        self.drop = None
 
 
 def scale_cast(dx, rowscale, N):
@@ -648,7 +651,7 @@ def _weights_struct(bp):
 
 class _EncoderRun:
     """What one composite forward leaves behind for backward: the ctypes argument arrays and the arena they point into."""
-    __slots__ = ("weights", "acts", "arena", "x", "dims", "views", "dps", "nb")
+    __slots__ = ("weights", "acts", "arena", "x", "dims", "views", "dps", "nb", "drops", "drop_tmp")
 
 
 def _encoder_forward_composite(x, cfg, need_grad, nb):
@@ -706,8 +709,28 @@ def _encoder_forward_composite(x, cfg, need_grad, nb):
             bp.module.mlp.neuron_output = None
             bp.module.attn.head_output = None
     run.views = views
+    run.drops = run.drop_tmp = None
+    if cfg.drop is not None:         # p > 0: the same sequence with the dropout passes in it (csrc/encoder.hip); p == 0 never comes here
+        if cfg.want_att:
+            raise L.DevitError("output_att under dropout p > 0 is not taken on the 16-bit path: run the model with precision=\"f32\"")
+        run.drops, run.drop_tmp = _drop_structs(cfg.drop, nb, mp, D, dev)
+        call("devit_encoder_fwd_drop", nb, weights, acts, run.drops, B, N, D, cfg.eps, stream_ptr())
+        return run
     call("devit_encoder_fwd", nb, weights, acts, B, N, D, cfg.eps, stream_ptr())
     return run
+
+
+def _drop_structs(drop, nb, mp, D, dev):
+    """(L.BlockDropout * nb, the fp32 temporary they share) of EncoderCfg.drop"""
+    from . import dropout
+    seed, rates = drop
+    tmp = torch.empty((mp, D), dtype=F32, device=dev)
+    arr = (L.BlockDropout * nb)()
+    for i in range(nb):
+        (thr, s), (thr_a, s_a) = dropout.threshold(rates[i][0]), dropout.threshold(rates[i][1])
+        arr[i].seed, arr[i].block, arr[i].thr, arr[i].thr_attn = seed, i, thr, thr_a
+        arr[i].scale_keep, arr[i].scale_keep_attn, arr[i].tmp = s, s_a, tmp.data_ptr()
+    return arr, tmp
 
 
 def _wgrads_struct(bp):
@@ -767,10 +790,20 @@ def _encoder_backward_composite(run, cfg, dx, dqkvs, defer):
         io.prev_dp2 = _p(pdp[1]) if pdp is not None else None
         io.prev_fc2_b_grad = grad_buf(prev.fc2_b).data_ptr() if prev is not None else None
         io.g2_bias_done = g_bias_done
+        masked = run.drops is not None and run.drops[i].thr > 0        # this block masks its g2 and takes fc2's bias gradient from it
+        if masked:
+            io.g2_bias_done = 0
+        below = run.drops is not None and prev is not None and run.drops[i - 1].thr > 0
+        if below:                        # ... so the block above hands it none
+            io.prev_fc2_b_grad = None
         io.dqkv_add = _p(dq)
         wg = _wgrads_struct(bp)
-        call("devit_block_bwd", C.byref(run.weights[i]), C.byref(run.acts[i]), C.byref(wg), C.byref(io), B, N, D, cfg.eps, st)
-        cur_dx, g_bias_done = dx_ptrs[out_slot], 1 if prev is not None else 0
+        if run.drops is not None:
+            call("devit_block_bwd_drop", C.byref(run.weights[i]), C.byref(run.acts[i]), C.byref(wg), C.byref(io), C.byref(run.drops[i]), B, N, D,
+                 cfg.eps, st)
+        else:
+            call("devit_block_bwd", C.byref(run.weights[i]), C.byref(run.acts[i]), C.byref(wg), C.byref(io), B, N, D, cfg.eps, st)
+        cur_dx, g_bias_done = dx_ptrs[out_slot], 1 if (prev is not None and not below) else 0
         defer.add(bp, [L.WgradJob.from_buffer_copy(got[k]) for k in range(ngot.value)], (dq,))
         if defer.last_of_group(i):
             defer.flush(mp)
@@ -791,7 +824,7 @@ class EncoderFn(torch.autograd.Function):
                                "or compact it with shrink.compact(model, trainable=True) to train through the compacted blocks")
         nb = len(cfg.blocks)
         # lean tail (EncoderCfg.lean_tokens): the last block runs on the token rows only
-        lean = cfg.lean_tokens if (cfg.lean_tokens and nb >= 2 and not cfg.want_att and not cfg.want_enc) else 0
+        lean = cfg.lean_tokens if (cfg.lean_tokens and nb >= 2 and not cfg.want_att and not cfg.want_enc and cfg.drop is None) else 0
         nbody = nb - 1 if lean else nb
         dp_last = cfg.dp_scales[nb - 1] if cfg.dp_scales is not None else None
         ctx.tail = None
@@ -968,6 +1001,28 @@ class PatchEmbedFn(torch.autograd.Function):
 # ----------------------------------------------------------------------------------------------
 # final norm on the cls/dist rows + classifier heads (models/de_vit.py:286-288,316-318)
 # ----------------------------------------------------------------------------------------------
+class PosDropFn(torch.autograd.Function):
+    """pos_drop (models/de_vit.py:173,264) on the fp32 token stream [B, T, D]: site 0, block 0 of the forward's seed; the backward regenerates the mask."""
+
+    @staticmethod
+    def forward(ctx, x, seed, p):
+        from . import dropout
+        L.require_device(x)
+        B, T, D = x.shape
+        y = x.contiguous().clone()
+        dropout.apply_(y.view(B * T, D), B * T, seed, L.DROP_POS, 0, p)
+        ctx.key = (seed, p)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from . import dropout
+        B, T, D = dy.shape
+        dx = dy.contiguous().clone()
+        dropout.apply_(dx.view(B * T, D), B * T, ctx.key[0], L.DROP_POS, 0, ctx.key[1])
+        return dx, None, None
+
+
 class HeadsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, norm_w, norm_b, head_w, head_b, headd_w, headd_b, ntok, eps, grad_ready):

@@ -8,6 +8,7 @@ import torch
 
 from . import _lib as L
 from ._lib import call, ptr, stream_ptr
+from . import dropout
 from .ops import grad_buf, layernorm_bwd, layernorm_fwd
 
 F32 = torch.float32
@@ -41,32 +42,44 @@ def lin_wgrad(dy, x, wg, bg, M):                  # wg[N, K] += dy[M, N]^T @ x[M
         call("devit_colsum_f32", ptr(dy), M, N, N, ptr(bg), 1, stream_ptr())
 
 
-def attn_fwd(qkv, B, N, H, gate):
+def attn_fwd(qkv, B, N, H, gate, drop=None):
+    """drop: None or (seed, block, p_attn > 0): attn_drop (site 1) on the normalised P.  P rows then have the mask's pitch ceil4(N) (zero pad
+    columns) so that the 16-byte dropout pass can walk them; returns o, P (undropped: the softmax backward reads it), the dropped P or None."""
     D = qkv.shape[1] // 3
     dev = qkv.device
-    P = torch.empty((B, H, N, N), dtype=F32, device=dev)
-    sgemm(qkv, 3 * D, 1, qkv[:, D:], 3 * D, 1, N, N, 64, out=P, ldc=N, batch=B * H, batch_inner=H, a_bo=N * 3 * D, a_bi=64,
-          b_bo=N * 3 * D, b_bi=64, c_bo=H * N * N, c_bi=N * N)
-    call("devit_softmax_rows_f32", ptr(P), B * H * N, N, N, 0.125, None, stream_ptr())
+    ld = N if drop is None else dropout.ceil4(N)
+    P = torch.empty((B, H, N, N), dtype=F32, device=dev) if drop is None else torch.zeros((B, H, N, ld), dtype=F32, device=dev)
+    sgemm(qkv, 3 * D, 1, qkv[:, D:], 3 * D, 1, N, N, 64, out=P, ldc=ld, batch=B * H, batch_inner=H, a_bo=N * 3 * D, a_bi=64,
+          b_bo=N * 3 * D, b_bi=64, c_bo=H * N * ld, c_bi=N * ld)
+    call("devit_softmax_rows_f32", ptr(P), B * H * N, N, ld, 0.125, None, stream_ptr())
+    Pd = None
+    if drop is not None:
+        Pd = P.clone()
+        dropout.apply_(Pd.view(B * H * N, ld), B * H * N, drop[0], L.DROP_ATTN, drop[1], drop[2], pitch=ld)
     o = torch.empty((B * N, D), dtype=F32, device=dev)
-    sgemm(P, N, 1, qkv[:, 2 * D:], 1, 3 * D, N, 64, N, out=o, ldc=D, batch=B * H, batch_inner=H, a_bo=H * N * N, a_bi=N * N,
-          b_bo=N * 3 * D, b_bi=64, c_bo=N * D, c_bi=64, batch_scale=gate)
-    return o, P
+    sgemm(P if Pd is None else Pd, ld, 1, qkv[:, 2 * D:], 1, 3 * D, N, 64, N, out=o, ldc=D, batch=B * H, batch_inner=H, a_bo=H * N * ld,
+          a_bi=N * ld, b_bo=N * 3 * D, b_bi=64, c_bo=N * D, c_bi=64, batch_scale=gate)
+    return o, P, Pd
 
 
-def attn_bwd(qkv, P, do, B, N, H, gate, dq_add):
+def attn_bwd(qkv, P, do, B, N, H, gate, dq_add, Pd=None, drop=None):
+    """Pd / drop as attn_fwd left them: dV = (dropped P)^T dO, dP is masked and scaled before the softmax backward (whose sum_j P dP is then
+    rowsum(dO O), O having been formed from the dropped P)."""
     D = qkv.shape[1] // 3
     dev = qkv.device
-    dS = torch.empty((B, H, N, N), dtype=F32, device=dev)
+    ld = P.shape[-1]
+    dS = torch.empty((B, H, N, N), dtype=F32, device=dev) if drop is None else torch.zeros((B, H, N, ld), dtype=F32, device=dev)
     kw = dict(batch=B * H, batch_inner=H)
-    sgemm(do, D, 1, qkv[:, 2 * D:], 3 * D, 1, N, N, 64, out=dS, ldc=N, a_bo=N * D, a_bi=64, b_bo=N * 3 * D, b_bi=64,
-          c_bo=H * N * N, c_bi=N * N, batch_scale=gate, **kw)                                   # dP = (g dO) V^T
-    call("devit_softmax_bwd_rows_f32", ptr(P), ptr(dS), B * H * N, N, N, 0.125, stream_ptr())
+    sgemm(do, D, 1, qkv[:, 2 * D:], 3 * D, 1, N, N, 64, out=dS, ldc=ld, a_bo=N * D, a_bi=64, b_bo=N * 3 * D, b_bi=64,
+          c_bo=H * N * ld, c_bi=N * ld, batch_scale=gate, **kw)                                 # dP = (g dO) V^T
+    if drop is not None:
+        dropout.apply_(dS.view(B * H * N, ld), B * H * N, drop[0], L.DROP_ATTN, drop[1], drop[2], pitch=ld)
+    call("devit_softmax_bwd_rows_f32", ptr(P), ptr(dS), B * H * N, N, ld, 0.125, stream_ptr())
     dqkv = dq_add.contiguous().float().clone() if dq_add is not None else torch.zeros_like(qkv)
-    pn = dict(a_bo=H * N * N, a_bi=N * N, c_bo=N * 3 * D, c_bi=64, accumulate=True, **kw)
-    sgemm(dS, N, 1, qkv[:, D:], 1, 3 * D, N, 64, N, out=dqkv, ldc=3 * D, b_bo=N * 3 * D, b_bi=64, **pn)         # dQ = dS K
-    sgemm(dS, 1, N, qkv, 1, 3 * D, N, 64, N, out=dqkv[:, D:], ldc=3 * D, b_bo=N * 3 * D, b_bi=64, **pn)         # dK = dS^T Q
-    sgemm(P, 1, N, do, 1, D, N, 64, N, out=dqkv[:, 2 * D:], ldc=3 * D, b_bo=N * D, b_bi=64, batch_scale=gate, **pn)  # dV
+    pn = dict(a_bo=H * N * ld, a_bi=N * ld, c_bo=N * 3 * D, c_bi=64, accumulate=True, **kw)
+    sgemm(dS, ld, 1, qkv[:, D:], 1, 3 * D, N, 64, N, out=dqkv, ldc=3 * D, b_bo=N * 3 * D, b_bi=64, **pn)        # dQ = dS K
+    sgemm(dS, 1, ld, qkv, 1, 3 * D, N, 64, N, out=dqkv[:, D:], ldc=3 * D, b_bo=N * 3 * D, b_bi=64, **pn)        # dK = dS^T Q
+    sgemm(P if Pd is None else Pd, 1, ld, do, 1, D, N, 64, N, out=dqkv[:, 2 * D:], ldc=3 * D, b_bo=N * D, b_bi=64, batch_scale=gate, **pn)  # dV
     return dqkv
 
 
@@ -76,7 +89,10 @@ def _scaled(dx2d, rowscale, N):
     return g
 
 
-def block_forward(x, bp, dp, eps, need_grad, want_att):
+def block_forward(x, bp, dp, eps, need_grad, want_att, drop=None):
+    """drop: None or (seed, block index, p, p_attn) of a training forward with dropout: the five sites of include/devit_hip.h through
+    devit_dropout_apply / _residual (fp32), attn_drop on the fp32 P."""
+    seed, blk, p, p_attn = drop if drop is not None else (0, 0, 0., 0.)
     B, N, D = x.shape
     M, H, dev = B * N, bp.num_heads, x.device
     x2 = x.view(M, D)
@@ -85,24 +101,37 @@ def block_forward(x, bp, dp, eps, need_grad, want_att):
     layernorm_fwd(x2, M, D, bp.n1w, bp.n1b, eps, y_f32=ln1, mean=mean1, rstd=rstd1)
     qkv = e(M, 3 * D)
     lin_fwd(ln1, bp.qkv_w, bp.qkv_b, M, qkv)
-    attn_o, P = attn_fwd(qkv, B, N, H, bp.head_gate)
+    attn_o, P, Pd = attn_fwd(qkv, B, N, H, bp.head_gate, (seed, blk, p_attn) if p_attn > 0. else None)
     x1, att = e(B, N, D), (e(M, D) if want_att else None)
     dp1, dp2 = dp if dp is not None else (None, None)
-    lin_fwd(attn_o, bp.proj_w, bp.proj_b, M, x1.view(M, D), kind=L.EPI_RESIDUAL_F32, res=x2, rowscale=dp1, rows_per_scale=N,
-            aux=att)
+    if p > 0.:           # proj_drop (site 2): the branch output to a temporary, the residual + DropPath statement with the mask in it
+        y = e(M, D)
+        lin_fwd(attn_o, bp.proj_w, bp.proj_b, M, y)
+        dropout.residual(x2, y, dp1, N, seed, L.DROP_PROJ, blk, p, out=x1.view(M, D))
+        if want_att:
+            att = dropout.apply_(y, M, seed, L.DROP_PROJ, blk, p)       # the 'attention' output is what proj_drop returns (de_vit.py:83,119)
+    else:
+        lin_fwd(attn_o, bp.proj_w, bp.proj_b, M, x1.view(M, D), kind=L.EPI_RESIDUAL_F32, res=x2, rowscale=dp1, rows_per_scale=N,
+                aux=att)
     ln2, mean2, rstd2 = e(M, D), e(M), e(M)
     layernorm_fwd(x1.view(M, D), M, D, bp.n2w, bp.n2b, eps, y_f32=ln2, mean=mean2, rstd=rstd2)
     Hd = bp.fc1_w.shape[0]
     h, h_pre = e(M, Hd), e(M, Hd)
     lin_fwd(ln2, bp.fc1_w, bp.fc1_b, M, h, kind=L.EPI_GELU_BF16, colscale=bp.neuron_gate, aux=h_pre)
     x2o = e(B, N, D)
-    lin_fwd(h, bp.fc2_w, bp.fc2_b, M, x2o.view(M, D), kind=L.EPI_RESIDUAL_F32, res=x1.view(M, D), rowscale=dp2,
-            rows_per_scale=N)
+    if p > 0.:           # Mlp.drop after GELU (site 3) and after fc2 (site 4)
+        dropout.apply_(h, M, seed, L.DROP_HIDDEN, blk, p)
+        y = e(M, D)
+        lin_fwd(h, bp.fc2_w, bp.fc2_b, M, y)
+        dropout.residual(x1.view(M, D), y, dp2, N, seed, L.DROP_FC2, blk, p, out=x2o.view(M, D))
+    else:
+        lin_fwd(h, bp.fc2_w, bp.fc2_b, M, x2o.view(M, D), kind=L.EPI_RESIDUAL_F32, res=x1.view(M, D), rowscale=dp2,
+                rows_per_scale=N)
     if bp.module is not None:
         bp.module.mlp.neuron_output = h.view(B, N, Hd)
         bp.module.attn.head_output = attn_o.view(B, N, H, D // H)
     s = dict(x=x, ln1=ln1, mean1=mean1, rstd1=rstd1, qkv=qkv, attn_o=attn_o, P=P, x1=x1, ln2=ln2, mean2=mean2, rstd2=rstd2,
-             h=h, h_pre=h_pre, dp1=dp1, dp2=dp2) if need_grad else {}
+             h=h, h_pre=h_pre, dp1=dp1, dp2=dp2, Pd=Pd, drop=drop) if need_grad else {}
     return x2o, qkv, att, s
 
 
@@ -111,9 +140,14 @@ def block_backward(dx, s, bp, dqkv_add, datt):
     M, H, dev = B * N, bp.num_heads, dx.device
     Hd = bp.fc1_w.shape[0]
     e = lambda *sh: torch.empty(sh, dtype=F32, device=dev)
+    seed, blk, p, p_attn = s["drop"] if s["drop"] is not None else (0, 0, 0., 0.)
     g2 = _scaled(dx.view(M, D), s["dp2"], N)
+    if p > 0.:
+        dropout.apply_(g2, M, seed, L.DROP_FC2, blk, p)
     dh = e(M, Hd)
     lin_dgrad(g2, bp.fc2_w, M, dh, kind=L.EPI_DGELU_BF16, colscale=bp.neuron_gate, aux_in=s["h_pre"])
+    if p > 0.:
+        dropout.apply_(dh, M, seed, L.DROP_HIDDEN, blk, p)
     lin_wgrad(g2, s["h"], grad_buf(bp.fc2_w), grad_buf(bp.fc2_b), M)
     dln2 = e(M, D)
     lin_dgrad(dh, bp.fc1_w, M, dln2)
@@ -124,10 +158,12 @@ def block_backward(dx, s, bp, dqkv_add, datt):
     g1 = _scaled(dx1.view(M, D), s["dp1"], N)
     if datt is not None:
         g1 = g1 + datt.float().view(M, D)
+    if p > 0.:
+        dropout.apply_(g1, M, seed, L.DROP_PROJ, blk, p)
     dattn = e(M, D)
     lin_dgrad(g1, bp.proj_w, M, dattn)
     lin_wgrad(g1, s["attn_o"], grad_buf(bp.proj_w), grad_buf(bp.proj_b), M)
-    dqkv = attn_bwd(s["qkv"], s["P"], dattn, B, N, H, bp.head_gate, dqkv_add)
+    dqkv = attn_bwd(s["qkv"], s["P"], dattn, B, N, H, bp.head_gate, dqkv_add, s["Pd"], (seed, blk, p_attn) if p_attn > 0. else None)
     dln1 = e(M, D)
     lin_dgrad(dqkv, bp.qkv_w, M, dln1)
     lin_wgrad(dqkv, s["ln1"], grad_buf(bp.qkv_w), grad_buf(bp.qkv_b), M)
@@ -146,7 +182,8 @@ class EncoderF32Fn(torch.autograd.Function):
         saved, qkvs, atts, encs = [], [], [], []
         for i, bp in enumerate(cfg.blocks):
             dp = cfg.dp_scales[i] if cfg.dp_scales is not None else None
-            x, qkv, att, s = block_forward(x, bp, dp, cfg.eps, need_grad, cfg.want_att)
+            drop = (cfg.drop[0], i) + tuple(cfg.drop[1][i]) if cfg.drop is not None else None
+            x, qkv, att, s = block_forward(x, bp, dp, cfg.eps, need_grad, cfg.want_att, drop)
             saved.append(s)
             if cfg.want_qkv:
                 qkvs.append(qkv)

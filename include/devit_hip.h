@@ -43,7 +43,8 @@ DEVIT_API const char* devit_last_error(void); /* host string, thread-local, vali
 /* 0 if device `dev` is gfx950; DEVIT_ERR_DEVICE otherwise (product path refuses to run). */
 DEVIT_API int devit_check_device(int dev);
 /* sizeof() of the ABI's structs as THIS library was compiled (which: 0 devit_epilogue, 1 devit_operand, 2 devit_block_weights,
- * 3 devit_block_wgrads, 4 devit_block_acts, 5 devit_block_bwd_io, 6 devit_index_job, 7 devit_wgrad_job, 8 devit_launch_info; anything else: 0).  A binding
+ * 3 devit_block_wgrads, 4 devit_block_acts, 5 devit_block_bwd_io, 6 devit_index_job, 7 devit_wgrad_job, 8 devit_launch_info, 9 devit_block_dropout;
+ * anything else: 0).  A binding
  * compares them with its own mirrors once at load time: a stale mirror of a struct that is passed as an ARRAY would otherwise be misread
  * from its second element on, with no error. */
 DEVIT_API size_t devit_abi_struct_size(int which);
@@ -51,7 +52,7 @@ DEVIT_API size_t devit_abi_struct_size(int which);
 /* ------------------------------------------------------------------------------------------
  * Launch observer: how an instrument (bench.py's per-kernel events, tools/step_gemm_table.py) sees the launches of a step without a
  * second host program.  While the CALLING THREAD has an observer installed, each of
- *     devit_gemm_bf16, devit_layernorm_fwd / _bwd, devit_attn_fwd / _bwd / _fwd_rows / _bwd_rows, devit_wgrad_grouped,
+ *     devit_gemm_bf16, devit_layernorm_fwd / _bwd, devit_attn_fwd / _bwd / _fwd_rows / _bwd_rows / _fwd_drop / _bwd_drop, devit_wgrad_grouped,
  *     devit_dgrad_layernorm_bwd (only when it takes the fused launch: unfused it calls the GEMM and LayerNorm entry points, which report)
  * calls it twice: phase 0 just before the entry point's first kernel launch (after its argument checks: a refused call reports nothing),
  * phase 1 just after its last, with the stream those kernels go to -- from inside devit_block_bwd that is the library's weight-gradient side
@@ -243,6 +244,44 @@ DEVIT_API int devit_attn_fwd_rows(const void* q, int q_ld, const void* kv, int k
 DEVIT_API int devit_attn_bwd_rows(const void* q, int q_ld, const void* kv, int kv_ld, const void* out, const void* dout,
                         const float* lse, const float* head_gate, void* dq, int dq_ld, void* dkv, int dkv_ld, int B, int NQ,
                         int N, int H, int head_dim, float scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Dropout (nn.Dropout with p > 0: models/de_vit.py:38,46 Mlp.drop, :72 attn_drop, :83 proj_drop, :173 pos_drop).  ONE mask definition,
+ * counter-based and never stored -- a backward regenerates what its forward used:
+ *   generator  Philox4x32-10
+ *   key        (seed & 0xffffffff, seed >> 32); seed = one 64-bit value per model forward
+ *   counter    (g & 0xffffffff, g >> 32, site, block), g = e >> 2, e = row * pitch + col the element's LOGICAL index, pitch % 4 == 0;
+ *              element e takes output word e & 3
+ *   keep       iff word >= thr, thr = min(floor(p * 2^32), 2^32 - 1) computed by the host in double precision (thr == 0 keeps everything)
+ *   kept values are multiplied by scale_keep = 1 / (1 - p) in fp32
+ *   site  0 pos_drop   fp32 token stream after embedding   block 0        [B*T][D]
+ *         1 attn_drop  the normalised softmax P            block index    row (b*H + h)*N + q, column k, pitch = ceil4(N)
+ *         2 proj_drop  proj's output                       block index    [M][D]
+ *         3 Mlp.drop   after GELU                          block index    [M][hidden]
+ *         4 Mlp.drop   after fc2                           block index    [M][D]
+ * devit_dropout_mask     keep [rows][cols] bytes (1 = kept) of a site: a debug / test entry point on the device function every kernel uses.
+ * devit_dropout_apply    in place on a bf16 (is_f32 == 0) or fp32 [rows][ld] buffer, columns 0..cols-1 of rows 0..rows-1 (pad rows are not
+ *                        touched); colsum (optional, fp32 [cols]) += the column sums of the masked result as stored: a Linear's bias
+ *                        gradient when the buffer is its dY.  16-byte accesses: cols and ld multiples of 8 (bf16) / 4 (fp32).
+ * devit_dropout_residual x_out = x + rowscale[m / rows_per_scale] * keep * scale_keep * y on fp32 [rows][cols] (x_out may alias x; pitch =
+ *                        cols): the residual + DropPath statement of DEVIT_EPI_RESIDUAL_F32 with the mask in it, for sites 2 and 4, whose
+ *                        GEMMs then store y through DEVIT_EPI_STORE_F32.
+ * devit_attn_fwd_drop / devit_attn_bwd_drop: devit_attn_fwd / devit_attn_bwd (bf16) with site 1 inside the kernel.  P is normalised, then
+ *                        masked and scaled; lse is that of the undropped row; dV = (P keep s)^T dO, dS = P (dP keep s - delta).  With thr == 0
+ *                        and scale_keep == 1 the outputs are bit for bit those of devit_attn_fwd / devit_attn_bwd.  Both report to the
+ *                        launch observer under their own names.
+ * ---------------------------------------------------------------------------------------- */
+DEVIT_API int devit_dropout_mask(unsigned long long seed, int site, int block, unsigned thr, int rows, int cols, long long pitch,
+                       unsigned char* keep, void* stream);
+DEVIT_API int devit_dropout_apply(void* x, int is_f32, int rows, int cols, int ld, long long pitch, unsigned long long seed, int site,
+                        int block, unsigned thr, float scale_keep, float* colsum, void* stream);
+DEVIT_API int devit_dropout_residual(const float* x, const float* y, float* x_out, const float* rowscale, int rows_per_scale, int rows,
+                           int cols, unsigned long long seed, int site, int block, unsigned thr, float scale_keep, void* stream);
+DEVIT_API int devit_attn_fwd_drop(const void* qkv, void* out, float* lse, const float* head_gate, int B, int N, int H, int head_dim,
+                        float scale, unsigned long long seed, int block, unsigned thr, float scale_keep, void* stream);
+DEVIT_API int devit_attn_bwd_drop(const void* qkv, const void* out, const void* dout, const float* lse, const float* head_gate,
+                        const void* dqkv_add, void* dqkv, int B, int N, int H, int head_dim, float scale, unsigned long long seed,
+                        int block, unsigned thr, float scale_keep, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Whole encoder blocks per call.  Replaces Block.forward (models/de_vit.py:103-121: norm1 -> Attention :65-87 ->
@@ -513,6 +552,29 @@ DEVIT_API int devit_comm_unique_id(void* id /* [DEVIT_COMM_ID_BYTES] host */);
 DEVIT_API int devit_comm_init(const void* id, int rank, int world, void** comm);
 DEVIT_API int devit_comm_allreduce_f32(void* comm, float* buf, size_t count, void* stream);
 DEVIT_API int devit_comm_destroy(void* comm);
+
+/* ------------------------------------------------------------------------------------------
+ * The encoder blocks with dropout p > 0 (section "Dropout" above): devit_encoder_fwd / devit_block_bwd with one devit_block_dropout per block
+ * beside the existing structs.  thr == 0 and thr_attn == 0 launch exactly what the plain entry points launch.  Otherwise, same order of
+ * kernels with these differences -- forward: attention through devit_attn_fwd_drop (thr_attn > 0); GELU epilogue, then devit_dropout_apply on
+ * the hidden (site 3); proj and fc2 store fp32 into `tmp` (DEVIT_EPI_STORE_F32) and devit_dropout_residual forms x1 / x2 (sites 2, 4; the
+ * full-row fc2 launch and DEVIT_BLK_ATT are not taken).  Backward: io->g2 is MASKED IN PLACE first (site 4) and fc2's bias gradient is the
+ * masked g2's column sums -- so io->g2_bias_done must be 0, and the block ABOVE a block with thr > 0 passes io->prev_fc2_b_grad = NULL --;
+ * dh_pre is masked after the dGELU dgrad (site 3); the LayerNorm backward behind fc1's dgrad runs without its column sums, g1 is masked (site 2)
+ * and proj's bias gradient comes from the masked g1; attention through devit_attn_bwd_drop.  Weight-gradient jobs read the masked buffers.
+ * Compacted blocks index their compact layout.  bf16 blocks only.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  unsigned long long seed; /* the forward's seed */
+  int block;               /* the block's index in the model: part of every counter */
+  unsigned thr, thr_attn;  /* thresholds of drop (sites 2, 3, 4) and attn_drop (site 1); 0 = that dropout is off */
+  float scale_keep, scale_keep_attn; /* 1 / (1 - p) */
+  float* tmp;              /* fp32 [pad_rows(M)][D] scratch (thr > 0), may be shared by all blocks of a call */
+} devit_block_dropout;
+DEVIT_API int devit_encoder_fwd_drop(int nblocks, const devit_block_weights* w, const devit_block_acts* acts, const devit_block_dropout* drop,
+                           int B, int N, int D, float eps, void* stream);
+DEVIT_API int devit_block_bwd_drop(const devit_block_weights* w, const devit_block_acts* acts, const devit_block_wgrads* grads,
+                         const devit_block_bwd_io* io, const devit_block_dropout* drop, int B, int N, int D, float eps, void* stream);
 
 #ifdef __cplusplus
 }
