@@ -186,7 +186,8 @@ DEVIT_API int devit_wgrad_grouped(const devit_wgrad_job* jobs, int njobs, int K,
  *   physical input row of logical row r: in_group > 0 ? (r / in_group) * in_stride + r % in_group : r
  *   (final norm: only the cls/dist rows are consumed, de_vit.py:288 -> in_group = 2, in_stride = 198)
  *   y_bf16 / y_f32: either may be NULL.  mean / rstd: [rows] saved for backward (may be NULL).
- *   D % 128 == 0, D <= 1024.
+ *   D: a multiple of 64 up to 384 (64, 192 and 320 run the ragged variant of the same kernels), or 512, 768, 1024; any other
+ *   width (448, 640, ..., > 1024) is DEVIT_ERR_SHAPE before anything is launched.
  * bwd: dx[phys row] = (dres ? dres[phys row] : 0) + LN'(dy[r]); dx_bf16 (optional) = rowscale * dx as the
  *   bf16 branch gradient consumed by the previous sub-block's dgrad / wgrad GEMMs;
  *   dgamma / dbeta [D] (accumulate != 0 adds); dx_bf16_colsum (optional) [D] (+)= column sums of dx_bf16 = the

@@ -540,6 +540,7 @@ def test_relation_loss(dev):
     flat (std 0.25) and the unit scale: at unit scale both softmaxes sit on the diagonal and S is a small difference of terms near 1."""
     from devit_amd import ops
     from _attn_model import relation_bounds, ratio
+    from _tail_model import rel_feature_loss_bounds
     from conftest import chk
     B, N, Hs, Ht = 3, 198, 2, 4
     Ds, Dt = Hs * 64, Ht * 64
@@ -573,6 +574,11 @@ def test_relation_loss(dev):
             r = ratio(s_buf.grad[:M, j * Ds:(j + 1) * Ds].double().view(B, N, Ds), want, bound)
             print(f"relation std {std} block {j}: worst |err| / bound {r:.3f}")
             assert chk(r, 1.0, name=f"relation/std{std}/block{j}"), (std, j, r)
+            # the loss VALUE at both scales against float64 (the fp32 reference above cannot resolve it at unit scale): _tail_model's bound
+            want_l, e_l = rel_feature_loss_bounds(fs, ft, 64, 64)
+            rl = ratio(losses[j].detach().double().cpu(), want_l, e_l)
+            print(f"relation std {std} block {j}: loss {float(losses[j]):.6e} float64 {float(want_l):.6e} |err| / bound {rl:.3f}")
+            assert chk(rl, 1.0, name=f"relation/std{std}/loss{j}"), (std, j, rl, float(losses[j]), float(want_l))
 
 
 def test_adamw_and_sumsq(dev):
