@@ -90,6 +90,9 @@ HSIC_BF16, HSIC_F16, HSIC_F32 = range(3)
 # dropout sites (include/devit_hip.h, "Dropout"): which nn.Dropout of the model a mask belongs to
 DROP_POS, DROP_ATTN, DROP_PROJ, DROP_HIDDEN, DROP_FC2 = range(5)
 
+# devit_gemm_route
+ROUTE_TILE128, ROUTE_TILE256, ROUTE_FULL_ROW, ROUTE_GEMM4 = 1, 3, 4, 5
+
 WGRAD_MAX_JOBS = 48
 ABI_VERSION = 3
 # devit_abi_struct_size(which) -> the mirror it must equal (checked at load time: an array of stale mirrors is misread silently)
@@ -113,6 +116,7 @@ SIGNATURES = {
     "devit_gemm_full_row_selected": (_I, [_I, _I, _I, _I]),
     "devit_wgrad_grouped": (_I, [C.POINTER(WgradJob), _I, _I, _I, _P]),
     "devit_gemm_bf16": (_I, [C.POINTER(Operand), C.POINTER(Operand), _I, _I, _I, _I, _I, C.POINTER(Epilogue), _P]),
+    "devit_gemm_route": (_I, [C.POINTER(Operand), C.POINTER(Operand), _I, _I, _I, _I, _I, C.POINTER(Epilogue)]),
     "devit_set_reserved_cus": (_I, [_I]),
     "devit_get_reserved_cus": (_I, []),
     "devit_layernorm_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _I, _P]),

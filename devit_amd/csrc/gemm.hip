@@ -1,5 +1,5 @@
 // Host side of the bf16 MFMA GEMM family: argument checks, the tile and kernel selection rules with the measurements behind them, and the C entry
-// points devit_gemm_bf16, devit_gemm_full_row_selected, devit_dgrad_layernorm_bwd(_fused), devit_set / get_reserved_cus.  The kernels and their
+// points devit_gemm_bf16, devit_gemm_route, devit_gemm_full_row_selected, devit_dgrad_layernorm_bwd(_fused), devit_set / get_reserved_cus.  The kernels and their
 // launchers live in gemm_tile128.hip / gemm_tile256.hip (gemm_tile.h), gemm4.hip and gemmfr.hip; devit_wgrad_grouped in wgradfr.hip.
 #include <stdlib.h>
 
@@ -78,10 +78,17 @@ extern "C" int devit_gemm_bf16(const devit_operand* Aop, const devit_operand* Bo
 }
 
 namespace {
-// devit_gemm_bf16; with `ln`, the launch whose bf16 output feeds the LayerNorm backward `ln` in the same kernel (devit_dgrad_layernorm_bwd: the
-// caller has checked devit_dgrad_layernorm_bwd_fused, anything else is an error here, never a silent other path)
-int gemm_launch(const devit_operand* Aop, const devit_operand* Bop, int M, int N, int K, int batch, int split_k, const devit_epilogue* ep,
-                const FusedLnBwd* ln, void* stream) {
+// What a launch runs on: the tile (cfg 1 = 128x128, 3 = 256x256, 4 = the full-row 256x384 kernel) and whether the four-wave kernel takes a 256x256
+// launch.  as_enum() is what devit_gemm_route reports.
+struct Route {
+  int cfg, variant;
+  bool use4;
+  int as_enum() const { return cfg == 4 ? DEVIT_ROUTE_FULL_ROW : use4 ? DEVIT_ROUTE_GEMM4 : cfg == 3 ? DEVIT_ROUTE_TILE256 : DEVIT_ROUTE_TILE128; }
+};
+
+// The argument checks of devit_gemm_bf16 and THE selection rule of the family, in one place: gemm_launch launches what this says, devit_gemm_route
+// reports it.  Host arithmetic and the environment only: no pointer is dereferenced but the three descriptors, nothing is launched, no device is asked.
+int gemm_route(const devit_operand* Aop, const devit_operand* Bop, int M, int N, int K, int batch, int split_k, const devit_epilogue* ep, Route& r) {
   DEVIT_CHECK(Aop && Bop && Aop->ptr && Bop->ptr && ep && ep->out, DEVIT_ERR_ARG, "devit_gemm_bf16: null pointer");
   const void* A = Aop->ptr;
   const void* B = Bop->ptr;
@@ -117,14 +124,6 @@ int gemm_launch(const devit_operand* Aop, const devit_operand* Bop, int M, int N
   DEVIT_CHECK(ep->dtype16 == 0 || ep->dtype16 == 1, DEVIT_ERR_ARG, "devit_gemm_bf16: dtype16 must be 0 (bf16) or 1 (f16)");
   DEVIT_CHECK(!f16 || (!a_kmajor && !b_kmajor && ep->kind != DEVIT_EPI_DGELU_BF16 && ep->kind != DEVIT_EPI_ATOMIC_F32),
               DEVIT_ERR_ARG, "devit_gemm_bf16: f16 operands are built for the forward layouts / epilogues only");
-  GemmParams g;
-  g.A = (const __bf16*)A; g.B = (const __bf16*)B;
-  g.lda = lda; g.ldb = ldb;
-  g.a_group = Aop->row_group; g.a_skip = Aop->row_skip; g.b_group = Bop->row_group; g.b_skip = Bop->row_skip;
-  g.a_bs = Aop->batch_stride; g.b_bs = Bop->batch_stride;
-  g.M = M; g.N = N; g.K = K;
-  g.tiles_m = 0; g.tiles_n = 0; g.split_k = split_k;
-  g.ep = *ep;
   // tile choice: 128x128 (4 waves, two workgroups per CU) or 256x256 (8 waves of 128x64, ping-pong schedule, one per CU)
   const int variant = (a_kmajor ? 2 : 0) + (b_kmajor ? 1 : 0);
   // Measured on the step's shapes (tools/gemm_tiles.py + tools/gpu_tiles.sh, M = 50688, TFLOP/s 256x256 vs 128x128):
@@ -168,6 +167,42 @@ int gemm_launch(const devit_operand* Aop, const devit_operand* Bop, int M, int N
               "M %% 256 == 0, >= 64 row tiles, K >= 192, DEVIT_GEMMFR != 0, no row_group / row_skip on B): M=%d N=%d K=%d row_group=%d", M, N, K,
               Bop->row_group);
   if (use_fr) cfg = 4;
+  // the four-wave kernel takes the 256x256 launches it is built for: row-major x row-major, whole 256-wide n-tiles, bf16
+  // Which 256x256 launches take it (round 4, per-shape times inside the serialized step, tools/step_gemm_table.py): the two kernels
+  // run their K loops at the same fill-bound rate (profiles/r04_a_gemm_four_wave.txt); the four-wave one is 2.5-3.4 % faster where the
+  // epilogue is a plain bf16 store or the fp32 residual at K >= 768 (teacher qkv 172.6 -> 168.3 us, fc2 266 -> 257), and 5-10 % SLOWER
+  // with the GELU epilogue (one wave per SIMD issues its vector instructions at half the rate two waves share) and on the batched
+  // Gram launches.  DEVIT_GEMM4=0 / 1 forces it off / on for everything it is built for (read per call: tests switch it).
+  const char* gemm4_env = getenv("DEVIT_GEMM4");
+  const bool gemm4_ok = cfg == 3 && variant == 0 && !f16 && N % 256 == 0 && K / BK >= 3 && split_k == 1 &&
+                        ep->kind != DEVIT_EPI_DGELU_BF16 && ep->kind != DEVIT_EPI_ATOMIC_F32;
+  const bool gemm4_pays = (ep->kind == DEVIT_EPI_STORE_BF16 || ep->kind == DEVIT_EPI_RESIDUAL_F32) && K >= 768 && batch == 1;
+  const bool use4 = gemm4_ok && (gemm4_env ? atoi(gemm4_env) != 0 : gemm4_pays);
+  r.cfg = cfg;
+  r.variant = variant;
+  r.use4 = use4;
+  const int bm = cfg == 1 ? 128 : 256, bn = cfg == 4 ? 384 : bm;
+  DEVIT_CHECK((long long)(M / bm) * ((N + bn - 1) / bn) * split_k * batch < (1ll << 31), DEVIT_ERR_SHAPE, "devit_gemm_bf16: too many tiles");
+  return DEVIT_OK;
+}
+
+// devit_gemm_bf16; with `ln`, the launch whose bf16 output feeds the LayerNorm backward `ln` in the same kernel (devit_dgrad_layernorm_bwd: the
+// caller has checked devit_dgrad_layernorm_bwd_fused, anything else is an error here, never a silent other path)
+int gemm_launch(const devit_operand* Aop, const devit_operand* Bop, int M, int N, int K, int batch, int split_k, const devit_epilogue* ep,
+                const FusedLnBwd* ln, void* stream) {
+  Route route;
+  const int rc_route = gemm_route(Aop, Bop, M, N, K, batch, split_k, ep, route);
+  if (rc_route != DEVIT_OK) return rc_route;
+  const int cfg = route.cfg, variant = route.variant, a_kmajor = Aop->kmajor, b_kmajor = Bop->kmajor;
+  const bool use4 = route.use4;
+  GemmParams g;
+  g.A = (const __bf16*)Aop->ptr; g.B = (const __bf16*)Bop->ptr;
+  g.lda = Aop->ld; g.ldb = Bop->ld;
+  g.a_group = Aop->row_group; g.a_skip = Aop->row_skip; g.b_group = Bop->row_group; g.b_skip = Bop->row_skip;
+  g.a_bs = Aop->batch_stride; g.b_bs = Bop->batch_stride;
+  g.M = M; g.N = N; g.K = K;
+  g.tiles_m = 0; g.tiles_n = 0; g.split_k = split_k;
+  g.ep = *ep;
   const int bm = cfg == 1 ? 128 : 256, bn = cfg == 4 ? 384 : bm;
   g.tiles_m = M / bm;
   g.tiles_n = (N + bn - 1) / bn;
@@ -187,7 +222,6 @@ int gemm_launch(const devit_operand* Aop, const devit_operand* Bop, int M, int N
     if (g.gn > g.tiles_n) g.gn = g.tiles_n;
   }
   const long long tiles = (long long)g.tiles_m * g.tiles_n * split_k * batch;
-  DEVIT_CHECK(tiles < (1ll << 31), DEVIT_ERR_SHAPE, "devit_gemm_bf16: too many tiles");
   g.total_tiles = (int)tiles;
   g.d_per_z = make_fastdiv(g.tiles_m * g.tiles_n);
   g.d_chunk = make_fastdiv(g.gn * g.tiles_m);
@@ -209,17 +243,6 @@ int gemm_launch(const devit_operand* Aop, const devit_operand* Bop, int M, int N
               "the fused dgrad + LayerNorm-backward launch needs the full-row kernel and one tile per workgroup: M=%d K=%d", M, K);
   if (nwg > (tiles + 7) / 8 * 8) nwg = (tiles + 7) / 8 * 8;
   hipStream_t s = (hipStream_t)stream;
-  // the four-wave kernel takes the 256x256 launches it is built for: row-major x row-major, whole 256-wide n-tiles, bf16
-  // Which 256x256 launches take it (round 4, per-shape times inside the serialized step, tools/step_gemm_table.py): the two kernels
-  // run their K loops at the same fill-bound rate (profiles/r04_a_gemm_four_wave.txt); the four-wave one is 2.5-3.4 % faster where the
-  // epilogue is a plain bf16 store or the fp32 residual at K >= 768 (teacher qkv 172.6 -> 168.3 us, fc2 266 -> 257), and 5-10 % SLOWER
-  // with the GELU epilogue (one wave per SIMD issues its vector instructions at half the rate two waves share) and on the batched
-  // Gram launches.  DEVIT_GEMM4=0 / 1 forces it off / on for everything it is built for (read per call: tests switch it).
-  const char* gemm4_env = getenv("DEVIT_GEMM4");
-  const bool gemm4_ok = cfg == 3 && variant == 0 && !f16 && N % 256 == 0 && K / BK >= 3 && split_k == 1 &&
-                        ep->kind != DEVIT_EPI_DGELU_BF16 && ep->kind != DEVIT_EPI_ATOMIC_F32;
-  const bool gemm4_pays = (ep->kind == DEVIT_EPI_STORE_BF16 || ep->kind == DEVIT_EPI_RESIDUAL_F32) && K >= 768 && batch == 1;
-  const bool use4 = gemm4_ok && (gemm4_env ? atoi(gemm4_env) != 0 : gemm4_pays);
   auto info = [&] {
     devit_launch_info i = {ln ? "devit_dgrad_layernorm_bwd" : "devit_gemm_bf16"};
     i.a_kmajor = a_kmajor != 0; i.b_kmajor = b_kmajor != 0; i.kind = ep->kind;
@@ -238,6 +261,13 @@ int gemm_launch(const devit_operand* Aop, const devit_operand* Bop, int M, int N
   });
 }
 }  // namespace
+
+// What devit_gemm_bf16 would run this call on (DEVIT_ROUTE_*), or the DEVIT_ERR_* of its argument checks: gemm_route itself, nothing launched
+extern "C" int devit_gemm_route(const devit_operand* A, const devit_operand* B, int M, int N, int K, int batch, int split_k, const devit_epilogue* ep) {
+  Route r;
+  const int rc = gemm_route(A, B, M, N, K, batch, split_k, ep, r);
+  return rc != DEVIT_OK ? rc : r.as_enum();
+}
 
 // Would devit_dgrad_layernorm_bwd take the fused launch?  The rule, in one place: the full-row kernel would run the product (N = D = 384, whole
 // 256-row tiles and enough of them, DEVIT_GEMMFR / DEVIT_GEMM_FORCE not against it) AND every workgroup of its grid gets at most one tile -- with a

@@ -182,6 +182,20 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+def gemm_route(a, lda, a_km, b, ldb, b_km, M, N, K, *, kind, out, ldc, bias=None, colscale=None, aux=None, aux_in=None,
+               res=None, rowscale=None, rows_per_scale=0, pos=None, patch_tokens=0, extra_tokens=0, exact_gelu=0, batch=1,
+               a_bs=0, b_bs=0, out_bs=0, m_valid=0, split_k=1, a_group=0, a_skip=0, b_group=0, b_skip=0, dtype16=0):
+    """devit_gemm_route() itself for the arguments gemm() takes (csrc/gemm.hip; no GPU needed, tensors of any device or plain integer addresses):
+    the L.ROUTE_* kernel the call would run on, or the negative DEVIT_ERR_* its argument checks return.  Not a restatement: one rule."""
+    def adr(t):
+        return t if t is None or isinstance(t, int) else t.data_ptr()
+    A = L.Operand(adr(a), lda, a_km, a_group, a_skip, a_bs)
+    Bo = L.Operand(adr(b), ldb, b_km, b_group, b_skip, b_bs)
+    ep = L.Epilogue(kind, adr(out), ldc, adr(bias), adr(colscale), adr(aux), adr(aux_in), adr(res), adr(rowscale),
+                    rows_per_scale, adr(pos), patch_tokens, extra_tokens, exact_gelu, out_bs, m_valid, dtype16)
+    return int(L.load().devit_gemm_route(C.byref(A), C.byref(Bo), M, N, K, batch, split_k, C.byref(ep)))
+
+
 def full_row_selected(M, N, K, kind=L.EPI_RESIDUAL_F32):
     """devit_gemm_full_row_selected() itself (csrc/gemm.hip; no GPU needed): would (row-major A) x (K-MAJOR B) with N outputs run on the full-row
     256x384 kernel?  (A k-major weight with the fp32 residual epilogue exists on that kernel only.)  Not a restatement: one rule, one parser of

@@ -122,7 +122,8 @@ typedef struct {
   const float* res;        /* RESIDUAL: [M][ldc] f32 input stream (may alias out) */
   const float* rowscale;   /* RESIDUAL: [M / rows_per_scale] per-sample DropPath scale or NULL */
   int rows_per_scale;      /* RESIDUAL: tokens per sample (198) */
-  const float* pos;        /* PATCH: [tok + T][N] f32 position embedding */
+  const float* pos;        /* PATCH: [tok + T][ldc] f32 position embedding: its row stride is the OUTPUT's ldc (= N when both are dense);
+                              rows tok .. tok + T - 1 and columns 0 .. N - 1 are read */
   int patch_tokens;        /* PATCH: T = 196 */
   int extra_tokens;        /* PATCH: tok = 2 (cls + dist) or 1 */
   int exact_gelu;          /* must be 0: the fused GELU is a fitted form, |err| <= 2.6e-5 (erff() variant not built) */
@@ -151,6 +152,14 @@ DEVIT_API int devit_gemm_bf16(const devit_operand* A, const devit_operand* B, in
  * with a k-major weight exists on that kernel only, so a caller that holds a k-major copy of a forward weight (devit_block_weights.fc2_w16t)
  * asks first. */
 DEVIT_API int devit_gemm_full_row_selected(int M, int N, int K, int kind);
+/* Which kernel devit_gemm_bf16 would run this call on -- its one selection rule, asked instead of restated (tests tie their shapes to the
+ * instantiation they mean to reach; a retune of the rule then fails them instead of silently moving them).  Returns a DEVIT_ROUTE_*: 128x128
+ * tiles, 256x256 eight-wave ping-pong tiles, the full-row 256x384 kernel or the four-wave 256x256 kernel; or the negative DEVIT_ERR_* that
+ * devit_gemm_bf16 returns from its argument checks for this call.  Reads DEVIT_GEMMFR / DEVIT_GEMM4 per call and DEVIT_GEMM_FORCE once per
+ * process, as the launch does.  Launches nothing, dereferences no data pointer (the pointers are checked for NULL and alignment), needs no device. */
+enum { DEVIT_ROUTE_TILE128 = 1, DEVIT_ROUTE_TILE256 = 3, DEVIT_ROUTE_FULL_ROW = 4, DEVIT_ROUTE_GEMM4 = 5 };
+DEVIT_API int devit_gemm_route(const devit_operand* A, const devit_operand* B, int M, int N, int K, int batch, int split_k,
+                     const devit_epilogue* ep);
 DEVIT_API int devit_set_reserved_cus(int n);
 DEVIT_API int devit_get_reserved_cus(void);
 
