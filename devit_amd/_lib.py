@@ -71,6 +71,11 @@ class WgradJob(C.Structure):
                 ("ldc", C.c_int), ("transposed", C.c_int), ("a_colsum", C.c_void_p)]
 
 
+class MixSample(C.Structure):
+    _fields_ = [("mode", C.c_int), ("lam", C.c_float), ("y0", C.c_int), ("y1", C.c_int), ("x0", C.c_int), ("x1", C.c_int),
+                ("reserved", C.c_int * 2)]
+
+
 # devit_launch_info.has
 HAS_Y_BF16, HAS_Y_F32, HAS_DY_F32, HAS_DRES, HAS_DX, HAS_DX_BF16, HAS_DQKV_ADD = 1, 2, 4, 8, 16, 32, 64
 
@@ -96,7 +101,8 @@ ROUTE_TILE128, ROUTE_TILE256, ROUTE_FULL_ROW, ROUTE_GEMM4 = 1, 3, 4, 5
 WGRAD_MAX_JOBS = 48
 ABI_VERSION = 3
 # devit_abi_struct_size(which) -> the mirror it must equal (checked at load time: an array of stale mirrors is misread silently)
-ABI_STRUCTS = {0: Epilogue, 1: Operand, 2: BlockWeights, 3: BlockWgrads, 4: BlockActs, 5: BlockBwdIO, 6: IndexJob, 7: WgradJob, 8: LaunchInfo, 9: BlockDropout}
+ABI_STRUCTS = {0: Epilogue, 1: Operand, 2: BlockWeights, 3: BlockWgrads, 4: BlockActs, 5: BlockBwdIO, 6: IndexJob, 7: WgradJob, 8: LaunchInfo, 9: BlockDropout,
+               10: MixSample}
 
 
 class DevitError(RuntimeError):
@@ -149,6 +155,8 @@ SIGNATURES = {
     "devit_im2row_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "devit_mix_im2row_bf16": (_I, [_P, _P, _P, _I, _I, C.c_double, _I, _I, _I, _I, _P]),
     "devit_mix_targets": (_I, [_P, _P, _I, _I, C.c_double, C.c_double, _P]),
+    "devit_mix_im2row_table": (_I, [_P, _P, _P, _P, _P, _I, _P]),
+    "devit_mix_targets_table": (_I, [_P, _P, _P, _I, _I, C.c_double, _P]),
     "devit_embed_tokens": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "devit_embed_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
     "devit_cast_bf16": (_I, [_P, _P, _Z, _I, _P]),

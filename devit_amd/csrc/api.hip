@@ -36,6 +36,7 @@ extern "C" size_t devit_abi_struct_size(int which) {
     case 7: return sizeof(devit_wgrad_job);
     case 8: return sizeof(devit_launch_info);
     case 9: return sizeof(devit_block_dropout);
+    case 10: return sizeof(devit_mix_sample);
     default: return 0;
   }
 }

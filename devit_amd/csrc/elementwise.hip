@@ -82,6 +82,81 @@ __global__ __launch_bounds__(256) void mix_targets_kernel(const long long* y, fl
   }
 }
 
+// ---- the same stage with one (mode, lam, box) per sample (timm Mixup mode='elem' / 'pair': _mix_elem / _mix_pair) ----------
+// blockIdx.y picks the sample, so its table entry is uniform over the workgroup: a mode 0 sample never loads its partner (B-1-b), a
+// cutmix sample loads it only for the 8-element chunks that meet the box.  Consecutive grid rows are the two samples of a pair
+// (0, B-1, 1, B-2, ...), so that the workgroups that read an image as their own and as their partner's are dispatched next to
+// each other (measured against sample order, profiles/r12_b_mix_table_cost.json "grid_mapping_us": 71.5 us against 91.0 us for an
+// all-mixup table at B = 256).  1 - lam is formed HERE in fp32 from the fp32 lam (timm: lam_batch is float32, and 1 - lam on a
+// np.float32 stays float32) -- mix_im2row_kernel above gets f32(1 - lam) from a double subtraction on the host, as timm's batch
+// mode does; both stay as they are.  No address depends on what the table holds: only selects and branches do, so any table bytes
+// are memory-safe (the host validates the values before it uploads them).
+struct MixTableArgs {
+  const float* img;
+  __bf16* rows;         // bf16 patch rows or NULL
+  __bf16* rows_f16;     // the same values as IEEE f16 or NULL
+  float* img_out;       // the mixed batch as fp32 images [B,3,224,224] (f32 models) or NULL; never img itself
+  const devit_mix_sample* table;
+  int B;
+};
+__global__ __launch_bounds__(256) void mix_im2row_table_kernel(const MixTableArgs a) {
+#pragma clang fp contract(off)   // x * lam + flip * (1 - lam) as three rounded operations, and 1 - lam a fourth
+  const int b = (blockIdx.y & 1) ? a.B - 1 - (int)(blockIdx.y >> 1) : (int)(blockIdx.y >> 1);
+  const devit_mix_sample s = a.table[b];
+  const float lam = s.lam, oml = 1.0f - lam;
+  const size_t img_b = (size_t)b * 3 * 224 * 224, img_p = (size_t)(a.B - 1 - b) * 3 * 224 * 224;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < 196 * 96; i += gridDim.x * 256) {
+    const int k8 = i % 96, t = i / 96, py = t / 14, px = t % 14;
+    const int c = k8 >> 5, kh = (k8 >> 1) & 15, kw0 = (k8 & 1) * 8;
+    const int y = py * 16 + kh, x = px * 16 + kw0;
+    const size_t off = ((size_t)c * 224 + y) * 224 + x;
+    const float* src = a.img + img_b + off;
+    const float* flp = a.img + img_p + off;
+    float v[8];
+    *(f32x4*)v = *(const f32x4*)src;
+    *(f32x4*)(v + 4) = *(const f32x4*)(src + 4);
+    if (s.mode == 1) {
+      float w[8];
+      *(f32x4*)w = *(const f32x4*)flp;
+      *(f32x4*)(w + 4) = *(const f32x4*)(flp + 4);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float p0 = v[e] * lam, p1 = w[e] * oml;
+        v[e] = p0 + p1;
+      }
+    } else if (s.mode == 2 && y >= s.y0 && y < s.y1 && x + 8 > s.x0 && x < s.x1) {
+      float w[8];
+      *(f32x4*)w = *(const f32x4*)flp;
+      *(f32x4*)(w + 4) = *(const f32x4*)(flp + 4);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = (x + e >= s.x0 && x + e < s.x1) ? w[e] : v[e];
+    }
+    const f32x4 lo = {v[0], v[1], v[2], v[3]}, hi = {v[4], v[5], v[6], v[7]};
+    const size_t chunk = (size_t)b * (196 * 96) + i;
+    if (a.rows) *(bf16x8*)(a.rows + chunk * 8) = cvt8<false>(lo, hi);
+    if (a.rows_f16) *(bf16x8*)(a.rows_f16 + chunk * 8) = cvt8<true>(lo, hi);
+    if (a.img_out) {
+      float* dst = a.img_out + img_b + off;
+      *(f32x4*)dst = lo;
+      *(f32x4*)(dst + 4) = hi;
+    }
+  }
+}
+
+// targets[b][c] = lam_b * smooth(y[b])[c] + (1.0f - lam_b) * smooth(y[B-1-b])[c]   (timm mixup_target with a [B,1] float32 lam)
+__global__ __launch_bounds__(256) void mix_targets_table_kernel(const long long* y, float* out, const devit_mix_sample* table, int B,
+                                                                int C, float off, float on) {
+#pragma clang fp contract(off)
+  const int total = B * C;
+  for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+    const int b = idx / C, c = idx % C;
+    const float lam = table[b].lam, oml = 1.0f - lam;
+    const float t1 = (int)y[b] == c ? on : off, t2 = (int)y[B - 1 - b] == c ? on : off;
+    const float p0 = t1 * lam, p1 = t2 * oml;
+    out[idx] = p0 + p1;
+  }
+}
+
 // ---- x[b, t] = token_t + pos[t] for the extra (cls / dist) tokens: models/de_vit.py:259-264 ----------
 __global__ __launch_bounds__(256) void embed_tokens_kernel(const float* cls, const float* dist, const float* pos,
                                                            float* x, int B, int T, int D, int ntok) {
@@ -369,6 +444,32 @@ extern "C" int devit_mix_targets(const long long* labels, float* targets, int B,
   const double off = smoothing / C, on = 1.0 - smoothing + off;      // timm mixup_target: off / on values in double
   hipLaunchKernelGGL(mix_targets_kernel, dim3(grid_for((size_t)B * C)), dim3(256), 0, (hipStream_t)stream, labels, targets, B,
                      C, (float)lam, (float)(1.0 - lam), (float)off, (float)on);
+  DEVIT_LAUNCH_CHECK();
+  return DEVIT_OK;
+}
+
+extern "C" int devit_mix_im2row_table(const float* img, void* rows, void* rows_f16, float* img_out, const devit_mix_sample* table,
+                                      int B, void* stream) {
+  DEVIT_CHECK(img && table && (rows || rows_f16 || img_out), DEVIT_ERR_ARG, "devit_mix_im2row_table: bad argument");
+  DEVIT_CHECK(B > 0 && B <= 65535, DEVIT_ERR_ARG, "devit_mix_im2row_table: B = %d outside 1 .. 65535 (one grid row per sample)", B);
+  DEVIT_CHECK(img_out != img, DEVIT_ERR_ARG,
+              "devit_mix_im2row_table: img_out is img (a sample's partner is read after the sample may have been written)");
+  // the table's VALUES are not checked here (device memory; reading it would synchronise): no address in the kernel depends on them
+  MixTableArgs a{img, (__bf16*)rows, (__bf16*)rows_f16, img_out, table, B};
+  // one 8-element chunk per thread (196 * 96 chunks per sample = 73.5 workgroups); a grid-stride over 16 workgroups per sample measured
+  // 7 to 11 us slower at B = 256 (profiles/r12_b_mix_table_cost.json, "grid_mapping_us")
+  hipLaunchKernelGGL(mix_im2row_table_kernel, dim3(74, B), dim3(256), 0, (hipStream_t)stream, a);
+  DEVIT_LAUNCH_CHECK();
+  return DEVIT_OK;
+}
+
+extern "C" int devit_mix_targets_table(const long long* labels, float* targets, const devit_mix_sample* table, int B, int C,
+                                       double smoothing, void* stream) {
+  DEVIT_CHECK(labels && targets && table && B > 0 && C > 0 && (size_t)B * C <= 0x7fffffffu, DEVIT_ERR_ARG,
+              "devit_mix_targets_table: bad argument");
+  const double off = smoothing / C, on = 1.0 - smoothing + off;      // as devit_mix_targets
+  hipLaunchKernelGGL(mix_targets_table_kernel, dim3(grid_for((size_t)B * C)), dim3(256), 0, (hipStream_t)stream, labels, targets,
+                     table, B, C, (float)off, (float)on);
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
 }

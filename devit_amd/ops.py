@@ -23,6 +23,7 @@ import contextlib
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -961,6 +962,117 @@ def mix_targets(labels, num_classes, lam, smoothing):
     labels = labels.contiguous().long()
     out = torch.empty((labels.shape[0], num_classes), dtype=F32, device=labels.device)
     call("devit_mix_targets", ptr(labels), ptr(out), labels.shape[0], num_classes, float(lam), float(smoothing), stream_ptr())
+    return out
+
+
+# ---- per-sample Mixup / CutMix (timm Mixup mode='elem' / 'pair'): one devit_mix_sample per image ----
+# host mirror of devit_mix_sample (32 bytes, _lib.MixSample): what Mixup.draw_table fills and mix_table uploads
+MIX_SAMPLE_DTYPE = np.dtype([("mode", "<i4"), ("lam", "<f4"), ("y0", "<i4"), ("y1", "<i4"), ("x0", "<i4"), ("x1", "<i4"),
+                             ("reserved", "<i4", (2,))])
+MIX_RING_SLOTS = 256
+_mix_ring = {}        # device -> [pinned uint8 [MIX_RING_SLOTS, bytes per slot], uploads so far]
+
+
+class MixTable:
+    """A validated table of B devit_mix_sample entries: `host` (numpy, MIX_SAMPLE_DTYPE) and its copy on the device, `dev` (uint8)."""
+
+    def __init__(self, host, dev):
+        self.host, self.dev, self.B = host, dev, host.shape[0]
+
+
+def mix_entries(entries):
+    """A numpy structured array with the fields of MIX_SAMPLE_DTYPE, or a list of (mode, lam, y0, y1, x0, x1) -> a validated
+    MIX_SAMPLE_DTYPE array.  ValueError for a mode outside {0, 1, 2}, lam outside [0, 1] or NaN, a box outside
+    0 <= lo <= hi <= 224, or mode 0 with lam != 1 (the images would stay as they are and the targets would not).  The kernels
+    are memory-safe for any table bytes and the C entry cannot read device memory, so this is where the values are checked."""
+    if isinstance(entries, np.ndarray) and entries.dtype.names:
+        cols = [np.asarray(entries[n]).reshape(-1) for n in ("mode", "lam", "y0", "y1", "x0", "x1")]
+    else:
+        rows = [tuple(e) for e in entries]
+        if any(len(r) != 6 for r in rows):
+            raise ValueError("mix_table: an entry is (mode, lam, y0, y1, x0, x1)")
+        cols = [np.asarray(c) for c in zip(*rows)] if rows else [np.zeros(0)] * 6
+    mode, lam, y0, y1, x0, x1 = cols
+    if mode.shape[0] < 1:
+        raise ValueError("mix_table: empty table")
+    lam = lam.astype(np.float64)
+    if not np.isin(mode, (0, 1, 2)).all():
+        raise ValueError(f"mix_table: mode must be 0 (none), 1 (mixup) or 2 (cutmix), got {sorted(set(mode.tolist()) - {0, 1, 2})}")
+    if not ((lam >= 0) & (lam <= 1)).all():             # (a NaN compares false)
+        raise ValueError(f"mix_table: lam must lie in [0, 1], got {lam[~((lam >= 0) & (lam <= 1))].tolist()}")
+    for lo, hi, ax in ((y0, y1, "y"), (x0, x1, "x")):
+        bad = ~((0 <= lo) & (lo <= hi) & (hi <= 224))
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"mix_table: entry {i}: box [{lo[i]}, {hi[i]}) on {ax} is not inside 0 <= lo <= hi <= 224")
+    if ((mode == 0) & (lam != 1)).any():
+        raise ValueError("mix_table: a mode 0 entry carries lam != 1: its image stays as it is, so its target must too")
+    host = np.zeros(mode.shape[0], dtype=MIX_SAMPLE_DTYPE)
+    for n, c in zip(("mode", "lam", "y0", "y1", "x0", "x1"), (mode, lam, y0, y1, x0, x1)):
+        host[n] = c
+    return host
+
+
+def mix_table(entries, device="cuda"):
+    """entries (see mix_entries) -> MixTable on `device`.  ValueError, before anything touches the device, for a mode outside
+    {0, 1, 2}, lam outside [0, 1] or NaN, a box outside 0 <= lo <= hi <= 224, and mode 0 with lam != 1.  The upload is an async copy
+    out of a pinned ring and never waits for the stream: the host runs steps ahead of the GPU, so every table in flight has a slot of
+    its own (as optim.FlatAdamW's scalars).  No event guards a slot: the ring holds MIX_RING_SLOTS = 256 uploads, and a caller more
+    than 255 uploads ahead of the stream (one upload per training step) would overwrite a table still in flight."""
+    host = mix_entries(entries)
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:      # 'cuda' and 'cuda:N' of the current device share one ring
+        device = torch.device("cuda", torch.cuda.current_device())
+    nbytes = host.nbytes
+    ring = _mix_ring.get(device)
+    if ring is None or ring[0].shape[1] < nbytes:
+        # (a ring that was outgrown is dropped, not reused: the pinned allocator keeps it until the copies out of it are done)
+        ring = _mix_ring[device] = [torch.zeros((MIX_RING_SLOTS, max(nbytes, 8192)), dtype=torch.uint8).pin_memory(), 0]
+    slot = ring[0][ring[1] % MIX_RING_SLOTS, :nbytes]
+    ring[1] += 1
+    slot.copy_(torch.from_numpy(host.view(np.uint8)))
+    dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    dev.copy_(slot, non_blocking=True)
+    return MixTable(host, dev)
+
+
+def _table_for(table, B):
+    if not isinstance(table, MixTable):
+        raise TypeError("expected the MixTable that ops.mix_table returns")
+    if table.B != B:
+        raise ValueError(f"the table has {table.B} entries, the batch {B} samples")
+    return table
+
+
+def mix_patch_rows_table(img, table, dtypes=None, f32_images=False):
+    """Per-sample Mixup / CutMix of a batch with its flip (sample b with B-1-b, entry b of `table`), straight to patch rows
+    (devit_mix_im2row_table) -> PatchRows; f32_images: the mixed batch as a NEW fp32 [B,3,224,224] tensor instead (what an
+    "f32" model reads).  `img` itself is only read."""
+    L.require_device(img)
+    if tuple(img.shape[1:]) != (3, 224, 224):
+        raise L.DevitError(f"mix_patch_rows_table: only [B,3,224,224] images (got {tuple(img.shape)})")
+    img = img.contiguous().float()
+    B = img.shape[0]
+    table = _table_for(table, B)
+    if f32_images:
+        out = torch.empty_like(img)
+        call("devit_mix_im2row_table", ptr(img), None, None, ptr(out), ptr(table.dev), B, stream_ptr())
+        return out
+    dtypes = dtypes or PATCH_ROW_DTYPES
+    rows = rows_alloc(B * 196, 768, torch.bfloat16, img.device) if torch.bfloat16 in dtypes else None
+    rows_h = rows_alloc(B * 196, 768, F16, img.device) if F16 in dtypes else None
+    call("devit_mix_im2row_table", ptr(img), ptr(rows), ptr(rows_h), None, ptr(table.dev), B, stream_ptr())
+    return PatchRows(rows, B, rows_h)
+
+
+def mix_targets_table(labels, num_classes, table, smoothing):
+    """[B, C] soft targets of the batch mixed per sample: row b = lam_b * smooth(y[b]) + (1 - lam_b) * smooth(y[B-1-b])
+    (timm mixup_target with a [B, 1] float32 lam)."""
+    L.require_device(labels)
+    labels = labels.contiguous().long()
+    table = _table_for(table, labels.shape[0])
+    out = torch.empty((labels.shape[0], num_classes), dtype=F32, device=labels.device)
+    call("devit_mix_targets_table", ptr(labels), ptr(out), ptr(table.dev), labels.shape[0], num_classes, float(smoothing), stream_ptr())
     return out
 
 

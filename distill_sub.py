@@ -186,10 +186,24 @@ class Mixup:
     """timm.data.Mixup(mode='batch') semantics (distill_sub.py:315-318, applied at engine.py:65-66).
     The draws (mixup vs cutmix, lambda ~ Beta, the box) are host-side numpy RNG as in timm; the arithmetic runs in two HIP
     kernels: devit_mix_im2row_bf16 turns the fp32 batch straight into the MIXED batch's bf16 patch rows (the mixed fp32
-    images never exist; student and teacher both read those rows) and devit_mix_targets builds the soft targets."""
+    images never exist; student and teacher both read those rows) and devit_mix_targets builds the soft targets.
+    mode='elem' / 'pair' (timm's _mix_elem / _mix_pair: one draw per sample / per pair b, B-1-b) go through the same stage with a
+    per-sample table (draw_table -> devit_mix_im2row_table / devit_mix_targets_table); cutmix_minmax=(min, max) draws the CutMix
+    box sides as a share of the image (timm's rand_bbox_minmax) in every mode."""
 
-    def __init__(self, mixup_alpha, cutmix_alpha, prob, switch_prob, label_smoothing, num_classes, precisions=("bf16",)):
+    MODES = ("batch", "elem", "pair")
+
+    def __init__(self, mixup_alpha, cutmix_alpha, prob, switch_prob, label_smoothing, num_classes, precisions=("bf16",), *,
+                 mode="batch", cutmix_minmax=None):
+        if mode not in self.MODES:                  # (timm falls back to 'batch' without a word)
+            raise ValueError(f"Mixup mode {mode!r}: one of {', '.join(self.MODES)}")
+        if cutmix_minmax is not None:
+            cutmix_minmax = tuple(float(v) for v in cutmix_minmax)
+            if len(cutmix_minmax) != 2 or not 0 <= cutmix_minmax[0] < cutmix_minmax[1] <= 1:
+                raise ValueError(f"cutmix_minmax {cutmix_minmax}: two values with 0 <= min < max <= 1")
+            cutmix_alpha = 1.0                      # timm: "force cutmix alpha == 1.0 when minmax active to keep logic simple & safe"
         self.ma, self.ca, self.prob, self.sw, self.eps, self.C = mixup_alpha, cutmix_alpha, prob, switch_prob, label_smoothing, num_classes
+        self.mode, self.cutmix_minmax = mode, cutmix_minmax
         self.set_precisions(*precisions)
 
     def set_precisions(self, *precisions):
@@ -204,6 +218,8 @@ class Mixup:
         if np.random.rand() < self.prob:
             cut = self.ca > 0 and (self.ma <= 0 or np.random.rand() < self.sw)
             lam = float(np.random.beta(self.ca, self.ca) if cut else np.random.beta(self.ma, self.ma))
+        if cut and self.cutmix_minmax is not None:
+            return (2,) + self._box_minmax(H, W)
         if cut:
             r = math.sqrt(1 - lam)
             ch, cw, cy, cx = int(H * r), int(W * r), np.random.randint(H), np.random.randint(W)
@@ -211,9 +227,65 @@ class Mixup:
             return 2, 1.0 - (y1 - y0) * (x1 - x0) / float(H * W), (y0, y1, x0, x1)
         return (1 if lam != 1.0 else 0), lam, (0, 0, 0, 0)
 
+    def _box_minmax(self, H, W):
+        """(lam, box) of timm's rand_bbox_minmax: the sides are drawn as a share of the image between min and max, then the corner;
+        nothing is clipped, and lam is the share of the image outside the box."""
+        lo, hi = self.cutmix_minmax
+        ch = np.random.randint(int(H * lo), int(H * hi))
+        cw = np.random.randint(int(W * lo), int(W * hi))
+        y0 = np.random.randint(0, H - ch)
+        x0 = np.random.randint(0, W - cw)
+        return 1.0 - ch * cw / float(H * W), (int(y0), int(y0 + ch), int(x0), int(x0 + cw))
+
+    def draw_table(self, B, H=224, W=224):
+        """One (mode, lam, box) per sample for mode 'elem' / 'pair', as a numpy array of ops.MIX_SAMPLE_DTYPE: timm's
+        _params_per_elem followed by the box draws of _mix_elem / _mix_pair, in their order, on the numpy global RNG.  lam is a
+        float32 vector as in timm; sample b's partner is B-1-b, and pair mode draws B/2 entries and mirrors them.
+        rand_bbox's `img_h * np.sqrt(1 - lam)` on the float32 lam is evaluated as NumPy 2 evaluates it (a python int times an
+        np.float32 scalar is float32); under NumPy 1.x timm gets a float64 product, whose int() can differ by one from this."""
+        from devit_amd.ops import MIX_SAMPLE_DTYPE
+        assert B % 2 == 0, 'Batch size should be even when using this'
+        n = B // 2 if self.mode == "pair" else B
+        lam, use_cutmix = np.ones(n, dtype=np.float32), np.zeros(n, dtype=bool)
+        if self.ma > 0 or self.ca > 0:
+            if self.ma > 0 and self.ca > 0:
+                use_cutmix = np.random.rand(n) < self.sw
+                lam_mix = np.where(use_cutmix, np.random.beta(self.ca, self.ca, size=n), np.random.beta(self.ma, self.ma, size=n))
+            elif self.ma > 0:
+                lam_mix = np.random.beta(self.ma, self.ma, size=n)
+            else:
+                use_cutmix = np.ones(n, dtype=bool)
+                lam_mix = np.random.beta(self.ca, self.ca, size=n)
+            lam = np.where(np.random.rand(n) < self.prob, lam_mix.astype(np.float32), lam)
+        tab = np.zeros(B, dtype=MIX_SAMPLE_DTYPE)
+        for i in range(n):
+            if lam[i] == 1:                         # timm: `if lam != 1.` -- the sample stays as it is
+                e = (0, np.float32(1), 0, 0, 0, 0)
+            elif not use_cutmix[i]:
+                e = (1, lam[i], 0, 0, 0, 0)
+            elif self.cutmix_minmax is not None:
+                l, box = self._box_minmax(H, W)
+                e = (2, np.float32(l)) + box
+            else:                                   # rand_bbox on the float32 lam: the ratio and its products are float32
+                r = np.sqrt(np.float32(1) - lam[i])
+                ch, cw, cy, cx = int(np.float32(H) * r), int(np.float32(W) * r), np.random.randint(H), np.random.randint(W)
+                y0, y1, x0, x1 = max(cy - ch // 2, 0), min(cy + ch // 2, H), max(cx - cw // 2, 0), min(cx + cw // 2, W)
+                e = (2, np.float32(1.0 - (y1 - y0) * (x1 - x0) / float(H * W)), y0, y1, x0, x1)
+            for j in ((i, B - 1 - i) if self.mode == "pair" else (i,)):
+                tab[j] = e + ((0, 0),)
+        return tab
+
     def __call__(self, x, y):
         from devit_amd import ops
         assert x.shape[0] % 2 == 0, 'Batch size should be even when using this'
+        if self.mode != "batch":
+            if tuple(x.shape[-2:]) != (224, 224):
+                raise NotImplementedError(f"Mixup mode {self.mode!r} is built on the 224 x 224 patch-row kernel, got {tuple(x.shape[-2:])} images")
+            table = ops.mix_table(self.draw_table(x.shape[0]), x.device)
+            targets = ops.mix_targets_table(y, self.C, table, self.eps)
+            if "f32" in self.precisions:        # the exact-fp32 parity models read fp32 images: the kernel's third output
+                return ops.mix_patch_rows_table(x, table, f32_images=True), targets
+            return ops.mix_patch_rows_table(x, table, dtypes=self.row_dtypes), targets
         mode, lam, box = self.draw(x.shape[-2], x.shape[-1])
         if "f32" in self.precisions or tuple(x.shape[-2:]) != (224, 224):
             # the exact-fp32 parity models read fp32 images (and the patch-row kernel is built for 224 x 224): timm's formulas on
@@ -226,6 +298,15 @@ class Mixup:
                 x[:, :, y0:y1, x0:x1] = flipped[:, :, y0:y1, x0:x1]
             return x, ops.mix_targets(y, self.C, lam, self.eps)
         return ops.mix_patch_rows(x, mode, lam, box, dtypes=self.row_dtypes), ops.mix_targets(y, self.C, lam, self.eps)
+
+
+def build_mixup(args, num_classes):
+    """The Mixup of distill_sub.py:312-318 from the parsed flags (--mixup-mode and --cutmix-minmax included), None when they
+    leave it off; shared by train_subdata.py and ensemble.py."""
+    if not (args.mixup > 0 or args.cutmix > 0. or args.cutmix_minmax is not None):
+        return None
+    return Mixup(args.mixup, args.cutmix, args.mixup_prob, args.mixup_switch_prob, args.smoothing, num_classes,
+                 mode=args.mixup_mode, cutmix_minmax=args.cutmix_minmax)
 
 
 class CosineEpochs:
@@ -308,9 +389,7 @@ def main(args):
     train_loader, val_loader, num_classes = build_loaders(args, num_classes, device, provider="division")
     args.num_classes = num_classes
 
-    mixup_fn = None
-    if args.mixup > 0 or args.cutmix > 0. or args.cutmix_minmax is not None:
-        mixup_fn = Mixup(args.mixup, args.cutmix, args.mixup_prob, args.mixup_switch_prob, args.smoothing, num_classes)
+    mixup_fn = build_mixup(args, num_classes)
 
     stu_nb = 1000 if args.model_path != '' else num_classes
     resize_dim = model_config[args.teacher_model]["embed_dim"] if args.distillation_token else None

@@ -91,8 +91,7 @@ def main(args):
     num_classes = sum(sub_classes)
     args.num_classes = num_classes
     train_loader, val_loader, _ = ds.build_loaders(args, num_classes, device, provider="whole", plain_sampler_over="train")   # ensemble.py:261-300
-    mixup_fn = ds.Mixup(args.mixup, args.cutmix, args.mixup_prob, args.mixup_switch_prob, args.smoothing, num_classes) \
-        if (args.mixup > 0 or args.cutmix > 0.) else None
+    mixup_fn = ds.build_mixup(args, num_classes) if (args.mixup > 0 or args.cutmix > 0.) else None
     teacher, model, ens_model = get_models(args, len(sub_classes), sub_classes, num_classes)
     if mixup_fn is not None:        # the fused Mixup + im2row emits the patch rows in every 16-bit type a model of the step reads
         mixup_fn.set_precisions("bf16", getattr(teacher, "precision", None))

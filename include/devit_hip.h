@@ -454,6 +454,32 @@ DEVIT_API int devit_im2row_bf16(const float* img, void* rows, int B, int C, int 
 DEVIT_API int devit_mix_im2row_bf16(const float* img, void* rows /* bf16 or NULL */, void* rows_f16 /* f16 or NULL */, int B, int mode,
                           double lam, int y0, int y1, int x0, int x1, void* stream);
 DEVIT_API int devit_mix_targets(const long long* labels, float* targets, int B, int C, double lam, double smoothing, void* stream);
+/* The same stage with one (mode, lam, box) PER SAMPLE (timm Mixup(mode='elem' / 'pair'), cutmix_minmax boxes): entry b of a device
+ * table of B devit_mix_sample says how sample b is mixed with its partner, which is always sample B-1-b (timm's _mix_elem and
+ * _mix_pair both use it; pair mode is a table with entry[b] == entry[B-1-b]).  struct id 10 of devit_abi_struct_size, 32 bytes.
+ *   mode 0: sample b as it is; 1: x[b] * lam + x[B-1-b] * (1.0f - lam); 2: x[b] with [y0,y1) x [x0,x1) copied from x[B-1-b].
+ * 1 - lam is computed IN FP32 from the fp32 lam, as timm's per-element path does (lam_batch is a float32 array, and 1 - lam on a
+ * np.float32 stays float32).  devit_mix_im2row_bf16 / devit_mix_targets above take f32(1 - lam) with the subtraction done in
+ * double by their host (torch's arithmetic with a python scalar): for a lam whose complement is not exact in fp32 the two families
+ * differ in the last bit of that factor, each as its timm mode does.  The products and the sum are rounded separately.
+ * devit_mix_im2row_table: any subset (not none) of three outputs -- bf16 rows, f16 rows, and img_out, the mixed batch as fp32
+ *   [B,3,224,224] in image layout (for precision="f32" models).  img_out must not be img: a sample's partner is read after the
+ *   sample may have been written.  B <= 65535.
+ * devit_mix_targets_table: targets[b][c] = t1 * lam_b + t2 * (1.0f - lam_b), t1 / t2 the smoothed one-hot values of y[b] / y[B-1-b]
+ *   (formed in double, rounded to fp32, as devit_mix_targets); lam_b is used whatever the mode, so a mode 0 entry carries lam 1.
+ * No address in either kernel depends on the table's contents (only selects and branches do), so both are memory-safe for any
+ * table bytes; the entries cannot be validated here without a synchronise and are the caller's to check before the upload. */
+typedef struct {
+  int mode;
+  float lam;
+  int y0, y1, x0, x1;
+  int reserved[2];
+} devit_mix_sample;
+DEVIT_API int devit_mix_im2row_table(const float* img, void* rows /* bf16 or NULL */, void* rows_f16 /* f16 or NULL */,
+                           float* img_out /* f32 images or NULL */, const devit_mix_sample* table /* device, B entries */, int B,
+                           void* stream);
+DEVIT_API int devit_mix_targets_table(const long long* labels, float* targets, const devit_mix_sample* table, int B, int C,
+                            double smoothing, void* stream);
 DEVIT_API int devit_embed_tokens(const float* cls, const float* dist, const float* pos, float* x, int B, int T, int D,
                        void* stream);
 DEVIT_API int devit_embed_bwd(const float* dx, int B, int T, int D, int ntok, float* dpos, float* dcls, float* ddist,

@@ -45,9 +45,7 @@ def main(args):
         raise SystemExit("--distillation-token (resize_dim models) is outside the DeViT path")
     train_loader, val_loader, num_classes = ds.build_loaders(args, num_classes, device, provider="division")   # train_subdata.py:335-380
     args.num_classes = num_classes
-    mixup_fn = None
-    if args.mixup > 0 or args.cutmix > 0. or args.cutmix_minmax is not None:
-        mixup_fn = ds.Mixup(args.mixup, args.cutmix, args.mixup_prob, args.mixup_switch_prob, args.smoothing, num_classes)
+    mixup_fn = ds.build_mixup(args, num_classes)
 
     # train_subdata.py:193-230
     model = devit_amd.create_model(args.model, pretrained=True, pretrained_path=args.model_path or None,
