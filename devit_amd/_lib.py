@@ -154,8 +154,10 @@ SIGNATURES = {
     "devit_hsic_head_pairs": (_I, [_P, _I, _I, _P, _P]),
     "devit_im2row_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "devit_mix_im2row_bf16": (_I, [_P, _P, _P, _I, _I, C.c_double, _I, _I, _I, _I, _P]),
+    "devit_mix_im2row_bf16_sized": (_I, [_P, _P, _P, _I, _I, C.c_double, _I, _I, _I, _I, _I, _I, _P]),
     "devit_mix_targets": (_I, [_P, _P, _I, _I, C.c_double, C.c_double, _P]),
     "devit_mix_im2row_table": (_I, [_P, _P, _P, _P, _P, _I, _P]),
+    "devit_mix_im2row_table_sized": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "devit_mix_targets_table": (_I, [_P, _P, _P, _I, _I, C.c_double, _P]),
     "devit_embed_tokens": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "devit_embed_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
@@ -176,6 +178,7 @@ SIGNATURES = {
     "devit_softmax_rows_f32": (_I, [_P, _I, _I, _I, _F, _P, _P]),
     "devit_softmax_bwd_rows_f32": (_I, [_P, _P, _I, _I, _I, _F, _P]),
     "devit_im2row_f32": (_I, [_P, _P, _I, _P]),
+    "devit_im2row_f32_sized": (_I, [_P, _P, _I, _I, _I, _P]),
     "devit_scale_rows_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "devit_colsum_f32": (_I, [_P, _I, _I, _I, _P, _I, _P]),
     "devit_comm_unique_id": (_I, [_P]),

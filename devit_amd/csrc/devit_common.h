@@ -59,6 +59,22 @@ inline int devit_observed(void* stream, Info&& info, Launch&& launch) {
 int devit_layernorm_bwd_finish(const float* partial, int nparts, int D, float* dgamma, float* dbeta, float* dx_bf16_colsum,
                                int accumulate, void* stream);
 
+// ---- image sizes of the patch-cutting kernels (elementwise.hip, sgemm.hip) ---------------------------
+// Square 3-channel images cut into 16 x 16 patches, side S = 16 G with G = 2 .. 14 patches (32 .. 224 pixels): T = G * G patch tokens, and
+// T + 2 <= 198 stays inside the attention kernels' 208 rows (240 pixels would be 227).  The kernels are instantiated on G, so the divisions
+// by G and T and the row strides are constants at every size: DEVIT_FOR_PATCH_GRID(G, X) expands X(g) for the instantiation that equals G.
+inline int devit_patch_grid(int C, int H, int W, int patch) {       // G, or 0 for a shape the kernels are not built for
+  return (C == 3 && patch == 16 && H == W && H % 16 == 0 && H >= 32 && H <= 224) ? H / 16 : 0;
+}
+#define DEVIT_PATCH_SIZES_MSG "3 x S x S images, S a multiple of 16 from 32 to 224, patch 16"
+#define DEVIT_FOR_PATCH_GRID(G, X)                                                                              \
+  switch (G) {                                                                                                  \
+    case 2: X(2); break;   case 3: X(3); break;   case 4: X(4); break;   case 5: X(5); break;   case 6: X(6); break;     \
+    case 7: X(7); break;   case 8: X(8); break;   case 9: X(9); break;   case 10: X(10); break; case 11: X(11); break;   \
+    case 12: X(12); break; case 13: X(13); break; case 14: X(14); break;                                          \
+    default: break;                                                                                             \
+  }
+
 // ---- scalar helpers ---------------------------------------------------------------------
 __device__ __forceinline__ float bf2f(__bf16 v) { return (float)v; }
 __device__ __forceinline__ __bf16 f2bf(float v) { return (__bf16)v; }

@@ -4,15 +4,20 @@
 
 namespace {
 
-// ---- im2row: image f32 [B,3,224,224] -> bf16 rows [B*196][768], k = c*256 + kh*16 + kw -------------
+// ---- im2row: image f32 [B,3,S,S] -> bf16 rows [B*T][768], k = c*256 + kh*16 + kw, token t = py*G + px -------------
 // (timm PatchEmbed Conv2d(3,D,16,16) as a GEMM operand; models/de_vit.py:166-168,258)
+// The patch-cutting kernels are templates on G = S / 16 (devit_common.h: 2 .. 14, T = G * G tokens): a 16-byte output chunk is 8 consecutive
+// pixels of one image row, at a float offset that is a multiple of 8 for every S % 16 == 0, so the two 16-byte loads stay aligned; G = 14 is
+// the 224-pixel kernel as it always was.
+template <int G>
 __global__ __launch_bounds__(256) void im2row_kernel(const float* img, __bf16* rows, int B, int f16) {
-  const int total = B * 196 * 96;  // 16-byte (8-element) output chunks
+  constexpr int T = G * G, S = G * 16;
+  const int total = B * T * 96;  // 16-byte (8-element) output chunks
   for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
     const int k8 = idx % 96, row = idx / 96;
-    const int b = row / 196, t = row % 196, py = t / 14, px = t % 14;
+    const int b = row / T, t = row % T, py = t / G, px = t % G;
     const int c = k8 >> 5, kh = (k8 >> 1) & 15, kw0 = (k8 & 1) * 8;
-    const float* src = img + (((size_t)b * 3 + c) * 224 + py * 16 + kh) * 224 + px * 16 + kw0;
+    const float* src = img + (((size_t)b * 3 + c) * S + py * 16 + kh) * S + px * 16 + kw0;
     const f32x4 v0 = *(const f32x4*)src, v1 = *(const f32x4*)(src + 4);
     *(bf16x8*)(rows + (size_t)idx * 8) = f16 ? cvt8<true>(v0, v1) : cvt8<false>(v0, v1);
   }
@@ -31,18 +36,20 @@ struct MixArgs {
   int B, mode, y0, y1, x0, x1;
   float lam, oml;      // f32(lam), f32(1 - lam) with the subtraction done in double on the host, as torch does for a python scalar
 };
+template <int G>
 __global__ __launch_bounds__(256) void mix_im2row_kernel(const MixArgs a) {
 #pragma clang fp contract(off)   // x * lam + flip * (1 - lam) as three rounded operations (hipcc would fuse a multiply-add)
-  const int total = a.B * 196 * 96;
+  constexpr int T = G * G, S = G * 16;
+  const int total = a.B * T * 96;
   const float lam = a.lam, oml = a.oml;
   for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
     const int k8 = idx % 96, row = idx / 96;
-    const int b = row / 196, t = row % 196, py = t / 14, px = t % 14;
+    const int b = row / T, t = row % T, py = t / G, px = t % G;
     const int c = k8 >> 5, kh = (k8 >> 1) & 15, kw0 = (k8 & 1) * 8;
     const int y = py * 16 + kh, x = px * 16 + kw0;
-    const size_t off = ((size_t)c * 224 + y) * 224 + x;
-    const float* src = a.img + (size_t)b * 3 * 224 * 224 + off;
-    const float* flp = a.img + (size_t)(a.B - 1 - b) * 3 * 224 * 224 + off;
+    const size_t off = ((size_t)c * S + y) * S + x;
+    const float* src = a.img + (size_t)b * 3 * S * S + off;
+    const float* flp = a.img + (size_t)(a.B - 1 - b) * 3 * S * S + off;
     float v[8];
     *(f32x4*)v = *(const f32x4*)src;
     *(f32x4*)(v + 4) = *(const f32x4*)(src + 4);
@@ -95,21 +102,23 @@ struct MixTableArgs {
   const float* img;
   __bf16* rows;         // bf16 patch rows or NULL
   __bf16* rows_f16;     // the same values as IEEE f16 or NULL
-  float* img_out;       // the mixed batch as fp32 images [B,3,224,224] (f32 models) or NULL; never img itself
+  float* img_out;       // the mixed batch as fp32 images [B,3,S,S] (f32 models) or NULL; never img itself
   const devit_mix_sample* table;
   int B;
 };
+template <int G>
 __global__ __launch_bounds__(256) void mix_im2row_table_kernel(const MixTableArgs a) {
 #pragma clang fp contract(off)   // x * lam + flip * (1 - lam) as three rounded operations, and 1 - lam a fourth
+  constexpr int T = G * G, S = G * 16;
   const int b = (blockIdx.y & 1) ? a.B - 1 - (int)(blockIdx.y >> 1) : (int)(blockIdx.y >> 1);
   const devit_mix_sample s = a.table[b];
   const float lam = s.lam, oml = 1.0f - lam;
-  const size_t img_b = (size_t)b * 3 * 224 * 224, img_p = (size_t)(a.B - 1 - b) * 3 * 224 * 224;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < 196 * 96; i += gridDim.x * 256) {
-    const int k8 = i % 96, t = i / 96, py = t / 14, px = t % 14;
+  const size_t img_b = (size_t)b * 3 * S * S, img_p = (size_t)(a.B - 1 - b) * 3 * S * S;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < T * 96; i += gridDim.x * 256) {
+    const int k8 = i % 96, t = i / 96, py = t / G, px = t % G;
     const int c = k8 >> 5, kh = (k8 >> 1) & 15, kw0 = (k8 & 1) * 8;
     const int y = py * 16 + kh, x = px * 16 + kw0;
-    const size_t off = ((size_t)c * 224 + y) * 224 + x;
+    const size_t off = ((size_t)c * S + y) * S + x;
     const float* src = a.img + img_b + off;
     const float* flp = a.img + img_p + off;
     float v[8];
@@ -132,7 +141,7 @@ __global__ __launch_bounds__(256) void mix_im2row_table_kernel(const MixTableArg
       for (int e = 0; e < 8; ++e) v[e] = (x + e >= s.x0 && x + e < s.x1) ? w[e] : v[e];
     }
     const f32x4 lo = {v[0], v[1], v[2], v[3]}, hi = {v[4], v[5], v[6], v[7]};
-    const size_t chunk = (size_t)b * (196 * 96) + i;
+    const size_t chunk = (size_t)b * (T * 96) + i;
     if (a.rows) *(bf16x8*)(a.rows + chunk * 8) = cvt8<false>(lo, hi);
     if (a.rows_f16) *(bf16x8*)(a.rows_f16 + chunk * 8) = cvt8<true>(lo, hi);
     if (a.img_out) {
@@ -415,27 +424,45 @@ inline int grid_for(size_t work_items, int cap = 2048) {
 
 }  // namespace
 
+// the grid-stride kernels index chunks with an int: B * T * 96 plus one grid stride must fit
+inline bool chunks_fit(int B, int G) { return (size_t)B * G * G * 96 <= 0x7fffffffu - 4096u * 256u; }
+
 extern "C" int devit_im2row_bf16(const float* img, void* rows, int B, int C, int H, int W, int patch, int dtype16,
                                  void* stream) {
   DEVIT_CHECK(img && rows && (dtype16 == 0 || dtype16 == 1), DEVIT_ERR_ARG, "devit_im2row_bf16: bad argument");
-  DEVIT_CHECK(C == 3 && H == 224 && W == 224 && patch == 16 && B > 0, DEVIT_ERR_SHAPE,
-              "devit_im2row_bf16: only 3x224x224 / patch 16 (got %dx%dx%d / %d)", C, H, W, patch);
-  hipLaunchKernelGGL(im2row_kernel, dim3(grid_for((size_t)B * 196 * 96, 4096)), dim3(256), 0, (hipStream_t)stream, img,
-                     (__bf16*)rows, B, dtype16);
+  const int G = devit_patch_grid(C, H, W, patch);
+  DEVIT_CHECK(G > 0 && B > 0, DEVIT_ERR_SHAPE, "devit_im2row_bf16: only " DEVIT_PATCH_SIZES_MSG " (got %dx%dx%d / %d)", C, H, W, patch);
+  DEVIT_CHECK(chunks_fit(B, G), DEVIT_ERR_SHAPE, "devit_im2row_bf16: B = %d is too many %dx%d images for one launch", B, H, W);
+#define DEVIT_LAUNCH_G(G_)                                                                                                    \
+  hipLaunchKernelGGL(im2row_kernel<G_>, dim3(grid_for((size_t)B * (G_ * G_) * 96, 4096)), dim3(256), 0, (hipStream_t)stream, img, \
+                     (__bf16*)rows, B, dtype16)
+  DEVIT_FOR_PATCH_GRID(G, DEVIT_LAUNCH_G)
+#undef DEVIT_LAUNCH_G
+  DEVIT_LAUNCH_CHECK();
+  return DEVIT_OK;
+}
+
+extern "C" int devit_mix_im2row_bf16_sized(const float* img, void* rows, void* rows_f16, int B, int mode, double lam, int y0,
+                                           int y1, int x0, int x1, int H, int W, void* stream) {
+  DEVIT_CHECK(img && (rows || rows_f16) && B > 0, DEVIT_ERR_ARG, "devit_mix_im2row_bf16: bad argument");
+  DEVIT_CHECK(mode >= 0 && mode <= 2, DEVIT_ERR_ARG, "devit_mix_im2row_bf16: mode %d (0 none, 1 mixup, 2 cutmix)", mode);
+  const int G = devit_patch_grid(3, H, W, 16);
+  DEVIT_CHECK(G > 0, DEVIT_ERR_SHAPE, "devit_mix_im2row_bf16: only " DEVIT_PATCH_SIZES_MSG " (got %dx%d)", H, W);
+  DEVIT_CHECK(chunks_fit(B, G), DEVIT_ERR_SHAPE, "devit_mix_im2row_bf16: B = %d is too many %dx%d images for one launch", B, H, W);
+  DEVIT_CHECK(mode != 2 || (0 <= y0 && y0 <= y1 && y1 <= H && 0 <= x0 && x0 <= x1 && x1 <= W), DEVIT_ERR_ARG,
+              "devit_mix_im2row_bf16: box [%d,%d) x [%d,%d) outside %dx%d", y0, y1, x0, x1, H, W);
+  MixArgs a{img, (__bf16*)rows, (__bf16*)rows_f16, B, mode, y0, y1, x0, x1, (float)lam, (float)(1.0 - lam)};
+#define DEVIT_LAUNCH_G(G_) \
+  hipLaunchKernelGGL(mix_im2row_kernel<G_>, dim3(grid_for((size_t)B * (G_ * G_) * 96, 4096)), dim3(256), 0, (hipStream_t)stream, a)
+  DEVIT_FOR_PATCH_GRID(G, DEVIT_LAUNCH_G)
+#undef DEVIT_LAUNCH_G
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
 }
 
 extern "C" int devit_mix_im2row_bf16(const float* img, void* rows, void* rows_f16, int B, int mode, double lam, int y0,
                                      int y1, int x0, int x1, void* stream) {
-  DEVIT_CHECK(img && (rows || rows_f16) && B > 0, DEVIT_ERR_ARG, "devit_mix_im2row_bf16: bad argument");
-  DEVIT_CHECK(mode >= 0 && mode <= 2, DEVIT_ERR_ARG, "devit_mix_im2row_bf16: mode %d (0 none, 1 mixup, 2 cutmix)", mode);
-  DEVIT_CHECK(mode != 2 || (0 <= y0 && y0 <= y1 && y1 <= 224 && 0 <= x0 && x0 <= x1 && x1 <= 224), DEVIT_ERR_ARG,
-              "devit_mix_im2row_bf16: box [%d,%d) x [%d,%d) outside 224x224", y0, y1, x0, x1);
-  MixArgs a{img, (__bf16*)rows, (__bf16*)rows_f16, B, mode, y0, y1, x0, x1, (float)lam, (float)(1.0 - lam)};
-  hipLaunchKernelGGL(mix_im2row_kernel, dim3(grid_for((size_t)B * 196 * 96, 4096)), dim3(256), 0, (hipStream_t)stream, a);
-  DEVIT_LAUNCH_CHECK();
-  return DEVIT_OK;
+  return devit_mix_im2row_bf16_sized(img, rows, rows_f16, B, mode, lam, y0, y1, x0, x1, 224, 224, stream);
 }
 
 extern "C" int devit_mix_targets(const long long* labels, float* targets, int B, int C, double lam, double smoothing,
@@ -448,19 +475,29 @@ extern "C" int devit_mix_targets(const long long* labels, float* targets, int B,
   return DEVIT_OK;
 }
 
-extern "C" int devit_mix_im2row_table(const float* img, void* rows, void* rows_f16, float* img_out, const devit_mix_sample* table,
-                                      int B, void* stream) {
+extern "C" int devit_mix_im2row_table_sized(const float* img, void* rows, void* rows_f16, float* img_out, const devit_mix_sample* table,
+                                            int B, int H, int W, void* stream) {
   DEVIT_CHECK(img && table && (rows || rows_f16 || img_out), DEVIT_ERR_ARG, "devit_mix_im2row_table: bad argument");
   DEVIT_CHECK(B > 0 && B <= 65535, DEVIT_ERR_ARG, "devit_mix_im2row_table: B = %d outside 1 .. 65535 (one grid row per sample)", B);
   DEVIT_CHECK(img_out != img, DEVIT_ERR_ARG,
               "devit_mix_im2row_table: img_out is img (a sample's partner is read after the sample may have been written)");
+  const int G = devit_patch_grid(3, H, W, 16);
+  DEVIT_CHECK(G > 0, DEVIT_ERR_SHAPE, "devit_mix_im2row_table: only " DEVIT_PATCH_SIZES_MSG " (got %dx%d)", H, W);
   // the table's VALUES are not checked here (device memory; reading it would synchronise): no address in the kernel depends on them
   MixTableArgs a{img, (__bf16*)rows, (__bf16*)rows_f16, img_out, table, B};
-  // one 8-element chunk per thread (196 * 96 chunks per sample = 73.5 workgroups); a grid-stride over 16 workgroups per sample measured
-  // 7 to 11 us slower at B = 256 (profiles/r12_b_mix_table_cost.json, "grid_mapping_us")
-  hipLaunchKernelGGL(mix_im2row_table_kernel, dim3(74, B), dim3(256), 0, (hipStream_t)stream, a);
+  // one 8-element chunk per thread (196 * 96 chunks per 224-pixel sample = 73.5 workgroups); a grid-stride over 16 workgroups per sample
+  // measured 7 to 11 us slower at B = 256 (profiles/r12_b_mix_table_cost.json, "grid_mapping_us")
+#define DEVIT_LAUNCH_G(G_) \
+  hipLaunchKernelGGL(mix_im2row_table_kernel<G_>, dim3((G_ * G_ * 96 + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, a)
+  DEVIT_FOR_PATCH_GRID(G, DEVIT_LAUNCH_G)
+#undef DEVIT_LAUNCH_G
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
+}
+
+extern "C" int devit_mix_im2row_table(const float* img, void* rows, void* rows_f16, float* img_out, const devit_mix_sample* table,
+                                      int B, void* stream) {
+  return devit_mix_im2row_table_sized(img, rows, rows_f16, img_out, table, B, 224, 224, stream);
 }
 
 extern "C" int devit_mix_targets_table(const long long* labels, float* targets, const devit_mix_sample* table, int B, int C,

@@ -27,6 +27,11 @@ struct Ctx {
   void* stream;
 };
 
+// DEVIT_BLK_QKV_PAD: zeroed rows behind the padded qkv buffer.  The relation loss reads a 256-row Gram window per image, the last one from row
+// (B - 1) N on: 256 - N rows behind the B N live ones -- 58 at N = 198, inside the 128 every N >= 128 gets; a short sequence (51 tokens of a
+// 112-pixel model) gets its 256 - N.
+inline int qkv_pad_rows(int N) { return N >= 128 ? 128 : 256 - N; }
+
 int zero_pad(const Ctx& c, void* buf, int cols, size_t elem, int extra_rows = 0) {
   if (!buf) return DEVIT_OK;
   const int rows = c.Mp + extra_rows - c.M;
@@ -152,7 +157,7 @@ int block_fwd(const Ctx& c, const devit_block_weights& w, const devit_block_acts
               DEVIT_ERR_ARG, "devit_encoder_fwd: DEVIT_BLK_SAVE needs the mean/rstd/lse/h_pre buffers");
   DEVIT_CHECK(!(a.flags & DEVIT_BLK_ATT) || b[DEVIT_ACT_ATT], DEVIT_ERR_ARG, "devit_encoder_fwd: DEVIT_BLK_ATT needs att");
   TRY(zero_pad(c, b[DEVIT_ACT_LN1], D, 2));
-  TRY(zero_pad(c, b[DEVIT_ACT_QKV], 3 * Da, 2, (a.flags & DEVIT_BLK_QKV_PAD) ? 128 : 0));
+  TRY(zero_pad(c, b[DEVIT_ACT_QKV], 3 * Da, 2, (a.flags & DEVIT_BLK_QKV_PAD) ? qkv_pad_rows(c.N) : 0));
   TRY(zero_pad(c, b[DEVIT_ACT_ATTN_O], Da, 2));
   TRY(zero_pad(c, b[DEVIT_ACT_LN2], D, 2));
   TRY(zero_pad(c, b[DEVIT_ACT_H], Hd, 2));
@@ -228,7 +233,7 @@ extern "C" int devit_block_acts_sizes(int B, int N, int D, int Da, int Hd, int f
   const bool save = flags & DEVIT_BLK_SAVE;
   sizes[DEVIT_ACT_LN1] = Mp * D * 2;
   sizes[DEVIT_ACT_MEAN1] = sizes[DEVIT_ACT_RSTD1] = sizes[DEVIT_ACT_MEAN2] = sizes[DEVIT_ACT_RSTD2] = save ? M * 4 : 0;
-  sizes[DEVIT_ACT_QKV] = (Mp + ((flags & DEVIT_BLK_QKV_PAD) ? 128 : 0)) * 3 * (size_t)Da * 2;
+  sizes[DEVIT_ACT_QKV] = (Mp + ((flags & DEVIT_BLK_QKV_PAD) ? qkv_pad_rows(N) : 0)) * 3 * (size_t)Da * 2;
   sizes[DEVIT_ACT_ATTN_O] = Mp * Da * 2;
   sizes[DEVIT_ACT_LSE] = save ? (size_t)B * (Da / 64) * N * 4 : 0;
   sizes[DEVIT_ACT_X1] = M * D * 4;

@@ -112,12 +112,14 @@ __global__ __launch_bounds__(256) void softmax_bwd_rows_kernel(const float* P, f
 }
 
 // fp32 helpers of the parity path
+template <int G>      // G = S / 16 patches per side (devit_common.h), 14 for 224 pixels
 __global__ __launch_bounds__(256) void im2row_f32_kernel(const float* img, float* rows, int B) {
-  const int total = B * 196 * 768;
+  constexpr int T = G * G, S = G * 16;
+  const int total = B * T * 768;
   for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
     const int k = idx % 768, row = idx / 768;
-    const int b = row / 196, t = row % 196, py = t / 14, px = t % 14, c = k >> 8, kh = (k >> 4) & 15, kw = k & 15;
-    rows[idx] = img[(((size_t)b * 3 + c) * 224 + py * 16 + kh) * 224 + px * 16 + kw];
+    const int b = row / T, t = row % T, py = t / G, px = t % G, c = k >> 8, kh = (k >> 4) & 15, kw = k & 15;
+    rows[idx] = img[(((size_t)b * 3 + c) * S + py * 16 + kh) * S + px * 16 + kw];
   }
 }
 __global__ __launch_bounds__(256) void scale_rows_f32_kernel(const float* src, float* dst, const float* rowscale,
@@ -179,11 +181,22 @@ extern "C" int devit_softmax_bwd_rows_f32(const float* P, float* dP, int rows, i
   return DEVIT_OK;
 }
 
-extern "C" int devit_im2row_f32(const float* img, float* rows, int B, void* stream) {
+extern "C" int devit_im2row_f32_sized(const float* img, float* rows, int B, int H, int W, void* stream) {
   DEVIT_CHECK(img && rows && B > 0, DEVIT_ERR_ARG, "devit_im2row_f32: bad argument");
-  hipLaunchKernelGGL(im2row_f32_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, img, rows, B);
+  const int G = devit_patch_grid(3, H, W, 16);
+  DEVIT_CHECK(G > 0, DEVIT_ERR_SHAPE, "devit_im2row_f32: only " DEVIT_PATCH_SIZES_MSG " (got %dx%d)", H, W);
+  // the kernel indexes elements with an int: B * T * 768 plus one grid stride must fit
+  DEVIT_CHECK((size_t)B * G * G * 768 <= 0x7fffffffu - 2048u * 256u, DEVIT_ERR_SHAPE,
+              "devit_im2row_f32: B = %d is too many %dx%d images for one launch", B, H, W);
+#define DEVIT_LAUNCH_G(G_) hipLaunchKernelGGL(im2row_f32_kernel<G_>, dim3(2048), dim3(256), 0, (hipStream_t)stream, img, rows, B)
+  DEVIT_FOR_PATCH_GRID(G, DEVIT_LAUNCH_G)
+#undef DEVIT_LAUNCH_G
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
+}
+
+extern "C" int devit_im2row_f32(const float* img, float* rows, int B, void* stream) {
+  return devit_im2row_f32_sized(img, rows, B, 224, 224, stream);
 }
 
 extern "C" int devit_scale_rows_f32(const float* src, float* dst, const float* rowscale, int rows_per_scale, int M, int D,

@@ -23,7 +23,8 @@ from . import ops
 from .dropout import check_p
 from .registry import register_model
 
-__all__ = ["Mlp", "Attention", "Block", "PatchEmbed", "VisionTransformer", "model_config", "dedeit", "devit"]
+__all__ = ["Mlp", "Attention", "Block", "PatchEmbed", "VisionTransformer", "model_config", "dedeit", "devit", "resize_pos_embed",
+           "checkpoint_filter_fn"]
 
 
 def _w16(lin, f16=False):
@@ -368,10 +369,13 @@ def _standalone_attention(m, x, output_qkv):
 
 
 class PatchEmbed(nn.Module):
-    """timm 0.5.4 PatchEmbed surface: Conv2d(3, D, 16, 16) weights, run as im2row + MFMA GEMM."""
+    """timm 0.5.4 PatchEmbed surface: Conv2d(3, D, 16, 16) weights, run as im2row + MFMA GEMM.  img_size: a square side
+    from ops.IMG_SIZES (multiples of 16 from 32 to 224); anything else is refused here, with the reason (ops.check_img_size)."""
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, embed_dim=768, norm_layer=None, flatten=True):
         super().__init__()
+        img_size = ops.check_img_size(img_size, patch_size, in_chans)
+        patch_size = 16
         self.img_size = (img_size, img_size)
         self.patch_size = (patch_size, patch_size)
         self.grid_size = (img_size // patch_size, img_size // patch_size)
@@ -379,8 +383,6 @@ class PatchEmbed(nn.Module):
         self.flatten = flatten
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size)
         self.norm = nn.Identity()
-        if img_size != 224 or patch_size != 16 or in_chans != 3:
-            raise NotImplementedError("the patch-embed kernels are built for 3x224x224 images, 16x16 patches")
 
 
 class VisionTransformer(nn.Module):
@@ -498,7 +500,8 @@ class VisionTransformer(nn.Module):
     # ---- forward --------------------------------------------------------------------------------------
     def embed(self, x):
         """patch_embed + cls/dist tokens + pos_embed (de_vit.py:258-264) -> fp32 [B, T, D]."""
-        L.require_device(x.rows if isinstance(x, ops.PatchRows) else x)
+        L.require_device(x._any if isinstance(x, ops.PatchRows) else x)
+        ops.expect_side(x, self.patch_embed.img_size[0], type(self).__name__)
         if self.precision == "f32":
             from . import ops_f32
             if isinstance(x, ops.PatchRows):
@@ -617,6 +620,49 @@ def _cfg(**kwargs):
             'std': (0.229, 0.224, 0.225), 'first_conv': 'patch_embed.proj', 'classifier': 'head', **kwargs}
 
 
+def resize_pos_embed(posemb, posemb_new, num_tokens=1, gs_new=()):
+    """Position embeddings [1, num_tokens + g*g, D] of a checkpoint for a model whose pos_embed is `posemb_new` ([1, num_tokens + G*G, D], or
+    gs_new = (G, G)): the token rows are kept, the g x g grid is resized to G x G with bicubic interpolation, align_corners=False
+    (models/de_vit.py:452-473, timm's resize_pos_embed).  torch on the CPU, at load time: not a hot path."""
+    tok, grid = posemb[:, :num_tokens], posemb[0, num_tokens:]
+    g_old = int(math.sqrt(grid.shape[0]))
+    if not len(gs_new):
+        gs_new = (int(math.sqrt(posemb_new.shape[1] - num_tokens)),) * 2
+    if g_old * g_old != grid.shape[0]:
+        raise ValueError(f"resize_pos_embed: {grid.shape[0]} position rows behind {num_tokens} token rows are not a square grid")
+    grid = grid.reshape(1, g_old, g_old, -1).permute(0, 3, 1, 2)
+    grid = nn.functional.interpolate(grid.float(), size=tuple(gs_new), mode='bicubic', align_corners=False)
+    grid = grid.permute(0, 2, 3, 1).reshape(1, gs_new[0] * gs_new[1], -1)
+    return torch.cat([tok, grid.to(posemb.dtype)], dim=1)
+
+
+def checkpoint_filter_fn(state_dict, model):
+    """A checkpoint as `model` can load it (models/de_vit.py:476-492): the 'model' entry of a DeiT-style file, a flat patch-projection
+    weight reshaped to the convolution's, and a pos_embed of another image size resized to the model's grid (resize_pos_embed) -- how
+    a 224-pixel checkpoint loads into a model built with a smaller img_size.  Key order is the checkpoint's."""
+    if 'model' in state_dict:
+        state_dict = state_dict['model']
+    out = {}
+    for k, v in state_dict.items():
+        if k.endswith('patch_embed.proj.weight') and v.dim() < 4:
+            O_, _, H_, W_ = model.patch_embed.proj.weight.shape
+            v = v.reshape(O_, -1, H_, W_)
+        elif k == 'pos_embed' and tuple(v.shape) != tuple(model.pos_embed.shape):
+            v = resize_pos_embed(v, model.pos_embed, getattr(model, 'num_tokens', 1), model.patch_embed.grid_size)
+        out[k] = v
+    return out
+
+
+def load_checkpoint(model, state_dict, strict=True):
+    """model.load_state_dict of a checkpoint that may have been trained at another image size (checkpoint_filter_fn); a checkpoint of the
+    model's own size is loaded as it is."""
+    sd = state_dict['model'] if 'model' in state_dict else state_dict
+    pos = sd.get('pos_embed')
+    if pos is not None and tuple(pos.shape) != tuple(model.pos_embed.shape):
+        sd = checkpoint_filter_fn(sd, model)
+    return model.load_state_dict(sd, strict=strict)
+
+
 def _make(name):
     def fn(pretrained=False, pretrained_path=None, **kwargs):
         geo = {**model_config[name], **kwargs}
@@ -624,10 +670,11 @@ def _make(name):
         model = VisionTransformer(**geo)
         if narrow:
             model.pin_precision("f32")
-        model.default_cfg = _cfg()
+        side = model.patch_embed.img_size[0]
+        model.default_cfg = _cfg(input_size=(3, side, side))
         if pretrained_path is not None and pretrained:
             ckpt = torch.load(pretrained_path, map_location='cpu', weights_only=False)
-            model.load_state_dict(ckpt['model'] if 'model' in ckpt else ckpt)
+            load_checkpoint(model, ckpt)
         return model
     fn.__name__ = name
     fn.__doc__ = f"{name}: registered like models/de_vit.py:495-513 / models/deit_vit.py:457-525 (dict-API class)."

@@ -11,14 +11,14 @@ from .registry import create_model
 class MultiViT(nn.Module):
     """models/ensemble_models.py:13-40."""
 
-    def __init__(self, model='dedeit', drop=0, drop_path=0.1, num_classes_list=[25, 25, 25, 25], num_div=4):
+    def __init__(self, model='dedeit', drop=0, drop_path=0.1, num_classes_list=[25, 25, 25, 25], num_div=4, img_size=None):
         super().__init__()
-        self.model = model
+        self.model = model          # img_size: the backbones' image side (None: the registered 224)
         assert len(num_classes_list) == num_div, 'num of classes is not match num of sub-models'
         self.backbones = nn.ModuleList([])
         for i, num_class in enumerate(num_classes_list):
             self.backbones.append(create_model(model_name=self.model, num_classes=int(num_class), drop_rate=drop,
-                                               drop_path_rate=drop_path, drop_block_rate=None))
+                                               drop_path_rate=drop_path, drop_block_rate=None, img_size=img_size))
             del self.backbones[i].head
             self.backbones[i].head = nn.Identity()          # attribute must exist for forward_features' head plumbing
             if 'deit' in self.model:

@@ -108,10 +108,10 @@ def relation_losses_vector(student_qkv, teacher_qkv):
 
 
 def _repack(feature):
-    """[B, H, N, hd] (any strides) -> packed bf16 [pad(B*N) + 128, 3*H*hd] with the feature in every component."""
+    """[B, H, N, hd] (any strides) -> packed bf16 [pad(B*N) + ops.qkv_pad_rows(N), 3*H*hd] with the feature in every component."""
     B, H, N, hd = feature.shape
     D = H * hd
-    buf = ops.rows_alloc(B * N, 3 * D, torch.bfloat16, feature.device, extra=128)
+    buf = ops.rows_alloc(B * N, 3 * D, torch.bfloat16, feature.device, extra=ops.qkv_pad_rows(N))
     f = feature.permute(0, 2, 1, 3).reshape(B * N, D)
     return buf, f, (B, N, H, hd, D)
 

@@ -145,6 +145,12 @@ def pad_rows(m):
     return (m + ROW_TILE - 1) // ROW_TILE * ROW_TILE
 
 
+def qkv_pad_rows(N):
+    """Zeroed rows behind a packed qkv buffer that the relation loss reads (csrc/encoder.hip: qkv_pad_rows; DEVIT_BLK_QKV_PAD): its Gram
+    windows are 256 rows per image, so the last image needs 256 - N rows behind its own -- inside the usual 128 from N = 128 on."""
+    return 128 if N >= 128 else 256 - N
+
+
 def rows_alloc(m, cols, dtype, device, extra=0):
     """[pad_rows(m) + extra, cols] buffer whose rows >= m are zero."""
     mp = pad_rows(m) + extra
@@ -705,7 +711,7 @@ def _encoder_forward_composite(x, cfg, need_grad, nb):
 
         def view(j, rows, cols, dt, arena=arena, offs=offs):
             return arena[offs[j]:offs[j] + rows * cols * dt.itemsize].view(dt).view(rows, cols)
-        qkv_rows = mp + (128 if flags & L.BLK_QKV_PAD else 0)
+        qkv_rows = mp + (qkv_pad_rows(N) if flags & L.BLK_QKV_PAD else 0)
         v = dict(qkv=view(L.ACT_QKV, qkv_rows, 3 * Da, dt), x2=view(L.ACT_X2, M, D, F32).view(B, N, D),
                  att=view(L.ACT_ATT, M, D, dt) if cfg.want_att else None)
         v["qkv"]._devit_arena = True          # a view of an arena from ARENA_ALLOC_STREAM's pool (engine._hand_over)
@@ -897,15 +903,55 @@ class EncoderFn(torch.autograd.Function):
 # ----------------------------------------------------------------------------------------------
 # patch embedding + token assembly (models/de_vit.py:258-264)
 # ----------------------------------------------------------------------------------------------
+IMG_SIZES = tuple(range(32, 225, 16))      # square image sides the patch-cutting kernels are built for (csrc/devit_common.h): grids 2 x 2 .. 14 x 14
+
+
+def check_img_size(img_size, patch_size=16, in_chans=3, exc=NotImplementedError):
+    """The side S of a supported image geometry -- square, 3 channels, 16 x 16 patches, S in IMG_SIZES -- or `exc` with the reason.
+    224 is the ceiling: the next size, 240 pixels, is 225 patches + 2 tokens = 227 rows, over the 208 the attention kernels hold."""
+    hw = tuple(img_size) if isinstance(img_size, (tuple, list)) else (img_size, img_size)
+    ps = tuple(patch_size) if isinstance(patch_size, (tuple, list)) else (patch_size, patch_size)
+    if len(hw) != 2 or hw[0] != hw[1]:
+        raise exc(f"image size {img_size}: the patch-embed kernels are built for square images (one of {list(IMG_SIZES)})")
+    if ps != (16, 16) or in_chans != 3:
+        raise exc(f"patch size {patch_size}, {in_chans} channels: the patch-embed kernels are built for 16 x 16 patches of 3-channel images")
+    S = hw[0]
+    if S not in IMG_SIZES:
+        why = ("240 pixels are 15 x 15 patches + 2 tokens = 227 rows, over the 208 the attention kernels hold" if isinstance(S, int) and S > 224
+               else "a multiple of 16, at least two patches a side")
+        raise exc(f"image size {S}: the patch-embed kernels are built for {list(IMG_SIZES)} ({why})")
+    return S
+
+
+def image_side(img, what):
+    """S of an fp32 image batch [B,3,S,S] (or of PatchRows), DevitError for a shape the patch-cutting kernels do not take."""
+    shape = tuple(img.shape)
+    if len(shape) != 4 or shape[0] < 1:
+        raise L.DevitError(f"{what}: expected images [B,3,S,S], got {shape}")
+    return check_img_size(shape[2:], 16, shape[1], exc=lambda m: L.DevitError(f"{what}: got {shape}: {m}"))
+
+
+def expect_side(x, S, what):
+    """A model built for S x S images refuses a batch (images or PatchRows) of another size: the kernels would run off the buffers."""
+    got = image_side(x, what)
+    if got != S:
+        raise L.DevitError(f"{what}: the model is built for {S} x {S} images (img_size={S}), the batch is {got} x {got} {tuple(x.shape)}")
+    return got
+
+
 class PatchRows:
-    """A batch of images already cut into bf16 patch rows [pad_rows(B*196), 768] (k = c*256 + kh*16 + kw): what every
+    """A batch of images already cut into bf16 patch rows [pad_rows(B*T), 768] (k = c*256 + kh*16 + kw; T = grid^2 patches of
+    an img_size x img_size image, 196 at 224): what every
     model's patch-embedding GEMM reads.  Models accept it in place of the fp32 image tensor, so one im2row pass -- plain
     (`patch_rows`) or fused with Mixup / CutMix (`mix_patch_rows`) -- serves the student, the teacher and all MultiViT
     backbones of a step.  Quacks like the image batch where host code only asks for its size and place."""
 
-    def __init__(self, rows, B, rows_f16=None):
+    def __init__(self, rows, B, rows_f16=None, img_size=224):
         self.rows, self.rows_f16, self.B = rows, rows_f16, B          # bf16 rows and / or the same values in IEEE f16
-        self.shape = (B, 3, 224, 224)
+        self.img_size = check_img_size(img_size)
+        self.grid = self.img_size // 16
+        self.num_patches = self.grid * self.grid
+        self.shape = (B, 3, self.img_size, self.img_size)
 
     _any = property(lambda self: self.rows if self.rows is not None else self.rows_f16)
     is_cuda = property(lambda self: self._any.is_cuda)
@@ -929,31 +975,33 @@ PATCH_ROW_DTYPES = (torch.bfloat16,)      # what patch_rows / mix_patch_rows pro
 
 
 def patch_rows(img, dtypes=None):
-    """fp32 [B,3,224,224] -> PatchRows (devit_im2row_bf16); dtypes: which 16-bit copies to make (bf16 and / or f16)."""
+    """fp32 [B,3,S,S] (S in IMG_SIZES) -> PatchRows (devit_im2row_bf16); dtypes: which 16-bit copies to make (bf16 and / or f16)."""
     if isinstance(img, PatchRows):
         return img
     L.require_device(img)
+    S = image_side(img, "patch_rows")
     img = img.contiguous().float()
-    B = img.shape[0]
+    B, T = img.shape[0], (S // 16) ** 2
     out = {}
     for dt in (dtypes or PATCH_ROW_DTYPES):
-        out[dt] = rows_alloc(B * 196, 768, dt, img.device)
-        call("devit_im2row_bf16", ptr(img), ptr(out[dt]), B, 3, 224, 224, 16, int(dt == F16), stream_ptr())
-    return PatchRows(out.get(torch.bfloat16), B, out.get(F16))
+        out[dt] = rows_alloc(B * T, 768, dt, img.device)
+        call("devit_im2row_bf16", ptr(img), ptr(out[dt]), B, 3, S, S, 16, int(dt == F16), stream_ptr())
+    return PatchRows(out.get(torch.bfloat16), B, out.get(F16), S)
 
 
 def mix_patch_rows(img, mode, lam=1.0, box=(0, 0, 0, 0), dtypes=None):
     """Mixup (mode 1) / CutMix (mode 2, box = (y0, y1, x0, x1)) of a batch with its flip, straight to patch rows
-    (devit_mix_im2row_bf16; timm Mixup mode='batch', engine.py:65-66)."""
+    (devit_mix_im2row_bf16_sized; timm Mixup mode='batch', engine.py:65-66).  The box lies inside the S x S image."""
     L.require_device(img)
+    S = image_side(img, "mix_patch_rows")
     img = img.contiguous().float()
-    B = img.shape[0]
+    B, T = img.shape[0], (S // 16) ** 2
     dtypes = dtypes or PATCH_ROW_DTYPES
-    rows = rows_alloc(B * 196, 768, torch.bfloat16, img.device) if torch.bfloat16 in dtypes else None
-    rows_h = rows_alloc(B * 196, 768, F16, img.device) if F16 in dtypes else None
-    call("devit_mix_im2row_bf16", ptr(img), ptr(rows), ptr(rows_h), B, int(mode), float(lam), int(box[0]), int(box[1]),
-         int(box[2]), int(box[3]), stream_ptr())
-    return PatchRows(rows, B, rows_h)
+    rows = rows_alloc(B * T, 768, torch.bfloat16, img.device) if torch.bfloat16 in dtypes else None
+    rows_h = rows_alloc(B * T, 768, F16, img.device) if F16 in dtypes else None
+    call("devit_mix_im2row_bf16_sized", ptr(img), ptr(rows), ptr(rows_h), B, int(mode), float(lam), int(box[0]), int(box[1]),
+         int(box[2]), int(box[3]), S, S, stream_ptr())
+    return PatchRows(rows, B, rows_h, S)
 
 
 def mix_targets(labels, num_classes, lam, smoothing):
@@ -976,14 +1024,14 @@ _mix_ring = {}        # device -> [pinned uint8 [MIX_RING_SLOTS, bytes per slot]
 class MixTable:
     """A validated table of B devit_mix_sample entries: `host` (numpy, MIX_SAMPLE_DTYPE) and its copy on the device, `dev` (uint8)."""
 
-    def __init__(self, host, dev):
-        self.host, self.dev, self.B = host, dev, host.shape[0]
+    def __init__(self, host, dev, img_size=224):
+        self.host, self.dev, self.B, self.img_size = host, dev, host.shape[0], img_size      # img_size: what the boxes were checked against
 
 
-def mix_entries(entries):
+def mix_entries(entries, img_size=224):
     """A numpy structured array with the fields of MIX_SAMPLE_DTYPE, or a list of (mode, lam, y0, y1, x0, x1) -> a validated
     MIX_SAMPLE_DTYPE array.  ValueError for a mode outside {0, 1, 2}, lam outside [0, 1] or NaN, a box outside
-    0 <= lo <= hi <= 224, or mode 0 with lam != 1 (the images would stay as they are and the targets would not).  The kernels
+    0 <= lo <= hi <= img_size (224 unless given), or mode 0 with lam != 1 (the images would stay as they are and the targets would not).  The kernels
     are memory-safe for any table bytes and the C entry cannot read device memory, so this is where the values are checked."""
     if isinstance(entries, np.ndarray) and entries.dtype.names:
         cols = [np.asarray(entries[n]).reshape(-1) for n in ("mode", "lam", "y0", "y1", "x0", "x1")]
@@ -1001,10 +1049,10 @@ def mix_entries(entries):
     if not ((lam >= 0) & (lam <= 1)).all():             # (a NaN compares false)
         raise ValueError(f"mix_table: lam must lie in [0, 1], got {lam[~((lam >= 0) & (lam <= 1))].tolist()}")
     for lo, hi, ax in ((y0, y1, "y"), (x0, x1, "x")):
-        bad = ~((0 <= lo) & (lo <= hi) & (hi <= 224))
+        bad = ~((0 <= lo) & (lo <= hi) & (hi <= img_size))
         if bad.any():
             i = int(np.flatnonzero(bad)[0])
-            raise ValueError(f"mix_table: entry {i}: box [{lo[i]}, {hi[i]}) on {ax} is not inside 0 <= lo <= hi <= 224")
+            raise ValueError(f"mix_table: entry {i}: box [{lo[i]}, {hi[i]}) on {ax} is not inside 0 <= lo <= hi <= {img_size}")
     if ((mode == 0) & (lam != 1)).any():
         raise ValueError("mix_table: a mode 0 entry carries lam != 1: its image stays as it is, so its target must too")
     host = np.zeros(mode.shape[0], dtype=MIX_SAMPLE_DTYPE)
@@ -1013,13 +1061,14 @@ def mix_entries(entries):
     return host
 
 
-def mix_table(entries, device="cuda"):
-    """entries (see mix_entries) -> MixTable on `device`.  ValueError, before anything touches the device, for a mode outside
-    {0, 1, 2}, lam outside [0, 1] or NaN, a box outside 0 <= lo <= hi <= 224, and mode 0 with lam != 1.  The upload is an async copy
+def mix_table(entries, device="cuda", img_size=224):
+    """entries (see mix_entries) -> MixTable on `device` for img_size x img_size images.  ValueError, before anything touches the device, for a mode outside
+    {0, 1, 2}, lam outside [0, 1] or NaN, a box outside 0 <= lo <= hi <= img_size, and mode 0 with lam != 1.  The upload is an async copy
     out of a pinned ring and never waits for the stream: the host runs steps ahead of the GPU, so every table in flight has a slot of
     its own (as optim.FlatAdamW's scalars).  No event guards a slot: the ring holds MIX_RING_SLOTS = 256 uploads, and a caller more
     than 255 uploads ahead of the stream (one upload per training step) would overwrite a table still in flight."""
-    host = mix_entries(entries)
+    img_size = check_img_size(img_size, exc=ValueError)
+    host = mix_entries(entries, img_size)
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:      # 'cuda' and 'cuda:N' of the current device share one ring
         device = torch.device("cuda", torch.cuda.current_device())
@@ -1033,36 +1082,38 @@ def mix_table(entries, device="cuda"):
     slot.copy_(torch.from_numpy(host.view(np.uint8)))
     dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
     dev.copy_(slot, non_blocking=True)
-    return MixTable(host, dev)
+    return MixTable(host, dev, img_size)
 
 
-def _table_for(table, B):
+def _table_for(table, B, img_size=None):
     if not isinstance(table, MixTable):
         raise TypeError("expected the MixTable that ops.mix_table returns")
     if table.B != B:
         raise ValueError(f"the table has {table.B} entries, the batch {B} samples")
+    if img_size is not None and table.img_size != img_size:       # its boxes were checked against another image
+        raise ValueError(f"the table was built for {table.img_size} x {table.img_size} images (ops.mix_table(img_size=...)), the batch is "
+                         f"{img_size} x {img_size}")
     return table
 
 
 def mix_patch_rows_table(img, table, dtypes=None, f32_images=False):
     """Per-sample Mixup / CutMix of a batch with its flip (sample b with B-1-b, entry b of `table`), straight to patch rows
-    (devit_mix_im2row_table) -> PatchRows; f32_images: the mixed batch as a NEW fp32 [B,3,224,224] tensor instead (what an
-    "f32" model reads).  `img` itself is only read."""
+    (devit_mix_im2row_table_sized) -> PatchRows; f32_images: the mixed batch as a NEW fp32 [B,3,S,S] tensor instead (what an
+    "f32" model reads).  `img` itself is only read; the table is one built for this image size (ops.mix_table(img_size=S))."""
     L.require_device(img)
-    if tuple(img.shape[1:]) != (3, 224, 224):
-        raise L.DevitError(f"mix_patch_rows_table: only [B,3,224,224] images (got {tuple(img.shape)})")
+    S = image_side(img, "mix_patch_rows_table")
     img = img.contiguous().float()
-    B = img.shape[0]
-    table = _table_for(table, B)
+    B, T = img.shape[0], (S // 16) ** 2
+    table = _table_for(table, B, S)
     if f32_images:
         out = torch.empty_like(img)
-        call("devit_mix_im2row_table", ptr(img), None, None, ptr(out), ptr(table.dev), B, stream_ptr())
+        call("devit_mix_im2row_table_sized", ptr(img), None, None, ptr(out), ptr(table.dev), B, S, S, stream_ptr())
         return out
     dtypes = dtypes or PATCH_ROW_DTYPES
-    rows = rows_alloc(B * 196, 768, torch.bfloat16, img.device) if torch.bfloat16 in dtypes else None
-    rows_h = rows_alloc(B * 196, 768, F16, img.device) if F16 in dtypes else None
-    call("devit_mix_im2row_table", ptr(img), ptr(rows), ptr(rows_h), None, ptr(table.dev), B, stream_ptr())
-    return PatchRows(rows, B, rows_h)
+    rows = rows_alloc(B * T, 768, torch.bfloat16, img.device) if torch.bfloat16 in dtypes else None
+    rows_h = rows_alloc(B * T, 768, F16, img.device) if F16 in dtypes else None
+    call("devit_mix_im2row_table_sized", ptr(img), ptr(rows), ptr(rows_h), None, ptr(table.dev), B, S, S, stream_ptr())
+    return PatchRows(rows, B, rows_h, S)
 
 
 def mix_targets_table(labels, num_classes, table, smoothing):
@@ -1084,11 +1135,14 @@ class PatchEmbedFn(torch.autograd.Function):
         dev = rows.device
         D = proj_w.shape[0]
         ntok = 2 if dist_token is not None else 1
-        T = 196 + ntok
-        M = B * 196
+        T = pos_embed.shape[1]                  # tokens of the MODEL: its patches + ntok
+        P = T - ntok
+        if pre.num_patches != P:                # (VisionTransformer.embed names both sizes before it gets here)
+            raise L.DevitError(f"PatchEmbedFn: pos_embed holds {P} patch positions, the batch {tuple(pre.shape)} has {pre.num_patches} patches")
+        M = B * P
         x = torch.empty((B, T, D), dtype=F32, device=dev)
         gemm(rows, 768, 0, w16, 768, 0, pad_rows(M), D, 768, kind=L.EPI_PATCH_F32, out=x, ldc=D, bias=proj_b,
-             pos=pos_embed, patch_tokens=196, extra_tokens=ntok, m_valid=M, dtype16=int(w16.dtype == F16))
+             pos=pos_embed, patch_tokens=P, extra_tokens=ntok, m_valid=M, dtype16=int(w16.dtype == F16))
         call("devit_embed_tokens", ptr(cls_token), ptr(dist_token), ptr(pos_embed), ptr(x), B, T, D, stream_ptr())
         ctx.rows, ctx.dims = rows, (B, T, D, ntok)
         ctx.params = (proj_w, proj_b, cls_token, dist_token, pos_embed)
@@ -1101,8 +1155,12 @@ class PatchEmbedFn(torch.autograd.Function):
         proj_w, proj_b, cls_token, dist_token, pos_embed = ctx.params
         dx = dx.contiguous()
         dev = dx.device
-        # bf16 copy of dx with pad rows (the wgrad reduces over padded patch rows; skipped rows map past the end)
-        dxb = rows_alloc(B * T, D, BF16, dev, extra=128)
+        # bf16 copy of dx with pad rows (the wgrad reduces over padded patch rows; skipped rows map past the end: the last reduction row
+        # pad_rows(B * P) - 1 lives at physical row r + ntok * (r / P + 1), which with few patches per image -- P = 4 at 32 pixels -- lies
+        # well behind the 128 spare rows that cover 224-pixel batches)
+        P = T - ntok
+        last = pad_rows(B * P) - 1
+        dxb = rows_alloc(B * T, D, BF16, dev, extra=max(128, last + ntok * (last // P + 1) + 1 - pad_rows(B * T)))
         dpos = torch.empty((T, D), dtype=F32, device=dev)
         dcls = torch.empty(D, dtype=F32, device=dev)
         ddist = torch.empty(D, dtype=F32, device=dev) if ntok == 2 else None
@@ -1114,11 +1172,11 @@ class PatchEmbedFn(torch.autograd.Function):
         if ntok == 2:
             grad_buf(dist_token).view(D).add_(ddist)
         grad_buf(proj_b).add_(dbias)
-        # dW[D, 768] += dx_patch^T @ rows ; reduction row r=(b,t) lives at physical row r + ntok*(r/196 + 1)
-        M = B * 196
+        # dW[D, 768] += dx_patch^T @ rows ; reduction row r=(b,t) lives at physical row r + ntok*(r/P + 1), P = T - ntok patches
+        M = B * P
         mp = pad_rows(M)
         gemm(dxb, D, 1, ctx.rows, 768, 1, D, 768, mp, kind=L.EPI_ATOMIC_F32, out=grad_buf(proj_w), ldc=768,
-             split_k=split_k_for(D, 768, mp // 64), a_group=196, a_skip=ntok)
+             split_k=split_k_for(D, 768, mp // 64), a_group=P, a_skip=ntok)
         if ctx.grad_ready is not None:
             ctx.grad_ready([p for p in ctx.params if p is not None])
         return (None,) * 8

@@ -9,7 +9,7 @@ import torch
 from . import _lib as L
 from ._lib import call, ptr, stream_ptr
 from . import dropout
-from .ops import grad_buf, layernorm_bwd, layernorm_fwd
+from .ops import grad_buf, image_side, layernorm_bwd, layernorm_fwd
 
 F32 = torch.float32
 
@@ -218,16 +218,21 @@ class PatchEmbedF32Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, proj_w, proj_b, cls_token, dist_token, pos_embed, grad_ready):
         L.require_device(img)
+        S = image_side(img, "PatchEmbedF32Fn")
         img = img.contiguous().float()
         B, D = img.shape[0], proj_w.shape[0]
         ntok = 2 if dist_token is not None else 1
-        T, M = 196 + ntok, B * 196
+        T = pos_embed.shape[1]                  # tokens of the MODEL: its patches + ntok
+        P = T - ntok
+        if (S // 16) ** 2 != P:                 # (VisionTransformer.embed names both sizes before it gets here)
+            raise L.DevitError(f"PatchEmbedF32Fn: pos_embed holds {P} patch positions, the batch {tuple(img.shape)} has {(S // 16) ** 2} patches")
+        M = B * P
         rows = torch.empty((M, 768), dtype=F32, device=img.device)
-        call("devit_im2row_f32", ptr(img), ptr(rows), B, stream_ptr())
+        call("devit_im2row_f32_sized", ptr(img), ptr(rows), B, S, S, stream_ptr())
         x = torch.empty((B, T, D), dtype=F32, device=img.device)
         w2 = proj_w.detach().reshape(D, 768)
         sgemm(rows, 768, 1, w2, 768, 1, M, D, 768, out=x, ldc=D, kind=L.EPI_PATCH_F32, bias=proj_b, pos=pos_embed,
-              patch_tokens=196, extra_tokens=ntok)
+              patch_tokens=P, extra_tokens=ntok)
         call("devit_embed_tokens", ptr(cls_token), ptr(dist_token), ptr(pos_embed), ptr(x), B, T, D, stream_ptr())
         ctx.rows, ctx.dims, ctx.params, ctx.grad_ready = rows, (B, T, D, ntok), (proj_w, proj_b, cls_token, dist_token, pos_embed), grad_ready
         return x
@@ -247,8 +252,9 @@ class PatchEmbedF32Fn(torch.autograd.Function):
         if ntok == 2:
             grad_buf(dist_token).view(D).add_(ddist)
         grad_buf(proj_b).add_(dbias)
-        # dW[d][k] += sum_r dx[phys(r)][d] * rows[r][k],  phys(r) = r + ntok * (r / 196 + 1)
-        sgemm(dx, 1, D, ctx.rows, 1, 768, D, 768, B * 196, out=grad_buf(proj_w), ldc=768, k_group=196, k_skip=ntok,
+        # dW[d][k] += sum_r dx[phys(r)][d] * rows[r][k],  phys(r) = r + ntok * (r / P + 1), P = T - ntok patches
+        P = T - ntok
+        sgemm(dx, 1, D, ctx.rows, 1, 768, D, 768, B * P, out=grad_buf(proj_w), ldc=768, k_group=P, k_skip=ntok,
               accumulate=True)
         if ctx.grad_ready is not None:
             ctx.grad_ready([p for p in ctx.params if p is not None])

@@ -34,5 +34,6 @@ def create_model(model_name, pretrained=False, checkpoint_path='', **kwargs):
     if checkpoint_path:
         import torch
         ckpt = torch.load(checkpoint_path, map_location='cpu', weights_only=False)
-        model.load_state_dict(ckpt['model'] if 'model' in ckpt else ckpt)
+        from .de_vit import load_checkpoint        # (a checkpoint of another image size: its position grid is resized)
+        load_checkpoint(model, ckpt) if hasattr(model, 'pos_embed') else model.load_state_dict(ckpt['model'] if 'model' in ckpt else ckpt)
     return model

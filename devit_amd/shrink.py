@@ -293,9 +293,12 @@ def _blocks(model):
     return [m for m in model.modules() if isinstance(m, Block)]
 
 
-def compacted_gflops(model, tokens=198, patch_dim=768, num_classes=None):
+def compacted_gflops(model, tokens=None, patch_dim=768, num_classes=None):
     """Forward GFLOPs per image (2 FLOP per MAC, the accounting of BASELINE.md §2) of the model as it would run:
-    compacted blocks at their run sizes, the others dense."""
+    compacted blocks at their run sizes, the others dense.  tokens: None takes the model's own count (198 for a distilled model at 224)."""
+    if tokens is None:
+        vits = [m for m in model.modules() if type(m).__name__ == "VisionTransformer"]
+        tokens = vits[0].pos_embed.shape[1] if vits else 198
     total = 0.0
     for blk in _blocks(model):
         D = blk.attn.qkv.weight.shape[1]
@@ -536,10 +539,18 @@ def rank_units(model, data_loader, device=None, batches=1):
 # the policy search (core/shrink_imp.py:66-82 `screen`, :138-179 `model_shrink`; shrink.py:406-418)
 # ------------------------------------------------------------------------------------------------------
 def model_geometry(model):
-    """emb / head / layer / mlp_ratio of the model for flops.macs_g (the reference hard-codes 384 / 6 / 12 / 4)."""
+    """emb / head / layer / mlp_ratio of the model for flops.macs_g (the reference hard-codes 384 / 6 / 12 / 4).  A model built for another
+    image size than 224 adds img_size and its seq_length (patches + one class token, as the reference counts at 224: 197), so that the
+    search's MACs target and every candidate's MACs are those of the size it runs at."""
     blocks = _blocks(model)
     emb = blocks[0].attn.qkv.weight.shape[1]
-    return dict(emb=emb, head=blocks[0].attn.num_heads, layer=len(blocks), mlp_ratio=blocks[0].mlp.hidden_features // emb)
+    geo = dict(emb=emb, head=blocks[0].attn.num_heads, layer=len(blocks), mlp_ratio=blocks[0].mlp.hidden_features // emb)
+    pe = getattr(model, "patch_embed", None)
+    side = pe.img_size[0] if pe is not None else 224
+    if side != 224:
+        from . import flops
+        geo.update(img_size=side, seq_length=flops.seq_length_for(side, 1))
+    return geo
 
 
 def dense_gflops(**geometry):
@@ -553,7 +564,7 @@ def macs_target(shrink_ratio, **geometry):
     return shrink_ratio * dense_gflops(**geometry)
 
 
-def _macs_g_rows(x, layer, emb=768, seq_length=197, mlp_ratio=4, head=12, num_class=1000):
+def _macs_g_rows(x, layer, emb=768, seq_length=197, mlp_ratio=4, head=12, num_class=1000, img_size=224):
     """flops.macs_g for every row of x [n, 2 * layer] at once (same operations in the same order, so the same doubles)."""
     import numpy as np
     head_dim = emb / head
@@ -561,7 +572,7 @@ def _macs_g_rows(x, layer, emb=768, seq_length=197, mlp_ratio=4, head=12, num_cl
     kept_heads = ((1 - x[:, layer:]) * head).astype(np.int64)
     hidden = (mlp_ratio * (1 - x[:, :layer]) * emb).astype(np.int64)
     per_block = sa * kept_heads + seq_length * 2 * head_dim * kept_heads * emb + (seq_length * hidden * 2 * emb + seq_length * emb * 2 * hidden)
-    return (2 * 3 * emb * 224 ** 2 + per_block.sum(1) + 2 * emb * num_class) / 1e9 / 2
+    return (2 * 3 * emb * img_size ** 2 + per_block.sum(1) + 2 * emb * num_class) / 1e9 / 2
 
 
 def screen(macs_target, population, lb, ub, layer, rng, max_draws=1 << 26, **geometry):

@@ -82,11 +82,11 @@ NUM_CLASSES = {'cifar100': 100, 'IMNET': 1000, 'cars': 196, 'pets': 37, 'flowers
 
 
 class SyntheticLoader:
-    """`steps` resident batches; same (images fp32 [B,3,224,224], labels int64 [B]) contract as the DataLoader."""
+    """`steps` resident batches; same (images fp32 [B,3,S,S], labels int64 [B]) contract as the DataLoader (S: --input-size)."""
 
-    def __init__(self, steps, batch, classes, device, seed):
+    def __init__(self, steps, batch, classes, device, seed, img_size=224):
         g = torch.Generator(device=device).manual_seed(seed)
-        self.img = torch.randn((batch, 3, 224, 224), generator=g, device=device)
+        self.img = torch.randn((batch, 3, img_size, img_size), generator=g, device=device)
         self.lab = torch.randint(0, classes, (batch,), generator=g, device=device)
         self.steps = steps
 
@@ -142,8 +142,9 @@ def build_loaders(args, num_classes, device, provider="division", plain_sampler_
     TRAIN sampler over the TEST set (its length sets the epoch length, and with it the LR schedule); kept, ensemble.py:271-273
     uses the train set."""
     if args.synthetic > 0:
-        return (SyntheticLoader(args.synthetic, args.batch_size, num_classes, device, 1234 + utils.get_rank()),
-                SyntheticLoader(max(1, args.synthetic // 8), args.batch_size, num_classes, device, 99), num_classes)
+        size = getattr(args, 'input_size', 224)
+        return (SyntheticLoader(args.synthetic, args.batch_size, num_classes, device, 1234 + utils.get_rank(), size),
+                SyntheticLoader(max(1, args.synthetic // 8), args.batch_size, num_classes, device, 99, size), num_classes)
     try:
         import importlib
         gd = importlib.import_module("data.get_dataset")
@@ -189,12 +190,14 @@ class Mixup:
     images never exist; student and teacher both read those rows) and devit_mix_targets builds the soft targets.
     mode='elem' / 'pair' (timm's _mix_elem / _mix_pair: one draw per sample / per pair b, B-1-b) go through the same stage with a
     per-sample table (draw_table -> devit_mix_im2row_table / devit_mix_targets_table); cutmix_minmax=(min, max) draws the CutMix
-    box sides as a share of the image (timm's rand_bbox_minmax) in every mode."""
+    box sides as a share of the image (timm's rand_bbox_minmax) in every mode.  img_size: the square side of the batches the table modes
+    will be called with (--input-size; one of devit_amd.ops.IMG_SIZES): they draw their boxes on it and refuse a batch of another size."""
 
     MODES = ("batch", "elem", "pair")
 
     def __init__(self, mixup_alpha, cutmix_alpha, prob, switch_prob, label_smoothing, num_classes, precisions=("bf16",), *,
-                 mode="batch", cutmix_minmax=None):
+                 mode="batch", cutmix_minmax=None, img_size=224):
+        self.img_size = img_size
         if mode not in self.MODES:                  # (timm falls back to 'batch' without a word)
             raise ValueError(f"Mixup mode {mode!r}: one of {', '.join(self.MODES)}")
         if cutmix_minmax is not None:
@@ -278,18 +281,21 @@ class Mixup:
     def __call__(self, x, y):
         from devit_amd import ops
         assert x.shape[0] % 2 == 0, 'Batch size should be even when using this'
+        H, W = x.shape[-2], x.shape[-1]
+        sized = H == W and H in ops.IMG_SIZES       # what the patch-row kernels cut (ops.check_img_size)
         if self.mode != "batch":
-            if tuple(x.shape[-2:]) != (224, 224):
-                raise NotImplementedError(f"Mixup mode {self.mode!r} is built on the 224 x 224 patch-row kernel, got {tuple(x.shape[-2:])} images")
-            table = ops.mix_table(self.draw_table(x.shape[0]), x.device)
+            if not sized or H != self.img_size:
+                raise NotImplementedError(f"Mixup mode {self.mode!r} is built on the patch-row kernel and was set up for {self.img_size} x "
+                                          f"{self.img_size} images (img_size=, one of {list(ops.IMG_SIZES)}), got {(H, W)} images")
+            table = ops.mix_table(self.draw_table(x.shape[0], H, W), x.device, img_size=H)
             targets = ops.mix_targets_table(y, self.C, table, self.eps)
             if "f32" in self.precisions:        # the exact-fp32 parity models read fp32 images: the kernel's third output
                 return ops.mix_patch_rows_table(x, table, f32_images=True), targets
             return ops.mix_patch_rows_table(x, table, dtypes=self.row_dtypes), targets
-        mode, lam, box = self.draw(x.shape[-2], x.shape[-1])
-        if "f32" in self.precisions or tuple(x.shape[-2:]) != (224, 224):
-            # the exact-fp32 parity models read fp32 images (and the patch-row kernel is built for 224 x 224): timm's formulas on
-            # the image tensor itself, mixed in place like timm does
+        mode, lam, box = self.draw(H, W)
+        if "f32" in self.precisions or not sized:
+            # the exact-fp32 parity models read fp32 images (and the patch-row kernel is built for the sides of ops.IMG_SIZES): timm's
+            # formulas on the image tensor itself, mixed in place like timm does
             flipped = x.flip(0)
             if mode == 1:
                 x.mul_(lam).add_(flipped, alpha=1.0 - lam)
@@ -306,7 +312,7 @@ def build_mixup(args, num_classes):
     if not (args.mixup > 0 or args.cutmix > 0. or args.cutmix_minmax is not None):
         return None
     return Mixup(args.mixup, args.cutmix, args.mixup_prob, args.mixup_switch_prob, args.smoothing, num_classes,
-                 mode=args.mixup_mode, cutmix_minmax=args.cutmix_minmax)
+                 mode=args.mixup_mode, cutmix_minmax=args.cutmix_minmax, img_size=getattr(args, 'input_size', 224))
 
 
 class CosineEpochs:
@@ -359,9 +365,25 @@ class StepRunner:
         pass
 
 
+def check_input_size(args):
+    """--input-size: the square sides the patch-embed kernels are built for (devit_amd.ops.IMG_SIZES); SystemExit with the list otherwise."""
+    from devit_amd.ops import IMG_SIZES
+    if getattr(args, 'input_size', 224) not in IMG_SIZES:
+        raise SystemExit(f"--input-size {args.input_size}: the patch-embed kernels are built for square images of side {list(IMG_SIZES)} "
+                         "(multiples of the 16-pixel patch; 224 is the ceiling: 240 pixels are 227 tokens, over the attention kernels' 208)")
+
+
+def load_weights_any_size(model, state_dict):
+    """load_state_dict of a checkpoint that may come from another image size: a 224-pixel teacher into a model built with a smaller
+    --input-size gets its position grid resized (devit_amd.de_vit.checkpoint_filter_fn)."""
+    from devit_amd.de_vit import load_checkpoint
+    return load_checkpoint(model, state_dict)
+
+
 def check_supported(args):
     """Flags the reference hands to timm factories that this build implements for one value only: refuse the others
     instead of silently training something else (create_optimizer / create_scheduler, distill_sub.py:340-343)."""
+    check_input_size(args)
     if args.opt.lower() != 'adamw':
         raise SystemExit(f"--opt {args.opt}: only adamw (the reference's default) is built on the fused optimizer kernel")
     if args.sched != 'cosine':
@@ -395,17 +417,17 @@ def main(args):
     resize_dim = model_config[args.teacher_model]["embed_dim"] if args.distillation_token else None
     model = devit_amd.create_model(args.model, pretrained=True, pretrained_path=args.model_path if args.finetune else None,
                                    num_classes=stu_nb, resize_dim=resize_dim, drop_rate=args.drop,
-                                   drop_path_rate=args.drop_path, drop_block_rate=None)
+                                   drop_path_rate=args.drop_path, drop_block_rate=None, img_size=args.input_size)
     if args.model_path != '':
         model.reset_classifier(num_classes=num_classes)
     model.to(device)
     teacher = None
     if args.distillation_type != 'none':
-        teacher = devit_amd.create_model(args.teacher_model, num_classes=num_classes, drop_rate=args.drop,
-                                         drop_path_rate=args.drop_path, drop_block_rate=None)
+        teacher = devit_amd.create_model(args.teacher_model, num_classes=num_classes, drop_rate=args.drop,     # (the relation loss needs the
+                                         drop_path_rate=args.drop_path, drop_block_rate=None, img_size=args.input_size)   # student's token count)
         tp = os.path.join(args.teacher_path, f'sub-dataset{args.start_division}', 'checkpoint.pth') if args.teacher_path else ''
         if tp and os.path.exists(tp):
-            teacher.load_state_dict(torch.load(tp, map_location='cpu'))
+            load_weights_any_size(teacher, torch.load(tp, map_location='cpu'))
         elif not args.synthetic:
             raise SystemExit(f"teacher checkpoint not found: {tp}")
         teacher.to(device).eval()

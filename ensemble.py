@@ -50,16 +50,17 @@ def get_models(args, num_subs, sub_classes, num_classes):
     teacher = None
     if args.distillation_type != 'none':
         teacher = devit_amd.create_model(args.teacher_model, num_classes=num_classes, drop_rate=args.drop,
-                                         drop_path_rate=args.drop_path, drop_block_rate=None)
+                                         drop_path_rate=args.drop_path, drop_block_rate=None, img_size=args.input_size)
         if args.teacher_path and os.path.exists(args.teacher_path):
-            teacher.load_state_dict(torch.load(args.teacher_path, map_location='cpu'))
+            ds.load_weights_any_size(teacher, torch.load(args.teacher_path, map_location='cpu'))
         elif not args.synthetic:
             raise SystemExit(f"teacher checkpoint not found: {args.teacher_path}")
         teacher.to(args.device).eval()
         for p_ in teacher.parameters():
             p_.requires_grad_(False)
         teacher.request_precision(args.teacher_precision)
-    model = MultiViT(model=args.model, drop=args.drop, drop_path=args.drop_path, num_div=num_subs, num_classes_list=sub_classes)
+    model = MultiViT(model=args.model, drop=args.drop, drop_path=args.drop_path, num_div=num_subs, num_classes_list=sub_classes,
+                     img_size=args.input_size)
     # sub_size from the constructed backbones (the reference reads a wrong 192 from its config table)
     ens_model = EnsMLP(model=args.model, num_class=num_classes, sub_size=model.backbones[0].embed_dim,
                        num_classes_list=sub_classes, teacher_size=model_config[args.teacher_model]['embed_dim'])

@@ -307,7 +307,8 @@ DEVIT_API int devit_attn_bwd_drop(const void* qkv, const void* out, const void* 
  *                         their rows >= M are zeroed by the forward (GEMM tiles read them, the weight-gradient GEMMs
  *                         reduce over them).  Pointers of buffers whose size is reported 0 may be NULL.
  *   flags               : DEVIT_BLK_SAVE   keep what backward needs (mean/rstd, lse, fc1 pre-activation)
- *                         DEVIT_BLK_QKV_PAD 128 zeroed overhang rows behind qkv (read by the relation-loss Gram windows)
+ *                         DEVIT_BLK_QKV_PAD zeroed overhang rows behind qkv (read by the relation-loss Gram windows, 256 rows
+ *                                           per image): 128 for N >= 128, 256 - N for a shorter sequence
  *                         DEVIT_BLK_ATT    also store the attention-branch output (pre-residual, de_vit.py:119) as bf16
  *   devit_encoder_fwd   : blocks 0..nblocks-1 in sequence; acts[i].x2 feeds acts[i+1].x (the caller points them at the
  *                         same memory); flags per block.
@@ -439,8 +440,12 @@ DEVIT_API int devit_hsic_head_pairs(const float* kmix1, int H, int B, float* red
 
 /* ------------------------------------------------------------------------------------------
  * Patch embedding helpers (timm PatchEmbed used at models/de_vit.py:166-168,258 and token assembly
- * :259-264).  im2row: f32 [B,3,224,224] -> bf16 [B*196][768] with k = c*256 + kh*16 + kw; the
- * projection itself is devit_gemm_bf16 with DEVIT_EPI_PATCH_F32.  embed_tokens writes
+ * :259-264).  im2row: f32 [B,3,S,S] -> bf16 [B*T][768] with k = c*256 + kh*16 + kw, token t = py*G + px; the
+ * projection itself is devit_gemm_bf16 with DEVIT_EPI_PATCH_F32.
+ * Image sizes: C = 3, patch = 16, H == W == S with S a multiple of 16 from 32 to 224 (G = S/16 = 2 .. 14 patches per side,
+ *   T = G*G tokens; 224 is the ceiling because T + 2 tokens must fit the attention kernels' 208 rows: 240 pixels are 227).
+ *   Anything else is DEVIT_ERR_SHAPE.  The entry points without H, W below are the 224-pixel calls; each has a `_sized`
+ *   sibling with the same arguments plus `int H, int W` in front of the stream, which at 224 is the same launch.  embed_tokens writes
  * x[b, t, :] = (t == 0 ? cls : dist) + pos[t] for the 1-2 extra tokens (dist == NULL: cls only).
  * embed_bwd: dpos[T][D] = sum_b dx[b]; dcls = dpos[0]; ddist = dpos[1]; dbias = sum_{t>=ntok} dpos[t];
  *   dx_bf16 (optional) = bf16 copy of dx for the patch-projection wgrad.
@@ -453,6 +458,9 @@ DEVIT_API int devit_im2row_bf16(const float* img, void* rows, int B, int C, int 
  * devit_mix_targets: [B][C] f32 = lam * smooth_one_hot(y) + (1 - lam) * smooth_one_hot(y.flip(0)), int64 labels. */
 DEVIT_API int devit_mix_im2row_bf16(const float* img, void* rows /* bf16 or NULL */, void* rows_f16 /* f16 or NULL */, int B, int mode,
                           double lam, int y0, int y1, int x0, int x1, void* stream);
+/* ... on [B,3,H,W] images (sizes: see above); the cutmix box is checked against H, W */
+DEVIT_API int devit_mix_im2row_bf16_sized(const float* img, void* rows /* bf16 or NULL */, void* rows_f16 /* f16 or NULL */, int B, int mode,
+                          double lam, int y0, int y1, int x0, int x1, int H, int W, void* stream);
 DEVIT_API int devit_mix_targets(const long long* labels, float* targets, int B, int C, double lam, double smoothing, void* stream);
 /* The same stage with one (mode, lam, box) PER SAMPLE (timm Mixup(mode='elem' / 'pair'), cutmix_minmax boxes): entry b of a device
  * table of B devit_mix_sample says how sample b is mixed with its partner, which is always sample B-1-b (timm's _mix_elem and
@@ -478,6 +486,10 @@ typedef struct {
 DEVIT_API int devit_mix_im2row_table(const float* img, void* rows /* bf16 or NULL */, void* rows_f16 /* f16 or NULL */,
                            float* img_out /* f32 images or NULL */, const devit_mix_sample* table /* device, B entries */, int B,
                            void* stream);
+/* ... on [B,3,H,W] images (img_out has the same shape); the host checks the table's boxes against H, W */
+DEVIT_API int devit_mix_im2row_table_sized(const float* img, void* rows /* bf16 or NULL */, void* rows_f16 /* f16 or NULL */,
+                           float* img_out /* f32 images or NULL */, const devit_mix_sample* table /* device, B entries */, int B,
+                           int H, int W, void* stream);
 DEVIT_API int devit_mix_targets_table(const long long* labels, float* targets, const devit_mix_sample* table, int B, int C,
                             double smoothing, void* stream);
 DEVIT_API int devit_embed_tokens(const float* cls, const float* dist, const float* pos, float* x, int B, int T, int D,
@@ -568,7 +580,8 @@ DEVIT_API int devit_gemm_f32(const float* A, long long sam, long long sak, long 
                    float alpha, const float* batch_scale, int accumulate, const devit_epilogue* ep, void* stream);
 DEVIT_API int devit_softmax_rows_f32(float* S, int rows, int ncols, int ld, float scale, float* lse, void* stream);
 DEVIT_API int devit_softmax_bwd_rows_f32(const float* P, float* dP, int rows, int ncols, int ld, float scale, void* stream);
-DEVIT_API int devit_im2row_f32(const float* img, float* rows, int B, void* stream);
+DEVIT_API int devit_im2row_f32(const float* img, float* rows, int B, void* stream);          /* [B,3,224,224] -> f32 [B*196][768] */
+DEVIT_API int devit_im2row_f32_sized(const float* img, float* rows, int B, int H, int W, void* stream);   /* [B,3,H,W] -> [B*T][768] */
 DEVIT_API int devit_scale_rows_f32(const float* src, float* dst, const float* rowscale, int rows_per_scale, int M, int D,
                          void* stream);
 DEVIT_API int devit_colsum_f32(const float* y, int M, int N, int ld, float* out, int accumulate, void* stream);

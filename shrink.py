@@ -24,7 +24,7 @@ import torch
 
 import devit_amd
 from devit_amd import shrink as shrink_ops
-from distill_sub import NUM_CLASSES, build_loaders
+from distill_sub import NUM_CLASSES, build_loaders, check_input_size
 
 
 def get_args_parser():
@@ -92,6 +92,7 @@ def main(args):
     if int(os.environ.get('WORLD_SIZE', '1')) > 1 or args.world_size > 1:
         raise SystemExit("shrink.py runs in a single process (the policy search evaluates its candidates one after the other on one GPU): "
                          "start it with plain `python shrink.py ...`, not under torch.distributed.run")
+    check_input_size(args)
     args.distributed, args.rank, args.gpu = False, 0, 0
     device = torch.device(args.device)
     torch.manual_seed(args.seed)
@@ -103,7 +104,7 @@ def main(args):
     args.num_classes = num_classes
 
     model = devit_amd.create_model(args.model, pretrained=False, num_classes=num_classes, drop_rate=args.drop,
-                                   drop_path_rate=args.drop_path, drop_block_rate=None)
+                                   drop_path_rate=args.drop_path, drop_block_rate=None, img_size=args.input_size)
     if args.finetune:
         load_weights(model, args.finetune, strict=False)
     if args.resume:

@@ -50,18 +50,18 @@ def main(args):
     # train_subdata.py:193-230
     model = devit_amd.create_model(args.model, pretrained=True, pretrained_path=args.model_path or None,
                                    num_classes=1000 if args.model_path else num_classes, drop_rate=args.drop,
-                                   drop_path_rate=args.drop_path, drop_block_rate=None)
+                                   drop_path_rate=args.drop_path, drop_block_rate=None, img_size=args.input_size)
     if args.model_path:
         model.reset_classifier(num_classes=num_classes)
     model.to(device)
     teacher = None
     if args.distillation_type != 'none':
         teacher = devit_amd.create_model(args.teacher_model, num_classes=num_classes, drop_rate=args.drop,
-                                         drop_path_rate=args.drop_path, drop_block_rate=None)
+                                         drop_path_rate=args.drop_path, drop_block_rate=None, img_size=args.input_size)
         tp = os.path.join(args.teacher_path, f'sub-dataset{args.start_division}', 'checkpoint.pth') if args.teacher_path else ''
         if tp and os.path.exists(tp):
             ck = torch.load(tp, map_location='cpu', weights_only=False)
-            teacher.load_state_dict(ck['model'] if args.dataset == 'IMNET' and 'model' in ck else ck)
+            ds.load_weights_any_size(teacher, ck['model'] if args.dataset == 'IMNET' and 'model' in ck else ck)
         teacher.to(device).eval()
         for p_ in teacher.parameters():
             p_.requires_grad_(False)
