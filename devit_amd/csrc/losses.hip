@@ -278,12 +278,44 @@ __global__ __launch_bounds__(1024) void mse_kernel(const float* a, const float* 
   }
 }
 
+// ---- token KL (nn.KLDivLoss(reduction="batchmean", log_target=True), utils/losses.py:192-193,228,241-242): student tokens s and teacher tokens t
+//      are read as log-probabilities as they stand: loss (+)= sum e^t (t - s) / batch, ds = -e^t / batch (independent of s).  Nothing is
+//      clamped: a non-finite token gives the non-finite loss torch gives.  One block, fixed summation order, as mse_kernel.
+__global__ __launch_bounds__(1024) void kldiv_kernel(const float* s, const float* t, size_t n, float batch, float* loss, float* ds,
+                                                     int accumulate) {
+  __shared__ float red[16];
+  float acc = 0.f;
+  for (size_t i = threadIdx.x; i < n; i += 1024) {
+    const float tv = t[i];
+    const float e = expf(tv);
+    acc += e * (tv - s[i]);
+    if (ds) ds[i] = -e / batch;
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float r = 0.f;
+    for (int i = 0; i < 16; ++i) r += red[i];
+    loss[0] = (accumulate ? loss[0] : 0.f) + r / batch;
+  }
+}
+
 }  // namespace
 
 extern "C" int devit_token_mse(const float* a, const float* b, size_t n, float* loss, float* da, int accumulate,
                                void* stream) {
   DEVIT_CHECK(a && b && loss && n > 0, DEVIT_ERR_ARG, "devit_token_mse: bad argument");
   hipLaunchKernelGGL(mse_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a, b, n, loss, da, accumulate);
+  DEVIT_LAUNCH_CHECK();
+  return DEVIT_OK;
+}
+
+extern "C" int devit_token_kldiv(const float* s, const float* t, size_t n, int batch, float* loss, float* ds, int accumulate,
+                                 void* stream) {
+  DEVIT_CHECK(s && t && loss && n > 0, DEVIT_ERR_ARG, "devit_token_kldiv: bad argument");
+  DEVIT_CHECK(batch > 0 && n % (size_t)batch == 0, DEVIT_ERR_SHAPE, "devit_token_kldiv: batch=%d must be positive and divide n=%zu", batch, n);
+  hipLaunchKernelGGL(kldiv_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, s, t, n, (float)batch, loss, ds, accumulate);
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
 }

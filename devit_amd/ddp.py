@@ -139,8 +139,12 @@ class RcclComm:
 
 def _report_group(name):
     """Which grad_ready report a parameter belongs to, in backward order: (0, 0) heads and final norm, (1, k) encoder
-    block k, (2, 0) embeddings (patch projection, class / distillation tokens, position embedding)."""
+    block k, (2, 0) embeddings (patch projection, class / distillation tokens, position embedding).  A parameter of
+    ensemble_models.MultiViT (`backbones.<i>.` in front of the name) reports with its backbone: (i, kind, block)."""
     name = name[7:] if name.startswith("module.") else name
+    if name.startswith("backbones."):
+        _, i, rest = name.split(".", 2)
+        return (int(i),) + _report_group(rest)
     if name.startswith("blocks."):
         return (1, int(name.split(".")[1]))
     if name.startswith(("patch_embed", "pos_embed", "cls_token", "dist_token")):
@@ -190,19 +194,26 @@ class BucketedGradReducer:
         self.buckets, start, last = [], 0, 0
         limit = bucket_bytes // 4
         nparams = len(flat.params)
-        first_block = next((g for g in groups if g[0] == 1), None)
-        final_block = next((g for g in reversed(groups) if g[0] == 1), None)   # block 0: its bucket cannot overlap much, keep it alone
+        # a report group is (kind, block), or (backbone, kind, block) under a MultiViT: the rule above holds per backbone, and a bucket
+        # never straddles two backbones (their backward passes run one after the other)
+        kind, model_of = (lambda g: g[-2]), (lambda g: g[:-2])
+        first_of, final_of = {}, {}
+        for g in groups:
+            if kind(g) == 1:
+                first_of.setdefault(model_of(g), g)      # the last block: first in flat (= backward) order
+                final_of[model_of(g)] = g                # block 0: its bucket cannot overlap much, keep it alone
         for i in range(nparams):
             end = flat.offsets[i + 1] if i + 1 < nparams else flat.numel
             last_of_group = i + 1 == nparams or groups[i + 1] != groups[i]
-            if plan == "layers" and first_block is not None:
+            if plan == "layers" and first_of:
                 nxt = groups[i + 1] if i + 1 < nparams else None
                 cut = last_of_group and (
                     i + 1 == nparams
-                    or groups[i] == first_block                       # heads + norm + last block: out first
-                    or nxt[0] == 2                                    # everything before the embeddings
-                    or nxt == final_block
-                    or (groups[i][0] == 1 and end - start + self._group_elems(groups, i + 1) > limit))
+                    or model_of(nxt) != model_of(groups[i])           # the next backbone
+                    or groups[i] == first_of.get(model_of(groups[i]))  # heads + norm + last block: out first
+                    or kind(nxt) == 2                                 # everything before the embeddings
+                    or nxt == final_of.get(model_of(nxt))
+                    or (kind(groups[i]) == 1 and end - start + self._group_elems(groups, i + 1) > limit))
             else:
                 cut = end - start >= limit or i + 1 == nparams
             if cut:
@@ -249,8 +260,10 @@ class BucketedGradReducer:
         self._events = []
 
     def attach(self, model):
-        """Route the model's grad_ready callbacks here (VisionTransformer.grad_ready)."""
-        model.grad_ready = _ReadyHook(self)
+        """Route the model's grad_ready callbacks here (VisionTransformer.grad_ready; every backbone of a MultiViT)."""
+        hook = _ReadyHook(self)
+        for m in getattr(model, "backbones", None) or [model]:
+            m.grad_ready = hook
         return self
 
     def mark_ready(self, params):

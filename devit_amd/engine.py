@@ -372,7 +372,9 @@ def ens_forward(model, ens_model, criterion, samples, targets, distillation_type
 def train_1epoch_ens_disjoint(model, ens_model, criterion, data_loader, optimizer, ens_optimizer, device, epoch, scaler,
                               args, log, model_ema=None, ens_model_ema=None, mixup_fn=None, max_norm=0, print_freq=10):
     """engine.py:143-210.  `optimizer` / `ens_optimizer` are any torch optimizers over the two parameter sets (the
-    reference uses two AdamW instances); gradients arrive in param.grad."""
+    reference uses two AdamW instances); gradients arrive in param.grad.  `scaler` (the reference's loss scaler slot): None runs torch's tail
+    -- coalesced gradient mean, clip_grad_norm_ per model, the two optimizers' step(); a runner `scaler(loss, optimizer, ens_optimizer,
+    clip_grad=)` (ensemble.EnsStepRunner) does backward, the gradient exchange and both optimizer steps itself, on the flat fused path."""
     from .utils import MetricLogger, SmoothedValue
     model.train(True)
     ens_model.train(True)
@@ -387,15 +389,18 @@ def train_1epoch_ens_disjoint(model, ens_model, criterion, data_loader, optimize
         optimizer.zero_grad(set_to_none=True)
         ens_optimizer.zero_grad(set_to_none=True)
         out = ens_forward(model, ens_model, criterion, samples, targets, args.distillation_type)
-        out['loss'].backward()
-        # the gradient mean DistributedDataParallel produces for both wrapped models (ensemble.py:332-334); no-op at world 1
-        from . import ddp
-        ddp.allreduce_mean_([p.grad for p in model.parameters()] + [p.grad for p in ens_model.parameters()])
-        if max_norm:
-            torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)
-            torch.nn.utils.clip_grad_norm_(ens_model.parameters(), max_norm)
-        optimizer.step()
-        ens_optimizer.step()
+        if scaler is not None:
+            scaler(out['loss'], optimizer, ens_optimizer, clip_grad=max_norm)
+        else:
+            out['loss'].backward()
+            # the gradient mean DistributedDataParallel produces for both wrapped models (ensemble.py:332-334); no-op at world 1
+            from . import ddp
+            ddp.allreduce_mean_([p.grad for p in model.parameters()] + [p.grad for p in ens_model.parameters()])
+            if max_norm:
+                torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)
+                torch.nn.utils.clip_grad_norm_(ens_model.parameters(), max_norm)
+            optimizer.step()
+            ens_optimizer.step()
         if step % print_freq == 0:
             lv = out['loss'].item()
             if not math.isfinite(lv):

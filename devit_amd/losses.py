@@ -209,16 +209,47 @@ class _TokenMseFn(torch.autograd.Function):
         return da * g, None
 
 
+class _TokenKldivFn(torch.autograd.Function):
+    """nn.KLDivLoss(reduction="batchmean", log_target=True)(student tokens, teacher tokens) for one token pair ('vit' models) or the sum over two
+    ('deit': the second pair is added into the same scalar by the kernel, `accumulate`).  One launch per pair gives loss and gradient."""
+
+    @staticmethod
+    def forward(ctx, s0, t0, s1=None, t1=None):
+        from ._lib import call, ptr, stream_ptr
+        L.require_device(s0)
+        loss = torch.empty(1, dtype=torch.float32, device=s0.device)
+        grads = []
+        for k, (s_, t_) in enumerate(((s0, t0), (s1, t1))):
+            if s_ is None:
+                grads.append(None)
+                continue
+            s_, t_ = s_.contiguous().float(), t_.contiguous().float()
+            ds = torch.empty_like(s_)
+            call("devit_token_kldiv", ptr(s_), ptr(t_), s_.numel(), s_.shape[0], ptr(loss), ptr(ds), k, stream_ptr())
+            grads.append(ds)
+        ctx.n = len([g for g in grads if g is not None])
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        ds = ctx.saved_tensors
+        return ds[0] * g, None, (ds[1] * g if ctx.n > 1 else None), None
+
+
 class EnsLoss(nn.Module):
     """utils/losses.py:180-244: (token_loss, cls_loss) of the ensemble stage.  The teacher forward runs inside, under
-    no_grad, with distill_token=True (:222-227)."""
+    no_grad, with distill_token=True (:222-227).  loss_type 'mse' is nn.MSELoss on the token pairs; 'kldiv' is
+    nn.KLDivLoss(reduction="batchmean", log_target=True) with the final-norm tokens of student and teacher read as log-probabilities as they
+    stand (:192-193) -- nothing normalises them, so d loss / d student token = -exp(teacher token) / batch does not depend on the student token.
+    That is the reference's definition and it is kept."""
 
     def __init__(self, base_criterion, teacher_model, model, distillation_type, alpha, tau, loss_type='mse'):
         super().__init__()
-        if loss_type != 'mse':
-            raise NotImplementedError("EnsLoss: only loss_type='mse' is on the DeViT path (ensemble.py default)")
+        if loss_type not in ('mse', 'kldiv'):
+            raise NotImplementedError(f"EnsLoss: loss_type={loss_type!r}; the reference knows 'mse' and 'kldiv' (utils/losses.py:192-194)")
         self.base_criterion, self.teacher_model, self.model = base_criterion, teacher_model, model
-        self.distillation_type, self.alpha, self.tau = distillation_type, alpha, tau
+        self.distillation_type, self.alpha, self.tau, self.loss_type = distillation_type, alpha, tau, loss_type
         self._cls = DistillLoss(base_criterion, distillation_type, alpha, tau)     # raises for a base criterion it does not fuse
 
     def forward(self, inputs, stu_outputs, labels):
@@ -229,8 +260,11 @@ class EnsLoss(nn.Module):
             tea = self.teacher_model(inputs, distill_token=True)
         tokens, stu_logits = stu_outputs
         cls_loss = self._cls(stu_logits, tea['output'], labels)          # (1-a) base + a distill, :236-237
+        kl = self.loss_type == 'kldiv'
         if 'vit' in self.model:
-            return _TokenMseFn.apply(tokens, tea['last_tokens']), cls_loss
+            return (_TokenKldivFn.apply(tokens, tea['last_tokens']) if kl else _TokenMseFn.apply(tokens, tea['last_tokens'])), cls_loss
         cls_token, dist_token = tokens
         tea_token, tea_token_dist = tea['last_tokens']
+        if kl:
+            return _TokenKldivFn.apply(cls_token, tea_token, dist_token, tea_token_dist), cls_loss
         return _TokenMseFn.apply(cls_token, tea_token) + _TokenMseFn.apply(dist_token, tea_token_dist), cls_loss

@@ -7,6 +7,9 @@ Flags shared with distill_sub.py keep their reference defaults except the ones e
 `--synthetic N` as in distill_sub.py.  Sub-model checkpoints are read from
 `{--model-path}/sub-dataset{i}/checkpoint.pth` and copied positionally (all tensors but the heads), the teacher from
 `--teacher-path`; with --synthetic and no paths the models are randomly initialised.
+
+Training runs on the flat fused path of the other two stages (ddp.FlatParams / BucketedGradReducer / optim.FlatAdamW: one buffer for all
+backbones, one for the fusion head); `--torch-optim` keeps two torch.optim.AdamW over the separate tensors.
 """
 import argparse
 import json
@@ -41,8 +44,35 @@ def get_args_parser():
     p.add_argument('--gates', default='', help='file written by devit_amd.shrink.save_gates for the MultiViT '
                                                '(the reference drops the gates of shrunk sub-models on reload)')
     p.add_argument('--physical-shrink', action='store_true',
-                   help='--eval only: remove the gated-off heads / neurons from the GEMMs (devit_amd.shrink.compact)')
+                   help='remove the gated-off heads / neurons of --gates from the GEMMs: devit_amd.shrink.compact for --eval, '
+                        'compact(trainable=True) when training on the fused tail (same function and gradients, the shrunk models\' FLOPs). '
+                        'On unless --no-physical-shrink is given; --torch-optim trains the masked models')
+    p.add_argument('--torch-optim', action='store_true',
+                   help='train with two torch.optim.AdamW and clip_grad_norm_ over the separate tensors instead of the flat fused tail '
+                        '(devit_amd.optim.FlatAdamW); no EMA is kept on this path')
+    p.add_argument('--model-ema-force-cpu', action='store_true', default=False,
+                   help='parsed for flag compatibility, without effect: the EMA of both models is kept by the fused optimizer kernel on the GPU')
     return p
+
+
+class EnsStepRunner:
+    """The `scaler` of engine.train_1epoch_ens_disjoint on the flat path (distill_sub.StepRunner for two models): backward, join the
+    gradient exchange of both flat buffers (they hold sums; grad_scale = 1 / world goes into the optimizer kernel), then one fused
+    clip + AdamW + EMA step per clip group -- all backbones under ONE norm, the fusion head under its own (engine.py:190-196)."""
+
+    def __init__(self, reducer, ens_reducer):
+        self.reducer, self.ens_reducer = reducer, ens_reducer
+
+    def __call__(self, loss, optimizer, ens_optimizer, clip_grad=None):
+        loss.backward()
+        self.reducer.finish()
+        self.ens_reducer.finish()
+        for opt in (optimizer, ens_optimizer):
+            opt.max_norm = clip_grad
+            opt.step()
+
+    def state_dict(self):
+        return {}
 
 
 def get_models(args, num_subs, sub_classes, num_classes):
@@ -112,8 +142,24 @@ def main(args):
     ddp.broadcast_module(ens_model)
     args.lr = args.lr * args.batch_size * utils.get_world_size() / 512.0                      # ensemble.py:339-340
     betas = tuple(args.opt_betas or (0.9, 0.999))
-    optimizer = torch.optim.AdamW(param_groups(model, args.weight_decay), lr=args.lr, eps=args.opt_eps, betas=betas)
-    ens_optimizer = torch.optim.AdamW(param_groups(ens_model, args.weight_decay), lr=args.lr, eps=args.opt_eps, betas=betas)
+    runner = None
+    if args.torch_optim:
+        optimizer = torch.optim.AdamW(param_groups(model, args.weight_decay), lr=args.lr, eps=args.opt_eps, betas=betas)
+        ens_optimizer = torch.optim.AdamW(param_groups(ens_model, args.weight_decay), lr=args.lr, eps=args.opt_eps, betas=betas)
+    else:
+        # one flat buffer for ALL backbones (one norm, one optimizer launch, one bf16 copy the GEMMs read) and one for the fusion head, whose
+        # fp32 GEMM reads the masters.  broadcast_module above already made the replicas equal.
+        flat, ens_flat = ddp.FlatParams(model).attach_bf16(model), ddp.FlatParams(ens_model)
+        runner = EnsStepRunner(ddp.BucketedGradReducer(flat).attach(model), ddp.BucketedGradReducer(ens_flat))
+        ema = args.model_ema_decay if args.model_ema else None
+        optimizer = optim.FlatAdamW(flat, lr=args.lr, eps=args.opt_eps, betas=betas, weight_decay=args.weight_decay, max_norm=args.clip_grad,
+                                    ema_decay=ema, no_decay=optim.no_decay_names(model))
+        ens_optimizer = optim.FlatAdamW(ens_flat, lr=args.lr, eps=args.opt_eps, betas=betas, weight_decay=args.weight_decay,
+                                        max_norm=args.clip_grad, ema_decay=ema, no_decay=optim.no_decay_names(ens_model))
+        if args.gates and args.physical_shrink:     # train at the shrunk models' FLOPs (the reference trains the masked models at the dense cost)
+            from devit_amd import shrink
+            rep = shrink.compact(model, trainable=True)
+            print(f"shrink: compacted {len(rep)} blocks for training, (heads run, neurons run) per block", sorted(set((r[1], r[3]) for r in rep)))
     lr_scheduler, ens_lr_scheduler = ds.CosineEpochs(optimizer, args), ds.CosineEpochs(ens_optimizer, args)   # :345-346
     if mixup_fn is not None:                 # ensemble.py:350-357: smoothing is handled by the mixup label transform
         base = losses.SoftTargetCrossEntropy()
@@ -128,14 +174,18 @@ def main(args):
         if args.distributed:
             ds.set_epoch(train_loader, epoch)
         train_stats = engine.train_1epoch_ens_disjoint(model, ens_model, criterion, train_loader, optimizer, ens_optimizer,
-                                                       device, epoch, None, args, None, mixup_fn=mixup_fn,
+                                                       device, epoch, runner, args, None, mixup_fn=mixup_fn,
                                                        max_norm=args.clip_grad)
         lr_scheduler.step(epoch)                                                                # ensemble.py:384-385
         ens_lr_scheduler.step(epoch)
         utils.save_on_master({'model': model.state_dict(), 'ens_model': ens_model.state_dict(),
                               'optimizer': optimizer.state_dict(), 'ens_optimizer': ens_optimizer.state_dict(),
                               'lr_scheduler': lr_scheduler.state_dict(), 'ens_lr_scheduler': ens_lr_scheduler.state_dict(),
-                              'epoch': epoch, 'scaler': {}, 'args': args}, output_dir / 'checkpoint_temp.pth')
+                              'epoch': epoch, 'scaler': {}, 'args': args,
+                              # the EMA of both models, keyed like their parameters (the reference computes it and never stores it)
+                              **({} if runner is None else {'model_ema': optimizer.ema_state_dict(model),
+                                                            'ens_model_ema': ens_optimizer.ema_state_dict(ens_model)})},
+                             output_dir / 'checkpoint_temp.pth')
         test_stats = engine.evaluate_ens_disjoint(val_loader, model, ens_model, device)
         print(f"Epoch: {epoch}/{args.epochs} [Train] Loss: {train_stats.get('loss', float('nan')):.4f} "
               f"[Eval] Top-1: {test_stats['acc1']:.4f} Top-5: {test_stats['acc5']:.4f}")

@@ -548,6 +548,15 @@ DEVIT_API int devit_cls_distill_loss(const float* logits, const float* logits_kd
  * loss[0] (+)= mean((a - b)^2); da (optional) = 2 (a - b) / n. */
 DEVIT_API int devit_token_mse(const float* a, const float* b, size_t n, float* loss, float* da, int accumulate, void* stream);
 
+/* EnsLoss loss_type='kldiv' (utils/losses.py:192-193,228,241-242):
+ * nn.KLDivLoss(reduction="batchmean", log_target=True)(input = student tokens s, target = teacher tokens t),
+ * both taken as log-probabilities as they stand (nothing is normalised or clamped):
+ *   loss[0] (+)= sum_i exp(t_i) * (t_i - s_i) / batch;    ds (optional) = -exp(t_i) / batch
+ * n = batch * token width.  DEVIT_ERR_ARG for a null s / t / loss or n == 0, DEVIT_ERR_SHAPE for batch <= 0 or
+ * n % batch != 0; nothing is launched then.  Deterministic (fixed summation order), no allocation, no sync. */
+DEVIT_API int devit_token_kldiv(const float* s, const float* t, size_t n, int batch, float* loss, float* ds,
+                                int accumulate, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * q/k/v feature-relation loss (utils/losses.py:307-328).  The per-image Grams F F^T run on
  * devit_gemm_bf16 (batched, padded to 256x256, DEVIT_EPI_STORE_F32); these two kernels do the rest:
