@@ -5,15 +5,23 @@ search and the shrink.py -> distill_sub.py chain.
 Bar for rel, red and the final scores: |score - ref| <= 2e-5 * max|ref| on identical inputs rounded to the type fed to the
 kernel (the project's fp32-kernel bar; the fp32 torch statement sits at 1e-7 .. 2.6e-7 of it on the
 CPU); act is a plain sum and is held to 1e-6 relative.  Every measured deviation goes through conftest.chk under a name that starts
-with "hsic", so it lands in the session's parity margins; profiles/hsic_parity.json is the committed copy of those rows."""
+with "hsic", so it lands in the session's parity margins; profiles/hsic_parity.json is the committed copy of those rows.
+
+Those bars are normed by the largest score of a call and see the composed result only.  The second half of this file (from "per-element bounds"
+on) holds every stage on its own -- the packed workspace, every element of Kmix - 1 and of W, rel, act and red -- below the bounds tests/_hsic_model.py
+counts from the kernel source, at the seams of the kernels' tiles, through the C ABI with poisoned memory and guarded outputs; its rows are named
+"hsic/<kernel>/<case>/<output>" and profiles/hsic_bounds_margins.json is their committed copy."""
 import argparse
 import json
+import math
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import _hsic_model as HM
+from _hsic_model import F32, ratio
 from conftest import GOLDEN, chk
 
 pytestmark = pytest.mark.gpu
@@ -300,3 +308,209 @@ def test_shrink_to_distill_sub_chain(tmp_path):
     distill_sub.main(d)
     line = json.loads(open(os.path.join(d.output_dir, "sub-dataset0", "log.txt")).read().splitlines()[-1])
     assert line["train_loss"] == line["train_loss"] and "test_acc1" in line
+
+
+# ============================================================================================ per-element bounds (tests/_hsic_model.py)
+# Every stage of csrc/hsic.hip against the float64 statement applied to the fp32 values the stage in front of it left on the device, element by
+# element, under bounds counted from the kernel source; launched through the C ABI with a workspace of exactly the queried size, NaN in the workspace,
+# in every output and in whatever of X the operand description does not name, and sentinel elements in front of and behind every written buffer.
+SENT, GUARD = -123.0, 64          # 64 fp32 guard elements are 256 bytes: the live part of a guarded buffer keeps the allocation's alignment
+
+
+@pytest.fixture(scope="module")
+def dev():
+    d = _need_gpu()
+    from devit_amd import _lib
+    _lib.require_device(torch.zeros(1, device=d))
+    return d
+
+
+def _abi(name, *args):
+    from devit_amd import _lib
+    return _lib.call(name, *[_lib.ptr(a) if isinstance(a, torch.Tensor) else a for a in args], _lib.stream_ptr())
+
+
+class Guarded:
+    """n fp32 elements, NaN, between two runs of GUARD sentinels that must come back bit for bit"""
+
+    def __init__(self, dev, *shape):
+        self.n = int(np.prod(shape))
+        self.flat = torch.full((GUARD + self.n + GUARD,), SENT, dtype=F32, device=dev)
+        self.v = self.flat[GUARD:GUARD + self.n].view(*shape)
+        self.v.fill_(math.nan)
+
+    def intact(self):
+        want = torch.full((GUARD,), SENT, dtype=F32, device=self.flat.device).view(torch.int32)
+        ok = torch.equal(self.flat[:GUARD].view(torch.int32), want) and torch.equal(self.flat[GUARD + self.n:].view(torch.int32), want)
+        assert ok, "a write outside an output's extent (guard elements changed)"
+        return True
+
+    def untouched(self):
+        return self.intact() and bool(torch.isnan(self.v).all())
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def _same_bits(a, b):
+    return torch.equal(_bits(a), _bits(b))
+
+
+def _hold(tag, got, ref, bnd):
+    r = ratio(got, ref, bnd)
+    print(f"hsic/{tag} {r:.3f}")
+    assert chk(r, 1.0, name=f"hsic/{tag}"), f"hsic/{tag}: worst |err| / bound {r:.3f}"
+
+
+def _place(X, c, dev, layout=None):
+    """X in a NaN-filled buffer at the case's strides and base offset -> (the view, batch stride, token stride)"""
+    off, sb, sn, total = HM.strides_of(dict(c, layout=layout or c["layout"]))
+    buf = torch.full((total,), math.nan, dtype=X.dtype, device=dev)
+    view = buf.as_strided(tuple(X.shape), (sb, sn, 1), off)
+    view.copy_(X.to(dev))
+    return view, sb, sn
+
+
+def _elem(dtype):
+    from devit_amd import _lib
+    return {torch.bfloat16: _lib.HSIC_BF16, torch.float16: _lib.HSIC_F16, torch.float32: _lib.HSIC_F32}[dtype]
+
+
+def _scores(dev, c, X, W, layout=None, want_act=True, want_kmix=True):
+    """one launch of devit_hsic_scores -> dict of Guarded rel, act, kmix1, ws (all intact), with ws exactly the queried bytes"""
+    B, N, units, group = c["B"], c["N"], c["units"], c["group"]
+    view, sb, sn = _place(X, c, dev, layout)
+    need = HM.workspace_bytes(B, N, units)
+    o = dict(rel=Guarded(dev, units), act=Guarded(dev, units) if (want_act and group == 1) else None,
+             kmix1=Guarded(dev, units, B, B) if want_kmix else None, ws=Guarded(dev, units, N, HM.padded(B)))
+    _abi("devit_hsic_scores", view, _elem(X.dtype), B, N, units, group, sb, sn, W, o["rel"].v, o["act"].v if o["act"] else None,
+         o["kmix1"].v if o["kmix1"] else None, o["ws"].v, need)
+    torch.cuda.synchronize()
+    assert all(b.intact() for b in o.values() if b is not None)
+    return o
+
+
+_SCORE_RUNS = {}
+
+
+def _score_run(dev, name):
+    """the full launch of a score case, made once (test_head_pairs_bounds feeds on the kmix1 of the group cases)"""
+    if name not in _SCORE_RUNS:
+        c = HM.case_by_name(name)
+        i = HM.score_inputs(c)
+        _SCORE_RUNS[name] = (c, i, i["W"].to(dev), _scores(dev, c, i["X"], i["W"].to(dev)))
+    return _SCORE_RUNS[name]
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in HM.score_cases()])
+def test_scores_hold_per_element_bounds(dev, name):
+    c, i, W, o = _score_run(dev, name)
+    B, group, units = c["B"], c["group"], c["units"]
+    X = i["X"]
+    ws, k = o["ws"].v, o["kmix1"].v
+    # pack: the workspace is features(X), unit-major, zero in samples B .. Bp
+    ref, bnd = HM.pack_bounds(X.to(dev), group)
+    if group == 1:
+        assert torch.equal(ws[:, :, :B], X.to(dev).float().permute(2, 1, 0)), "pack (group == 1) is a conversion and a copy"
+    else:
+        _hold(f"pack/{name}/ws", ws[:, :, :B], ref, bnd)
+    assert bool((ws[:, :, B:] == 0).all()), "samples B .. Bp of the workspace are zero"
+    # pair: kmix1 per element from the workspace as it stands; rel and act from the device's own kmix1 / workspace
+    kref, kbnd = HM.kmix1_bounds(ws[:, :, :B])
+    _hold(f"pair/{name}/kmix1", k, kref, kbnd)
+    assert torch.equal(k, k.transpose(1, 2)) and bool((torch.diagonal(k, dim1=1, dim2=2) == 0).all())
+    _hold(f"pair/{name}/rel", o["rel"].v, *HM.rel_bounds(k, W))
+    if group == 1:
+        _hold(f"pair/{name}/act", o["act"].v, *HM.act_bounds(ws))
+    for u in range(4, units, 6):                                    # a masked unit: exactly zero everywhere
+        assert not bool(k[u].any()) and float(o["rel"].v[u]) == 0.0 and (group != 1 or float(o["act"].v[u]) == 0.0)
+    # what does not depend on numerics: optional outputs left out, a second launch, the contiguous form
+    o2 = _scores(dev, c, X, W, want_kmix=False)
+    assert _same_bits(o2["rel"].v, o["rel"].v) and (group != 1 or _same_bits(o2["act"].v, o["act"].v)), "kmix1 == NULL changes rel or act"
+    o3 = _scores(dev, c, X, W, want_act=False)
+    assert _same_bits(o3["rel"].v, o["rel"].v) and _same_bits(o3["kmix1"].v, k), "act == NULL changes rel or kmix1"
+    o4 = _scores(dev, c, X, W, layout="contig")                     # for a contiguous case: the second identical launch
+    for key in ("rel", "act", "kmix1", "ws"):
+        assert o[key] is None or _same_bits(o4[key].v, o[key].v), f"{key}: the contiguous form / a second launch gives other bits"
+
+
+def _head_pairs(dev, k):
+    H, B = k.shape[0], k.shape[1]
+    red = Guarded(dev, H)
+    _abi("devit_hsic_head_pairs", k, H, B, red.v)
+    torch.cuda.synchronize()
+    assert red.intact()
+    return red
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in HM.head_cases()] + ["synthetic"])
+def test_head_pairs_bounds(dev, name):
+    if name == "synthetic":
+        k = HM.synthetic_kmix1().to(dev)
+    else:
+        k = _score_run(dev, name)[3]["kmix1"].v
+    before = k.clone()
+    red = _head_pairs(dev, k)
+    _hold(f"head_pairs/{name}/red", red.v, *HM.red_bounds(k))
+    assert _same_bits(_head_pairs(dev, k).v, red.v) and torch.equal(k, before)
+
+
+def _target(dev, c, y):
+    B, C = c["B"], c["C"]
+    ybuf = torch.full((GUARD + B * C + GUARD,), math.nan, dtype=F32, device=dev)          # NaN around the operand
+    yv = ybuf[GUARD:GUARD + B * C].view(B, C)
+    yv.copy_(y.to(dev))
+    W, ws = Guarded(dev, B, B), Guarded(dev, B, C)
+    _abi("devit_hsic_target", yv, B, C, c["softmax"], W.v, ws.v, B * C * 4)
+    torch.cuda.synchronize()
+    assert W.intact() and ws.intact()
+    return W
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in HM.target_cases()])
+def test_target_holds_per_element_bounds(dev, name):
+    c = HM.case_by_name(name)
+    y = HM.target_inputs(c)
+    W = _target(dev, c, y)
+    _hold(f"target/{name}/W", W.v, *HM.target_bounds(y.to(dev), c["softmax"]))
+    assert torch.equal(W.v, W.v.t()), "both triangles of W are the same products in the same order"
+    assert _same_bits(_target(dev, c, y).v, W.v)
+    if c["C"] == 1 and c["softmax"]:
+        assert not bool(W.v.any())                                   # one class: p = 1, z = 0, W = 0 exactly
+
+
+def test_refused_calls_write_nothing(dev):
+    """the return codes are the CPU ABI test's; here: every output of a refused call still holds its NaN fill, the guards their sentinels"""
+    from devit_amd._lib import DevitError
+    c = HM.case_by_name("B65_N3_u6_g1_bf16_token_pad")
+    i = HM.score_inputs(c)
+    B, N, units = c["B"], c["N"], c["units"]
+    view, sb, sn = _place(i["X"], c, dev)
+    W = i["W"].to(dev)
+    need = HM.workspace_bytes(B, N, units)
+    el = _elem(i["X"].dtype)
+    rel, act, k, ws = Guarded(dev, units), Guarded(dev, units), Guarded(dev, units, B, B), Guarded(dev, units, N, HM.padded(B))
+    bad = [(view, el, B, N, units, 1, sb, sn, W, rel.v, act.v, k.v, ws.v, need - 4),                  # workspace four bytes short
+           (view, el, B, N, units, 1, sb, sn, W, rel.v, act.v, k.v, ws.flat[GUARD + 1:], need),       # workspace not 16-byte aligned
+           (view, el, B, N, units, 1, sb, units - 1, W, rel.v, act.v, k.v, ws.v, need),               # token rows overlap
+           (view, el, B, N, units, 1, (N - 1) * sn + units - 1, sn, W, rel.v, act.v, k.v, ws.v, need),          # samples overlap
+           (view, el, B, N, units // 2, 2, sb, sn, W, rel.v, act.v, k.v, ws.v, need),                 # act with group > 1
+           (view, 3, B, N, units, 1, sb, sn, W, rel.v, act.v, k.v, ws.v, need),                       # element type
+           (view, el, 257, N, units, 1, sb, sn, W, rel.v, act.v, k.v, ws.v, need),                    # batch
+           (view, el, B, 0, units, 1, sb, sn, W, rel.v, act.v, k.v, ws.v, need)]                      # no token
+    for args in bad:
+        with pytest.raises(DevitError):
+            _abi("devit_hsic_scores", *args)
+    tc = HM.case_by_name("B65_C257_softmax")
+    y = HM.target_inputs(tc).to(dev)
+    Wo, tws, red = Guarded(dev, 65, 65), Guarded(dev, 65, 257), Guarded(dev, 17)
+    for args in [(y, 65, 257, 1, Wo.v, tws.v, 65 * 257 * 4 - 4), (y, 1, 257, 1, Wo.v, tws.v, 65 * 257 * 4), (y, 65, 0, 1, Wo.v, tws.v, 65 * 257 * 4)]:
+        with pytest.raises(DevitError):
+            _abi("devit_hsic_target", *args)
+    kk = HM.synthetic_kmix1().to(dev)
+    for args in [(kk, 17, 65, red.v), (kk, 1, 65, red.v), (kk, 3, 257, red.v), (kk, 3, 1, red.v)]:
+        with pytest.raises(DevitError):
+            _abi("devit_hsic_head_pairs", *args)
+    torch.cuda.synchronize()
+    assert all(b.untouched() for b in (rel, act, k, ws, Wo, tws, red))
