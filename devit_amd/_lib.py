@@ -76,6 +76,12 @@ class MixSample(C.Structure):
                 ("reserved", C.c_int * 2)]
 
 
+class OptChunk(C.Structure):
+    _fields_ = [("first4", C.c_uint), ("count4", C.c_uint), ("segment", C.c_int), ("flags", C.c_int)]
+
+
+OPT_CHUNK_GRANULES, OPT_CHUNK_NO_DECAY = 1024, 1
+
 # devit_launch_info.has
 HAS_Y_BF16, HAS_Y_F32, HAS_DY_F32, HAS_DRES, HAS_DX, HAS_DX_BF16, HAS_DQKV_ADD = 1, 2, 4, 8, 16, 32, 64
 
@@ -102,7 +108,7 @@ WGRAD_MAX_JOBS = 48
 ABI_VERSION = 3
 # devit_abi_struct_size(which) -> the mirror it must equal (checked at load time: an array of stale mirrors is misread silently)
 ABI_STRUCTS = {0: Epilogue, 1: Operand, 2: BlockWeights, 3: BlockWgrads, 4: BlockActs, 5: BlockBwdIO, 6: IndexJob, 7: WgradJob, 8: LaunchInfo, 9: BlockDropout,
-               10: MixSample}
+               10: MixSample, 11: OptChunk}
 
 
 class DevitError(RuntimeError):
@@ -169,6 +175,10 @@ SIGNATURES = {
     "devit_sumsq_workspace": (_Z, []),
     "devit_sumsq_f32": (_I, [_P, _Z, _P, _P, _Z, _P]),
     "devit_adamw_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _F, _F, _P]),
+    "devit_sgd_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _Z, _F, _I, _F, _F, _F, _F, _P]),
+    "devit_adam_l2_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _F, _F, _P]),
+    "devit_lamb_workspace": (_Z, [_I, _I]),
+    "devit_lamb_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P, _Z, _P]),
     "devit_cls_distill_loss": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
     "devit_token_mse": (_I, [_P, _P, _Z, _P, _P, _I, _P]),
     "devit_token_kldiv": (_I, [_P, _P, _Z, _I, _P, _P, _I, _P]),

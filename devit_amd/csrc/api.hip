@@ -37,6 +37,7 @@ extern "C" size_t devit_abi_struct_size(int which) {
     case 8: return sizeof(devit_launch_info);
     case 9: return sizeof(devit_block_dropout);
     case 10: return sizeof(devit_mix_sample);
+    case 11: return sizeof(devit_opt_chunk);
     default: return 0;
   }
 }

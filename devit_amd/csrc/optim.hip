@@ -1,0 +1,281 @@
+// Optimizer tails over the flat parameter buffer besides AdamW (elementwise.hip: adamw_kernel): SGD with momentum (plain and
+// Nesterov), Adam with L2 decay coupled into the gradient, and LAMB with per-tensor trust ratios -- timm 0.5.4's `momentum`,
+// `nesterov`, `adam`, `lamb` / `lambc` (create_optimizer, distill_sub.py:340).  Every tail shares AdamW's frame: the global-norm
+// clip folded into the gradient load, the per-granule weight decay exemption, the EMA and the bf16 re-cast of the new weights.
+// All of them are HBM-bound streams: one thread owns a 16-byte granule of every buffer, loads and stores are 16 bytes wide.
+#include "devit_common.h"
+
+namespace {
+
+struct OptArgs {
+  float* p; const float* g; float* m; float* v; float* ema; __bf16* p_bf16;   // m: the momentum buffer of SGD; v unused there
+  const float* gnorm_sq;            // device scalar: sum of squared grads (NULL = no clipping; LAMB always needs it)
+  const float* dyn;                 // device: lr (SGD) or lr, 1 - beta1^step, 1 - beta2^step
+  const unsigned char* no_decay4;   // one byte per granule: != 0 -> no weight decay there (NULL: decay all)
+  size_t n;
+  float beta1, beta2, eps, wd, max_norm, ema_decay, grad_scale;   // beta1: the momentum of SGD
+  int nesterov;
+};
+
+// grad_scale * min(1, max_norm / (||g|| * grad_scale + 1e-6)): adamw_kernel's statement, operation for operation
+__device__ __forceinline__ float tail_clip(const float* gnorm_sq, float max_norm, float grad_scale) {
+  float clip = grad_scale;
+  if (gnorm_sq) {
+    const float nrm = sqrtf(*gnorm_sq) * grad_scale;
+    const float c = max_norm / (nrm + 1e-6f);   // torch.nn.utils.clip_grad_norm_
+    clip *= c < 1.0f ? c : 1.0f;
+  }
+  return clip;
+}
+
+// ema = ema*d + (1-d)*p and p_bf16 = bf16(p) for one granule (both optional)
+__device__ __forceinline__ void model_tail(float* ema, __bf16* p_bf16, size_t i, f32x4 p, float ema_decay) {
+  if (ema) {
+    f32x4 e = *(const f32x4*)(ema + i * 4);
+    e = e * ema_decay + (1.0f - ema_decay) * p;
+    *(f32x4*)(ema + i * 4) = e;
+  }
+  if (p_bf16) {
+    bf16x4 ob = {f2bf(p[0]), f2bf(p[1]), f2bf(p[2]), f2bf(p[3])};
+    *(bf16x4*)(p_bf16 + i * 4) = ob;
+  }
+}
+
+// ---- torch.optim.SGD(momentum = mu, nesterov, dampening = 0): d = g' + wd p;  buf' = mu buf + d;  p' = p - lr (nesterov ? d + mu buf' : buf')
+// buf starts at zero, which is torch's first step (buf = d).
+__global__ __launch_bounds__(256) void sgd_kernel(const OptArgs a) {
+  const float clip = tail_clip(a.gnorm_sq, a.max_norm, a.grad_scale);
+  const float lr = a.dyn[0], mu = a.beta1;
+  const size_t n4 = a.n / 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    f32x4 p = *(const f32x4*)(a.p + i * 4);
+    const f32x4 g = *(const f32x4*)(a.g + i * 4) * clip;
+    f32x4 buf = *(const f32x4*)(a.m + i * 4);
+    const float wd = (a.no_decay4 && a.no_decay4[i]) ? 0.0f : a.wd;
+    const f32x4 d = g + wd * p;
+    buf = mu * buf + d;
+    p -= lr * (a.nesterov ? d + mu * buf : buf);
+    *(f32x4*)(a.p + i * 4) = p;
+    *(f32x4*)(a.m + i * 4) = buf;
+    model_tail(a.ema, a.p_bf16, i, p, a.ema_decay);
+  }
+}
+
+// ---- torch.optim.Adam: the decay enters the gradient (d = g' + wd p) and with it both moments; the update is adamw_kernel's form
+__global__ __launch_bounds__(256) void adam_l2_kernel(const OptArgs a) {
+  const float clip = tail_clip(a.gnorm_sq, a.max_norm, a.grad_scale);
+  const float lr = a.dyn[0], bc1 = a.dyn[1], bc2 = a.dyn[2];
+  const size_t n4 = a.n / 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    f32x4 p = *(const f32x4*)(a.p + i * 4);
+    const f32x4 g = *(const f32x4*)(a.g + i * 4) * clip;
+    f32x4 m = *(const f32x4*)(a.m + i * 4), v = *(const f32x4*)(a.v + i * 4);
+    const float wd = (a.no_decay4 && a.no_decay4[i]) ? 0.0f : a.wd;
+    const f32x4 d = g + wd * p;
+    m = a.beta1 * m + (1.0f - a.beta1) * d;
+    v = a.beta2 * v + (1.0f - a.beta2) * d * d;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) p[e] -= (lr / bc1) * m[e] / (sqrtf(v[e]) / sqrtf(bc2) + a.eps);
+    *(f32x4*)(a.p + i * 4) = p;
+    *(f32x4*)(a.m + i * 4) = m;
+    *(f32x4*)(a.v + i * 4) = v;
+    model_tail(a.ema, a.p_bf16, i, p, a.ema_decay);
+  }
+}
+
+// ---- LAMB (timm Lamb: bias_correction, grad_averaging, max_grad_norm = 1, always_adapt = False) ---------------------------------
+// The trust ratio ||p|| / ||u|| is per PARAMETER TENSOR, so the flat buffer is cut into chunks (devit_opt_chunk: at most
+// LAMB_CHUNK4 granules of ONE tensor), one workgroup each:
+//   lamb_moments_kernel  m', v' stored; u formed; per chunk of a decayed tensor (sum p^2, sum u^2) -> partials[chunk]
+//   lamb_trust_kernel    one wave per tensor adds its chunks' partials in a fixed order -> trust[tensor]
+//   lamb_apply_kernel    u recomputed from p, m', v' (lamb_update, the function phase 1 used), p' = p - lr trust u, EMA, bf16 copy
+// No float atomics: every sum has one order, two runs give the same bits.  Tensors of the no-decay group take trust = 1
+// without a norm (always_adapt is off).
+constexpr unsigned LAMB_CHUNK4 = 1024;
+constexpr int CHUNK_NO_DECAY = 1;
+
+// u = (m' / bc1) / (sqrt(v') / sqrt(bc2) + eps) + wd p, every operation rounded on its own so that phases 1 and 3 agree to the bit
+__device__ __forceinline__ f32x4 lamb_update(f32x4 p, f32x4 m, f32x4 v, float bc1, float sqrt_bc2, float eps, float wd) {
+#pragma clang fp contract(off)
+  f32x4 u;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float r = (m[e] / bc1) / (sqrtf(v[e]) / sqrt_bc2 + eps);
+    u[e] = r + wd * p[e];
+  }
+  return u;
+}
+
+struct LambArgs {
+  OptArgs o;
+  const devit_opt_chunk* chunks;
+  float* partials;   // [nchunks][2]: sum p^2, sum u^2 (chunks of decayed tensors only)
+  float* trust;      // [nsegments]
+  int nchunks, nsegments, trust_clip;
+};
+
+// a chunk the kernels may address: inside the buffer, at most LAMB_CHUNK4 granules, a segment the trust array has.  The host
+// validates the whole table before it uploads it (optim.validate_chunk_table); this keeps even a corrupted one inside the buffers.
+__device__ __forceinline__ bool chunk_ok(const devit_opt_chunk c, size_t n4, int nsegments) {
+  return c.count4 <= LAMB_CHUNK4 && (size_t)c.first4 + c.count4 <= n4 && c.segment >= 0 && c.segment < nsegments;
+}
+
+__global__ __launch_bounds__(256) void lamb_moments_kernel(const LambArgs a) {
+  __shared__ float red[2][4];
+  const devit_opt_chunk c = a.chunks[blockIdx.x];
+  if (!chunk_ok(c, a.o.n / 4, a.nsegments)) return;
+  float clip = tail_clip(a.o.max_norm > 0.0f ? a.o.gnorm_sq : nullptr, a.o.max_norm, a.o.grad_scale);
+  const float n1 = sqrtf(*a.o.gnorm_sq) * clip;        // the norm of the gradients the optimizer sees
+  if (n1 > 1.0f) clip = clip / n1;                     // timm Lamb's own max_grad_norm = 1.0, on top of --clip-grad
+  const float bc1 = a.o.dyn[1], sqrt_bc2 = sqrtf(a.o.dyn[2]);
+  const bool decayed = !(c.flags & CHUNK_NO_DECAY);
+  const float wd = decayed ? a.o.wd : 0.0f;
+  float sp = 0.f, su = 0.f;
+  for (unsigned t = threadIdx.x; t < c.count4; t += 256) {
+    const size_t i = (size_t)c.first4 + t;
+    const f32x4 p = *(const f32x4*)(a.o.p + i * 4);
+    const f32x4 g = *(const f32x4*)(a.o.g + i * 4) * clip;
+    f32x4 m = *(const f32x4*)(a.o.m + i * 4), v = *(const f32x4*)(a.o.v + i * 4);
+    m = a.o.beta1 * m + (1.0f - a.o.beta1) * g;
+    v = a.o.beta2 * v + (1.0f - a.o.beta2) * g * g;
+    *(f32x4*)(a.o.m + i * 4) = m;
+    *(f32x4*)(a.o.v + i * 4) = v;
+    if (decayed) {
+      const f32x4 u = lamb_update(p, m, v, bc1, sqrt_bc2, a.o.eps, wd);
+      sp += p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + p[3] * p[3];
+      su += u[0] * u[0] + u[1] * u[1] + u[2] * u[2] + u[3] * u[3];
+    }
+  }
+  if (!decayed) return;                                // block-uniform
+  sp = wave_sum(sp);
+  su = wave_sum(su);
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sp; red[1][threadIdx.x >> 6] = su; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const f32x2 out = {red[0][0] + red[0][1] + red[0][2] + red[0][3], red[1][0] + red[1][1] + red[1][2] + red[1][3]};
+    *(f32x2*)(a.partials + (size_t)blockIdx.x * 2) = out;
+  }
+}
+
+// one wave per tensor.  The table is sorted by segment (validated on the host): the tensor's chunks are one run, found by a
+// lower-bound search; lane l adds chunks l, l + 64, ... of the run, then the wave sums.
+__global__ __launch_bounds__(64) void lamb_trust_kernel(const LambArgs a) {
+  const int seg = blockIdx.x;
+  int lo = 0, hi = a.nchunks;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (a.chunks[mid].segment < seg) lo = mid + 1; else hi = mid;
+  }
+  float sp = 0.f, su = 0.f;
+  bool decayed = false;
+  if (lo < a.nchunks && a.chunks[lo].segment == seg && !(a.chunks[lo].flags & CHUNK_NO_DECAY)) {
+    decayed = true;
+    for (int ch = lo + (int)threadIdx.x; ch < a.nchunks && a.chunks[ch].segment == seg; ch += 64) {
+      const f32x2 v = *(const f32x2*)(a.partials + (size_t)ch * 2);
+      sp += v[0];
+      su += v[1];
+    }
+  }
+  sp = wave_sum(sp);
+  su = wave_sum(su);
+  if (threadIdx.x == 0) {
+    float t = 1.0f;
+    if (decayed) {
+      const float wn = sqrtf(sp), un = sqrtf(su);
+      if (wn > 0.0f && un > 0.0f) t = wn / un;
+      if (a.trust_clip && t > 1.0f) t = 1.0f;
+    }
+    a.trust[seg] = t;
+  }
+}
+
+__global__ __launch_bounds__(256) void lamb_apply_kernel(const LambArgs a) {
+  const devit_opt_chunk c = a.chunks[blockIdx.x];
+  if (!chunk_ok(c, a.o.n / 4, a.nsegments)) return;
+  const float lr = a.o.dyn[0], bc1 = a.o.dyn[1], sqrt_bc2 = sqrtf(a.o.dyn[2]);
+  const float wd = (c.flags & CHUNK_NO_DECAY) ? 0.0f : a.o.wd;
+  const float step = lr * a.trust[c.segment];
+  for (unsigned t = threadIdx.x; t < c.count4; t += 256) {
+    const size_t i = (size_t)c.first4 + t;
+    f32x4 p = *(const f32x4*)(a.o.p + i * 4);
+    const f32x4 m = *(const f32x4*)(a.o.m + i * 4), v = *(const f32x4*)(a.o.v + i * 4);
+    p -= step * lamb_update(p, m, v, bc1, sqrt_bc2, a.o.eps, wd);
+    *(f32x4*)(a.o.p + i * 4) = p;
+    model_tail(a.o.ema, a.o.p_bf16, i, p, a.o.ema_decay);
+  }
+}
+
+inline int grid_for(size_t work_items, int cap) {
+  size_t g = (work_items + 255) / 256;
+  return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
+}
+
+}  // namespace
+
+extern "C" int devit_sgd_step(float* p, const float* g, float* buf, float* ema, void* p_bf16, const unsigned char* no_decay4,
+                              const float* gnorm_sq, const float* dyn, size_t n, float momentum, int nesterov,
+                              float weight_decay, float max_norm, float ema_decay, float grad_scale, void* stream) {
+  DEVIT_CHECK(p && g && buf && dyn, DEVIT_ERR_ARG, "devit_sgd_step: bad argument");
+  DEVIT_CHECK(n % 4 == 0, DEVIT_ERR_SHAPE, "devit_sgd_step: n must be a multiple of 4 (pad the flat buffer)");
+  OptArgs a = {};
+  a.p = p; a.g = g; a.m = buf; a.ema = ema; a.p_bf16 = (__bf16*)p_bf16; a.gnorm_sq = gnorm_sq; a.dyn = dyn;
+  a.no_decay4 = no_decay4; a.n = n; a.beta1 = momentum; a.nesterov = nesterov != 0; a.wd = weight_decay;
+  a.max_norm = max_norm; a.ema_decay = ema_decay; a.grad_scale = grad_scale;
+  hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  DEVIT_LAUNCH_CHECK();
+  return DEVIT_OK;
+}
+
+static void fill_adam_args(OptArgs& a, float* p, const float* g, float* m, float* v, float* ema, void* p_bf16,
+                           const unsigned char* no_decay4, const float* gnorm_sq, const float* dyn, size_t n, float beta1,
+                           float beta2, float eps, float weight_decay, float max_norm, float ema_decay, float grad_scale) {
+  a.p = p; a.g = g; a.m = m; a.v = v; a.ema = ema; a.p_bf16 = (__bf16*)p_bf16; a.gnorm_sq = gnorm_sq; a.dyn = dyn;
+  a.no_decay4 = no_decay4; a.n = n; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
+  a.max_norm = max_norm; a.ema_decay = ema_decay; a.grad_scale = grad_scale; a.nesterov = 0;
+}
+
+extern "C" int devit_adam_l2_step(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16,
+                                  const unsigned char* no_decay4, const float* gnorm_sq, const float* dyn, size_t n,
+                                  float beta1, float beta2, float eps, float weight_decay, float max_norm, float ema_decay,
+                                  float grad_scale, void* stream) {
+  DEVIT_CHECK(p && g && m && v && dyn, DEVIT_ERR_ARG, "devit_adam_l2_step: bad argument");
+  DEVIT_CHECK(n % 4 == 0, DEVIT_ERR_SHAPE, "devit_adam_l2_step: n must be a multiple of 4 (pad the flat buffer)");
+  OptArgs a;
+  fill_adam_args(a, p, g, m, v, ema, p_bf16, no_decay4, gnorm_sq, dyn, n, beta1, beta2, eps, weight_decay, max_norm, ema_decay,
+                 grad_scale);
+  hipLaunchKernelGGL(adam_l2_kernel, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  DEVIT_LAUNCH_CHECK();
+  return DEVIT_OK;
+}
+
+extern "C" size_t devit_lamb_workspace(int nchunks, int nsegments) {
+  if (nchunks < 0 || nsegments < 0) return 0;
+  return ((size_t)nchunks * 2 + (size_t)nsegments) * sizeof(float);
+}
+
+extern "C" int devit_lamb_step(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16, const float* gnorm_sq,
+                               const float* dyn, size_t n, const devit_opt_chunk* chunks, int nchunks, int nsegments,
+                               int trust_clip, float beta1, float beta2, float eps, float weight_decay, float max_norm,
+                               float ema_decay, float grad_scale, void* workspace, size_t workspace_bytes, void* stream) {
+  DEVIT_CHECK(p && g && m && v && dyn && gnorm_sq && chunks && workspace, DEVIT_ERR_ARG,
+              "devit_lamb_step: bad argument (gnorm_sq is required: LAMB clips the gradient to norm 1 itself)");
+  DEVIT_CHECK(n % 4 == 0, DEVIT_ERR_SHAPE, "devit_lamb_step: n must be a multiple of 4 (pad the flat buffer)");
+  DEVIT_CHECK(nchunks > 0 && nsegments > 0 && n / 4 <= 0xffffffffu, DEVIT_ERR_SHAPE,
+              "devit_lamb_step: nchunks = %d, nsegments = %d must be positive, n / 4 must fit 32 bits", nchunks, nsegments);
+  DEVIT_CHECK(workspace_bytes >= devit_lamb_workspace(nchunks, nsegments) && ((size_t)workspace & 7) == 0, DEVIT_ERR_ARG,
+              "devit_lamb_step: workspace of %zu bytes, devit_lamb_workspace(%d, %d) = %zu (8-byte aligned)", workspace_bytes,
+              nchunks, nsegments, devit_lamb_workspace(nchunks, nsegments));
+  LambArgs a;
+  fill_adam_args(a.o, p, g, m, v, ema, p_bf16, nullptr, gnorm_sq, dyn, n, beta1, beta2, eps, weight_decay, max_norm, ema_decay,
+                 grad_scale);
+  a.chunks = chunks; a.nchunks = nchunks; a.nsegments = nsegments; a.trust_clip = trust_clip != 0;
+  a.partials = (float*)workspace;
+  a.trust = a.partials + (size_t)nchunks * 2;
+  hipLaunchKernelGGL(lamb_moments_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, a);
+  DEVIT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lamb_trust_kernel, dim3(nsegments), dim3(64), 0, (hipStream_t)stream, a);
+  DEVIT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lamb_apply_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, a);
+  DEVIT_LAUNCH_CHECK();
+  return DEVIT_OK;
+}

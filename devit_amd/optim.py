@@ -1,10 +1,16 @@
 """Optimizer tail of the DEKD step on flat buffers: global-norm clip + AdamW + EMA + bf16 weight re-cast in two
 launches (devit_sumsq_f32, devit_adamw_step).  Replaces timm NativeScaler -> clip_grad_norm_ -> AdamW.step and
-ModelEma.update (engine.py:127,131-132; ~600 tiny kernels in the reference)."""
+ModelEma.update (engine.py:127,131-132; ~600 tiny kernels in the reference).
+
+timm's other optimizers that the reference's `--opt` reaches through create_optimizer share that frame: FlatSGD (`momentum`,
+`nesterov`), FlatAdam (`adam`: L2 decay coupled into the gradient) and FlatLamb (`lamb`, `lambc`: per-tensor trust ratios over a
+chunk table, three launches); create_flat_optimizer maps the command line to one of the four."""
 import torch
 
 from . import _lib as L
 from ._lib import call, ptr, stream_ptr
+
+OPT_NAMES = ("adamw", "adam", "momentum", "nesterov", "lamb", "lambc")
 
 
 def no_decay_names(model):
@@ -15,14 +21,14 @@ def no_decay_names(model):
             if p.requires_grad and (p.ndim <= 1 or n.endswith(".bias") or n in skip)}
 
 
-class FlatAdamW:
-    """AdamW over ddp.FlatParams.  `no_decay`: parameter names exempt from weight decay (see no_decay_names; every
-    tensor starts on a 4-element granule of the flat buffer, so the exemption is one byte per granule)."""
+class _FlatTail:
+    """What every optimizer over ddp.FlatParams shares: the buffers and the scalar ring (_setup), the surface the training loops use
+    (param_groups[0]["lr"], zero_grad, max_norm, ema_state_dict) and, for the classes below FlatAdamW, the step's frame and the state dict."""
+    opt_name = "adamw"
+    state_keys = ("m", "v")
 
-    def __init__(self, flat, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None, ema_decay=None,
-                 no_decay=None):
-        self.flat, self.betas, self.eps, self.weight_decay = flat, betas, eps, weight_decay
-        self.max_norm, self.ema_decay = max_norm, ema_decay
+    def _setup(self, flat, lr, weight_decay, max_norm, ema_decay, no_decay, dyn_len):
+        self.flat, self.weight_decay, self.max_norm, self.ema_decay = flat, weight_decay, max_norm, ema_decay
         dev = flat.flat.device
         self.no_decay4 = None
         if weight_decay and no_decay:
@@ -31,20 +37,79 @@ class FlatAdamW:
                 if name in no_decay:
                     mask[o // 4:(o + p.numel() + 3) // 4] = 1
             self.no_decay4 = mask.to(dev)
-        self.m = torch.zeros_like(flat.flat)
-        self.v = torch.zeros_like(flat.flat)
+        for k in self.state_keys:
+            setattr(self, k, torch.zeros_like(flat.flat))
         self.ema = flat.flat.clone() if ema_decay is not None else None
         self.step_count = 0
         self.param_groups = [{"lr": lr, "params": flat.params}]
         self.gnorm_sq = torch.zeros(1, dtype=torch.float32, device=dev)
         # per-step scalars (lr, bias corrections) travel through pinned memory with an async copy; the host runs ahead of
         # the GPU, so every step in flight needs its own slot (a ring far deeper than the launch queue)
-        self._dyn_host = torch.zeros((256, 3), dtype=torch.float32).pin_memory() if dev.type == "cuda" else torch.zeros((256, 3))
-        self._dyn = torch.zeros(3, dtype=torch.float32, device=dev)
+        host = torch.zeros((256, dyn_len), dtype=torch.float32)
+        self._dyn_host = host.pin_memory() if dev.type == "cuda" else host
+        self._dyn = torch.zeros(dyn_len, dtype=torch.float32, device=dev)
         self._ws = torch.empty(4096, dtype=torch.uint8, device=dev)
+
+    def _begin_step(self, scalars, need_norm=False):
+        """step_count, the step's scalars into the device `dyn`, the gradient's squared norm when the step clips (or needs it) -> clip?"""
+        L.require_device(self.flat.flat)
+        self.step_count += 1
+        slot = self._dyn_host[self.step_count % self._dyn_host.shape[0]]
+        for i, s in enumerate(scalars(self.step_count)):
+            slot[i] = s
+        self._dyn.copy_(slot, non_blocking=True)
+        f = self.flat
+        clip = self.max_norm is not None and self.max_norm > 0
+        if clip or need_norm:
+            call("devit_sumsq_f32", ptr(f.flat_grad), f.numel, ptr(self.gnorm_sq), ptr(self._ws), self._ws.numel(),
+                 stream_ptr())
+        return clip
+
+    def _end_step(self):
+        self.flat.grad_scale = 1.0
+        self.flat.refresh_kmajor()      # the kernel rewrote flat16 in place: the k-major weight copies derived from it follow
 
     def zero_grad(self, set_to_none=False):
         self.flat.zero_grad()
+
+    def ema_state_dict(self, model):
+        """EMA weights keyed like model.state_dict() (timm get_state_dict(model_ema), distill_sub.py:429)."""
+        if self.ema is None:
+            return None
+        f, out = self.flat, {}
+        by_id = {id(p): n for n, p in model.named_parameters()}
+        for p, o in zip(f.params, f.offsets):
+            out[by_id[id(p)]] = self.ema[o:o + p.numel()].view_as(p).clone()
+        return {k: out[k] for k in model.state_dict() if k in out}
+
+    def _check_kind(self, sd):
+        kind = sd.get("opt", "adamw")           # FlatAdamW's checkpoints carry no name
+        if kind != self.opt_name:
+            raise ValueError(f"optimizer state of --opt {kind} cannot be loaded into --opt {self.opt_name}")
+
+    def state_dict(self):
+        sd = {"opt": self.opt_name, "ema": self.ema, "step": self.step_count, "lr": self.param_groups[0]["lr"]}
+        sd.update({k: getattr(self, k) for k in self.state_keys})
+        return sd
+
+    def load_state_dict(self, sd):
+        self._check_kind(sd)
+        for k in self.state_keys:
+            getattr(self, k).copy_(sd[k])
+        if self.ema is not None and sd.get("ema") is not None:
+            self.ema.copy_(sd["ema"])
+        self.step_count = sd["step"]
+        self.param_groups[0]["lr"] = sd["lr"]
+
+
+class FlatAdamW(_FlatTail):
+    """AdamW over ddp.FlatParams.  `no_decay`: parameter names exempt from weight decay (see no_decay_names; every
+    tensor starts on a 4-element granule of the flat buffer, so the exemption is one byte per granule)."""
+
+    def __init__(self, flat, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None, ema_decay=None,
+                 no_decay=None):
+        self.betas, self.eps = betas, eps
+        self._setup(flat, lr, weight_decay, max_norm, ema_decay, no_decay, 3)
 
     def step(self):
         L.require_device(self.flat.flat)
@@ -68,22 +133,156 @@ class FlatAdamW:
         f.grad_scale = 1.0
         f.refresh_kmajor()      # the kernel rewrote flat16 in place: the k-major weight copies derived from it follow (one launch)
 
-    def ema_state_dict(self, model):
-        """EMA weights keyed like model.state_dict() (timm get_state_dict(model_ema), distill_sub.py:429)."""
-        if self.ema is None:
-            return None
-        f, out = self.flat, {}
-        by_id = {id(p): n for n, p in model.named_parameters()}
-        for p, o in zip(f.params, f.offsets):
-            out[by_id[id(p)]] = self.ema[o:o + p.numel()].view_as(p).clone()
-        return {k: out[k] for k in model.state_dict() if k in out}
-
     def state_dict(self):
         return {"m": self.m, "v": self.v, "ema": self.ema, "step": self.step_count, "lr": self.param_groups[0]["lr"]}
 
     def load_state_dict(self, sd):
+        self._check_kind(sd)
         self.m.copy_(sd["m"]); self.v.copy_(sd["v"])
         if self.ema is not None and sd.get("ema") is not None:
             self.ema.copy_(sd["ema"])
         self.step_count = sd["step"]
         self.param_groups[0]["lr"] = sd["lr"]
+
+
+class FlatSGD(_FlatTail):
+    """torch.optim.SGD(momentum, nesterov, dampening 0) over ddp.FlatParams with timm's two weight-decay groups: `--opt momentum` and
+    `--opt nesterov` (devit_sgd_step)."""
+    state_keys = ("buf",)
+
+    def __init__(self, flat, lr=5e-4, momentum=0.9, nesterov=False, weight_decay=0.0, max_norm=None, ema_decay=None, no_decay=None):
+        self.momentum, self.nesterov = momentum, bool(nesterov)
+        self.opt_name = "nesterov" if nesterov else "momentum"
+        self._setup(flat, lr, weight_decay, max_norm, ema_decay, no_decay, 1)
+
+    def step(self):
+        clip = self._begin_step(lambda t: (self.param_groups[0]["lr"],))
+        f = self.flat
+        call("devit_sgd_step", ptr(f.flat), ptr(f.flat_grad), ptr(self.buf), ptr(self.ema), ptr(f.flat16), ptr(self.no_decay4),
+             ptr(self.gnorm_sq) if clip else None, ptr(self._dyn), f.numel, self.momentum, int(self.nesterov),
+             self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0), float(f.grad_scale), stream_ptr())
+        self._end_step()
+
+
+class FlatAdam(_FlatTail):
+    """torch.optim.Adam over ddp.FlatParams: the weight decay is L2, added to the gradient before the moments (`--opt adam`,
+    devit_adam_l2_step)."""
+    opt_name = "adam"
+
+    def __init__(self, flat, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None, ema_decay=None, no_decay=None):
+        self.betas, self.eps = betas, eps
+        self._setup(flat, lr, weight_decay, max_norm, ema_decay, no_decay, 3)
+
+    def _scalars(self, t):
+        return self.param_groups[0]["lr"], 1.0 - self.betas[0] ** t, 1.0 - self.betas[1] ** t
+
+    def step(self):
+        clip = self._begin_step(self._scalars)
+        f = self.flat
+        call("devit_adam_l2_step", ptr(f.flat), ptr(f.flat_grad), ptr(self.m), ptr(self.v), ptr(self.ema), ptr(f.flat16),
+             ptr(self.no_decay4), ptr(self.gnorm_sq) if clip else None, ptr(self._dyn), f.numel, self.betas[0], self.betas[1],
+             self.eps, self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0), float(f.grad_scale),
+             stream_ptr())
+        self._end_step()
+
+
+def lamb_chunk_table(names, sizes, offsets, no_decay, chunk_granules=L.OPT_CHUNK_GRANULES):
+    """The devit_opt_chunk table of a flat buffer, an int32 CPU tensor [nchunks][4] (first granule, granule count, segment, flags): tensor s
+    (names[s], sizes[s] elements from offsets[s], a multiple of 4) is cut into chunks of at most `chunk_granules` granules, in order;
+    flags bit 0 marks the tensors in `no_decay`.  The padding between tensors belongs to no chunk."""
+    rows = []
+    for s, (name, numel, off) in enumerate(zip(names, sizes, offsets)):
+        if off % 4:
+            raise ValueError(f"{name}: offset {off} is not on a 4-element granule")
+        first, count = off // 4, (numel + 3) // 4
+        flag = L.OPT_CHUNK_NO_DECAY if name in no_decay else 0
+        for c in range(0, count, chunk_granules):
+            rows.append((first + c, min(chunk_granules, count - c), s, flag))
+    return torch.tensor(rows, dtype=torch.int32).reshape(-1, 4)
+
+
+def validate_chunk_table(table, sizes, offsets, numel, chunk_granules=L.OPT_CHUNK_GRANULES):
+    """Raise ValueError unless `table` (lamb_chunk_table's layout) is what the kernels may trust: every chunk inside [0, numel / 4) and
+    inside the tensor it names, at most `chunk_granules` long, the chunks disjoint and sorted by segment, one flag per tensor, and
+    every granule of every tensor covered exactly once.  The kernels index the buffers with these numbers."""
+    t = table.to(torch.int64)
+    if t.ndim != 2 or t.shape[1] != 4 or t.shape[0] == 0:
+        raise ValueError("chunk table: expected [nchunks > 0][4]")
+    first, count, seg, flags = t.unbind(1)
+    if bool((first < 0).any()) or bool((count < 1).any()) or bool((count > chunk_granules).any()) or bool((first + count > numel // 4).any()):
+        raise ValueError("chunk table: a chunk is empty, longer than a chunk may be, or outside the flat buffer")
+    if bool((seg < 0).any()) or bool((seg >= len(sizes)).any()) or bool((seg[1:] < seg[:-1]).any()):
+        raise ValueError("chunk table: a segment index is out of range, or the table is not sorted by segment")
+    lo = torch.tensor([o // 4 for o in offsets])[seg]
+    hi = torch.tensor([(o + n + 3) // 4 for o, n in zip(offsets, sizes)])[seg]
+    if bool((first < lo).any()) or bool((first + count > hi).any()):
+        raise ValueError("chunk table: a chunk reaches outside its tensor")
+    covered = torch.zeros(numel // 4 + 1, dtype=torch.int64)
+    covered.index_add_(0, first, torch.ones_like(first))
+    covered.index_add_(0, first + count, -torch.ones_like(first))
+    covered = covered.cumsum(0)[:-1]
+    want = torch.zeros(numel // 4, dtype=torch.int64)
+    for o, n in zip(offsets, sizes):
+        want[o // 4:(o + n + 3) // 4] += 1
+    if bool((covered > 1).any()):
+        raise ValueError("chunk table: chunks overlap")
+    if not torch.equal(covered, want):
+        raise ValueError("chunk table: a granule of a tensor is not covered, or padding is")
+    per_seg = {}
+    for s, f in zip(seg.tolist(), flags.tolist()):
+        if per_seg.setdefault(s, f) != f:
+            raise ValueError(f"chunk table: the chunks of tensor {s} disagree on their flags")
+    return table
+
+
+class FlatLamb(_FlatTail):
+    """timm Lamb (bias_correction, grad_averaging, max_grad_norm = 1, always_adapt off) over ddp.FlatParams: `--opt lamb`, and `--opt lambc`
+    with trust_clip.  The trust ratio is per parameter tensor: the flat buffer is described to devit_lamb_step by a chunk table built
+    (and validated) here once.  Tensors of the no-decay group -- all of them when weight_decay is 0 -- take trust 1, as in timm."""
+
+    def __init__(self, flat, lr=5e-4, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, max_norm=None, ema_decay=None, no_decay=None,
+                 trust_clip=False):
+        self.betas, self.eps, self.trust_clip = betas, eps, bool(trust_clip)
+        self.opt_name = "lambc" if trust_clip else "lamb"
+        self._setup(flat, lr, weight_decay, max_norm, ema_decay, no_decay, 3)
+        sizes = [p.numel() for p in flat.params]
+        exempt = set(flat.names) if not weight_decay else set(no_decay or ())
+        self.chunks_host = validate_chunk_table(lamb_chunk_table(flat.names, sizes, flat.offsets, exempt), sizes, flat.offsets, flat.numel)
+        dev = flat.flat.device
+        self.nchunks, self.nsegments = self.chunks_host.shape[0], len(sizes)
+        self.chunks = self.chunks_host.to(dev)
+        self._lamb_ws = torch.empty((2 * self.nchunks + self.nsegments) * 4, dtype=torch.uint8, device=dev)
+
+    _scalars = FlatAdam._scalars
+
+    def trust(self):
+        """the trust ratios of the last step, one per tensor of flat.names (1 for the no-decay group)"""
+        return self._lamb_ws.view(torch.float32)[2 * self.nchunks:]
+
+    def step(self):
+        self._begin_step(self._scalars, need_norm=True)
+        f = self.flat
+        call("devit_lamb_step", ptr(f.flat), ptr(f.flat_grad), ptr(self.m), ptr(self.v), ptr(self.ema), ptr(f.flat16),
+             ptr(self.gnorm_sq), ptr(self._dyn), f.numel, ptr(self.chunks), self.nchunks, self.nsegments, int(self.trust_clip),
+             self.betas[0], self.betas[1], self.eps, self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0),
+             float(f.grad_scale), ptr(self._lamb_ws), self._lamb_ws.numel(), stream_ptr())
+        self._end_step()
+
+
+def create_flat_optimizer(args, flat, model):
+    """timm create_optimizer(args, model) for the fused tails: `--opt` (adamw, adam, momentum, nesterov, lamb, lambc), `--momentum`,
+    `--opt-eps`, `--opt-betas`, `--weight-decay`, `--clip-grad`, `--model-ema` / `--model-ema-decay` -> the optimizer over `flat`, with
+    timm's two weight-decay groups of `model`."""
+    name = args.opt.lower()
+    kw = dict(lr=args.lr, weight_decay=args.weight_decay, max_norm=args.clip_grad,
+              ema_decay=args.model_ema_decay if getattr(args, "model_ema", False) else None, no_decay=no_decay_names(model))
+    if name in ("momentum", "nesterov"):
+        return FlatSGD(flat, momentum=args.momentum, nesterov=name == "nesterov", **kw)
+    adam = dict(eps=args.opt_eps, betas=tuple(args.opt_betas or (0.9, 0.999)), **kw)
+    if name == "adamw":
+        return FlatAdamW(flat, **adam)
+    if name == "adam":
+        return FlatAdam(flat, **adam)
+    if name in ("lamb", "lambc"):
+        return FlatLamb(flat, trust_clip=name == "lambc", **adam)
+    raise ValueError(f"--opt {args.opt}: not one of {', '.join(OPT_NAMES)}")

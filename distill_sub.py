@@ -381,11 +381,16 @@ def load_weights_any_size(model, state_dict):
 
 
 def check_supported(args):
-    """Flags the reference hands to timm factories that this build implements for one value only: refuse the others
-    instead of silently training something else (create_optimizer / create_scheduler, distill_sub.py:340-343)."""
+    """Flags the reference hands to timm factories that this build implements for some values only (--opt: the six names of
+    optim.OPT_NAMES; --sched: cosine): refuse the others instead of silently training something else (create_optimizer /
+    create_scheduler, distill_sub.py:340-343)."""
     check_input_size(args)
-    if args.opt.lower() != 'adamw':
-        raise SystemExit(f"--opt {args.opt}: only adamw (the reference's default) is built on the fused optimizer kernel")
+    if args.opt.lower() == 'sgd':
+        raise SystemExit("--opt sgd: use nesterov: timm's sgd is Nesterov SGD (or momentum for the plain form)")
+    if args.opt.lower() not in optim.OPT_NAMES:
+        raise SystemExit(f"--opt {args.opt}: the fused optimizer tails are {', '.join(optim.OPT_NAMES)}")
+    if getattr(args, 'torch_optim', False) and args.opt.lower() != 'adamw':
+        raise SystemExit(f"--torch-optim --opt {args.opt}: the torch tail of the ensemble stage is two torch.optim.AdamW; drop --torch-optim")
     if args.sched != 'cosine':
         raise SystemExit(f"--sched {args.sched}: only cosine (the reference's default) is implemented")
     if args.lr_noise is not None:
@@ -442,10 +447,7 @@ def main(args):
     flat.attach_bf16(model)
     reducer = ddp.BucketedGradReducer(flat).attach(model)
     args.lr = args.lr * args.batch_size * utils.get_world_size() / 512.0             # distill_sub.py:338
-    optimizer = optim.FlatAdamW(flat, lr=args.lr, eps=args.opt_eps, betas=tuple(args.opt_betas or (0.9, 0.999)),
-                                weight_decay=args.weight_decay, max_norm=args.clip_grad,
-                                ema_decay=args.model_ema_decay if args.model_ema else None,
-                                no_decay=optim.no_decay_names(model))       # timm's two parameter groups
+    optimizer = optim.create_flat_optimizer(args, flat, model)       # --opt, with timm's two parameter groups
     loss_scaler, lr_scheduler = StepRunner(reducer), CosineEpochs(optimizer, args)
     if mixup_fn is not None:                 # distill_sub.py:345-352: smoothing is handled by the mixup label transform
         base = losses.SoftTargetCrossEntropy()

@@ -151,11 +151,8 @@ def main(args):
         # fp32 GEMM reads the masters.  broadcast_module above already made the replicas equal.
         flat, ens_flat = ddp.FlatParams(model).attach_bf16(model), ddp.FlatParams(ens_model)
         runner = EnsStepRunner(ddp.BucketedGradReducer(flat).attach(model), ddp.BucketedGradReducer(ens_flat))
-        ema = args.model_ema_decay if args.model_ema else None
-        optimizer = optim.FlatAdamW(flat, lr=args.lr, eps=args.opt_eps, betas=betas, weight_decay=args.weight_decay, max_norm=args.clip_grad,
-                                    ema_decay=ema, no_decay=optim.no_decay_names(model))
-        ens_optimizer = optim.FlatAdamW(ens_flat, lr=args.lr, eps=args.opt_eps, betas=betas, weight_decay=args.weight_decay,
-                                        max_norm=args.clip_grad, ema_decay=ema, no_decay=optim.no_decay_names(ens_model))
+        optimizer = optim.create_flat_optimizer(args, flat, model)
+        ens_optimizer = optim.create_flat_optimizer(args, ens_flat, ens_model)
         if args.gates and args.physical_shrink:     # train at the shrunk models' FLOPs (the reference trains the masked models at the dense cost)
             from devit_amd import shrink
             rep = shrink.compact(model, trainable=True)

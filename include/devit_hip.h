@@ -43,8 +43,8 @@ DEVIT_API const char* devit_last_error(void); /* host string, thread-local, vali
 /* 0 if device `dev` is gfx950; DEVIT_ERR_DEVICE otherwise (product path refuses to run). */
 DEVIT_API int devit_check_device(int dev);
 /* sizeof() of the ABI's structs as THIS library was compiled (which: 0 devit_epilogue, 1 devit_operand, 2 devit_block_weights,
- * 3 devit_block_wgrads, 4 devit_block_acts, 5 devit_block_bwd_io, 6 devit_index_job, 7 devit_wgrad_job, 8 devit_launch_info, 9 devit_block_dropout;
- * anything else: 0).  A binding
+ * 3 devit_block_wgrads, 4 devit_block_acts, 5 devit_block_bwd_io, 6 devit_index_job, 7 devit_wgrad_job, 8 devit_launch_info, 9 devit_block_dropout,
+ * 10 devit_mix_sample, 11 devit_opt_chunk; anything else: 0).  A binding
  * compares them with its own mirrors once at load time: a stale mirror of a struct that is passed as an ARRAY would otherwise be misread
  * from its second element on, with no error. */
 DEVIT_API size_t devit_abi_struct_size(int which);
@@ -533,6 +533,47 @@ DEVIT_API int devit_adamw_step(float* p, const float* g, float* m, float* v, flo
                      const unsigned char* no_decay4, const float* gnorm_sq, const float* dyn, size_t n, float beta1,
                      float beta2, float eps, float weight_decay, float max_norm, float ema_decay, float grad_scale,
                      void* stream);
+
+/* The same tail for timm's other optimizers (create_optimizer names `momentum`, `nesterov`, `adam`, `lamb`, `lambc`).  Shared with
+ * devit_adamw_step, argument for argument: g' = g * clip with clip = grad_scale * min(1, max_norm / (sqrt(gnorm_sq) * grad_scale + 1e-6))
+ * (gnorm_sq == NULL: clip = grad_scale), the no_decay4 granule mask (weight decay 0 there), ema = ema*d + (1-d)*p', p_bf16 = bf16(p')
+ * (ema, p_bf16 optional), dyn on the device, n % 4 == 0.  Everything is fp32; wd is the granule's weight decay.
+ *   devit_sgd_step      torch.optim.SGD(momentum = mu, nesterov, dampening 0); dyn = float[1] {lr}; buf starts at zero
+ *                         d = g' + wd p;  buf' = mu buf + d;  p' = p - lr (nesterov ? d + mu buf' : buf')
+ *   devit_adam_l2_step  torch.optim.Adam (L2 decay coupled into the gradient); dyn = float[3] as devit_adamw_step
+ *                         d = g' + wd p;  m' = b1 m + (1-b1) d;  v' = b2 v + (1-b2) d d;  p' = p - (lr/bc1) m' / (sqrt(v')/sqrt(bc2) + eps)
+ *   devit_lamb_step     timm Lamb (bias_correction, grad_averaging, max_grad_norm = 1, always_adapt = False); dyn = float[3]
+ *                         gnorm_sq is REQUIRED; max_norm <= 0: no outer clip (clip = grad_scale)
+ *                         n1 = sqrt(gnorm_sq) * clip;  g'' = g' / max(1, n1);  m' = b1 m + (1-b1) g'';  v' = b2 v + (1-b2) g'' g''
+ *                         u = (m'/bc1) / (sqrt(v')/sqrt(bc2) + eps), + wd p in a decayed tensor
+ *                         per decayed tensor trust = (||p|| > 0 and ||u|| > 0) ? ||p|| / ||u|| : 1, min(trust, 1) with trust_clip
+ *                         (`lambc`); tensors of the no-decay group take trust = 1;  p' = p - lr trust u
+ * LAMB's norms run over ONE parameter tensor, so its caller describes the flat buffer by a device table of devit_opt_chunk (struct id
+ * 11 of devit_abi_struct_size, 16 bytes): chunk c covers granules [first4, first4 + count4) -- count4 <= 1024, all of tensor
+ * `segment` (0 <= segment < nsegments) -- with flags bit 0 set when that tensor is exempt from weight decay.  The table is sorted by
+ * segment, its chunks are disjoint, and granules that no chunk covers (padding between tensors) are left untouched.  The caller
+ * validates the table before it uploads it; the kernels additionally skip a chunk that would reach outside [0, n / 4) or
+ * nsegments.  Three launches (moments and per-chunk partial norms; one wave per tensor adds them in chunk order; the update with u
+ * recomputed from p, m', v'), no atomics: the same input gives the same bits.  workspace >= devit_lamb_workspace(nchunks,
+ * nsegments) bytes, 8-byte aligned, owned by the caller: [nchunks][2] partial sums, then trust[nsegments]. */
+typedef struct {
+  unsigned first4;
+  unsigned count4;
+  int segment;
+  int flags;
+} devit_opt_chunk;
+DEVIT_API int devit_sgd_step(float* p, const float* g, float* buf, float* ema, void* p_bf16, const unsigned char* no_decay4,
+                   const float* gnorm_sq, const float* dyn, size_t n, float momentum, int nesterov, float weight_decay,
+                   float max_norm, float ema_decay, float grad_scale, void* stream);
+DEVIT_API int devit_adam_l2_step(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16,
+                       const unsigned char* no_decay4, const float* gnorm_sq, const float* dyn, size_t n, float beta1,
+                       float beta2, float eps, float weight_decay, float max_norm, float ema_decay, float grad_scale,
+                       void* stream);
+DEVIT_API size_t devit_lamb_workspace(int nchunks, int nsegments);
+DEVIT_API int devit_lamb_step(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16, const float* gnorm_sq,
+                    const float* dyn, size_t n, const devit_opt_chunk* chunks, int nchunks, int nsegments, int trust_clip,
+                    float beta1, float beta2, float eps, float weight_decay, float max_norm, float ema_decay, float grad_scale,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * DEKD logit loss + gradient in one launch.  Replaces DistillLoss.forward (utils/losses.py:156-177)

@@ -74,10 +74,7 @@ def main(args):
     flat.attach_bf16(model)
     reducer = ddp.BucketedGradReducer(flat).attach(model)
     args.lr = args.lr * args.batch_size * utils.get_world_size() / 512.0             # train_subdata.py:404-405
-    optimizer = optim.FlatAdamW(flat, lr=args.lr, eps=args.opt_eps, betas=tuple(args.opt_betas or (0.9, 0.999)),
-                                weight_decay=args.weight_decay, max_norm=args.clip_grad,
-                                ema_decay=args.model_ema_decay if args.model_ema else None,
-                                no_decay=optim.no_decay_names(model))
+    optimizer = optim.create_flat_optimizer(args, flat, model)
     loss_scaler, lr_scheduler = ds.StepRunner(reducer), ds.CosineEpochs(optimizer, args)
     if mixup_fn is not None:                                                         # :409-416
         base = losses.SoftTargetCrossEntropy()
