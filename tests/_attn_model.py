@@ -26,7 +26,11 @@ emulate():    the same operations with the roundings the kernels document (atten
               p = exp2(fma(s, c2, -max * c2)), fp32 row sum of the unrounded p, P rounded to the 16-bit type before P V, one rounding
               of o * (gate / sum); backward: p = exp2(fma(s, c2, -lse * log2(e))), delta = fp32 rowsum(dO * stored out) * scale,
               dS = p * fma(dP, gate * scale, -delta) rounded to bf16 before dQ / dK, P rounded to bf16 before dV, dV * gate in fp32,
-              `add` added in fp32, one rounding of every stored gradient.  `mutate` plants one of four bugs (MUTATIONS)."""
+              `add` added in fp32, one rounding of every stored gradient.  `mutate` plants one of the bugs of MUTATIONS.
+
+Dropout on the softmax (the *_drop kernels): all three take keep (bool or 0/1, [B][H][NQ][N]) and s (the fp32 value of 1 / (1 - p)); with
+keep=None they are what they were.  Statement: Pd = P * keep s, O = g Pd V, dV = g Pd^T dO, dP = dO V^T, delta = rowsum(dO * O),
+dS = P * (g keep s dP - delta); dQ, dK as above, lse of the UNDROPPED row.  Bounds: _bounds_dropped(); emulation: _emulate_dropped()."""
 import math
 
 import torch
@@ -39,7 +43,10 @@ LSE_BAR = 1e-5
 SLOPE_BAR = 2.0 ** -9
 LOG2E_F32 = 1.4426950408889634          # the literals of attention.hip; rounded to fp32 where the kernel does
 LN2_F32 = 0.6931471805599453
-MUTATIONS = ("dq_drops_last_key", "dk_drops_ds_tile", "dv_drops_p_tile", "delta_from_pregate_out")
+MUTATIONS = ("dq_drops_last_key", "dk_drops_ds_tile", "dv_drops_p_tile", "delta_from_pregate_out",
+             # the *_drop kernels (keep / s given)
+             "drop_bwd_mask_other_block", "drop_bwd_mask_pitch_n", "drop_lse_of_dropped_row", "drop_delta_from_undropped_out",
+             "drop_dv_scaled_twice", "drop_quad_trade_transposed")
 
 
 # ------------------------------------------------------------------------------------------ layout
@@ -69,19 +76,32 @@ def _gate(gate, H, like):
 
 
 # ------------------------------------------------------------------------------------------ reference
-def reference(q, k, v, gate, scale, dout=None, add=None):
+def _keep_scale(keep, s, like):
+    """m = keep * s as float64 [B][H][NQ][N]; s is the fp32 value of 1 / (1 - p)"""
+    assert s is not None and float(torch.tensor(s, dtype=F32)) == float(s), "s: the fp32 value of 1 / (1 - p)"
+    assert keep.shape == like.shape, (keep.shape, like.shape)
+    return keep.to(like.device).to(F64) * float(s)
+
+
+def reference(q, k, v, gate, scale, dout=None, add=None, keep=None, s=None):
     H = q.shape[1]
     g = _gate(gate, H, q)
     S = scale * (q @ k.transpose(-1, -2))
     lse = torch.logsumexp(S, -1)
     P = torch.exp(S - lse[..., None])
-    O = g * (P @ v)
+    m = None if keep is None else _keep_scale(keep, s, P)
+    Pd = P if m is None else P * m
+    O = g * (Pd @ v)
     r = dict(S=S, P=P, O=O, lse=lse, g=g)
+    if m is not None:
+        r.update(Pd=Pd, m=m)
     if dout is not None:
-        dV0 = g * (P.transpose(-1, -2) @ dout)
+        dV0 = g * (Pd.transpose(-1, -2) @ dout)
         dP = dout @ v.transpose(-1, -2)
         delta = (dout * O).sum(-1, keepdim=True)
-        dS = P * (g * dP - delta)
+        dS = P * (g * dP - delta) if m is None else P * (g * m * dP - delta)
+        if m is not None:
+            r.update(gmdP=g * m * dP, delta=delta)
         dQ0 = scale * (dS @ k)
         dK0 = scale * (dS.transpose(-1, -2) @ q)
         aq, ak, av = add if add is not None else (0.0, 0.0, 0.0)
@@ -89,13 +109,15 @@ def reference(q, k, v, gate, scale, dout=None, add=None):
     return r
 
 
-def bounds(q, k, v, gate, scale, dout=None, add=None, u=U_BF16, f16=False):
+def bounds(q, k, v, gate, scale, dout=None, add=None, u=U_BF16, f16=False, keep=None, s=None):
     """-> (reference dict, dict of elementwise bounds for O, lse and, with dout, dQ / dK / dV)"""
-    r = reference(q, k, v, gate, scale, dout, add)
+    r = reference(q, k, v, gate, scale, dout, add, keep, s)
     N = k.shape[2]
     g, P, S = r["g"].abs(), r["P"], r["S"]
     chain = N + 64
     E_S = E32 * 66 * (scale * (q.abs() @ k.abs().transpose(-1, -2)) + S.abs())
+    if keep is not None:
+        return r, _bounds_dropped(r, q, k, v, scale, dout, u, E_S, chain)
     PW = P * (u + E_S)
     E_O = g * (PW @ v.abs()) + u * r["O"].abs()
     if f16:
@@ -110,6 +132,30 @@ def bounds(q, k, v, gate, scale, dout=None, add=None, u=U_BF16, f16=False):
         b["dQ"] = scale * (E_dS @ k.abs()) + u * r["dQ"].abs() + E32 * chain * scale * (adS @ k.abs())
         b["dK"] = scale * (E_dS.transpose(-1, -2) @ q.abs()) + u * r["dK"].abs() + E32 * chain * scale * (adS.transpose(-1, -2) @ q.abs())
     return r, b
+
+
+def _bounds_dropped(r, q, k, v, scale, dout, u, E_S, chain):
+    """bounds() for the *_drop kernels (bf16 only): the plain bounds with Pd = P keep s in P's place in every P-weighted sum, and the
+    fp32 products dropout adds, each with an e32 of the quantity it scales:
+        forward (attention_fwd.inc)   sc = (gate * dk.s) / sum: the product gate * dk.s and the product o * sc that applies it
+        dV      (attention_bwd.inc)   pp = p * s in ATTN_DROPPED, and dv * gate at the store
+        dS                            dp * s in ATTN_DROPPED and gs = gate * scale, both on the g keep s dP term; delta * scale and
+                                      the fma's own rounding on the delta side
+    so W = u + E_S + 2 e32 and E_dS gains 2 e32 P (|g keep s dP| + |delta|).  delta is read from the stored (dropped) `out`."""
+    g, P, Pd = r["g"].abs(), r["P"], r["Pd"]
+    W = u + E_S + 2 * E32
+    PW = Pd * W
+    E_O = g * (PW @ v.abs()) + u * r["O"].abs()
+    b = dict(O=E_O, lse=LSE_BAR * r["lse"].abs().clamp_min(1.0))
+    if dout is not None:
+        ado = dout.abs()
+        E_delta = (ado * E_O).sum(-1, keepdim=True)
+        adS = r["dS"].abs()
+        E_dS = W * adS + P * E_delta + 2 * E32 * P * (r["gmdP"].abs() + r["delta"].abs())
+        b["dV"] = g * (PW.transpose(-1, -2) @ ado) + u * r["dV"].abs() + E32 * chain * g * (Pd.transpose(-1, -2) @ ado)
+        b["dQ"] = scale * (E_dS @ k.abs()) + u * r["dQ"].abs() + E32 * chain * scale * (adS @ k.abs())
+        b["dK"] = scale * (E_dS.transpose(-1, -2) @ q.abs()) + u * r["dK"].abs() + E32 * chain * scale * (adS.transpose(-1, -2) @ q.abs())
+    return b
 
 
 def ratio(got, ref, bound):
@@ -135,9 +181,25 @@ def _r16(x, f16=False):
     return x.to(F32).to(F16 if f16 else BF16).to(F64)       # the kernels round fp32 values
 
 
-def emulate(q, k, v, gate, scale, dout=None, add=None, f16=False, mutate=None):
+def quad_transposed(keep):
+    """the keep bit of (query 4a + r, key 4b + p) taken for (query 4a + p, key 4b + r): what a transposed word trade would give.  Rows past
+    NQ repeat the last row (the kernel's clamp), key columns past N are kept (they are masked as padded keys anyway)."""
+    B, H, NQ, N = keep.shape
+    nq4, n4 = (NQ + 3) & ~3, (N + 3) & ~3
+    kp = torch.ones((B, H, nq4, n4), dtype=torch.bool, device=keep.device)
+    kp[:, :, :NQ, :N] = keep.bool()
+    kp[:, :, NQ:, :N] = keep.bool()[:, :, NQ - 1:NQ, :]
+    kp = kp.view(B, H, nq4 // 4, 4, n4 // 4, 4).transpose(3, 5).reshape(B, H, nq4, n4)
+    return kp[:, :, :NQ, :N].contiguous()
+
+
+def emulate(q, k, v, gate, scale, dout=None, add=None, f16=False, mutate=None, keep=None, s=None, keep_bwd=None):
     """-> dict O, lse and, with dout, dQ / dK / dV: float64 tensors holding what the kernels would store (see the module docstring)"""
     assert mutate is None or mutate in MUTATIONS
+    if keep is not None:
+        assert not f16, "the *_drop kernels are bf16 only"
+        return _emulate_dropped(q, k, v, gate, scale, dout, add, mutate, keep, s, keep_bwd)
+    assert mutate is None or not mutate.startswith("drop_")
     H, N = q.shape[1], k.shape[2]
     g = _r32(_gate(gate, H, q))
     sc32 = float(torch.tensor(scale, dtype=F32))
@@ -181,6 +243,72 @@ def emulate(q, k, v, gate, scale, dout=None, add=None, f16=False, mutate=None):
     return r
 
 
+def _emulate_dropped(q, k, v, gate, scale, dout, add, mutate, keep, s, keep_bwd):
+    """the *_drop kernels (bf16): the fp32 row sum and lse are of the UNDROPPED p, dropped p is zeroed before the bf16 rounding, the
+    output is scaled by fp32(fp32(g s) / sum); backward: pp = fp32(p s) or 0 rounded to bf16 for dV, dS = p * fma(fp32(dp s) or 0, gate
+    scale, -delta).  keep_bwd: the mask the backward regenerates (the two wrong-mask mutations; default: the forward's)."""
+    assert mutate is None or mutate.startswith("drop_"), mutate
+    H, N = q.shape[1], k.shape[2]
+    g = _r32(_gate(gate, H, q))
+    s32 = float(torch.tensor(s, dtype=F32))
+    assert s32 == float(s)
+    kf = keep.to(q.device).bool()
+    sc32 = float(torch.tensor(scale, dtype=F32))
+    c2 = float(torch.tensor(sc32, dtype=F32) * torch.tensor(LOG2E_F32, dtype=F32))
+    sr = _r32(q @ k.transpose(-1, -2))
+    mxs = _r32(sr.amax(-1, keepdim=True) * c2)
+    p = _r32(torch.exp2(_r32(sr * c2 - mxs)))
+    pd = torch.where(kf, p, torch.zeros_like(p))
+    psum = _r32((pd if mutate == "drop_lse_of_dropped_row" else p).sum(-1, keepdim=True))
+    lse = _r32(_r32(mxs + _r32(torch.log2(psum))) * float(torch.tensor(LN2_F32, dtype=F32)))
+    O = _r16(_r32(_r16(pd) @ v) * _r32(_r32(g * s32) / psum))
+    r = dict(O=O, lse=lse[..., 0])
+    if dout is None:
+        return r
+    kb = kf
+    if mutate in ("drop_bwd_mask_other_block", "drop_bwd_mask_pitch_n"):
+        assert keep_bwd is not None, "these two need the mask the wrong backward would regenerate"
+        kb = keep_bwd.to(q.device).bool()
+    if mutate == "drop_quad_trade_transposed":
+        kb = quad_transposed(kf)
+    mb = torch.where(kb, torch.full_like(p, s32), torch.zeros_like(p))
+    lse2 = _r32(lse * float(torch.tensor(LOG2E_F32, dtype=F32)))
+    out_for_delta = O
+    if mutate == "drop_delta_from_undropped_out":
+        out_for_delta = _r16(_r32(_r16(p) @ v) * _r32(g / psum))
+    delta = _r32(_r32((dout * out_for_delta).sum(-1, keepdim=True)) * sc32)
+    pb = _r32(torch.exp2(_r32(sr * c2 - lse2)))
+    dp = _r32(dout @ v.transpose(-1, -2))
+    gs = _r32(g * sc32)
+    pp = _r32(pb * mb)
+    ds = _r32(pb * _r32(_r32(dp * mb) * gs - delta))
+    p16, ds16 = _r16(pp), _r16(ds)
+    dq = _r32(ds16 @ k)
+    dk = _r32(ds16.transpose(-1, -2) @ q)
+    dv = _r32(_r32(p16.transpose(-1, -2) @ dout) * g)
+    if mutate == "drop_dv_scaled_twice":
+        dv = _r32(dv * s32)
+    aq, ak, av = add if add is not None else (0.0, 0.0, 0.0)
+    r.update(dQ=_r16(dq + aq), dK=_r16(dk + ak), dV=_r16(dv + av))
+    return r
+
+
+def attn_keep(seed, block, thr, B, H, N, NQ=None, pitch=None):
+    """the keep mask of the *_drop kernels from the numpy mirror: site 1, logical tensor [B H NQ][N] at pitch ceil4(N) -> bool [B][H][NQ][N]"""
+    import numpy as np
+
+    import _philox as PH
+    NQ = N if NQ is None else NQ
+    pitch = (N + 3) & ~3 if pitch is None else pitch
+    if pitch % 4 == 0:
+        return torch.from_numpy(PH.keep_mask(seed, 1, block, thr, B * H * NQ, N, pitch)).view(B, H, NQ, N)
+    # a pitch the header forbids (what a kernel that forgot ceil4 would index): the same counter layout on e = row * pitch + col
+    e = np.arange(B * H * NQ, dtype=np.uint64)[:, None] * np.uint64(pitch) + np.arange(N, dtype=np.uint64)[None, :]
+    gq = e >> np.uint64(2)
+    w = PH.philox4x32_10((gq & PH.MASK, gq >> np.uint64(32), np.uint64(1), np.uint64(block)), (seed & 0xFFFFFFFF, seed >> 32))
+    return torch.from_numpy(np.choose((e & np.uint64(3)).astype(np.int64), w) >= np.uint32(thr)).view(B, H, NQ, N)
+
+
 # ------------------------------------------------------------------------------------------ fixed inputs (CPU generator: the same on every machine)
 REGIMES = {"flat": (0.25, 1.0), "unit": (1.0, 1.0), "peaked": (1.0, 4.0)}        # std of qkv, factor on Q
 SHAPES = [(2, 198, 6), (3, 197, 2), (2, 208, 3), (2, 192, 6), (2, 193, 12), (4, 17, 2), (4, 16, 1), (5, 1, 2), (2, 64, 16), (2, 33, 3),
@@ -195,6 +323,20 @@ def packed_cases():
         for j, regime in enumerate(REGIMES):
             out.append((B, N, H, regime, (i + j) % 2 == 0, (i + 2 * j) % 3 == 0))
     return out
+
+
+# the *_drop kernels: (B, N, H, regime, gated (the 0.5, 2, 0, 1 mix: a zero head from H = 3), dqkv_add, p, block)
+DROP_SEED = 20240807
+DROP_CASES = [(2, 198, 6, "unit", True, True, 0.1, 4), (2, 198, 6, "peaked", True, False, 0.5, 1), (1, 208, 1, "flat", False, True, 0.5, 4),
+              (1, 208, 1, "unit", True, False, 0.1, 1), (2, 193, 3, "peaked", True, False, 0.1, 1), (2, 193, 3, "unit", True, True, 0.5, 4),
+              (1, 65, 4, "flat", True, True, 0.5, 1), (2, 17, 2, "unit", False, False, 0.1, 4), (1, 5, 2, "peaked", True, True, 0.5, 4),
+              (1, 1, 2, "flat", True, False, 0.1, 1), (2, 5, 3, "flat", True, False, 0.1, 1)]
+
+
+def drop_params(p):
+    """(thr, the fp32 value of 1 / (1 - p)) as the header states them"""
+    import _philox as PH
+    return PH.threshold(p), float(torch.tensor(1.0 / (1.0 - p), dtype=F32))
 
 
 def gate_mix(H, nonzero=False):
@@ -283,11 +425,11 @@ def relation_emulate(fs, ft, weight, hd_s, hd_t, mutate=False):
 
 
 # ------------------------------------------------------------------------------------------ the shared check
-def check_packed(chk, tag, qkv, B, N, H, gate, scale, out, lse, dout=None, dqkv=None, add=None, u=U_BF16, f16=False):
+def check_packed(chk, tag, qkv, B, N, H, gate, scale, out, lse, dout=None, dqkv=None, add=None, u=U_BF16, f16=False, keep=None, s=None):
     """One packed launch's outputs (2-D buffers, live rows first) against the model: O, lse and, where given, dQ / dK / dV each against
     its own bound, through chk(worst err / bound, 1.0, name=...).  -> dict name -> ratio; raises AssertionError on the first that is >= 1."""
     q, k, v, do, ad = split_packed(qkv, B, N, H, dout, add)
-    ref, bnd = bounds(q, k, v, gate, scale, do, ad, u=u, f16=f16)
+    ref, bnd = bounds(q, k, v, gate, scale, do, ad, u=u, f16=f16, keep=keep, s=s)
     got = dict(O=heads(out, B, N, H), lse=lse.to(F64).view(B, H, N))
     if dqkv is not None:
         D = H * HD

@@ -1,10 +1,13 @@
 """Dropout p > 0 on the HIP path (csrc/dropout.hip, the *_drop kernels of csrc/attention.hip) against the header's mask definition, restated in
-numpy by tests/_philox.py, and against fp32 torch statements that use the mask the library dumps (devit_dropout_mask)."""
+numpy by tests/_philox.py, and against fp32 torch statements that use the mask the library dumps (devit_dropout_mask).  The second half of
+the file holds the same kernels element by element to the float64 models of tests/_drop_model.py and tests/_attn_model.py (keep, s), with
+masks from the numpy mirror only, and the bf16 block path to the statement by the distance of the gradients a wrong backward mask moves."""
 import numpy as np
 import pytest
 import torch
 
 import _attn_model as A
+import _drop_model as DM
 import _philox as PH
 from conftest import chk
 
@@ -407,3 +410,212 @@ def test_switches(dev, model_case, precision):
         torch.manual_seed(0)
         z = m(img)
         assert torch.equal(x[0], z[0]) and torch.equal(x[1], z[1]) and not torch.equal(x[0], y[0])
+
+
+# ========================================================================================== per-element bounds (tests/_drop_model.py,
+# the keep / s arguments of tests/_attn_model.py): masks from the numpy mirror only, never from devit_dropout_mask
+GUARD = 64
+
+
+def guarded(payload, dev, fill=7):
+    """-> (whole buffer, the payload's view): GUARD elements of `fill` on either side of a flat copy of `payload` (256 / 128 / 64 bytes:
+    the payload stays 16-byte aligned)"""
+    n = payload.numel()
+    whole = torch.full((n + 2 * GUARD,), fill, dtype=payload.dtype, device=dev)
+    whole[GUARD:GUARD + n] = payload.reshape(-1).to(dev)
+    return whole, whole[GUARD:GUARD + n]
+
+
+def guards_intact(whole, fill=7):
+    return bool((whole[:GUARD] == fill).all()) and bool((whole[-GUARD:] == fill).all())
+
+
+def judged(tag, res):
+    print(tag, res)
+    bad = [n for n, x in res.items() if not chk(x, 1.0, name=f"{tag}/{n}")]
+    assert not bad, (tag, res)
+
+
+@pytest.mark.parametrize("case", [c["name"] for c in DM.MASK_CASES])
+def test_mask_cases_equal_the_mirror(dev, case):
+    from devit_amd._lib import call, ptr, stream_ptr
+    c = DM.CASES["mask/" + case]
+    whole, keep = guarded(torch.full((c["rows"] * c["cols"],), 7, dtype=torch.uint8), dev)
+    call("devit_dropout_mask", c["seed"], c["site"], c["block"], DM.thr_s(c["p"])[0], c["rows"], c["cols"], c["pitch"], ptr(keep), stream_ptr())
+    torch.cuda.synchronize()
+    assert guards_intact(whole)
+    judged("dropout_bounds/mask/" + case, DM.judge_mask(c, keep.view(c["rows"], c["cols"]).cpu()))
+
+
+@pytest.mark.parametrize("case", [c["name"] for c in DM.APPLY_CASES])
+def test_apply_cases_against_the_model(dev, case):
+    from devit_amd._lib import call, ptr, stream_ptr
+    c = DM.CASES["apply/" + case]
+    inp = DM.inputs(c)
+    thr, s = DM.thr_s(c["p"])
+    xw, x = guarded(inp["x"], dev)
+    cw, colsum = guarded(inp["colsum0"], dev)
+    call("devit_dropout_apply", ptr(x), 1 if c["dtype"] == F32 else 0, c["rows"], c["cols"], c["ld"], c["pitch"], c["seed"], c["site"], c["block"],
+         thr, s, ptr(colsum) if c["colsum"] else None, stream_ptr())
+    torch.cuda.synchronize()
+    assert guards_intact(xw) and guards_intact(cw)
+    if not c["colsum"]:
+        assert torch.equal(colsum.cpu(), inp["colsum0"])
+    judged("dropout_bounds/apply/" + case, DM.judge_apply(c, inp, x.view(c["rows"], c["ld"]).cpu(), colsum.cpu() if c["colsum"] else None))
+
+
+@pytest.mark.parametrize("case", [c["name"] for c in DM.RESIDUAL_CASES])
+def test_residual_cases_against_the_model(dev, case):
+    from devit_amd._lib import call, ptr, stream_ptr
+    c = DM.CASES["residual/" + case]
+    inp = DM.inputs(c)
+    thr, s = DM.thr_s(c["p"])
+    xw, x = guarded(inp["x"], dev)
+    yw, y = guarded(inp["y"], dev)
+    ow, out = (xw, x) if c["in_place"] else guarded(torch.full_like(inp["x"], 7.0), dev)
+    rs = None if inp["rowscale"] is None else inp["rowscale"].to(dev)
+    call("devit_dropout_residual", ptr(x), ptr(y), ptr(out), ptr(rs), c["rps"], c["rows"], c["cols"], c["seed"], c["site"], c["block"], thr, s,
+         stream_ptr())
+    torch.cuda.synchronize()
+    assert guards_intact(xw) and guards_intact(yw) and guards_intact(ow)
+    assert torch.equal(y.cpu(), inp["y"].reshape(-1)) and (c["in_place"] or torch.equal(x.cpu(), inp["x"].reshape(-1)))
+    judged("dropout_bounds/residual/" + case, DM.judge_residual(c, inp, out.view(c["rows"], c["cols"]).cpu()))
+
+
+@pytest.mark.parametrize("B,N,H,regime,gated,with_add,p,block", A.DROP_CASES)
+def test_dropped_attention_against_the_bounds(dev, B, N, H, regime, gated, with_add, p, block):
+    """devit_attn_fwd_drop / devit_attn_bwd_drop, every element of out, dq, dk, dv against _attn_model.bounds(..., keep, s) with keep from the
+    numpy mirror; lse has the plain kernels' bits; a head gated off is exactly 0 (its bound is)"""
+    from devit_amd._lib import call, ptr, stream_ptr
+    M, D = B * N, H * 64
+    inp = A.make_inputs(B, N, H, regime)
+    gate = (A.gate_mix(H) if gated else torch.ones(H)).to(dev)
+    thr, s = A.drop_params(p)
+    keep = A.attn_keep(A.DROP_SEED, block, thr, B, H, N)
+    qkv, dout = padded(inp["qkv"], dev), padded(inp["dout"], dev)
+    add = padded(inp["add"], dev) if with_add else None
+    out = padded(torch.zeros((M, D), dtype=BF16), dev)
+    lw, lse = guarded(torch.full((B * H * N,), 7.0), dev, fill=7.0)
+    lse0 = torch.empty_like(lse)
+    dqkv = torch.full((qkv.shape[0], 3 * D), 7.0, dtype=BF16, device=dev)
+    call("devit_attn_fwd", ptr(qkv), ptr(out), ptr(lse0), ptr(gate), B, N, H, 64, SCALE, 0, stream_ptr())
+    out.zero_()
+    call("devit_attn_fwd_drop", ptr(qkv), ptr(out), ptr(lse), ptr(gate), B, N, H, 64, SCALE, A.DROP_SEED, block, thr, s, stream_ptr())
+    call("devit_attn_bwd_drop", ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(gate), ptr(add), ptr(dqkv), B, N, H, 64, SCALE, A.DROP_SEED, block,
+         thr, s, stream_ptr())
+    torch.cuda.synchronize()
+    assert guards_intact(lw, 7.0) and bool((dqkv[M:] == 7.0).all()) and bool((out[M:] == 0).all())
+    assert torch.equal(lse, lse0)
+    A.check_packed(chk, f"dropout_bounds/attention/B{B}-N{N}-H{H}-{regime}-p{p}-blk{block}" + ("-add" if with_add else ""), qkv.cpu(), B, N, H,
+                   gate.cpu() if gated else None, SCALE, out.cpu(), lse.cpu(), dout.cpu(), dqkv.cpu(), add.cpu() if with_add else None,
+                   keep=keep, s=s)
+
+
+# ------------------------------------------------------------------------------------------ a backward must use its forward's mask
+class _MaskFn(torch.autograd.Function):
+    """x * m_fwd forward, dy * m_bwd backward: a backward that regenerated another mask than its forward used"""
+    @staticmethod
+    def forward(ctx, x, m_fwd, m_bwd):
+        ctx.save_for_backward(m_bwd)
+        return x * m_fwd
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy * ctx.saved_tensors[0], None, None
+
+
+_MIRROR = {}          # the mirror's masks of one model forward, generated once (read-only)
+
+
+def mirror_statement(state, img, dps, seed, p, p_attn, dev, wrong=None):
+    """torch_statement() with the masks of the numpy mirror; wrong = (site, block): that site's BACKWARD takes block + 1's mask"""
+    F = torch.nn.functional
+    P = {k: v.clone().requires_grad_(True) for k, v in state.items()}
+    B, D, H, N = img.shape[0], 384, 6, 198
+    s, s_a = float(np.float32(1.0 / (1.0 - p))), float(np.float32(1.0 / (1.0 - p_attn)))
+
+    def mirror(site, block, pp, rows, cols):
+        key = (seed, site, block, pp, rows, cols, str(dev))
+        if key not in _MIRROR:
+            _MIRROR[key] = torch.from_numpy(PH.keep_mask(seed, site, block, PH.threshold(pp), rows, cols, (cols + 3) & ~3)).to(dev).float()
+        return _MIRROR[key]
+
+    def drop(x, site, block, pp, sc, rows, cols):
+        m = mirror(site, block, pp, rows, cols).view(x.shape) * sc
+        if wrong == (site, block):
+            return _MaskFn.apply(x, m, mirror(site, block + 1, pp, rows, cols).view(x.shape) * sc)
+        return x * m
+    x = F.conv2d(img, P["patch_embed.proj.weight"], P["patch_embed.proj.bias"], stride=16).flatten(2).transpose(1, 2)
+    x = torch.cat((P["cls_token"].expand(B, -1, -1), P["dist_token"].expand(B, -1, -1), x), dim=1) + P["pos_embed"]
+    x = drop(x, 0, 0, p, s, B * N, D)
+    for i in range(2):
+        g = lambda n: P[f"blocks.{i}.{n}"]
+        dp1, dp2 = dps[i] if dps is not None and dps[i] is not None else (torch.ones(B, device=dev),) * 2
+        h = F.layer_norm(x, (D,), g("norm1.weight"), g("norm1.bias"), 1e-6)
+        qkv = F.linear(h, g("attn.qkv.weight"), g("attn.qkv.bias")).reshape(B, N, 3, H, 64).permute(2, 0, 3, 1, 4)
+        q, k, v = qkv[0], qkv[1], qkv[2]
+        a = drop(((q @ k.transpose(-2, -1)) * 0.125).softmax(dim=-1), 1, i, p_attn, s_a, B * H * N, N)
+        o = (a @ v).transpose(1, 2).reshape(B, N, D)
+        y = drop(F.linear(o, g("attn.proj.weight"), g("attn.proj.bias")), 2, i, p, s, B * N, D)
+        x = x + dp1.view(B, 1, 1) * y
+        h = F.layer_norm(x, (D,), g("norm2.weight"), g("norm2.bias"), 1e-6)
+        h = drop(F.gelu(F.linear(h, g("mlp.fc1.weight"), g("mlp.fc1.bias"))), 3, i, p, s, B * N, 1536)
+        y = drop(F.linear(h, g("mlp.fc2.weight"), g("mlp.fc2.bias")), 4, i, p, s, B * N, D)
+        x = x + dp2.view(B, 1, 1) * y
+    x = F.layer_norm(x, (D,), P["norm.weight"], P["norm.bias"], 1e-6)
+    return F.linear(x[:, 0], P["head.weight"], P["head.bias"]), F.linear(x[:, 1], P["head_dist.weight"], P["head_dist.bias"]), P
+
+
+def rel_l2(a, b):
+    return float((a.double() - b.double().view_as(a)).norm() / b.double().norm().clamp_min(1e-300))
+
+
+WITNESS_FLOOR = 0.05
+
+
+def test_bf16_block_path_backward_uses_its_forwards_masks(dev, model_case):
+    """The bf16 model (devit_encoder_fwd_drop / devit_block_bwd_drop) against the fp32 torch statement fed the numpy mirror's masks, by the
+    relative L2 DISTANCE of every witness gradient.  The bar comes from the statement alone: for each site and block the statement is run
+    once more with that site's backward mask taken from block + 1; d_wrong is that run's distance from the right statement, per
+    parameter tensor.  A site's witnesses are the three (block, tensor) pairs with the largest d_wrong, chosen so that every block has
+    one: each block's largest first, then the largest of the rest.  Every witness must have d_wrong >= 0.05, and the model must stay below
+    d_wrong / 3 on it.  Site 0 (pos_drop) exists once, at block 0.  (The attention mask moves only what lies before the softmax of its
+    own block: two tensors per block by more than 0.05, which is why the three are taken per site and not per block.)"""
+    from devit_amd import de_vit
+    c = model_case
+    w = c["w"]
+
+    def grads_of(wrong=None):
+        lo, lk, P = mirror_statement(c["state"], c["img"], c["dps"], MODEL_SEED, 0.1, 0.1, dev, wrong)
+        ((lo * w[0]).sum() + (lk * w[1]).sum()).backward()
+        return {n: t.grad.detach() for n, t in P.items() if t.grad is not None}
+    right = grads_of()
+    m = make_model(dev, "bf16")
+    m.load_state_dict(c["state"])
+    orig = de_vit.draw_dp_scales
+    de_vit.draw_dp_scales = lambda *a, **k: c["dps"]
+    try:
+        lo, lk = m(c["img"])
+    finally:
+        de_vit.draw_dp_scales = orig
+    ((lo * w[0]).sum() + (lk * w[1]).sum()).backward()
+    torch.cuda.synchronize()
+    model = {n: p.grad.detach() for n, p in m.named_parameters() if p.grad is not None}
+    assert set(model) == set(right)
+    d_model = {n: rel_l2(model[n], right[n]) for n in right}
+    bad = []
+    for site in range(5):
+        runs = {}
+        for block in ((0,) if site == 0 else (0, 1)):
+            wrong = grads_of((site, block))
+            runs[block] = {n: rel_l2(wrong[n], right[n]) for n in right}
+        pairs = sorted(((d, b, n) for b, dw in runs.items() for n, d in dw.items()), reverse=True)
+        witnesses = [max(p for p in pairs if p[1] == b) for b in runs]
+        witnesses += [p for p in pairs if p not in witnesses][:3 - len(witnesses)]
+        assert len(witnesses) == 3 and {b for _, b, _ in witnesses} == set(runs)
+        for d_wrong, block, n in witnesses:
+            print(f"site {site} block {block} witness {n}: d_wrong {d_wrong:.4f} d_model {d_model[n]:.4f}")
+            assert d_wrong >= WITNESS_FLOOR, (site, block, n, d_wrong)
+            if not chk(d_model[n], d_wrong / 3.0, name=f"dropout_bounds/block_path/site{site}-blk{block}/{n}"):
+                bad.append((site, block, n, d_model[n], d_wrong))
+    assert not bad, bad
