@@ -184,6 +184,11 @@ SIGNATURES = {
     "devit_token_kldiv": (_I, [_P, _P, _Z, _I, _P, _P, _I, _P]),
     "devit_relation_stats": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "devit_relation_grad": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "devit_add_scale_cast_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "devit_hid_normalize": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "devit_hid_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "devit_hid_grad": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
+    "devit_hid_normalize_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "devit_gemm_f32": (_I, [_P, _LL, _LL, _LL, _LL, _P, _LL, _LL, _LL, _LL, _I, _I, _I, _I, _I, _LL, _LL, _I, _I, _F, _P, _I,
                             C.POINTER(Epilogue), _P]),
     "devit_softmax_rows_f32": (_I, [_P, _I, _I, _I, _F, _P, _P]),

@@ -303,9 +303,10 @@ def block_drop_rates(blocks, training):
 
 
 def run_blocks(blocks, x, training, want_qkv, want_att, want_enc, grad_ready=None, dp_scales="draw", exact_gelu=0,
-               precision="bf16", qkv_pad_layers=None, lean_tokens=0, dropout_seed=None):
+               precision="bf16", qkv_pad_layers=None, lean_tokens=0, dropout_seed=None, enc_layers=None):
     """Run a list of Blocks as one EncoderFn node.  Returns (x, qkv tuples, att tensors, enc tensors).
-    lean_tokens > 0 (see lean_tail): x comes back as [B, lean_tokens, D] and the last block's qkv entry is None."""
+    lean_tokens > 0 (see lean_tail): x comes back as [B, lean_tokens, D] and the last block's qkv entry is None.
+    enc_layers (with want_enc): the blocks whose output is handed out; the other entries of the enc list are None (None: every block)."""
     L.require_device(x)
     if x.dtype != torch.float32:
         x = x.float()
@@ -323,10 +324,11 @@ def run_blocks(blocks, x, training, want_qkv, want_att, want_enc, grad_ready=Non
     rates = block_drop_rates(blocks, training)
     if rates is not None and precision == "f16":
         raise L.DevitError('precision="f16" is the frozen-teacher forward: it has no dropout; put the model in eval() mode')
-    lean = lean_tokens if (lean_tokens and nb >= 2 and precision != "f32" and not want_att and not want_enc and rates is None and
+    enc_last = want_enc and (enc_layers is None or nb - 1 in enc_layers)      # (a selector that leaves the last block out keeps the lean tail)
+    lean = lean_tokens if (lean_tokens and nb >= 2 and precision != "f32" and not want_att and not enc_last and rates is None and
                            (not want_qkv or (qkv_pad_layers is not None and nb - 1 not in qkv_pad_layers))) else 0
     cfg = ops.EncoderCfg(bps, training, dp_scales, want_qkv, want_att, want_enc, exact_gelu=exact_gelu,
-                         grad_ready=grad_ready, qkv_pad_layers=qkv_pad_layers, lean_tokens=lean)
+                         grad_ready=grad_ready, qkv_pad_layers=qkv_pad_layers, lean_tokens=lean, enc_layers=enc_layers if want_enc else None)
     cfg.grad_enabled = torch.is_grad_enabled()
     if rates is not None:
         cfg.drop = (draw_dropout_seed(dropout_seed), rates)
@@ -429,6 +431,9 @@ class VisionTransformer(nn.Module):
             self.resize_att_mlp = nn.Linear(self.embed_dim, self.resize_dim)
             self.resize_encoder_mlp = nn.Linear(self.embed_dim, self.resize_dim)
         self.grad_ready = None      # set by devit_amd.ddp.BucketedGradReducer
+        # with output_encoders=True: the set of blocks whose output the 'encoder' list holds (the other entries are None); None: every block.
+        # A selector without the last block keeps the lean tail (lean_tail) and the arenas of the blocks nobody reads out of the result.
+        self.enc_layers = None
         self.exact_gelu = 0
         # "bf16": the training path.  "f16": the same kernels with IEEE f16 operands / stored activations, forward only --
         # for frozen teachers (DeiT-B logits 1.1e-3 from fp32 instead of 6.8e-3; step 1.4 % slower: both measured).  "f32": exact-fp32 parity
@@ -540,7 +545,8 @@ class VisionTransformer(nn.Module):
                                           grad_ready=self.grad_ready, exact_gelu=self.exact_gelu,
                                           precision=self.precision,
                                           qkv_pad_layers=getattr(self, "qkv_pad_layers", None),
-                                          lean_tokens=self.num_tokens if getattr(self, "_lean_tail", False) else 0, dropout_seed=seed)
+                                          lean_tokens=self.num_tokens if getattr(self, "_lean_tail", False) else 0, dropout_seed=seed,
+                                          enc_layers=getattr(self, "enc_layers", None))
         depth = len(self.blocks)
         encoder_outputs = [emb] if output_emb else []
         encoder_outputs += encs if output_encoders else [None] * depth

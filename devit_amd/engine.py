@@ -30,6 +30,27 @@ def _hand_over(out, main):
             continue                      # tagged by the composite path: lives in the main stream's pool already
         if packed.untyped_storage().nbytes() <= packed.numel() * packed.element_size():    # its own allocation
             packed.record_stream(main)
+    for t in out.get('encoder') or ():    # (hid_gama > 0: one block's hidden states -- a view of its arena on the 16-bit path, as the qkv buffers)
+        if t is not None and t.untyped_storage().nbytes() <= t.numel() * t.element_size():
+            t.record_stream(main)
+
+
+def _hid_layer(m):
+    """The block whose output enters the hidden-state relation loss: the one whose q/k/v enter the relation losses (engine.py:91-92)."""
+    return len(m.blocks) // 2 - 1
+
+
+def _forward_outputs(m, samples):
+    """m(samples) with the outputs the step reads: q/k/v, and -- when the step asked for it (m._hid_request, set by distill_forward /
+    TeacherLookahead for hid_gama > 0) -- the 'encoder' output of the middle block alone (enc_layers), which keeps the lean tail."""
+    vit = m.module if hasattr(m, "module") else m
+    if not getattr(vit, "_hid_request", False):
+        return m(samples, output_qkv=True)
+    prev, vit.enc_layers = getattr(vit, "enc_layers", None), {_hid_layer(vit)}
+    try:
+        return m(samples, output_qkv=True, output_encoders=True)
+    finally:
+        vit.enc_layers = prev
 
 
 def _side_forward(teacher_model, samples, main, side):
@@ -37,17 +58,27 @@ def _side_forward(teacher_model, samples, main, side):
     prev, ops.ARENA_ALLOC_STREAM = ops.ARENA_ALLOC_STREAM, main
     try:
         with torch.cuda.stream(side), torch.no_grad(), de_vit.lean_tail(teacher_model):
-            return teacher_model(samples, output_qkv=True)
+            return _forward_outputs(teacher_model, samples)
     finally:
         ops.ARENA_ALLOC_STREAM = prev
 
 
 def distill_forward(model, teacher_model, samples, targets, gama=(0.2, 0.1, 0.3), kind="hard", alpha=0.5, tau=1.0,
-                    criterion=None, dp_scales="draw", teacher_outputs=None, after_student=None):
+                    criterion=None, dp_scales="draw", teacher_outputs=None, after_student=None, hid_gama=0.0):
     """One DEKD forward.  Returns dict(loss, cls_loss, q_loss, k_loss, v_loss, logits, teacher_logits).
     teacher_outputs: the teacher's outputs for `samples` if they were computed ahead (TeacherLookahead).
-    after_student: called once the student's forward is enqueued (TeacherLookahead.launch of the NEXT batch)."""
+    after_student: called once the student's forward is enqueued (TeacherLookahead.launch of the NEXT batch).
+    hid_gama > 0: loss += hid_gama * cal_hid_relation_loss of the middle blocks' hidden states (utils/losses.py:295-304; the layer pair the q/k/v
+    relation losses use), returned as `hid_loss`; student and teacher then hand out that one block's 'encoder' output (enc_layers).  0: the step as
+    it was, dict and all."""
     vit = model.module if hasattr(model, "module") else model
+    hid_gama = float(hid_gama)
+    if not hid_gama >= 0.:
+        raise ValueError(f"hid_gama must be >= 0, got {hid_gama}")
+    hid = hid_gama > 0.
+    vit._hid_request = hid
+    if teacher_outputs is None:          # (a TeacherLookahead made its request when it was built)
+        (teacher_model.module if hasattr(teacher_model, "module") else teacher_model)._hid_request = hid
     # only the middle block's q/k/v enter the relation loss (engine.py:91-100): the other blocks' packed qkv buffers
     # need no zeroed overhang rows
     for m in (vit, teacher_model):
@@ -59,9 +90,9 @@ def distill_forward(model, teacher_model, samples, targets, gama=(0.2, 0.1, 0.3)
     # only the logits and the middle block's q/k/v are read below: the last block runs on its two token rows (de_vit.lean_tail)
     with de_vit.lean_tail(vit):
         if dp_scales != "draw":   # explicit DropPath masks (parity tests)
-            outputs = _forward_with_dp(vit, samples, dp_scales)
+            outputs = _forward_with_dp(vit, samples, dp_scales, hid)
         else:
-            outputs = model(samples, output_qkv=True)                               # engine.py:70
+            outputs = _forward_outputs(model, samples)                              # engine.py:70
     logits, qkvs = outputs['output'], outputs['qkv']
     if after_student is not None:
         after_student()
@@ -85,8 +116,18 @@ def distill_forward(model, teacher_model, samples, targets, gama=(0.2, 0.1, 0.3)
         q_loss, k_loss, v_loss = losses.relation_losses_packed(qkvs[sl // 2 - 1], teacher_qkvs[tl // 2 - 1])
         q_loss, k_loss, v_loss = q_loss / sl, k_loss / sl, v_loss / sl                  # :102-104
         loss = cls_loss + float(gama[0]) * q_loss + float(gama[1]) * k_loss + float(gama[2]) * v_loss   # :105-106
-    return dict(loss=loss, cls_loss=cls_loss, q_loss=q_loss, k_loss=k_loss, v_loss=v_loss, logits=logits,
-                teacher_logits=teacher_logits)
+    out = dict(loss=loss, cls_loss=cls_loss, q_loss=q_loss, k_loss=k_loss, v_loss=v_loss, logits=logits,
+               teacher_logits=teacher_logits)
+    if hid:
+        s_enc, t_enc = outputs.get('encoder'), teacher_outputs.get('encoder')
+        s_hid = s_enc[sl // 2 - 1] if s_enc else None
+        t_hid = t_enc[tl // 2 - 1] if t_enc else None
+        if s_hid is None or t_hid is None:
+            raise RuntimeError("distill_forward(hid_gama > 0): the %s outputs hold no hidden states of the middle block -- teacher outputs computed "
+                               "ahead must come from TeacherLookahead(teacher, hid=True)" % ("student's" if s_hid is None else "teacher's"))
+        out['hid_loss'] = losses.cal_hid_relation_loss([s_hid], [t_hid], exact=getattr(vit, "precision", "bf16") == "f32")
+        out['loss'] = loss + hid_gama * out['hid_loss']
+    return out
 
 
 _side_stream = {}
@@ -107,7 +148,7 @@ def _teacher_forward(teacher_model, samples):
     forward has drained, so the tail rounds of one model's GEMMs are filled by the other's workgroups."""
     if os.environ.get("DEVIT_TEACHER_STREAM", "1") != "1" or not samples.is_cuda:
         with torch.no_grad(), de_vit.lean_tail(teacher_model):
-            return teacher_model(samples, output_qkv=True)
+            return _forward_outputs(teacher_model, samples)
     main = torch.cuda.current_stream()
     side = _side_stream.setdefault(samples.device.index, torch.cuda.Stream())
     out = _side_forward(teacher_model, samples, main, side)   # NOTE: call BEFORE the student forward is enqueued to overlap
@@ -157,10 +198,12 @@ class TeacherLookahead:
         for k: t_out = look.take(batch_k); look.submit(batch_k+1); distill_forward(..., batch_k, teacher_outputs=t_out)
     """
 
-    def __init__(self, teacher_model):
+    def __init__(self, teacher_model, hid=False):
+        """hid: the forwards also hand out the middle block's hidden states (distill_forward(hid_gama > 0) reads them)"""
         self.teacher = teacher_model
         if getattr(teacher_model, "qkv_pad_layers", None) is None and hasattr(teacher_model, "blocks"):
             teacher_model.qkv_pad_layers = {len(teacher_model.blocks) // 2 - 1}
+        (teacher_model.module if hasattr(teacher_model, "module") else teacher_model)._hid_request = bool(hid)
         self._pending = None
 
     def submit(self, samples, defer=False):
@@ -253,14 +296,15 @@ class _PreparedBatches:
             cur = nxt
 
 
-def _forward_with_dp(vit, samples, dp_scales):
+def _forward_with_dp(vit, samples, dp_scales, hid=False):
     x = vit.embed(samples)
-    xo, qkvs, _, _ = de_vit.run_blocks(list(vit.blocks), x, vit.training, True, False, False,
-                                       grad_ready=vit.grad_ready, dp_scales=dp_scales, precision=vit.precision,
-                                       qkv_pad_layers=getattr(vit, "qkv_pad_layers", None),
-                                       lean_tokens=vit.num_tokens if getattr(vit, "_lean_tail", False) else 0)
+    xo, qkvs, _, encs = de_vit.run_blocks(list(vit.blocks), x, vit.training, True, False, hid,
+                                          grad_ready=vit.grad_ready, dp_scales=dp_scales, precision=vit.precision,
+                                          qkv_pad_layers=getattr(vit, "qkv_pad_layers", None),
+                                          lean_tokens=vit.num_tokens if getattr(vit, "_lean_tail", False) else 0,
+                                          enc_layers={_hid_layer(vit)} if hid else None)
     heads = vit._tokens_and_logits(xo, True)
-    return {'output': (heads[1], heads[2]) if vit.training else (heads[1] + heads[2]) / 2, 'qkv': qkvs}
+    return {'output': (heads[1], heads[2]) if vit.training else (heads[1] + heads[2]) / 2, 'qkv': qkvs, 'encoder': encs}
 
 
 def train_1epoch_qkv(model, teacher_model, criterion, data_loader, optimizer, device, epoch, loss_scaler, log, args,
@@ -270,16 +314,17 @@ def train_1epoch_qkv(model, teacher_model, criterion, data_loader, optimizer, de
     from .utils import MetricLogger, SmoothedValue
     model.train(True)
     metric_logger = MetricLogger(delimiter="  ")
-    for name in ('lr', 'cls_loss', 'q_loss', 'k_loss', 'v_loss'):
+    hid_gama = float(getattr(args, "hid_gama", 0.0) or 0.0)        # --hid-gama: the hidden-state relation term (0: the step and its log line as they were)
+    for name in ('lr', 'cls_loss', 'q_loss', 'k_loss', 'v_loss') + (('hid_loss',) if hid_gama > 0 else ()):
         metric_logger.add_meter(name, SmoothedValue(window_size=1, fmt='{value:.6f}'))
     header = 'Epoch: [{}]'.format(epoch)
     step = 0
     lookahead = bool(getattr(args, "teacher_lookahead", True)) and device is not None and str(device).startswith("cuda")
-    batches = _PreparedBatches(data_loader, device, mixup_fn, TeacherLookahead(teacher_model) if lookahead else None,
+    batches = _PreparedBatches(data_loader, device, mixup_fn, TeacherLookahead(teacher_model, hid=hid_gama > 0) if lookahead else None,
                                row_dtypes=row_dtypes_for(model, teacher_model))
     for samples, targets, teacher_out in metric_logger.log_every(batches, print_freq, header):
         out = distill_forward(model, teacher_model, samples, targets, gama=args.gama, criterion=criterion,
-                              teacher_outputs=teacher_out, after_student=batches.launch_teacher)
+                              teacher_outputs=teacher_out, after_student=batches.launch_teacher, hid_gama=hid_gama)
         loss = out['loss']
         log_now = (step % print_freq == 0)
         if log_now:
@@ -289,6 +334,8 @@ def train_1epoch_qkv(model, teacher_model, criterion, data_loader, optimizer, de
                 sys.exit(1)
             metric_logger.update(cls_loss=out['cls_loss'].item(), q_loss=out['q_loss'].item(),
                                  k_loss=out['k_loss'].item(), v_loss=out['v_loss'].item(), loss=loss_value)
+            if hid_gama > 0:
+                metric_logger.update(hid_loss=out['hid_loss'].item())
         optimizer.zero_grad()
         loss_scaler(loss, optimizer, clip_grad=max_norm, parameters=model.parameters())
         if model_ema is not None:

@@ -3,6 +3,7 @@
   DistillLoss(base_criterion, distillation_type, alpha, tau)(outputs, teacher_outputs, labels)   :122-177
   feature_relation_loss(teacher_feature, student_feature)                                        :307-328
   relation_losses_packed(student_qkv, teacher_qkv)   -- the three q/k/v losses of engine.py:95 in one node
+  cal_hid_relation_loss(stu_hid_list, tea_hid_list)                                              :295-304
 """
 import torch
 import torch.nn as nn
@@ -144,6 +145,19 @@ def feature_relation_loss(teacher_feature, student_feature):
         t_buf = _RepackFn.apply(teacher_feature)
     losses = ops.RelationLossFn.apply(s_buf, t_buf, B, N, hd_s, hd_t)
     return losses[0]
+
+
+def cal_hid_relation_loss(stu_hid_list, tea_hid_list, exact=False):
+    """utils/losses.py:295-304: for every (student, teacher) pair of hidden states [B, N, Ds] / [B, N, Dt] (the 'encoder' outputs of the models;
+    the lists are walked with zip), rows normalised with x / max(|x|, 1e-12), per-image Grams h^ h^T, mean((G_s - G_t)^2) over B N N; the sum over
+    the pairs divided by len(stu_hid_list).  The gradient goes to the student.  N <= 208, widths multiples of 64 up to 1024.
+    exact=True (what engine sets for a precision="f32" student): fp32 h^ and exact-fp32 Grams / products instead of the bf16 MFMA GEMMs."""
+    layers = len(stu_hid_list)
+    loss = 0.
+    for s, t in zip(stu_hid_list, tea_hid_list):
+        L.require_device(s)
+        loss = loss + ops.HidRelationLossFn.apply(s, t.detach(), layers, bool(exact))
+    return loss
 
 
 class DistillationLoss(nn.Module):

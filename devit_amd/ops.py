@@ -453,8 +453,10 @@ class EncoderCfg:
     """Non-tensor arguments of EncoderFn."""
 
     def __init__(self, blocks, training, dp_scales, want_qkv, want_att, want_enc, eps=1e-6, exact_gelu=0,
-                 grad_ready=None, qkv_pad_layers=None, lean_tokens=0):
+                 grad_ready=None, qkv_pad_layers=None, lean_tokens=0, enc_layers=None):
         self.blocks, self.training, self.dp_scales = blocks, training, dp_scales
+        # with want_enc: the blocks whose output is handed out in the 'encoder' list (None: every block); the others come back as None
+        self.enc_layers = None if enc_layers is None else frozenset(enc_layers)
         self.want_qkv, self.want_att, self.want_enc = want_qkv, want_att, want_enc
         self.eps, self.exact_gelu, self.grad_ready = eps, exact_gelu, grad_ready
         # blocks whose packed qkv output gets the zeroed overhang rows RelationLossFn reads (None: every block)
@@ -762,10 +764,26 @@ def _wgrads_struct(bp):
     return g
 
 
-def _encoder_backward_composite(run, cfg, dx, dqkvs, defer):
-    """dx: fp32 [B,N,D] contiguous gradient of the encoder output.  Returns the gradient of the encoder input."""
+def _encoder_backward_composite(run, cfg, dx, dqkvs, defer, dencs=None):
+    """dx: fp32 [B,N,D] contiguous gradient of the encoder output.  Returns the gradient of the encoder input.
+    dencs: None, or per block of the run the fp32 [B,N,D] gradient that arrived for its exposed output (None where none did): added to the
+    residual-stream gradient before that block's backward runs (ops_f32.EncoderF32Fn.backward).  The top block's is added to dx here; block
+    i < nb - 1 gets its through devit_add_scale_cast_bf16 between the calls for blocks i + 1 and i: dx_in += denc_i, and the bf16 branch
+    gradient g of block i, which block i + 1's LayerNorm backward wrote from the old dx_in, is rewritten as bf16(dp2_i * dx_in) -- one rounding of
+    the sum.  Block i + 1 then hands down no fc2 bias gradient (it would be the column sums of the stale g): block i takes its own."""
     B, N, D = run.dims
     M, dev, nb = B * N, dx.device, run.nb
+    if dencs is not None and not any(d is not None for d in dencs):
+        dencs = None
+    if dencs is not None:
+        for d in dencs:
+            if d is not None and (tuple(d.shape) != (B, N, D) or d.dtype != F32):
+                raise L.DevitError(f"EncoderFn.backward: the gradient of an 'encoder' output must be fp32 {(B, N, D)}, got {d.dtype} {tuple(d.shape)}")
+        if dencs[nb - 1] is not None:
+            dx = dx + dencs[nb - 1]
+
+    def injected(i):                     # block i's incoming gradient gets an exposed-output term between the calls
+        return dencs is not None and 0 <= i < nb - 1 and dencs[i] is not None
     mp = pad_rows(M)
     sz, offs, tot = _bwd_sizes(B, N, D, {(run.weights[i].attn_width, run.weights[i].hidden) for i in range(nb)})
     # Workspace: the transient buffers shared by all blocks + two fp32 dx buffers that alternate + per-block SLOTS for what a deferred
@@ -814,8 +832,8 @@ def _encoder_backward_composite(run, cfg, dx, dqkvs, defer):
         masked = run.drops is not None and run.drops[i].thr > 0        # this block masks its g2 and takes fc2's bias gradient from it
         if masked:
             io.g2_bias_done = 0
-        below = run.drops is not None and prev is not None and run.drops[i - 1].thr > 0
-        if below:                        # ... so the block above hands it none
+        below = (run.drops is not None and prev is not None and run.drops[i - 1].thr > 0) or injected(i - 1)
+        if below:                        # ... so the block above hands it none (nor when the g it writes for the block below is rewritten)
             io.prev_fc2_b_grad = None
         io.dqkv_add = _p(dq)
         wg = _wgrads_struct(bp)
@@ -825,6 +843,14 @@ def _encoder_backward_composite(run, cfg, dx, dqkvs, defer):
         else:
             call("devit_block_bwd", C.byref(run.weights[i]), C.byref(run.acts[i]), C.byref(wg), C.byref(io), B, N, D, cfg.eps, st)
         cur_dx, g_bias_done = dx_ptrs[out_slot], 1 if (prev is not None and not below) else 0
+        if injected(i - 1):
+            # On `st`, behind the LayerNorm backward that wrote dx_in and g_prev and in front of everything that reads them: block i - 1's call
+            # is enqueued after this launch, its weight-gradient side stream forks from an event recorded on `st` at that time
+            # (csrc/encoder.hip: fork), and the deferred jobs that read this g slot are launched on `st` later still.
+            add = dencs[i - 1].contiguous()
+            if add.data_ptr() % 16:
+                add = add.clone()
+            call("devit_add_scale_cast_bf16", C.c_void_p(cur_dx), ptr(add), C.c_void_p(base + slot(i - 1)[0]), C.c_void_p(io.prev_dp2), N, M, D, st)
         defer.add(bp, [L.WgradJob.from_buffer_copy(got[k]) for k in range(ngot.value)], (dq,))
         if defer.last_of_group(i):
             defer.flush(mp)
@@ -845,14 +871,20 @@ class EncoderFn(torch.autograd.Function):
                                "or compact it with shrink.compact(model, trainable=True) to train through the compacted blocks")
         nb = len(cfg.blocks)
         # lean tail (EncoderCfg.lean_tokens): the last block runs on the token rows only
-        lean = cfg.lean_tokens if (cfg.lean_tokens and nb >= 2 and not cfg.want_att and not cfg.want_enc and cfg.drop is None) else 0
+        # (with an enc_layers selector the tail stays lean unless the last block's output is one of those handed out)
+        enc_sel = cfg.enc_layers if cfg.want_enc else None
+        enc_last = cfg.want_enc and (enc_sel is None or nb - 1 in enc_sel)
+        lean = cfg.lean_tokens if (cfg.lean_tokens and nb >= 2 and not cfg.want_att and not enc_last and cfg.drop is None) else 0
         nbody = nb - 1 if lean else nb
         dp_last = cfg.dp_scales[nb - 1] if cfg.dp_scales is not None else None
         ctx.tail = None
         run = _encoder_forward_composite(x, cfg, need_grad, nbody)
         qkvs = [v["qkv"] for v in run.views] if cfg.want_qkv else []
         atts = [v["att"] for v in run.views] if cfg.want_att else []
-        encs = [run.views[i]["x2"].clone() if i == nb - 1 else run.views[i]["x2"] for i in range(nb)] if cfg.want_enc else []
+        if cfg.want_enc and enc_sel is not None:      # the selected blocks' outputs, None for the others (the lean last block is never selected)
+            encs = [None if i not in enc_sel else run.views[i]["x2"].clone() if i == nb - 1 else run.views[i]["x2"] for i in range(nb)]
+        else:
+            encs = [run.views[i]["x2"].clone() if i == nb - 1 else run.views[i]["x2"] for i in range(nb)] if cfg.want_enc else []
         ctx.cfg, ctx.need_grad = cfg, need_grad
         ctx.run = run if need_grad else None
         ctx.counts = (len(qkvs), len(atts), len(encs))
@@ -871,9 +903,9 @@ class EncoderFn(torch.autograd.Function):
             raise L.DevitError("EncoderFn.backward called but the forward ran without grad bookkeeping")
         nq, na, ne = ctx.counts
         dqkvs, datts, dencs = dothers[:nq], dothers[nq:nq + na], dothers[nq + na:]
-        if any(d is not None for d in datts) or any(d is not None for d in dencs):
-            raise L.DevitError("gradients into the exposed 'attention' / 'encoder' outputs are not taken on the 16-bit path: "
-                               'run the model with precision="f32" (ops_f32.EncoderF32Fn implements both)')
+        if any(d is not None for d in datts):
+            raise L.DevitError("gradients into the exposed 'attention' outputs are not taken on the 16-bit path: "
+                               'run the model with precision="f32" (ops_f32.EncoderF32Fn implements them)')
         nb = len(cfg.blocks)
         nparams = 12 * nb
         if ctx.tail is not None:          # lean tail: dx is the [B, ntok, D] gradient of the token rows
@@ -896,7 +928,8 @@ class EncoderFn(torch.autograd.Function):
         B, N, D = run.dims
         if dx is None:
             dx = torch.zeros((B, N, D), dtype=F32, device=run.x.device)
-        dx_in = _encoder_backward_composite(run, cfg, dx.contiguous(), dqkvs if nq else None, defer)
+        # (a lean forward hands out no output of its last block: dencs[nb] is None there, and the body's top block is nb - 1)
+        dx_in = _encoder_backward_composite(run, cfg, dx.contiguous(), dqkvs if nq else None, defer, list(dencs[:nb]) if ne else None)
         return (dx_in, None) + (None,) * nparams
 
 
@@ -1419,3 +1452,100 @@ class RelationLossFn(torch.autograd.Function):
                  a_bs=256 * 256, b_bs=N * 3 * Ds, out_bs=N * 3 * Ds, m_valid=N)
         ctx.grams = ctx.stats = None
         return d, None, None, None, None, None
+
+
+# ---- hidden-state relation loss (utils/losses.py:295-304, cal_hid_relation_loss) -- csrc/hid.hip ----
+HID_EPS = 1e-12       # torch.nn.functional.normalize's default eps
+
+
+def hid_normalize(h, exact=False):
+    """fp32 [B, N, D] -> (h^ = h / max(|h|, 1e-12) packed as bf16 (exact: fp32) [pad_rows(B N) + qkv_pad_rows(N), ld], ld = D rounded up to 128, with zero
+    pad columns and zero rows behind B N: what the 256-row Gram windows and the 128-wide GEMM tiles read; inv fp32 [B N] = 1 / max(|h|, 1e-12))."""
+    L.require_device(h)
+    if h.dim() != 3:
+        raise L.DevitError(f"cal_hid_relation_loss: hidden states are [B, N, D], got {tuple(h.shape)}")
+    B, N, D = h.shape
+    h = h.contiguous().float()
+    if h.data_ptr() % 16:
+        h = h.clone()
+    ld = (D + 127) // 128 * 128
+    rows = pad_rows(B * N) + qkv_pad_rows(N)
+    hn = torch.empty((rows, ld), dtype=F32 if exact else BF16, device=h.device)
+    inv = torch.empty(B * N, dtype=F32, device=h.device)
+    call("devit_hid_normalize", ptr(h), ptr(hn), ptr(inv), B, N, D, ld, rows, int(exact), HID_EPS, stream_ptr())
+    return hn, inv
+
+
+def hid_gram(hn, B, N, D, exact=False):
+    """Per-image Grams h^ h^T of a hid_normalize buffer as padded fp32 [B, 256, 256] (entries outside N x N: the neighbouring image's rows, or,
+    in exact mode, zeros: nobody reads them)."""
+    ld = hn.shape[1]
+    if exact:
+        from .ops_f32 import sgemm
+        g = torch.zeros((B, 256, 256), dtype=F32, device=hn.device)
+        sgemm(hn, ld, 1, hn, ld, 1, N, N, D, out=g, ldc=256, batch=B, a_bo=N * ld, b_bo=N * ld, c_bo=65536)
+        return g
+    g = torch.empty((B, 256, 256), dtype=F32, device=hn.device)
+    gemm(hn, ld, 0, hn, ld, 0, 256, 256, ld, kind=L.EPI_STORE_F32, out=g, ldc=256, batch=B, a_bs=N * ld, b_bs=N * ld, out_bs=65536)
+    return g
+
+
+def hid_stats(gs, gt, B, N, layers=1):
+    """fp32 [1]: sum (G_s - G_t)^2 / (B N^2 layers)"""
+    row_sq = torch.empty(B * N, dtype=F32, device=gs.device)
+    loss = torch.empty(1, dtype=F32, device=gs.device)
+    call("devit_hid_stats", ptr(gs), ptr(gt), B, N, 256, layers, ptr(row_sq), ptr(loss), stream_ptr())
+    return loss
+
+
+def hid_grad(gs, gt, upstream, B, N, layers=1, exact=False):
+    """S = (4 upstream / (B N^2 layers)) (G_s - G_t): bf16 (exact: fp32) [B, 256, 256], zero outside N x N; upstream: fp32 device scalar or None (1)"""
+    S = torch.empty((B, 256, 256), dtype=F32 if exact else BF16, device=gs.device)
+    call("devit_hid_grad", ptr(gs), ptr(gt), ptr(upstream), B, N, 256, layers, ptr(S), int(exact), stream_ptr())
+    return S
+
+
+def hid_dhn(S, hn, B, N, D, exact=False):
+    """dh^ = S h^ per image: fp32 [B N, ld] (fp32 accumulation over the 256-wide window; S is zero there outside N x N)"""
+    ld = hn.shape[1]
+    if exact:
+        from .ops_f32 import sgemm
+        dhn = torch.zeros((B * N, ld), dtype=F32, device=hn.device)
+        sgemm(S, 256, 1, hn, 1, ld, N, D, N, out=dhn, ldc=ld, batch=B, a_bo=65536, b_bo=N * ld, c_bo=N * ld)
+        return dhn
+    dhn = torch.empty((B * N, ld), dtype=F32, device=hn.device)
+    gemm(S, 256, 0, hn, ld, 1, 256, ld, 256, kind=L.EPI_STORE_F32, out=dhn, ldc=ld, batch=B, a_bs=65536, b_bs=N * ld, out_bs=N * ld,
+         m_valid=N)
+    return dhn
+
+
+def hid_normalize_bwd(hn, dhn, inv, B, N, D):
+    """dh = inv (dh^ - h^ (h^ . dh^)): fp32 [B, N, D]"""
+    dh = torch.empty((B, N, D), dtype=F32, device=hn.device)
+    call("devit_hid_normalize_bwd", ptr(hn), ptr(dhn), ptr(inv), ptr(dh), B, N, D, hn.shape[1], int(hn.dtype == F32), stream_ptr())
+    return dh
+
+
+class HidRelationLossFn(torch.autograd.Function):
+    """One (student, teacher) pair of cal_hid_relation_loss: mean((G_s - G_t)^2) / layers with G = h^ h^T per image of the row-normalised
+    hidden states.  s: fp32 [B, N, Ds], t: fp32 [B, N, Dt]; the gradient goes to the student.  exact: fp32 h^, Grams and products
+    (devit_gemm_f32) instead of one bf16 rounding of h^ and of S."""
+
+    @staticmethod
+    def forward(ctx, s, t, layers, exact):
+        B, N, Ds = s.shape
+        if tuple(t.shape[:2]) != (B, N):
+            raise L.DevitError(f"cal_hid_relation_loss: student {tuple(s.shape)} and teacher {tuple(t.shape)} differ in batch or tokens")
+        hs, inv_s = hid_normalize(s, exact)
+        ht, _ = hid_normalize(t, exact)
+        gs, gt = hid_gram(hs, B, N, Ds, exact), hid_gram(ht, B, N, t.shape[2], exact)
+        ctx.keep, ctx.meta = (hs, inv_s, gs, gt), (B, N, Ds, layers, exact)
+        return hid_stats(gs, gt, B, N, layers)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        hs, inv_s, gs, gt = ctx.keep
+        B, N, Ds, layers, exact = ctx.meta
+        ctx.keep = None
+        S = hid_grad(gs, gt, g.contiguous().float(), B, N, layers, exact)
+        return hid_normalize_bwd(hs, hid_dhn(S, hs, B, N, Ds, exact), inv_s, B, N, Ds), None, None, None

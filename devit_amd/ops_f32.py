@@ -189,7 +189,9 @@ class EncoderF32Fn(torch.autograd.Function):
                 qkvs.append(qkv)
             if cfg.want_att:
                 atts.append(att)
-            if cfg.want_enc:
+            if cfg.want_enc and cfg.enc_layers is not None and i not in cfg.enc_layers:
+                encs.append(None)
+            elif cfg.want_enc:
                 encs.append(x.clone() if i == len(cfg.blocks) - 1 else x)
         ctx.cfg, ctx.saved, ctx.need_grad = cfg, saved, need_grad
         ctx.counts = (len(qkvs), len(atts), len(encs))

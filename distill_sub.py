@@ -31,6 +31,13 @@ from devit_amd import ddp, engine, losses, optim, utils
 from devit_amd.de_vit import model_config
 
 
+def _non_negative(text):
+    v = float(text)
+    if not v >= 0.:
+        raise argparse.ArgumentTypeError(f"must be >= 0, got {text}")
+    return v
+
+
 def get_args_parser():
     p = argparse.ArgumentParser('DeViT sub-model distillation (MI355X)', add_help=False)
     a = p.add_argument
@@ -59,6 +66,9 @@ def get_args_parser():
     a('--distillation-inter', type=bool, default=True); a('--distillation-token', action='store_true')
     a('--distillation-alpha', default=0.5, type=float); a('--distillation-tau', default=1.0, type=float)
     a('--gama', nargs='+', default=[0.2, 0.1, 0.3])
+    a('--hid-gama', type=_non_negative, default=0.0, metavar='G',
+      help='weight of the hidden-state relation loss of the middle blocks (the reference\'s cal_hid_relation_loss, utils/losses.py:295-304); '
+           '0: the DEKD step as it is')
     a('--data-path', default=r'./datasets'); a('--dataset', default='cifar100', choices=['cifar100', 'IMNET', 'cars', 'pets', 'flowers'])
     a('--inat-category', default='name'); a('--num_division', metavar='N', type=int, default=4); a('--start-division', metavar='N', type=int, default=0)
     a('--device', default='cuda'); a('--seed', default=0, type=int); a('--resume', default=''); a('--start_epoch', default=0, type=int)

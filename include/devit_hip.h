@@ -613,6 +613,36 @@ DEVIT_API int devit_relation_grad(const float* gram_t, const float* gram_s, cons
                         int out_is_f32, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Hidden-state distillation (csrc/hid.hip).
+ *
+ * devit_add_scale_cast_bf16: a gradient that arrives for an exposed encoder output, injected between two devit_block_bwd calls:
+ *   dx[m][d] += add[m][d] (fp32, in place);  g_bf16[m][d] = bf16((dx + add)[m][d] * (rowscale ? rowscale[m / rows_per_scale] : 1))
+ * -- the fp32 add is torch's, the bf16 value one rounding of the scaled sum, as devit_scale_cast_bf16's.  Rows >= M are not touched.
+ *
+ * cal_hid_relation_loss (utils/losses.py:295-304) for one (student, teacher) pair of fp32 [B][N][D] hidden states:
+ *   loss = mean_{b,i,j} (G_s - G_t)^2 / layers,  G = h^ h^T per image,  h^ = h / max(|h|, eps)
+ * The Grams and dh^ = S h^ run on the batched devit_gemm_bf16 (256 x 256 windows per image, as the q/k/v relation loss) or, in exact
+ * mode, on devit_gemm_f32; these four entry points do the rest.  N <= 208, D a multiple of 64 up to 1024 (DEVIT_ERR_SHAPE otherwise).
+ *   normalize     : out[rows_total][ld] = h^ as bf16 (out_is_f32: fp32), ld a multiple of 128 >= D; columns >= D and rows >= B N are
+ *                   written as zeros; inv[B N] = 1 / max(|h|, eps)
+ *   stats         : row_sq[B N] (workspace) and loss[0] = sum (G_s - G_t)^2 / (B N^2 layers) over the padded fp32 Grams [B][256][256];
+ *                   fixed summation order
+ *   grad          : S = (4 upstream / (B N^2 layers)) (G_s - G_t), bf16 (out_is_f32: fp32) [B][256][256], zero outside N x N;
+ *                   upstream: device scalar or NULL (= 1)
+ *   normalize_bwd : dh[B N][D] = inv (dh^ - h^ (h^ . dh^)) in fp32; hn as normalize wrote it, dhn fp32 with the same leading dimension
+ * ---------------------------------------------------------------------------------------- */
+DEVIT_API int devit_add_scale_cast_bf16(float* dx, const float* add, void* g_bf16, const float* rowscale, int rows_per_scale, int M,
+                              int D, void* stream);
+DEVIT_API int devit_hid_normalize(const float* h, void* out, float* inv, int B, int N, int D, int ld, int rows_total, int out_is_f32,
+                        float eps, void* stream);
+DEVIT_API int devit_hid_stats(const float* gram_s, const float* gram_t, int B, int N, int ldr, int layers, float* row_sq, float* loss,
+                    void* stream);
+DEVIT_API int devit_hid_grad(const float* gram_s, const float* gram_t, const float* upstream, int B, int N, int ldr, int layers,
+                   void* S_out, int out_is_f32, void* stream);
+DEVIT_API int devit_hid_normalize_bwd(const void* hn, const float* dhn, const float* inv, float* dh, int B, int N, int D, int ld,
+                            int hn_is_f32, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Exact-fp32 companion path ("parity mode", csrc/sgemm.hip): the same op sequences with fp32 activations and
  * k-ordered fmaf accumulation, for asserting BASELINE.json's 1e-3 logit bar against the reference's fp32 CPU
  * path.  Not tuned (a few TFLOP/s); never used by bench.py.
