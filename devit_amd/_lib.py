@@ -131,6 +131,10 @@ SIGNATURES = {
     "devit_gemm_route": (_I, [C.POINTER(Operand), C.POINTER(Operand), _I, _I, _I, _I, _I, C.POINTER(Epilogue)]),
     "devit_set_reserved_cus": (_I, [_I]),
     "devit_get_reserved_cus": (_I, []),
+    "devit_set_deterministic": (_I, [_I]),
+    "devit_get_deterministic": (_I, []),
+    "devit_det_workspace_bytes": (_Z, []),
+    "devit_set_det_workspace": (_I, [_P, _Z]),
     "devit_layernorm_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _I, _P]),
     "devit_layernorm_bwd_workspace": (_Z, [_I, _I]),
     "devit_layernorm_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _Z, _P]),
@@ -240,8 +244,13 @@ def require_device(t: torch.Tensor):
         _checked_devices.add(idx)
 
 
+before_call = None      # ops' deterministic mode: registers the device's workspace before the first launch that may need it
+
+
 def call(name, *args):
     lib = load()
+    if before_call is not None:
+        before_call()
     rc = getattr(lib, name)(*args)
     if rc != 0:
         raise DevitError(f"{name} failed ({rc}): {lib.devit_last_error().decode()}")

@@ -1,6 +1,7 @@
 // Dropout p > 0 as passes of its own beside the GEMMs (nn.Dropout at models/de_vit.py:38,46 Mlp.drop, :72 attn_drop on the fp32 composite's P,
 // :83 proj_drop, :173 pos_drop): the mask of dropout.h applied in place, or inside the residual + DropPath statement.  HBM-bound: every
 // lane moves 16 bytes per access, one Philox call per four elements; rows are walked grid-stride.  Nothing here runs at p == 0.
+#include "det.h"
 #include "dropout.h"
 
 namespace {
@@ -16,57 +17,16 @@ struct ApplyArgs {
 };
 
 // F32 == false: 8 bf16 per lane (two Philox calls); true: 4 floats (one)
-template <bool F32>
-__global__ __launch_bounds__(CX* RY) void dropout_apply_kernel(const ApplyArgs a) {
-  constexpr int V = F32 ? 4 : 8;
-  __shared__ float red[RY][CX][V];
-  const int c0 = (blockIdx.x * CX + threadIdx.x) * V;
-  const bool live = c0 < a.cols;
-  float acc[V];
-#pragma unroll
-  for (int e = 0; e < V; ++e) acc[e] = 0.f;
-  if (live) {
-    for (int r = blockIdx.y * RY + threadIdx.y; r < a.rows; r += gridDim.y * RY) {
-      const unsigned long long e0 = (unsigned long long)r * (unsigned long long)a.pitch + (unsigned long long)c0;
-      if constexpr (F32) {
-        float* p = (float*)a.x + (size_t)r * a.ld + c0;
-        f32x4 v = *(const f32x4*)p;
-        const u32x4 w = drop_words(a.d, e0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          v[e] = w[e] >= a.d.thr ? v[e] * a.d.s : 0.f;
-          acc[e] += v[e];
-        }
-        *(f32x4*)p = v;
-      } else {
-        __bf16* p = (__bf16*)a.x + (size_t)r * a.ld + c0;
-        bf16x8 v = *(const bf16x8*)p;
-        const u32x4 w0 = drop_words(a.d, e0), w1 = drop_words(a.d, e0 + 4);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const unsigned w = e < 4 ? w0[e] : w1[e - 4];
-          v[e] = f2bf(w >= a.d.thr ? bf2f(v[e]) * a.d.s : 0.f);
-          acc[e] += bf2f(v[e]);          // the sums are of what the buffer now holds (a Linear's bias gradient when it is a dY)
-        }
-        *(bf16x8*)p = v;
-      }
-    }
-  }
-  if (a.colsum) {                        // (uniform over the grid)
-#pragma unroll
-    for (int e = 0; e < V; ++e) red[threadIdx.y][threadIdx.x][e] = acc[e];
-    __syncthreads();
-    if (threadIdx.y == 0 && live) {
-#pragma unroll
-      for (int e = 0; e < V; ++e) {
-        float s = red[0][threadIdx.x][e];
-#pragma unroll
-        for (int y = 1; y < RY; ++y) s += red[y][threadIdx.x][e];
-        atomicAdd(a.colsum + c0 + e, s);
-      }
-    }
-  }
-}
+#define DROPOUT_APPLY_KERNEL dropout_apply_kernel
+#define DROPOUT_APPLY_DET 0
+#include "dropout_apply_kernel.inc"
+#undef DROPOUT_APPLY_KERNEL
+#undef DROPOUT_APPLY_DET
+#define DROPOUT_APPLY_KERNEL dropout_apply_det_kernel
+#define DROPOUT_APPLY_DET 1
+#include "dropout_apply_kernel.inc"
+#undef DROPOUT_APPLY_KERNEL
+#undef DROPOUT_APPLY_DET
 
 struct ResidualArgs {
   const float* x;       // [rows][cols]
@@ -154,6 +114,18 @@ extern "C" int devit_dropout_apply(void* x, int is_f32, int rows, int cols, int 
   // with column sums every workgroup ends in one atomic per column on the same words: one workgroup per CU then owns a long strip of rows
   // (2048 workgroups: 408 us for 78 MB at D = 384, all of it the atomics)
   const dim3 grid = row_grid(rows, cols / V, colsum ? 256 : 2048);
+  if (colsum && grid.y > 1 && devit_det::on()) {   // deterministic mode (det.h): the strips' sums go to the workspace and are added to colsum in strip order
+    float* ws = nullptr;
+    const int rc = devit_det::workspace("devit_dropout_apply", (size_t)grid.y * cols * sizeof(float), &ws);
+    if (rc != DEVIT_OK) return rc;
+    a.colsum = ws;
+    if (is_f32)
+      hipLaunchKernelGGL(dropout_apply_det_kernel<true>, grid, dim3(CX, RY), 0, (hipStream_t)stream, a);
+    else
+      hipLaunchKernelGGL(dropout_apply_det_kernel<false>, grid, dim3(CX, RY), 0, (hipStream_t)stream, a);
+    DEVIT_LAUNCH_CHECK();
+    return devit_det::fold(ws, (int)grid.y, (size_t)cols, 1, cols, colsum, 0, 1, 0, (hipStream_t)stream);
+  }
   if (is_f32)
     hipLaunchKernelGGL(dropout_apply_kernel<true>, grid, dim3(CX, RY), 0, (hipStream_t)stream, a);
   else

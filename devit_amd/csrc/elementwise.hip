@@ -1,5 +1,6 @@
 // HBM-bound helper kernels of the DeViT path: patch im2row, token assembly, casts, column sums
 // (bias gradients), embedding backward, small strided f32 GEMM (classifier heads), fused AdamW+EMA.
+#include "det.h"
 #include "devit_common.h"
 
 namespace {
@@ -265,39 +266,16 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float* partial,
 // gridDim.y slices of the batch per (t, d4) column, four independent 16-byte loads in flight, partial sums combined by
 // fp32 atomics into a zeroed / accumulating dpos (8 adds per address).  (One thread per column walking all 256 images
 // with one load in flight: 74 workgroups, 1.1 TB/s.)
-__global__ __launch_bounds__(256) void embed_bwd_kernel(const float* dx, int B, int T, int D, float* dpos,
-                                                        __bf16* dx_bf16) {
-  const int total = T * D / 4;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int d = (idx % (D / 4)) * 4, t = idx / (D / 4);
-  const int b0 = (int)((long long)B * blockIdx.y / gridDim.y), b1 = (int)((long long)B * (blockIdx.y + 1) / gridDim.y);
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  auto one = [&](int b, f32x4& v) { v = load_stream((const f32x4*)(dx + ((size_t)b * T + t) * D + d)); };
-  auto put = [&](int b, const f32x4& v) {
-    s += v;
-    if (dx_bf16) {
-      const bf16x4 ob = {f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
-      *(bf16x4*)(dx_bf16 + ((size_t)b * T + t) * D + d) = ob;
-    }
-  };
-  int b = b0;
-  for (; b + 4 <= b1; b += 4) {
-    f32x4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) one(b + u, v[u]);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) put(b + u, v[u]);
-  }
-  for (; b < b1; ++b) {
-    f32x4 v;
-    one(b, v);
-    put(b, v);
-  }
-  float* dst = dpos + (size_t)t * D + d;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) unsafeAtomicAdd(dst + e, s[e]);
-}
+#define EMBED_BWD_KERNEL embed_bwd_kernel
+#define EMBED_BWD_DET 0
+#include "embed_bwd_kernel.inc"
+#undef EMBED_BWD_KERNEL
+#undef EMBED_BWD_DET
+#define EMBED_BWD_KERNEL embed_bwd_det_kernel
+#define EMBED_BWD_DET 1
+#include "embed_bwd_kernel.inc"
+#undef EMBED_BWD_KERNEL
+#undef EMBED_BWD_DET
 // dcls / ddist / dbias from dpos (tiny)
 __global__ __launch_bounds__(256) void embed_bwd_tail_kernel(const float* dpos, int T, int D, int ntok, float* dcls,
                                                              float* ddist, float* dbias, int accumulate) {
@@ -567,9 +545,20 @@ extern "C" int devit_embed_bwd(const float* dx, int B, int T, int D, int ntok, f
   hipError_t me = hipMemsetAsync(dpos, 0, (size_t)T * D * sizeof(float), (hipStream_t)stream);
   DEVIT_CHECK(me == hipSuccess, DEVIT_ERR_LAUNCH, "devit_embed_bwd: hipMemsetAsync: %s", hipGetErrorString(me));
   const int slices = B >= 64 ? 8 : 1;
-  hipLaunchKernelGGL(embed_bwd_kernel, dim3((T * D / 4 + 255) / 256, slices), dim3(256), 0, (hipStream_t)stream, dx, B,
-                     T, D, dpos, (__bf16*)dx_bf16);
-  DEVIT_LAUNCH_CHECK();
+  if (slices > 1 && devit_det::on()) {   // deterministic mode (det.h): the slices' sums go to the workspace and are added to dpos in slice order
+    float* ws = nullptr;
+    const int rc = devit_det::workspace("devit_embed_bwd", (size_t)slices * T * D * sizeof(float), &ws);
+    if (rc != DEVIT_OK) return rc;
+    hipLaunchKernelGGL(embed_bwd_det_kernel, dim3((T * D / 4 + 255) / 256, slices), dim3(256), 0, (hipStream_t)stream, dx, B, T, D, ws,
+                       (__bf16*)dx_bf16);
+    DEVIT_LAUNCH_CHECK();
+    const int rf = devit_det::fold(ws, slices, (size_t)T * D, 1, T * D, dpos, 0, 1, 0, (hipStream_t)stream);
+    if (rf != DEVIT_OK) return rf;
+  } else {
+    hipLaunchKernelGGL(embed_bwd_kernel, dim3((T * D / 4 + 255) / 256, slices), dim3(256), 0, (hipStream_t)stream, dx, B,
+                       T, D, dpos, (__bf16*)dx_bf16);
+    DEVIT_LAUNCH_CHECK();
+  }
   hipLaunchKernelGGL(embed_bwd_tail_kernel, dim3((D + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      (const float*)dpos, T, D, ntok, dcls, ddist, dbias, accumulate);
   DEVIT_LAUNCH_CHECK();

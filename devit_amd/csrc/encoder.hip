@@ -6,6 +6,7 @@
 // see there).  Host code only.
 #include <mutex>
 
+#include "det.h"
 #include "devit_common.h"
 
 namespace {
@@ -109,7 +110,8 @@ struct WgradSide {
 constexpr int MAX_DEVICES = 16;
 int wgrad_side(WgradSide** out) {
   const char* env = getenv("DEVIT_WGRAD_STREAM");      // (read per call: tests switch it)
-  const bool on = !(env && atoi(env) == 0);
+  // (deterministic mode keeps them on `stream` too: one stream orders every launch that uses the registered workspace, det.h)
+  const bool on = !(env && atoi(env) == 0) && !devit_det::on();
   static WgradSide per_dev[MAX_DEVICES];
   static std::once_flag once[MAX_DEVICES];
   *out = nullptr;

@@ -3,6 +3,7 @@
 // launchers live in gemm_tile128.hip / gemm_tile256.hip (gemm_tile.h), gemm4.hip and gemmfr.hip; devit_wgrad_grouped in wgradfr.hip.
 #include <stdlib.h>
 
+#include "det.h"
 #include "gemm_host.h"
 #include "ln_rows.h"
 
@@ -85,6 +86,17 @@ struct Route {
   bool use4;
   int as_enum() const { return cfg == 4 ? DEVIT_ROUTE_FULL_ROW : use4 ? DEVIT_ROUTE_GEMM4 : cfg == 3 ? DEVIT_ROUTE_TILE256 : DEVIT_ROUTE_TILE128; }
 };
+
+// Deterministic mode (det.h): an ATOMIC_F32 launch some of whose addresses receive more than one partial sum -- K slices onto the tile, (slice, n-tile)
+// pairs onto the fused row sums -- runs the DET_F32 instantiation into the workspace, [batch][split_k] dense M x N slabs and behind them
+// [split_k][tiles_n] rows of M sums, and fold launches add them to the destinations in index order.  Slice count and K ranges are the default's.
+bool det_split(int N, int split_k, const devit_epilogue* ep) {
+  return ep->kind == DEVIT_EPI_ATOMIC_F32 && (split_k > 1 || (ep->aux && N / 128 > 1)) && devit_det::on();
+}
+size_t det_slab_floats(int M, int N, int batch, int split_k) { return (size_t)batch * split_k * M * N; }
+size_t det_bytes(int M, int N, int batch, int split_k, const devit_epilogue* ep) {
+  return (det_slab_floats(M, N, batch, split_k) + (ep->aux ? (size_t)split_k * (N / 128) * M : 0)) * sizeof(float);
+}
 
 // The argument checks of devit_gemm_bf16 and THE selection rule of the family, in one place: gemm_launch launches what this says, devit_gemm_route
 // reports it.  Host arithmetic and the environment only: no pointer is dereferenced but the three descriptors, nothing is launched, no device is asked.
@@ -183,6 +195,14 @@ int gemm_route(const devit_operand* Aop, const devit_operand* Bop, int M, int N,
   r.use4 = use4;
   const int bm = cfg == 1 ? 128 : 256, bn = cfg == 4 ? 384 : bm;
   DEVIT_CHECK((long long)(M / bm) * ((N + bn - 1) / bn) * split_k * batch < (1ll << 31), DEVIT_ERR_SHAPE, "devit_gemm_bf16: too many tiles");
+  if (ep->kind == DEVIT_EPI_ATOMIC_F32 && batch > 1 && devit_det::on()) {
+    // batches whose outputs overlap (out_batch_stride smaller than one output) are further partial sums per address that no slice index orders
+    const long long m_lim = ep->m_valid > 0 ? ep->m_valid : M;
+    DEVIT_CHECK(ep->out_batch_stride >= (m_lim - 1) * (long long)ep->ldc + N, DEVIT_ERR_ARG,
+                "devit_gemm_bf16: deterministic mode refuses ATOMIC_F32 with batch=%d whose outputs overlap (out_batch_stride=%lld): the batches would "
+                "add into one address in arrival order", batch, ep->out_batch_stride);
+  }
+  if (det_split(N, split_k, ep)) return devit_det::workspace("devit_gemm_bf16", det_bytes(M, N, batch, split_k, ep), nullptr);
   return DEVIT_OK;
 }
 
@@ -203,6 +223,17 @@ int gemm_launch(const devit_operand* Aop, const devit_operand* Bop, int M, int N
   g.M = M; g.N = N; g.K = K;
   g.tiles_m = 0; g.tiles_n = 0; g.split_k = split_k;
   g.ep = *ep;
+  const bool det = det_split(N, split_k, ep);
+  if (det) {
+    float* ws = nullptr;
+    const int rc = devit_det::workspace("devit_gemm_bf16", det_bytes(M, N, batch, split_k, ep), &ws);
+    if (rc != DEVIT_OK) return rc;
+    g.ep.kind = DEVIT_EPI_DET_F32;
+    g.ep.out = ws;
+    g.ep.ldc = N;
+    g.ep.out_batch_stride = 0;
+    if (ep->aux) g.ep.aux = ws + det_slab_floats(M, N, batch, split_k);
+  }
   const int bm = cfg == 1 ? 128 : 256, bn = cfg == 4 ? 384 : bm;
   g.tiles_m = M / bm;
   g.tiles_n = (N + bn - 1) / bn;
@@ -257,7 +288,12 @@ int gemm_launch(const devit_operand* Aop, const devit_operand* Bop, int M, int N
       return devit_layernorm_bwd_finish(ln->ln.partial, g.tiles_m, N, ln->dgamma, ln->dbeta, ln->dx_bf16_colsum, ln->accumulate, stream);
     }
     if (use4) return launch_gemm4(g, (unsigned)nwg, s);
-    return cfg == 3 ? launch_gemm_tile256(g, variant, (unsigned)nwg, s) : launch_gemm_tile128(g, variant, (unsigned)nwg, s);
+    if (!det) return cfg == 3 ? launch_gemm_tile256(g, variant, (unsigned)nwg, s) : launch_gemm_tile128(g, variant, (unsigned)nwg, s);
+    int rc = launch_gemm_tile128(g, variant, (unsigned)nwg, s);
+    const int m_lim = ep->m_valid > 0 ? ep->m_valid : M;
+    if (rc == DEVIT_OK) rc = devit_det::fold((const float*)g.ep.out, split_k, (size_t)M * N, m_lim, N, (float*)ep->out, ep->ldc, batch, ep->out_batch_stride, s);
+    if (rc == DEVIT_OK && ep->aux) rc = devit_det::fold((const float*)g.ep.aux, split_k * g.tiles_n, (size_t)M, 1, m_lim, (float*)ep->aux, 0, 1, 0, s);
+    return rc;
   });
 }
 }  // namespace

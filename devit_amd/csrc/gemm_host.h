@@ -9,6 +9,10 @@ namespace devit_gemm {
 
 constexpr int BK = 64;
 
+// Internal epilogue kind behind devit_epilogue_kind's last value: the split-K epilogue of deterministic mode (gemm.hip rewrites ATOMIC_F32 to it;
+// no caller passes it): partial tiles by plain stores into the workspace instead of fp32 atomics into the destination.
+constexpr int DEVIT_EPI_DET_F32 = DEVIT_EPI_STORE_F32 + 1;
+
 // n / d for 0 <= n < 2^31 by multiply-shift (Granlund-Montgomery round-up): three SALU ops instead of the
 // float-reciprocal sequence hipcc emits for a scalar division.  Host-initialised.
 struct FastDiv {

@@ -26,7 +26,10 @@ __device__ __forceinline__ float sum8_bf16(bf16x8 v, float acc) {
 template <int BM, int BN, int WAVES_M, int WAVES_N, int NSTAGE, bool A_KM, bool B_KM, int KIND, bool F16 = false>
 __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void gemm_kernel(const GemmArgs g) {
-  static_assert(!F16 || (KIND != DEVIT_EPI_DGELU_BF16 && KIND != DEVIT_EPI_ATOMIC_F32 && !A_KM && !B_KM),
+  // the split-K kinds: partial sums leave by fp32 atomics (ATOMIC_F32), or -- deterministic mode, gemm.hip -- by plain stores into the (batch, slice)'s
+  // own slab of a workspace that a fold launch adds to the destination in slice order (DET_F32: same K loop, another epilogue, its own instantiation)
+  constexpr bool SPLITK = KIND == DEVIT_EPI_ATOMIC_F32 || KIND == devit_gemm::DEVIT_EPI_DET_F32;
+  static_assert(!F16 || (KIND != DEVIT_EPI_DGELU_BF16 && !SPLITK && !A_KM && !B_KM),
                 "f16 operands: forward layouts / epilogues only (the frozen teacher has no backward)");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NWAVES = WAVES_M * WAVES_N;
@@ -36,7 +39,7 @@ void gemm_kernel(const GemmArgs g) {
   // Every epilogue but the split-K atomic one runs straight from the accumulators: the MFMAs then take the B operand
   // (output columns) on their row side, see epilogue_direct().  The atomic one stages through the ring's LDS, so its
   // stream stops at every tile end.
-  constexpr bool DIRECT = KIND != DEVIT_EPI_ATOMIC_F32;
+  constexpr bool DIRECT = !SPLITK;
   constexpr bool PAIRED = KIND == DEVIT_EPI_STORE_BF16 || KIND == DEVIT_EPI_GELU_BF16 || KIND == DEVIT_EPI_DGELU_BF16;
   constexpr int A_TILE_BYTES = BM * BK * 2, B_TILE_BYTES = BN * BK * 2;
   // Ring: two B slots, THREE A slots.  A is the operand that streams from HBM (an activation; B is a weight that lives in
@@ -300,7 +303,7 @@ void gemm_kernel(const GemmArgs g) {
     float rsum[MI];
 #pragma unroll
     for (int i = 0; i < MI; ++i) rsum[i] = 0.f;
-    const bool rowsum_on = KIND == DEVIT_EPI_ATOMIC_F32 && g.ep.aux != nullptr && wn == 0;
+    const bool rowsum_on = SPLITK && g.ep.aux != nullptr && wn == 0;
     int rs_wait = 0;          // K-steps until this tile's next turn
     if (rowsum_on) rs_wait = (ct.n0 / BN - ct.kt0 % g.tiles_n + g.tiles_n) % g.tiles_n;
 
@@ -309,7 +312,7 @@ void gemm_kernel(const GemmArgs g) {
       const char* cur_b = smem + B_RING + cb_slot * B_TILE_BYTES;
       ca_slot = ca_slot + 1 == NA ? 0 : ca_slot + 1;
       cb_slot ^= 1;
-      const bool rs_now = KIND == DEVIT_EPI_ATOMIC_F32 && rowsum_on && rs_wait == 0;
+      const bool rs_now = SPLITK && rowsum_on && rs_wait == 0;
 #ifdef DEVIT_GEMM_NOCOMPUTE   // diagnostic build: the fill pipeline alone
       if (g.K < 0)
 #endif
@@ -325,14 +328,14 @@ void gemm_kernel(const GemmArgs g) {
 #pragma unroll
           for (int j = 0; j < NI; ++j)
             acc[i][j] = DIRECT ? mfma16t<F16>(bfr[j], af[i], acc[i][j]) : mfma16t<F16>(af[i], bfr[j], acc[i][j]);
-        if constexpr (KIND == DEVIT_EPI_ATOMIC_F32) {
+        if constexpr (SPLITK) {
           if (rs_now) {
 #pragma unroll
             for (int i = 0; i < MI; ++i) rsum[i] = sum8_bf16(af[i], rsum[i]);
           }
         }
       }
-      if constexpr (KIND == DEVIT_EPI_ATOMIC_F32) rs_wait = rs_wait == 0 ? g.tiles_n - 1 : rs_wait - 1;
+      if constexpr (SPLITK) rs_wait = rs_wait == 0 ? g.tiles_n - 1 : rs_wait - 1;
     };
     const devit_epilogue& ep = g.ep;
     const int nw = ct.n0 + wn * WN;
@@ -366,6 +369,9 @@ void gemm_kernel(const GemmArgs g) {
       __syncthreads();  // all fragment reads done before the ring is reused as the staging area
       float* cw = (float*)smem + wave * 4096;
       float* out = (float*)ep.out + ob;
+      // DET_F32: ep.out / ep.aux are the workspace; slab zz = batch * split_k + slice holds this tile's [M][N] partial, dense (ldc == N)
+      const int zz = KIND == devit_gemm::DEVIT_EPI_DET_F32 ? fdiv(tile, g.d_per_z) : 0;
+      if constexpr (KIND == devit_gemm::DEVIT_EPI_DET_F32) out = (float*)ep.out + (size_t)zz * g.M * g.N;
       auto do_pass = [&](auto pass_c) {
         constexpr int pass = decltype(pass_c)::value;
 #pragma unroll
@@ -379,6 +385,9 @@ void gemm_kernel(const GemmArgs g) {
         const int mw = ct.m0 + wm * WM + pass * 64;
         for (int row = 0; row < 64; ++row) {
           const float v = cw[row * 64 + lane];
+          if constexpr (KIND == devit_gemm::DEVIT_EPI_DET_F32) {
+            if (mw + row < m_lim) out[(size_t)(mw + row) * ep.ldc + nw + lane] = v;
+          } else
 #if defined(DEVIT_GEMM_NOATOMIC)  // ablation build: the split-K epilogue without its atomics
           if (mw + row < m_lim && v == 1.2345e30f) out[(size_t)(mw + row) * ep.ldc + nw + lane] = v;
 #else
@@ -397,6 +406,9 @@ void gemm_kernel(const GemmArgs g) {
           v += __shfl_xor(v, 16, 64);
           v += __shfl_xor(v, 32, 64);
           const int row = ct.m0 + wm * WM + i * 16 + lane;
+          if constexpr (KIND == devit_gemm::DEVIT_EPI_DET_F32) {   // partial (slice, n-tile): its own [M] row of the workspace behind the slabs
+            if (lane < 16 && row < m_lim) rs_out[(size_t)(zz * g.tiles_n + ct.n0 / BN) * g.M + row] = v;
+          } else
           if (lane < 16 && row < m_lim) unsafeAtomicAdd(rs_out + row, v);
         }
       }
@@ -419,7 +431,7 @@ void gemm_kernel(const GemmArgs g) {
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool A_KM, bool B_KM, int KIND, bool F16 = false>
 int launch_one(const GemmArgs& g, unsigned grid, hipStream_t s) {
   constexpr int ring = (3 * BM + 2 * BN) * 128, stagebytes = WAVES_M * WAVES_N * 16384;
-  constexpr int lds = (KIND == DEVIT_EPI_ATOMIC_F32 && stagebytes > ring) ? stagebytes : ring;
+  constexpr int lds = ((KIND == DEVIT_EPI_ATOMIC_F32 || KIND == devit_gemm::DEVIT_EPI_DET_F32) && stagebytes > ring) ? stagebytes : ring;
   return devit_gemm::launch_kernel<gemm_kernel<BM, BN, WAVES_M, WAVES_N, 2, A_KM, B_KM, KIND, F16>, lds>(grid, WAVES_M * WAVES_N * 64, s, g);
 }
 // forward layouts: bf16 or (ep.dtype16: the frozen teacher) f16 operands
@@ -440,10 +452,12 @@ int launch_gemm_tile(const devit_gemm::GemmParams& p, int variant, unsigned grid
     case 1 * 16 + DEVIT_EPI_STORE_BF16: return launch_one<BM, BN, WAVES_M, WAVES_N, false, true, DEVIT_EPI_STORE_BF16>(g, grid, s);
     case 1 * 16 + DEVIT_EPI_STORE_F32: return launch_one<BM, BN, WAVES_M, WAVES_N, false, true, DEVIT_EPI_STORE_F32>(g, grid, s);
     case 1 * 16 + DEVIT_EPI_DGELU_BF16: return launch_one<BM, BN, WAVES_M, WAVES_N, false, true, DEVIT_EPI_DGELU_BF16>(g, grid, s);
+    case 3 * 16 + devit_gemm::DEVIT_EPI_DET_F32:
     case 3 * 16 + DEVIT_EPI_ATOMIC_F32:   // k-major x k-major never takes the 256x256 tile (gemm.hip's tile choice excludes it): not instantiated
     case 3 * 16 + DEVIT_EPI_STORE_F32:    // there (the 256x256 atomic kernel needed 257 registers: 1 spill)
       if constexpr (BM == 128) {
         if (g.ep.kind == DEVIT_EPI_ATOMIC_F32) return launch_one<BM, BN, WAVES_M, WAVES_N, true, true, DEVIT_EPI_ATOMIC_F32>(g, grid, s);
+        if (g.ep.kind == devit_gemm::DEVIT_EPI_DET_F32) return launch_one<BM, BN, WAVES_M, WAVES_N, true, true, devit_gemm::DEVIT_EPI_DET_F32>(g, grid, s);
         return launch_one<BM, BN, WAVES_M, WAVES_N, true, true, DEVIT_EPI_STORE_F32>(g, grid, s);
       } else {
         devit_set_error("devit_gemm_bf16: k-major x k-major operands run on 128x128 tiles only");

@@ -2,6 +2,7 @@
 // the q/k/v feature-relation loss (the Gram products run on the MFMA GEMM, see relation_* in ops.py).
 //   cls loss   : utils/losses.py:135-177 (DistillLoss) + timm SoftTargetCrossEntropy
 //   relation   : utils/losses.py:307-328 (feature_relation_loss), closed form in SURVEY.md App. A
+#include "det.h"
 #include "devit_common.h"
 
 namespace {
@@ -37,114 +38,16 @@ __device__ __forceinline__ void row_lse(const float (&x)[MAXC_PER_LANE], int n, 
 // One wave per row, 16 rows per workgroup, B / 16 workgroups; each workgroup adds its weighted share to the three loss
 // scalars (zeroed by the launcher) with fp32 atomics -- 16 adds per scalar at B = 256.  (One workgroup walking all rows
 // was a 135 us chain of dependent row reductions.)
-__global__ __launch_bounds__(1024) void cls_loss_kernel(const ClsArgs a) {
-  __shared__ float red[16][2];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int C = a.C;
-  float base_acc = 0.f, dist_acc = 0.f;
-  for (int b = blockIdx.x * 16 + wv; b < a.B; b += 16 * gridDim.x) {
-    float xo[MAXC_PER_LANE], xk[MAXC_PER_LANE], xt[MAXC_PER_LANE], yy[MAXC_PER_LANE];
-    int n = 0;
-#pragma unroll
-    for (int i = 0; i < MAXC_PER_LANE; ++i) {
-      const int c = lane + i * 64;
-      if (c < C) {
-        xo[i] = a.lo[(size_t)b * C + c];
-        xk[i] = a.lk[(size_t)b * C + c];
-        xt[i] = a.lt ? a.lt[(size_t)b * C + c] : 0.f;
-        yy[i] = a.y[(size_t)b * C + c];
-        n = i + 1;
-      } else {
-        xo[i] = xk[i] = xt[i] = -INFINITY;
-        yy[i] = 0.f;
-      }
-    }
-    // n differs between lanes only in the last partial group: make the loop bound wave-uniform and
-    // rely on the -inf / 0 padding above
-    n = (C + 63) / 64;
-    float mo, lseo;
-    row_lse(xo, n, 1.0f, mo, lseo);
-    float ysum = 0.f, bl = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXC_PER_LANE; ++i)
-      if (i < n && lane + i * 64 < C) {
-        ysum += yy[i];
-        bl -= yy[i] * (xo[i] - lseo);
-      }
-    ysum = wave_sum(ysum);
-    base_acc += wave_sum(bl);
-    const float wbase = (a.kind == 0 ? 1.0f : 1.0f - a.alpha) / (float)a.B;
-#pragma unroll
-    for (int i = 0; i < MAXC_PER_LANE; ++i) {
-      const int c = lane + i * 64;
-      if (i < n && c < C) a.dlo[(size_t)b * C + c] = (expf(xo[i] - lseo) * ysum - yy[i]) * wbase;
-    }
-    if (a.kind == 2) {  // hard: CE(kd, argmax teacher)   utils/losses.py:153
-      float best = -INFINITY;
-      int bi = 0x7fffffff;
-#pragma unroll
-      for (int i = 0; i < MAXC_PER_LANE; ++i) {
-        const int c = lane + i * 64;
-        if (i < n && c < C && xt[i] > best) { best = xt[i]; bi = c; }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {   // max value, ties -> lowest index (torch.argmax on CPU)
-        const float ob = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-      }
-      float mk, lsek;
-      row_lse(xk, n, 1.0f, mk, lsek);
-      float xsel = 0.f;
-#pragma unroll
-      for (int i = 0; i < MAXC_PER_LANE; ++i)
-        if (i < n && lane + i * 64 == bi) xsel = xk[i];
-      xsel = wave_sum(xsel);
-      dist_acc += lsek - xsel;
-      const float wd = a.alpha / (float)a.B;
-#pragma unroll
-      for (int i = 0; i < MAXC_PER_LANE; ++i) {
-        const int c = lane + i * 64;
-        if (i < n && c < C) a.dlk[(size_t)b * C + c] = (expf(xk[i] - lsek) - (c == bi ? 1.f : 0.f)) * wd;
-      }
-    } else if (a.kind == 1) {  // soft: KL(log_softmax(kd/T) || log_softmax(tea/T)) T^2 / numel   :140-148
-      const float it = 1.0f / a.tau;
-      float mk, lsek, mt, lset;
-      row_lse(xk, n, it, mk, lsek);
-      row_lse(xt, n, it, mt, lset);
-      float kl = 0.f;
-      const float wd = a.alpha * a.tau / ((float)a.B * (float)C);
-#pragma unroll
-      for (int i = 0; i < MAXC_PER_LANE; ++i) {
-        const int c = lane + i * 64;
-        if (i < n && c < C) {
-          const float la = xk[i] * it - lsek, lb = xt[i] * it - lset;
-          kl += expf(lb) * (lb - la);
-          a.dlk[(size_t)b * C + c] = (expf(la) - expf(lb)) * wd;
-        }
-      }
-      dist_acc += wave_sum(kl);
-    } else {
-#pragma unroll
-      for (int i = 0; i < MAXC_PER_LANE; ++i) {
-        const int c = lane + i * 64;
-        if (i < n && c < C) a.dlk[(size_t)b * C + c] = 0.f;
-      }
-    }
-  }
-  if (lane == 0) { red[wv][0] = base_acc; red[wv][1] = dist_acc; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float bs = 0.f, ds = 0.f;
-    for (int i = 0; i < 16; ++i) { bs += red[i][0]; ds += red[i][1]; }
-    bs /= (float)a.B;
-    if (a.kind == 2) ds /= (float)a.B;
-    else if (a.kind == 1) ds *= a.tau * a.tau / ((float)a.B * (float)C);
-    unsafeAtomicAdd(a.loss + 1, bs);
-    unsafeAtomicAdd(a.loss + 2, ds);
-    unsafeAtomicAdd(a.loss + 0, a.kind == 0 ? bs : bs * (1.0f - a.alpha) + ds * a.alpha);
-  }
-}
+#define CLS_LOSS_KERNEL cls_loss_kernel
+#define CLS_LOSS_DET 0
+#include "cls_loss_kernel.inc"
+#undef CLS_LOSS_KERNEL
+#undef CLS_LOSS_DET
+#define CLS_LOSS_KERNEL cls_loss_det_kernel
+#define CLS_LOSS_DET 1
+#include "cls_loss_kernel.inc"
+#undef CLS_LOSS_KERNEL
+#undef CLS_LOSS_DET
 
 // ---- relation loss, stage 1: per-row log-sum-exp of R/sqrt(hd) for teacher and student Grams, and the
 //      row's KL contribution sum_j e^{t_ij}(t_ij - s_ij).  R_* are [B][ldr][ldr] f32 (padded Grams).
@@ -331,7 +234,17 @@ extern "C" int devit_cls_distill_loss(const float* logits, const float* logits_k
   ClsArgs a{logits, logits_kd, teacher_logits, soft_targets, loss3, dlogits, dlogits_kd, B, C, kind, alpha, tau};
   hipError_t me = hipMemsetAsync(loss3, 0, 3 * sizeof(float), (hipStream_t)stream);
   DEVIT_CHECK(me == hipSuccess, DEVIT_ERR_LAUNCH, "devit_cls_distill_loss: hipMemsetAsync: %s", hipGetErrorString(me));
-  hipLaunchKernelGGL(cls_loss_kernel, dim3((B + 15) / 16), dim3(1024), 0, (hipStream_t)stream, a);
+  const int groups = (B + 15) / 16;
+  if (groups > 1 && devit_det::on()) {   // deterministic mode (det.h): the workgroups' shares go to the workspace and are added to the scalars in workgroup order
+    float* ws = nullptr;
+    const int rc = devit_det::workspace("devit_cls_distill_loss", (size_t)groups * 3 * sizeof(float), &ws);
+    if (rc != DEVIT_OK) return rc;
+    a.loss = ws;
+    hipLaunchKernelGGL(cls_loss_det_kernel, dim3(groups), dim3(1024), 0, (hipStream_t)stream, a);
+    DEVIT_LAUNCH_CHECK();
+    return devit_det::fold(ws, groups, 3, 1, 3, loss3, 0, 1, 0, (hipStream_t)stream);
+  }
+  hipLaunchKernelGGL(cls_loss_kernel, dim3(groups), dim3(1024), 0, (hipStream_t)stream, a);
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
 }

@@ -133,6 +133,56 @@ def _record(phase, stream, i):
         rec.append(hbm_record(i) + (_start, ev))
 
 
+# ----------------------------------------------------------------------------------------------
+# deterministic mode (include/devit_hip.h, "Deterministic mode"): fixed-order reductions instead of fp32 atomics in arrival order
+# ----------------------------------------------------------------------------------------------
+_det_ws = {}            # device index -> the registered workspace (kept alive here; allocated once, at the first launch in the mode)
+
+
+def is_deterministic():
+    on = bool(L.load().devit_get_deterministic())
+    L.before_call = _det_workspace if on else None
+    return on
+
+
+def set_deterministic(flag):
+    """Process-wide, off by default.  On: every reduction of the training step that combines partial sums by fp32 atomics runs in a fixed order
+    instead (same input, seed and launch configuration -> same bits, at world size 1).  Needs no device."""
+    L.before_call = None
+    L.call("devit_set_deterministic", int(bool(flag)))
+    is_deterministic()
+
+
+@contextlib.contextmanager
+def deterministic(flag=True):
+    """`with ops.deterministic():` -- the mode inside the block, the previous state behind it (also when the block raises)."""
+    prev = is_deterministic()
+    set_deterministic(flag)
+    try:
+        yield
+    finally:
+        set_deterministic(prev)
+
+
+def _det_workspace():
+    """Register the current device's workspace with the library, once: L.before_call while the mode is on, so every entry point finds it."""
+    if not torch.cuda.is_available():
+        return
+    dev = torch.cuda.current_device()
+    if dev not in _det_ws:
+        ws = _det_ws[dev] = torch.empty(int(L.load().devit_det_workspace_bytes()), dtype=torch.uint8, device=torch.device("cuda", dev))
+        L.call("devit_set_det_workspace", ptr(ws), ws.numel())
+
+
+def _det_first_call():
+    """The library's default comes from DEVIT_DETERMINISTIC: asked at the first call, when the library is there to be asked."""
+    if is_deterministic():
+        _det_workspace()
+
+
+L.before_call = _det_first_call
+
+
 def call(name, *args):
     """_lib.call; while an instrument is set, with its observer around the call."""
     if (PROFILE is None and PROFILE_HBM is None and PROFILE_WGRAD is None) or _observer is not None:
@@ -196,6 +246,8 @@ def gemm_route(a, lda, a_km, b, ldb, b_km, M, N, K, *, kind, out, ldc, bias=None
     the L.ROUTE_* kernel the call would run on, or the negative DEVIT_ERR_* its argument checks return.  Not a restatement: one rule."""
     def adr(t):
         return t if t is None or isinstance(t, int) else t.data_ptr()
+    if L.before_call is not None:         # (deterministic mode: the query sees the workspace the launch would find)
+        L.before_call()
     A = L.Operand(adr(a), lda, a_km, a_group, a_skip, a_bs)
     Bo = L.Operand(adr(b), ldb, b_km, b_group, b_skip, b_bs)
     ep = L.Epilogue(kind, adr(out), ldc, adr(bias), adr(colscale), adr(aux), adr(aux_in), adr(res), adr(rowscale),

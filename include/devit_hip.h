@@ -164,6 +164,28 @@ DEVIT_API int devit_set_reserved_cus(int n);
 DEVIT_API int devit_get_reserved_cus(void);
 
 /* ------------------------------------------------------------------------------------------
+ * Deterministic mode.  Off by default (DEVIT_DETERMINISTIC=1 in the environment, read once, turns it on); process-wide, like the reserved CUs.
+ * The entry points whose kernels combine partial sums by fp32 atomics in arrival order -- devit_gemm_bf16 with DEVIT_EPI_ATOMIC_F32 (tile and
+ * aux row sums), devit_wgrad_grouped (tiles and a_colsum), devit_embed_bwd (dpos), devit_dropout_apply (colsum), devit_cls_distill_loss (the three
+ * scalars), and devit_block_bwd[_drop] through them -- then give the same bits on every run of the same call: wherever an address has more than one
+ * partial sum, the partials p_0 .. p_{S-1} (S = K slices, row strips, workgroups: the default path's counts and ranges) are written to the workspace
+ * and a second kernel computes
+ *     out <- fp32(out + (((p_0 + p_1) + p_2) + ... + p_{S-1}))       in fp32, left to right by slice / strip / workgroup index,
+ * so that the result does not depend on what the destination held either.  Call sites do not change.  devit_block_bwd[_drop] keeps its
+ * weight-gradient launches on the caller's stream in this mode (as with DEVIT_WGRAD_STREAM=0).
+ * Workspace: caller-owned device memory, registered per device (the current one) with devit_set_det_workspace; NULL / 0 takes it back.  Launches
+ * that use it must be ordered by the caller (one stream, or events): two of them running at once would share it.  devit_det_workspace_bytes() is
+ * enough for every launch of the training step (256 MiB; a caller whose launches need more registers more).  A launch that needs more than is registered returns
+ * DEVIT_ERR_ARG with a message -- devit_gemm_route reports the same -- and never falls back to the atomics.
+ * devit_gemm_bf16 with DEVIT_EPI_ATOMIC_F32 and batch > 1 is refused in the mode (DEVIT_ERR_ARG) when the batches' outputs overlap
+ * (out_batch_stride smaller than one output): they would add into one address in arrival order.
+ * devit_set / get_deterministic and devit_det_workspace_bytes need no device. */
+DEVIT_API int devit_set_deterministic(int on);      /* 0 / 1 */
+DEVIT_API int devit_get_deterministic(void);
+DEVIT_API size_t devit_det_workspace_bytes(void);
+DEVIT_API int devit_set_det_workspace(void* ws, size_t bytes);
+
+/* ------------------------------------------------------------------------------------------
  * Weight gradients of several nn.Linear layers as ONE launch (autograd's dW = dY^T X of models/de_vit.py:67,82,36,45, i.e. what
  * engine.py:123-127's backward() leaves in .grad): a table of jobs, each
  *     out[i][j] += sum_k a[k][i] * b[k][j]      i < a_cols, j < 384           (transposed == 0: out is [a_cols][ldc])
