@@ -1,5 +1,5 @@
 // HBM-bound helper kernels of the DeViT path: patch im2row, token assembly, casts, column sums
-// (bias gradients), embedding backward, small strided f32 GEMM (classifier heads), fused AdamW+EMA.
+// (bias gradients), embedding backward, small strided f32 GEMM (classifier heads).
 #include "det.h"
 #include "devit_common.h"
 
@@ -328,73 +328,6 @@ __global__ __launch_bounds__(256) void sgemm_small_kernel(const float* A, long l
   }
 }
 
-// ---- fused AdamW (+ global-norm clip) + EMA + bf16 re-cast over a flat parameter buffer -----------------
-// torch.optim.AdamW + timm NativeScaler clip_grad_norm_ + timm ModelEma.update (engine.py:127,131-132)
-struct AdamArgs {
-  float* p; const float* g; float* m; float* v; float* ema; __bf16* p_bf16;
-  const float* gnorm_sq;  // device scalar: sum of squared grads (NULL = no clipping)
-  const float* dyn;       // device [3]: lr, 1 - beta1^step, 1 - beta2^step (changes every step; graph-safe)
-  const unsigned char* no_decay4;   // one byte per 4-element granule: != 0 -> no weight decay there (NULL: decay all)
-  size_t n;
-  float beta1, beta2, eps, wd, max_norm, ema_decay, grad_scale;
-};
-__global__ __launch_bounds__(256) void adamw_kernel(const AdamArgs a) {
-  float clip = a.grad_scale;
-  const float lr = a.dyn[0], bc1 = a.dyn[1], bc2 = a.dyn[2];
-  if (a.gnorm_sq) {
-    const float nrm = sqrtf(*a.gnorm_sq) * a.grad_scale;
-    const float c = a.max_norm / (nrm + 1e-6f);   // torch.nn.utils.clip_grad_norm_
-    clip *= c < 1.0f ? c : 1.0f;
-  }
-  const size_t n4 = a.n / 4;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    f32x4 p = *(const f32x4*)(a.p + i * 4);
-    const f32x4 g = *(const f32x4*)(a.g + i * 4) * clip;
-    f32x4 m = *(const f32x4*)(a.m + i * 4), v = *(const f32x4*)(a.v + i * 4);
-    if (!(a.no_decay4 && a.no_decay4[i])) p *= (1.0f - lr * a.wd);
-    m = a.beta1 * m + (1.0f - a.beta1) * g;
-    v = a.beta2 * v + (1.0f - a.beta2) * g * g;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) p[e] -= (lr / bc1) * m[e] / (sqrtf(v[e]) / sqrtf(bc2) + a.eps);
-    *(f32x4*)(a.p + i * 4) = p;
-    *(f32x4*)(a.m + i * 4) = m;
-    *(f32x4*)(a.v + i * 4) = v;
-    if (a.ema) {
-      f32x4 e = *(const f32x4*)(a.ema + i * 4);
-      e = e * a.ema_decay + (1.0f - a.ema_decay) * p;
-      *(f32x4*)(a.ema + i * 4) = e;
-    }
-    if (a.p_bf16) {
-      bf16x4 ob = {f2bf(p[0]), f2bf(p[1]), f2bf(p[2]), f2bf(p[3])};
-      *(bf16x4*)(a.p_bf16 + i * 4) = ob;
-    }
-  }
-}
-
-// sum of squares of a flat f32 buffer -> out[0] (two-stage, deterministic)
-__global__ __launch_bounds__(256) void sumsq_stage1(const float* g, size_t n, float* partial) {
-  __shared__ float red[4];
-  float s = 0.f;
-  const size_t n4 = n / 4;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    const f32x4 v = *(const f32x4*)(g + i * 4);
-    s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
-  }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-__global__ __launch_bounds__(256) void sumsq_stage2(const float* partial, int n, float* out) {
-  __shared__ float red[4];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = red[0] + red[1] + red[2] + red[3];
-}
-
 inline int grid_for(size_t work_items, int cap = 2048) {
   size_t g = (work_items + 255) / 256;
   return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
@@ -571,36 +504,6 @@ extern "C" int devit_sgemm_small(const float* A, long long sam, long long sak, c
   DEVIT_CHECK(A && B && C && M > 0 && N > 0 && K > 0, DEVIT_ERR_ARG, "devit_sgemm_small: bad argument");
   hipLaunchKernelGGL(sgemm_small_kernel, dim3(grid_for((size_t)M * N * 8, 8192)), dim3(256), 0, (hipStream_t)stream, A, sam,
                      sak, B, sbn, sbk, bias, C, ldc, M, N, K, alpha, accumulate);
-  DEVIT_LAUNCH_CHECK();
-  return DEVIT_OK;
-}
-
-extern "C" size_t devit_sumsq_workspace(void) { return 1024 * sizeof(float); }
-
-extern "C" int devit_sumsq_f32(const float* g, size_t n, float* out, void* workspace, size_t workspace_bytes,
-                               void* stream) {
-  DEVIT_CHECK(g && out && workspace && workspace_bytes >= 1024 * sizeof(float), DEVIT_ERR_ARG, "devit_sumsq_f32: bad argument");
-  DEVIT_CHECK(n % 4 == 0, DEVIT_ERR_SHAPE, "devit_sumsq_f32: n must be a multiple of 4 (pad the flat buffer)");
-  hipLaunchKernelGGL(sumsq_stage1, dim3(1024), dim3(256), 0, (hipStream_t)stream, g, n, (float*)workspace);
-  DEVIT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sumsq_stage2, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, 1024, out);
-  DEVIT_LAUNCH_CHECK();
-  return DEVIT_OK;
-}
-
-extern "C" int devit_adamw_step(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16,
-                                const unsigned char* no_decay4, const float* gnorm_sq, const float* dyn, size_t n,
-                                float beta1, float beta2, float eps,
-                                float weight_decay, float max_norm, float ema_decay, float grad_scale,
-                                void* stream) {
-  DEVIT_CHECK(p && g && m && v && dyn, DEVIT_ERR_ARG, "devit_adamw_step: bad argument");
-  DEVIT_CHECK(n % 4 == 0, DEVIT_ERR_SHAPE, "devit_adamw_step: n must be a multiple of 4 (pad the flat buffer)");
-  AdamArgs a;
-  a.p = p; a.g = g; a.m = m; a.v = v; a.ema = ema; a.p_bf16 = (__bf16*)p_bf16; a.gnorm_sq = gnorm_sq; a.n = n;
-  a.no_decay4 = no_decay4;
-  a.dyn = dyn; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
-  a.max_norm = max_norm; a.ema_decay = ema_decay; a.grad_scale = grad_scale;
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream, a);
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
 }

@@ -1,8 +1,10 @@
-// Optimizer tails over the flat parameter buffer besides AdamW (elementwise.hip: adamw_kernel): SGD with momentum (plain and
-// Nesterov), Adam with L2 decay coupled into the gradient, and LAMB with per-tensor trust ratios -- timm 0.5.4's `momentum`,
-// `nesterov`, `adam`, `lamb` / `lambc` (create_optimizer, distill_sub.py:340).  Every tail shares AdamW's frame: the global-norm
-// clip folded into the gradient load, the per-granule weight decay exemption, the EMA and the bf16 re-cast of the new weights.
-// All of them are HBM-bound streams: one thread owns a 16-byte granule of every buffer, loads and stores are 16 bytes wide.
+// The optimizer of the flat parameter buffer: the squared gradient norm (devit_sumsq_f32) and the five fused tails of `--opt` -- AdamW,
+// SGD with momentum (plain and Nesterov), Adam with L2 decay coupled into the gradient, and LAMB with per-tensor trust ratios: timm 0.5.4's
+// `adamw`, `momentum`, `nesterov`, `adam`, `lamb` / `lambc` (create_optimizer, distill_sub.py:340).  One frame, written once: the arguments
+// (OptArgs), the global-norm clip folded into the gradient load (tail_clip), the per-granule weight decay exemption, the EMA and the bf16
+// re-cast of the new weights (model_tail), and on the host one validation + fill (fill_args) and one launch (launch_tail).  A tail adds its
+// update rule between the two.  All of them are HBM-bound streams: one thread owns a 16-byte granule of every buffer, loads and stores are 16
+// bytes wide.
 #include "devit_common.h"
 
 namespace {
@@ -17,7 +19,7 @@ struct OptArgs {
   int nesterov;
 };
 
-// grad_scale * min(1, max_norm / (||g|| * grad_scale + 1e-6)): adamw_kernel's statement, operation for operation
+// grad_scale * min(1, max_norm / (||g|| * grad_scale + 1e-6)): timm NativeScaler's clip_grad_norm_ and the mean of DDP, every tail's first line
 __device__ __forceinline__ float tail_clip(const float* gnorm_sq, float max_norm, float grad_scale) {
   float clip = grad_scale;
   if (gnorm_sq) {
@@ -41,6 +43,28 @@ __device__ __forceinline__ void model_tail(float* ema, __bf16* p_bf16, size_t i,
   }
 }
 
+// ---- torch.optim.AdamW + timm NativeScaler clip_grad_norm_ + timm ModelEma.update (engine.py:127,131-132): the decay is decoupled,
+// p *= 1 - lr wd on the granules that are not exempt; dyn (lr, 1 - beta1^step, 1 - beta2^step) changes every step and is graph-safe
+__global__ __launch_bounds__(256) void adamw_kernel(const OptArgs a) {
+  const float clip = tail_clip(a.gnorm_sq, a.max_norm, a.grad_scale);
+  const float lr = a.dyn[0], bc1 = a.dyn[1], bc2 = a.dyn[2];
+  const size_t n4 = a.n / 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    f32x4 p = *(const f32x4*)(a.p + i * 4);
+    const f32x4 g = *(const f32x4*)(a.g + i * 4) * clip;
+    f32x4 m = *(const f32x4*)(a.m + i * 4), v = *(const f32x4*)(a.v + i * 4);
+    if (!(a.no_decay4 && a.no_decay4[i])) p *= (1.0f - lr * a.wd);
+    m = a.beta1 * m + (1.0f - a.beta1) * g;
+    v = a.beta2 * v + (1.0f - a.beta2) * g * g;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) p[e] -= (lr / bc1) * m[e] / (sqrtf(v[e]) / sqrtf(bc2) + a.eps);
+    *(f32x4*)(a.p + i * 4) = p;
+    *(f32x4*)(a.m + i * 4) = m;
+    *(f32x4*)(a.v + i * 4) = v;
+    model_tail(a.ema, a.p_bf16, i, p, a.ema_decay);
+  }
+}
+
 // ---- torch.optim.SGD(momentum = mu, nesterov, dampening = 0): d = g' + wd p;  buf' = mu buf + d;  p' = p - lr (nesterov ? d + mu buf' : buf')
 // buf starts at zero, which is torch's first step (buf = d).
 __global__ __launch_bounds__(256) void sgd_kernel(const OptArgs a) {
@@ -61,7 +85,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(const OptArgs a) {
   }
 }
 
-// ---- torch.optim.Adam: the decay enters the gradient (d = g' + wd p) and with it both moments; the update is adamw_kernel's form
+// ---- torch.optim.Adam: the decay enters the gradient (d = g' + wd p) and with it both moments; the update is adamw_kernel's, without its p *= 1 - lr wd
 __global__ __launch_bounds__(256) void adam_l2_kernel(const OptArgs a) {
   const float clip = tail_clip(a.gnorm_sq, a.max_norm, a.grad_scale);
   const float lr = a.dyn[0], bc1 = a.dyn[1], bc2 = a.dyn[2];
@@ -205,47 +229,99 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(const LambArgs a) {
   }
 }
 
+// ---- sum of squares of a flat f32 buffer -> out[0] (two-stage, deterministic): the norm tail_clip reads
+__global__ __launch_bounds__(256) void sumsq_stage1(const float* g, size_t n, float* partial) {
+  __shared__ float red[4];
+  float s = 0.f;
+  const size_t n4 = n / 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const f32x4 v = *(const f32x4*)(g + i * 4);
+    s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+__global__ __launch_bounds__(256) void sumsq_stage2(const float* partial, int n, float* out) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) out[0] = red[0] + red[1] + red[2] + red[3];
+}
+
 inline int grid_for(size_t work_items, int cap) {
   size_t g = (work_items + 255) / 256;
   return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
 }
 
-}  // namespace
+// every entry point's argument check and fill: `who` names it in the messages; v is required where the tail keeps two moments
+int fill_args(OptArgs& a, const char* who, bool two_moments, float* p, const float* g, float* m, float* v, float* ema, void* p_bf16,
+              const unsigned char* no_decay4, const float* gnorm_sq, const float* dyn, size_t n, float beta1, float beta2, float eps,
+              float weight_decay, float max_norm, float ema_decay, float grad_scale, int nesterov) {
+  DEVIT_CHECK(p && g && m && (v || !two_moments) && dyn, DEVIT_ERR_ARG, "%s: bad argument", who);
+  DEVIT_CHECK(n % 4 == 0, DEVIT_ERR_SHAPE, "%s: n must be a multiple of 4 (pad the flat buffer)", who);
+  a.p = p; a.g = g; a.m = m; a.v = v; a.ema = ema; a.p_bf16 = (__bf16*)p_bf16; a.gnorm_sq = gnorm_sq; a.dyn = dyn;
+  a.no_decay4 = no_decay4; a.n = n; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
+  a.max_norm = max_norm; a.ema_decay = ema_decay; a.grad_scale = grad_scale; a.nesterov = nesterov != 0;
+  return DEVIT_OK;
+}
 
-extern "C" int devit_sgd_step(float* p, const float* g, float* buf, float* ema, void* p_bf16, const unsigned char* no_decay4,
-                              const float* gnorm_sq, const float* dyn, size_t n, float momentum, int nesterov,
-                              float weight_decay, float max_norm, float ema_decay, float grad_scale, void* stream) {
-  DEVIT_CHECK(p && g && buf && dyn, DEVIT_ERR_ARG, "devit_sgd_step: bad argument");
-  DEVIT_CHECK(n % 4 == 0, DEVIT_ERR_SHAPE, "devit_sgd_step: n must be a multiple of 4 (pad the flat buffer)");
-  OptArgs a = {};
-  a.p = p; a.g = g; a.m = buf; a.ema = ema; a.p_bf16 = (__bf16*)p_bf16; a.gnorm_sq = gnorm_sq; a.dyn = dyn;
-  a.no_decay4 = no_decay4; a.n = n; a.beta1 = momentum; a.nesterov = nesterov != 0; a.wd = weight_decay;
-  a.max_norm = max_norm; a.ema_decay = ema_decay; a.grad_scale = grad_scale;
-  hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+// a grid-stride tail: one thread per granule up to 4096 workgroups
+int launch_tail(void (*kernel)(const OptArgs), const OptArgs& a, void* stream) {
+  hipLaunchKernelGGL(kernel, dim3(grid_for(a.n / 4, 4096)), dim3(256), 0, (hipStream_t)stream, a);
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
 }
 
-static void fill_adam_args(OptArgs& a, float* p, const float* g, float* m, float* v, float* ema, void* p_bf16,
-                           const unsigned char* no_decay4, const float* gnorm_sq, const float* dyn, size_t n, float beta1,
-                           float beta2, float eps, float weight_decay, float max_norm, float ema_decay, float grad_scale) {
-  a.p = p; a.g = g; a.m = m; a.v = v; a.ema = ema; a.p_bf16 = (__bf16*)p_bf16; a.gnorm_sq = gnorm_sq; a.dyn = dyn;
-  a.no_decay4 = no_decay4; a.n = n; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
-  a.max_norm = max_norm; a.ema_decay = ema_decay; a.grad_scale = grad_scale; a.nesterov = 0;
+}  // namespace
+
+extern "C" size_t devit_sumsq_workspace(void) { return 1024 * sizeof(float); }
+
+extern "C" int devit_sumsq_f32(const float* g, size_t n, float* out, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  DEVIT_CHECK(g && out && workspace && workspace_bytes >= 1024 * sizeof(float), DEVIT_ERR_ARG, "devit_sumsq_f32: bad argument");
+  DEVIT_CHECK(n % 4 == 0, DEVIT_ERR_SHAPE, "devit_sumsq_f32: n must be a multiple of 4 (pad the flat buffer)");
+  hipLaunchKernelGGL(sumsq_stage1, dim3(1024), dim3(256), 0, (hipStream_t)stream, g, n, (float*)workspace);
+  DEVIT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(sumsq_stage2, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, 1024, out);
+  DEVIT_LAUNCH_CHECK();
+  return DEVIT_OK;
+}
+
+extern "C" int devit_adamw_step(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16,
+                                const unsigned char* no_decay4, const float* gnorm_sq, const float* dyn, size_t n,
+                                float beta1, float beta2, float eps, float weight_decay, float max_norm, float ema_decay,
+                                float grad_scale, void* stream) {
+  OptArgs a;
+  if (int rc = fill_args(a, "devit_adamw_step", true, p, g, m, v, ema, p_bf16, no_decay4, gnorm_sq, dyn, n, beta1, beta2, eps,
+                         weight_decay, max_norm, ema_decay, grad_scale, 0))
+    return rc;
+  return launch_tail(adamw_kernel, a, stream);
+}
+
+extern "C" int devit_sgd_step(float* p, const float* g, float* buf, float* ema, void* p_bf16, const unsigned char* no_decay4,
+                              const float* gnorm_sq, const float* dyn, size_t n, float momentum, int nesterov,
+                              float weight_decay, float max_norm, float ema_decay, float grad_scale, void* stream) {
+  OptArgs a;
+  if (int rc = fill_args(a, "devit_sgd_step", false, p, g, buf, nullptr, ema, p_bf16, no_decay4, gnorm_sq, dyn, n, momentum, 0.0f, 0.0f,
+                         weight_decay, max_norm, ema_decay, grad_scale, nesterov))
+    return rc;
+  return launch_tail(sgd_kernel, a, stream);
 }
 
 extern "C" int devit_adam_l2_step(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16,
                                   const unsigned char* no_decay4, const float* gnorm_sq, const float* dyn, size_t n,
                                   float beta1, float beta2, float eps, float weight_decay, float max_norm, float ema_decay,
                                   float grad_scale, void* stream) {
-  DEVIT_CHECK(p && g && m && v && dyn, DEVIT_ERR_ARG, "devit_adam_l2_step: bad argument");
-  DEVIT_CHECK(n % 4 == 0, DEVIT_ERR_SHAPE, "devit_adam_l2_step: n must be a multiple of 4 (pad the flat buffer)");
   OptArgs a;
-  fill_adam_args(a, p, g, m, v, ema, p_bf16, no_decay4, gnorm_sq, dyn, n, beta1, beta2, eps, weight_decay, max_norm, ema_decay,
-                 grad_scale);
-  hipLaunchKernelGGL(adam_l2_kernel, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream, a);
-  DEVIT_LAUNCH_CHECK();
-  return DEVIT_OK;
+  if (int rc = fill_args(a, "devit_adam_l2_step", true, p, g, m, v, ema, p_bf16, no_decay4, gnorm_sq, dyn, n, beta1, beta2, eps,
+                         weight_decay, max_norm, ema_decay, grad_scale, 0))
+    return rc;
+  return launch_tail(adam_l2_kernel, a, stream);
 }
 
 extern "C" size_t devit_lamb_workspace(int nchunks, int nsegments) {
@@ -259,15 +335,15 @@ extern "C" int devit_lamb_step(float* p, const float* g, float* m, float* v, flo
                                float ema_decay, float grad_scale, void* workspace, size_t workspace_bytes, void* stream) {
   DEVIT_CHECK(p && g && m && v && dyn && gnorm_sq && chunks && workspace, DEVIT_ERR_ARG,
               "devit_lamb_step: bad argument (gnorm_sq is required: LAMB clips the gradient to norm 1 itself)");
-  DEVIT_CHECK(n % 4 == 0, DEVIT_ERR_SHAPE, "devit_lamb_step: n must be a multiple of 4 (pad the flat buffer)");
+  LambArgs a;
+  if (int rc = fill_args(a.o, "devit_lamb_step", true, p, g, m, v, ema, p_bf16, nullptr, gnorm_sq, dyn, n, beta1, beta2, eps, weight_decay,
+                         max_norm, ema_decay, grad_scale, 0))
+    return rc;
   DEVIT_CHECK(nchunks > 0 && nsegments > 0 && n / 4 <= 0xffffffffu, DEVIT_ERR_SHAPE,
               "devit_lamb_step: nchunks = %d, nsegments = %d must be positive, n / 4 must fit 32 bits", nchunks, nsegments);
   DEVIT_CHECK(workspace_bytes >= devit_lamb_workspace(nchunks, nsegments) && ((size_t)workspace & 7) == 0, DEVIT_ERR_ARG,
               "devit_lamb_step: workspace of %zu bytes, devit_lamb_workspace(%d, %d) = %zu (8-byte aligned)", workspace_bytes,
               nchunks, nsegments, devit_lamb_workspace(nchunks, nsegments));
-  LambArgs a;
-  fill_adam_args(a.o, p, g, m, v, ema, p_bf16, nullptr, gnorm_sq, dyn, n, beta1, beta2, eps, weight_decay, max_norm, ema_decay,
-                 grad_scale);
   a.chunks = chunks; a.nchunks = nchunks; a.nsegments = nsegments; a.trust_clip = trust_clip != 0;
   a.partials = (float*)workspace;
   a.trust = a.partials + (size_t)nchunks * 2;

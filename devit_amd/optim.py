@@ -1,10 +1,11 @@
-"""Optimizer tail of the DEKD step on flat buffers: global-norm clip + AdamW + EMA + bf16 weight re-cast in two
-launches (devit_sumsq_f32, devit_adamw_step).  Replaces timm NativeScaler -> clip_grad_norm_ -> AdamW.step and
-ModelEma.update (engine.py:127,131-132; ~600 tiny kernels in the reference).
+"""Optimizer tail of the DEKD step on flat buffers: global-norm clip + update + EMA + bf16 weight re-cast in two launches (devit_sumsq_f32,
+then the tail's step).  Replaces timm NativeScaler -> clip_grad_norm_ -> optimizer.step and ModelEma.update (engine.py:127,131-132; ~600 tiny
+kernels in the reference).
 
-timm's other optimizers that the reference's `--opt` reaches through create_optimizer share that frame: FlatSGD (`momentum`,
-`nesterov`), FlatAdam (`adam`: L2 decay coupled into the gradient) and FlatLamb (`lamb`, `lambc`: per-tensor trust ratios over a
-chunk table, three launches); create_flat_optimizer maps the command line to one of the four."""
+Five tails on one frame (_FlatTail: the buffers, the scalar ring, the step's begin and end, the state dict), one for every optimizer the
+reference's `--opt` reaches through timm's create_optimizer: FlatAdamW (`adamw`), FlatSGD (`momentum`, `nesterov`), FlatAdam (`adam`: L2 decay
+coupled into the gradient) and FlatLamb (`lamb`, `lambc`: per-tensor trust ratios over a chunk table, three launches).  A class adds its
+hyper-parameters and its one C call; create_flat_optimizer maps the command line to one of them."""
 import torch
 
 from . import _lib as L
@@ -23,7 +24,7 @@ def no_decay_names(model):
 
 class _FlatTail:
     """What every optimizer over ddp.FlatParams shares: the buffers and the scalar ring (_setup), the surface the training loops use
-    (param_groups[0]["lr"], zero_grad, max_norm, ema_state_dict) and, for the classes below FlatAdamW, the step's frame and the state dict."""
+    (param_groups[0]["lr"], zero_grad, max_norm, ema_state_dict), the step's frame and the state dict."""
     opt_name = "adamw"
     state_keys = ("m", "v")
 
@@ -49,6 +50,10 @@ class _FlatTail:
         self._dyn_host = host.pin_memory() if dev.type == "cuda" else host
         self._dyn = torch.zeros(dyn_len, dtype=torch.float32, device=dev)
         self._ws = torch.empty(4096, dtype=torch.uint8, device=dev)
+
+    def _scalars(self, t):
+        """the Adam family's `dyn` at step t: lr and the two bias corrections"""
+        return self.param_groups[0]["lr"], 1.0 - self.betas[0] ** t, 1.0 - self.betas[1] ** t
 
     def _begin_step(self, scalars, need_norm=False):
         """step_count, the step's scalars into the device `dyn`, the gradient's squared norm when the step clips (or needs it) -> clip?"""
@@ -112,37 +117,19 @@ class FlatAdamW(_FlatTail):
         self._setup(flat, lr, weight_decay, max_norm, ema_decay, no_decay, 3)
 
     def step(self):
-        L.require_device(self.flat.flat)
-        self.step_count += 1
-        b1, b2 = self.betas
-        slot = self._dyn_host[self.step_count % self._dyn_host.shape[0]]
-        slot[0] = self.param_groups[0]["lr"]
-        slot[1] = 1.0 - b1 ** self.step_count
-        slot[2] = 1.0 - b2 ** self.step_count
-        self._dyn.copy_(slot, non_blocking=True)
+        clip = self._begin_step(self._scalars)
         f = self.flat
-        clip = self.max_norm is not None and self.max_norm > 0
-        if clip:
-            call("devit_sumsq_f32", ptr(f.flat_grad), f.numel, ptr(self.gnorm_sq), ptr(self._ws), self._ws.numel(),
-                 stream_ptr())
         # f.grad_scale: 1 / world after the summing bucket all-reduce (ddp.BucketedGradReducer.finish) -- the mean of DDP
         call("devit_adamw_step", ptr(f.flat), ptr(f.flat_grad), ptr(self.m), ptr(self.v), ptr(self.ema), ptr(f.flat16),
-             ptr(self.no_decay4), ptr(self.gnorm_sq) if clip else None, ptr(self._dyn), f.numel, b1, b2, self.eps,
+             ptr(self.no_decay4), ptr(self.gnorm_sq) if clip else None, ptr(self._dyn), f.numel, self.betas[0], self.betas[1], self.eps,
              self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0), float(f.grad_scale),
              stream_ptr())
-        f.grad_scale = 1.0
-        f.refresh_kmajor()      # the kernel rewrote flat16 in place: the k-major weight copies derived from it follow (one launch)
+        self._end_step()
 
     def state_dict(self):
-        return {"m": self.m, "v": self.v, "ema": self.ema, "step": self.step_count, "lr": self.param_groups[0]["lr"]}
-
-    def load_state_dict(self, sd):
-        self._check_kind(sd)
-        self.m.copy_(sd["m"]); self.v.copy_(sd["v"])
-        if self.ema is not None and sd.get("ema") is not None:
-            self.ema.copy_(sd["ema"])
-        self.step_count = sd["step"]
-        self.param_groups[0]["lr"] = sd["lr"]
+        sd = super().state_dict()
+        del sd["opt"]                           # AdamW's checkpoints carry no name (and load as AdamW: _check_kind)
+        return sd
 
 
 class FlatSGD(_FlatTail):
@@ -172,9 +159,6 @@ class FlatAdam(_FlatTail):
     def __init__(self, flat, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None, ema_decay=None, no_decay=None):
         self.betas, self.eps = betas, eps
         self._setup(flat, lr, weight_decay, max_norm, ema_decay, no_decay, 3)
-
-    def _scalars(self, t):
-        return self.param_groups[0]["lr"], 1.0 - self.betas[0] ** t, 1.0 - self.betas[1] ** t
 
     def step(self):
         clip = self._begin_step(self._scalars)
@@ -252,8 +236,6 @@ class FlatLamb(_FlatTail):
         self.nchunks, self.nsegments = self.chunks_host.shape[0], len(sizes)
         self.chunks = self.chunks_host.to(dev)
         self._lamb_ws = torch.empty((2 * self.nchunks + self.nsegments) * 4, dtype=torch.uint8, device=dev)
-
-    _scalars = FlatAdam._scalars
 
     def trust(self):
         """the trust ratios of the last step, one per tensor of flat.names (1 for the no-decay group)"""

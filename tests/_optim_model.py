@@ -1,11 +1,13 @@
-"""Float64 statements, first-order elementwise error bounds, fp32 emulations with planted bugs, case lists and seeded inputs for the optimizer tails
-of csrc/optim.hip: devit_sgd_step (momentum, nesterov), devit_adam_l2_step (adam) and devit_lamb_step (lamb, lambc).  Plain torch on the CPU, in the
-conventions of tests/_tail_model.py (whose U, ratio, gen and AdamW inputs it reuses); shared by tests/test_optim_model.py (the model under test, no
-GPU) and tests/test_gpu_optim.py (the kernels under test), which therefore see the same inputs.
+"""Float64 statements, first-order elementwise error bounds, fp32 emulations with planted bugs, case lists and seeded inputs for the optimizer of
+csrc/optim.hip: the squared gradient norm (devit_sumsq_f32) and the five fused tails -- devit_adamw_step (adamw), devit_sgd_step (momentum, nesterov),
+devit_adam_l2_step (adam) and devit_lamb_step (lamb, lambc).  Plain torch on the CPU, in the conventions of tests/_tail_model.py (whose U, ratio and
+gen it reuses); shared by tests/test_optim_model.py (the model under test, no GPU) and tests/test_gpu_optim.py (the kernels under test), which
+therefore see the same inputs.
 
 Every bound is u = 2^-24 times the absolute values of the terms that enter an element times the roundings on the longest path to it, counted from the
-kernel's statement: a correctly rounded operation 1, sqrtf and `/` 2; a fused multiply-add only removes a rounding.  Shared by all tails
-(optim.hip: tail_clip, as adamw_kernel): clip = sqrtf 2, times grad_scale 1, + 1e-6 1, the division 2, clip *= c 1: 7; g' = g * clip: CLIP_R = 8."""
+kernel's statement: a correctly rounded operation 1, sqrtf and `/` 2; a fused multiply-add only removes a rounding.  The tails share one frame, and so
+do their statements: the clip (optim.hip: tail_clip -> clip64, _clip32): sqrtf 2, times grad_scale 1, + 1e-6 1, the division 2, clip *= c 1: 7;
+g' = g * clip: CLIP_R = 8; the exemption from weight decay by granule (_exempt); the Adam update (_adam_update); the EMA (model_tail -> _ema)."""
 import math
 
 import torch
@@ -13,24 +15,60 @@ import torch
 import _tail_model as T
 from _tail_model import F32, F64, U, _f
 
-OPT_HP = dict(beta1=0.9, beta2=0.999, eps=1e-8, wd=0.05, ema_decay=0.999, lr=1e-3, momentum=0.9)
+ADAM_HP = dict(beta1=0.9, beta2=0.999, eps=1e-8, wd=0.05, ema_decay=0.999, lr=1e-3)
+OPT_HP = dict(ADAM_HP, momentum=0.9)
 CLIP_R = 8
 CHUNK = 4096                     # elements of a LAMB chunk: 1024 granules
 # outputs that are a few roundings of values of their own magnitude: the bound is a correct implementation's worst case (see _tail_model.SHORT_PATHS)
-SHORT_PATHS = {"p", "m", "v", "ema", "buf"}
+SHORT_PATHS = {"p": "the decay or the update's quotient, the subtraction", "m": "m = beta1 m + (1 - beta1) g': 3 on |beta1 m| + |m'|", "v": "as m",
+               "ema": "ema = ema d + (1 - d) p: 3", "buf": "buf = mu buf + d: as m"}
 
+ADAMW_NS = (8, 12292, 4194316)           # the sizes of step_cases
+SUMSQ_NS = (4, 1024, 12292, 1048584, 4194316)
+ADAMW_MUTATIONS = ("clip_without_grad_scale", "decay_on_exempt_granule", "granule_index_per_element")
 SGD_MUTATIONS = ("decay_on_exempt_granule", "granule_index_per_element", "nesterov_uses_old_buf")
 ADAM_MUTATIONS = ("decay_on_exempt_granule", "granule_index_per_element", "decoupled_decay")
 LAMB_MUTATIONS = ("norm_over_chunk", "norm_includes_next_granule", "trust_on_no_decay_tensor", "internal_clip_forgotten", "lambc_not_capped")
 
 
+# ============================================================================================ the norm (sumsq_stage1, sumsq_stage2)
+def sumsq_inputs(n, ints):
+    g = T.gen("sumsq", n, ints)
+    return T.randint(g, -2, 2, n) if ints else T.randn(g, n) * 0.3
+
+
+def sumsq_bounds(gv):
+    """1024 blocks of 256 threads: per thread ceil(n / 4 / 262144) trips of a four-term expression added to s (4 products + 4 adds: 5 on the longest
+    path), 6 shuffle adds and 3 through LDS (sumsq_stage1); stage 2: 4 in sequence, 6 and 3"""
+    n = gv.numel()
+    cnt = 5 * ((n // 4 + 262143) // 262144) + 9 + 13
+    ref = (gv.to(F64) ** 2).sum()
+    return ref, U * cnt * ref
+
+
+# ============================================================================================ what the tails share
 def step_cases():
-    """the cases of devit_sgd_step and devit_adam_l2_step: n = 8, n = 12292 (an odd number of granules, the mask alternating by granule) and one at
-    n = 4194316 (the grid stride's second trip); clip active (0.05) and not (1e9), with and without gnorm_sq, EMA and the bf16 copy, grad_scale 1 / 0.5"""
-    return T.adamw_cases()
+    """the cases of devit_adamw_step, devit_sgd_step and devit_adam_l2_step: n = 8, n = 12292 (an odd number of granules, the mask alternating by
+    granule) and one at n = 4194316 (the grid stride's second trip); clip active (0.05) and not (1e9), with and without gnorm_sq, EMA and the bf16
+    copy, grad_scale 1 / 0.5.  dicts: n, max_norm, gnorm (gnorm_sq given), grad_scale, mask, ema, p16"""
+    return [dict(n=8, max_norm=0.05, gnorm=True, grad_scale=1.0, mask=True, ema=True, p16=True),
+            dict(n=8, max_norm=1e9, gnorm=True, grad_scale=0.5, mask=False, ema=False, p16=False),
+            dict(n=12292, max_norm=0.05, gnorm=True, grad_scale=0.5, mask=True, ema=True, p16=True),
+            dict(n=12292, max_norm=0.05, gnorm=False, grad_scale=0.5, mask=True, ema=False, p16=True),
+            dict(n=12292, max_norm=1e9, gnorm=True, grad_scale=1.0, mask=False, ema=True, p16=False),
+            dict(n=4194316, max_norm=0.05, gnorm=True, grad_scale=0.5, mask=True, ema=True, p16=True)]
 
 
-step_inputs = T.adamw_inputs
+def step_inputs(c):
+    """p, three gradients (one per step; elements 0, 5 and every 7th are 0 at step 1), the no_decay4 mask alternating by granule"""
+    n = c["n"]
+    g = T.gen("adamw", n, c["max_norm"], c["grad_scale"])
+    p = T.randn(g, n)
+    grads = [T.randn(g, n) * 0.3 for _ in range(3)]
+    grads[0][::7] = 0.0
+    grads[0][5] = 0.0
+    mask = (torch.arange(n // 4) % 2).to(torch.uint8)
+    return dict(p=p, grads=grads, mask=mask if c["mask"] else None)
 
 
 def _hp(hp, step):
@@ -55,12 +93,82 @@ def _decayed_grad(p, g, mask, gnorm_sq, max_norm, grad_scale, wd):
     return g2, d, e_d
 
 
+def _adam_update(m2, v2, e_m, e_v, lr, bc1, bc2, eps):
+    """upd = ((lr / bc1) m') / (sqrtf(v') / sqrtf(bc2) + eps) -> (upd, e_upd): s = sqrtf / sqrtf: e_v / (2 v') + 2, 2, 2; + eps 1; lr / bc1 2, times
+    m' 1 + e_m, the division 2 + e_denom"""
+    s = v2.sqrt() / math.sqrt(bc2)
+    denom = s + eps
+    rel_v = torch.where(v2 > 0, e_v / (2 * v2.clamp_min(1e-300)), torch.zeros_like(v2))
+    e_denom = s * (rel_v + 6 * U) + U * denom
+    upd = (lr / bc1) * m2 / denom
+    return upd, upd.abs() * (5 * U + e_denom / denom) + (lr / bc1) * e_m / denom
+
+
 def _ema(ref, bnd, ema, d):
     if ema is not None:
         e, od = ema.to(F64), _f(1.0 - d)
         ref["ema"] = e * d + od * ref["p"]                 # ema d 1, (1 - d) p' 1 + e_p, the add 1 on |ema'|
         bnd["ema"] = U * ((e * d).abs() + (od * ref["p"]).abs()) + od * bnd["p"] + U * ref["ema"].abs()
     return ref, bnd
+
+
+def _exempt(mask, n, mutate):
+    if mask is None or mutate == "decay_on_exempt_granule":
+        return torch.zeros(n, dtype=torch.bool)
+    if mutate == "granule_index_per_element":
+        return mask[torch.arange(n) % mask.numel()].bool()
+    return mask.repeat_interleave(4).bool()
+
+
+def _clip32(gnorm_sq, max_norm, grad_scale, norm_scaled=True):
+    """tail_clip in fp32 torch; norm_scaled=False plants a bug: the norm is taken of the unscaled gradients"""
+    f = lambda x: torch.tensor(x, dtype=F32)
+    clip = f(grad_scale)
+    if gnorm_sq is not None:
+        c = f(max_norm) / (torch.sqrt(gnorm_sq.to(F32).reshape(())) * f(grad_scale if norm_scaled else 1.0) + f(1e-6))
+        clip = clip * torch.minimum(c, f(1.0))
+    return clip
+
+
+# ============================================================================================ AdamW (adamw_kernel)
+def adamw_step_bounds(p, g, m, v, ema, mask, gnorm_sq, step, max_norm, grad_scale, hp=ADAM_HP):
+    """One step of the header's formula in float64 from the GIVEN fp32 state (p, m, v, ema before the step; gnorm_sq as given or None) -> (ref dict
+    p, m, v, ema, bounds dict), with the hyper-parameters as the fp32 values the entry point receives (1 - beta is exact in fp32):
+    m':  beta1 m 1, (1 - beta1) g' 1 + the 8 of g', the add 1 on |m'|:      u (|beta1 m| + 9 |(1 - beta1) g'|) + u |m'|
+    v':  beta2 v 1, (1 - beta2) g' g' 2 + 16, the add 1:                    u (|beta2 v| + 18 |(1 - beta2) g'^2|) + u |v'|
+    p':  the decay p *= (1 - lr wd): lr wd 1, 1 - 1, the product 1: 3 u |p|;  e_upd (_adam_update);  the subtraction 1 on |p'|"""
+    b1, b2, eps, wd, d, lr, bc1, bc2 = _hp(hp, step)
+    ob1, ob2 = _f(1.0 - b1), _f(1.0 - b2)
+    p, g, m, v = (t.to(F64) for t in (p, g, m, v))
+    g2 = g * clip64(gnorm_sq, max_norm, grad_scale)
+    fac = 1.0 - lr * wd
+    decay = torch.full_like(p, fac) if mask is None else torch.where(mask.repeat_interleave(4).bool(), torch.ones_like(p), torch.full_like(p, fac))
+    m2 = b1 * m + ob1 * g2
+    v2 = b2 * v + ob2 * g2 * g2
+    e_m = U * ((b1 * m).abs() + (CLIP_R + 1) * (ob1 * g2).abs()) + U * m2.abs()
+    e_v = U * ((b2 * v).abs() + (2 * CLIP_R + 2) * (ob2 * g2 * g2)) + U * v2.abs()
+    upd, e_upd = _adam_update(m2, v2, e_m, e_v, lr, bc1, bc2, eps)
+    p2 = p * decay - upd
+    return _ema(dict(p=p2, m=m2, v=v2), dict(p=3 * U * p.abs() + e_upd + U * p2.abs(), m=e_m, v=e_v), ema, d)
+
+
+def adamw_step_emulate(p, g, m, v, ema, mask, gnorm_sq, step, max_norm, grad_scale, hp=ADAM_HP, mutate=None):
+    """fp32 torch; mutations: clip_without_grad_scale (the norm is not scaled), decay_on_exempt_granule (the mask is ignored),
+    granule_index_per_element (no_decay4 is indexed by the element, not by the granule of four)"""
+    assert mutate is None or mutate in ADAMW_MUTATIONS
+    f = lambda x: torch.tensor(x, dtype=F32)
+    b1, b2, eps, wd, d, lr = (f(hp[k]) for k in ("beta1", "beta2", "eps", "wd", "ema_decay", "lr"))
+    bc1, bc2 = f(1 - hp["beta1"] ** step), f(1 - hp["beta2"] ** step)
+    p, g, m, v = (t.to(F32) for t in (p, g, m, v))
+    g2 = g * _clip32(gnorm_sq, max_norm, grad_scale, norm_scaled=mutate != "clip_without_grad_scale")
+    pd = torch.where(_exempt(mask, p.numel(), mutate), p, p * (f(1.0) - lr * wd))
+    m2 = b1 * m + (f(1.0) - b1) * g2
+    v2 = b2 * v + (f(1.0) - b2) * g2 * g2
+    p2 = pd - (lr / bc1) * m2 / (torch.sqrt(v2) / torch.sqrt(bc2) + eps)
+    out = dict(p=p2, m=m2, v=v2)
+    if ema is not None:
+        out["ema"] = ema.to(F32) * d + (f(1.0) - d) * p2
+    return out
 
 
 # ============================================================================================ SGD with momentum (sgd_kernel)
@@ -83,23 +191,6 @@ def sgd_step_bounds(p, g, buf, ema, mask, gnorm_sq, step, max_norm, grad_scale, 
     return _ema(ref, bnd, ema, d_)
 
 
-def _exempt(mask, n, mutate):
-    if mask is None or mutate == "decay_on_exempt_granule":
-        return torch.zeros(n, dtype=torch.bool)
-    if mutate == "granule_index_per_element":
-        return mask[torch.arange(n) % mask.numel()].bool()
-    return mask.repeat_interleave(4).bool()
-
-
-def _clip32(gnorm_sq, max_norm, grad_scale):
-    f = lambda x: torch.tensor(x, dtype=F32)
-    clip = f(grad_scale)
-    if gnorm_sq is not None:
-        c = f(max_norm) / (torch.sqrt(gnorm_sq.to(F32).reshape(())) * f(grad_scale) + f(1e-6))
-        clip = clip * torch.minimum(c, f(1.0))
-    return clip
-
-
 def sgd_step_emulate(p, g, buf, ema, mask, gnorm_sq, step, max_norm, grad_scale, nesterov, hp=OPT_HP, mutate=None):
     """fp32 torch; mutations: decay_on_exempt_granule (the mask is ignored), granule_index_per_element (no_decay4 indexed by the element),
     nesterov_uses_old_buf (the look-ahead takes buf, not buf')"""
@@ -118,17 +209,6 @@ def sgd_step_emulate(p, g, buf, ema, mask, gnorm_sq, step, max_norm, grad_scale,
 
 
 # ============================================================================================ Adam with L2 decay (adam_l2_kernel)
-def _adam_update(m2, v2, e_m, e_v, lr, bc1, bc2, eps):
-    """upd = ((lr / bc1) m') / (sqrtf(v') / sqrtf(bc2) + eps) -> (upd, e_upd), as adamw_step_bounds counts it: s = sqrtf / sqrtf: e_v / (2 v') + 2, 2, 2;
-    + eps 1; lr / bc1 2, times m' 1 + e_m, the division 2 + e_denom"""
-    s = v2.sqrt() / math.sqrt(bc2)
-    denom = s + eps
-    rel_v = torch.where(v2 > 0, e_v / (2 * v2.clamp_min(1e-300)), torch.zeros_like(v2))
-    e_denom = s * (rel_v + 6 * U) + U * denom
-    upd = (lr / bc1) * m2 / denom
-    return upd, upd.abs() * (5 * U + e_denom / denom) + (lr / bc1) * e_m / denom
-
-
 def adam_step_bounds(p, g, m, v, ema, mask, gnorm_sq, step, max_norm, grad_scale, hp=OPT_HP):
     """torch.optim.Adam from the GIVEN fp32 state: d = g' + wd p; m' = b1 m + (1 - b1) d; v' = b2 v + (1 - b2) d d; p' = p - upd (no p *= 1 - lr wd).
     m': b1 m 1, (1 - b1) d 1 + e_d, the add 1 on |m'|.   v': b2 v 1, ((1 - b2) d) d 2 + 2 |d| e_d, the add 1.   p': e_upd, the subtraction 1."""
@@ -215,7 +295,7 @@ def lamb_step_bounds(p, g, m, v, ema, layout, gnorm_sq, step, max_norm, grad_sca
     """timm Lamb from the GIVEN fp32 state -> (ref, bounds) for p, m, v, ema over the flat buffer (elements of no tensor: unchanged, bound 0) and trust
     [len(layout)].  max_norm <= 0: no outer clip.
     c2 = clip / max(1, n1), n1 = sqrtf(gnorm_sq) clip: clip 7, n1 2 + 1 + 7 = 10, the division 2: 19; g'' = g c2: RG = 20
-    m', v' as adamw from g'' (RG + 1, 2 RG + 2).   u0 = (m' / bc1) / (sqrtf(v') / sqrtf(bc2) + eps): m' / bc1 2 + e_m / bc1; the denominator as
+    m', v' as adamw_step_bounds from g'' (RG + 1, 2 RG + 2).   u0 = (m' / bc1) / (sqrtf(v') / sqrtf(bc2) + eps): m' / bc1 2 + e_m / bc1; the denominator as
     _adam_update; the division 2.   u = u0 + wd p: 1 on |wd p|, 1 on |u| (decayed tensors).
     sum p^2, sum u^2: lamb_sum_roundings, + 2 |u| e_u per term; sqrtf 2 each, the division 2 -> e_trust.
     p' = p - (lr trust) u: e_trust |lr u| + lr trust e_u, lr trust 1, the product 1, the subtraction 1 on |p'|"""

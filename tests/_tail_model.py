@@ -1,5 +1,5 @@
 """Float64 statements, first-order elementwise error bounds, fp32 emulations with planted bugs, case lists and seeded inputs for the kernels
-behind the C ABI that are neither GEMM, attention, dropout nor HSIC: csrc/layernorm.hip + ln_rows.h, elementwise.hip, losses.hip, the index
+behind the C ABI that are neither GEMM, attention, dropout, HSIC nor the optimizer (tests/_optim_model.py): csrc/layernorm.hip + ln_rows.h, elementwise.hip, losses.hip, the index
 copies of shrink.hip and the exact-fp32 companions of sgemm.hip.  Plain torch on the CPU; shared by tests/test_tail_model.py (the model itself
 under test, no GPU) and tests/test_gpu_tail.py (the kernels under test), which therefore see the same inputs.
 
@@ -39,9 +39,7 @@ def ratio(got, ref, bound):
 # outputs (the names tests/test_tail_model.py gives them) whose bound is a handful of roundings of the output's own magnitude, with the count
 SHORT_PATHS = {"dlo": "cls_distill_loss dlogits: where y dominates, the subtraction, wbase (3) and its product: 5",
                "dlk": "cls_distill_loss dlogits_kd: the subtraction, wd (<= 3) and its product, on p at 2 + its log-probability",
-               "da": "token_mse da = 2 d inv: 4", "S_f32": "relation_grad S: three additions of four exponentials of 2 + 1 each, times up",
-               "p": "adamw p: the decay (3), the update's quotient, the subtraction", "m": "adamw m = beta1 m + (1 - beta1) g': 3 on |beta1 m| + |m'|",
-               "v": "adamw v: as m", "ema": "adamw ema = ema d + (1 - d) p: 3"}
+               "da": "token_mse da = 2 d inv: 4", "S_f32": "relation_grad S: three additions of four exponentials of 2 + 1 each, times up"}
 
 
 def stored16(bound, ref, f16=False):
@@ -680,122 +678,6 @@ def rel_grad_emulate(gram_t, gram_s, lse_t, lse_s, upstream, hd_t, hd_s, bf16_ou
     lt, ls = lse_t.to(F32), lse_s.to(F32)
     v = (torch.exp(rs - ls[:, :, None]) + torch.exp(rs - ls[:, None, :]) - torch.exp(rt - lt[:, :, None]) - torch.exp(rt - lt[:, None, :])) * up
     return v.to(BF16) if bf16_out else v
-
-
-# ============================================================================================ optimizer tail (elementwise.hip:279-334)
-SUMSQ_NS = (4, 1024, 12292, 1048584, 4194316)
-ADAMW_NS = (8, 12292, 4194316)
-ADAMW_MUTATIONS = ("clip_without_grad_scale", "decay_on_exempt_granule", "granule_index_per_element")
-ADAM_HP = dict(beta1=0.9, beta2=0.999, eps=1e-8, wd=0.05, ema_decay=0.999, lr=1e-3)
-
-
-def sumsq_inputs(n, ints):
-    g = gen("sumsq", n, ints)
-    return randint(g, -2, 2, n) if ints else randn(g, n) * 0.3
-
-
-def sumsq_bounds(gv):
-    """1024 blocks of 256 threads: per thread ceil(n / 4 / 262144) trips of a four-term expression added to s (4 products + 4 adds: 5 on the longest
-    path; :317-320), 6 shuffle adds and 3 (:321-324); stage 2: 4 in sequence, 6 and 3 (:329-333)"""
-    n = gv.numel()
-    cnt = 5 * ((n // 4 + 262143) // 262144) + 9 + 13
-    ref = (gv.to(F64) ** 2).sum()
-    return ref, U * cnt * ref
-
-
-def adamw_cases():
-    """dicts: n, max_norm (clip active at 0.05, inactive at 1e9), gnorm (gnorm_sq given), grad_scale, mask, ema, p16"""
-    return [dict(n=8, max_norm=0.05, gnorm=True, grad_scale=1.0, mask=True, ema=True, p16=True),
-            dict(n=8, max_norm=1e9, gnorm=True, grad_scale=0.5, mask=False, ema=False, p16=False),
-            dict(n=12292, max_norm=0.05, gnorm=True, grad_scale=0.5, mask=True, ema=True, p16=True),
-            dict(n=12292, max_norm=0.05, gnorm=False, grad_scale=0.5, mask=True, ema=False, p16=True),
-            dict(n=12292, max_norm=1e9, gnorm=True, grad_scale=1.0, mask=False, ema=True, p16=False),
-            dict(n=4194316, max_norm=0.05, gnorm=True, grad_scale=0.5, mask=True, ema=True, p16=True)]
-
-
-def adamw_inputs(c):
-    """p, three gradients (one per step; elements 0, 5 and every 7th are 0 at step 1), the no_decay4 mask alternating by granule"""
-    n = c["n"]
-    g = gen("adamw", n, c["max_norm"], c["grad_scale"])
-    p = randn(g, n)
-    grads = [randn(g, n) * 0.3 for _ in range(3)]
-    grads[0][::7] = 0.0
-    grads[0][5] = 0.0
-    mask = (torch.arange(n // 4) % 2).to(torch.uint8)
-    return dict(p=p, grads=grads, mask=mask if c["mask"] else None)
-
-
-def adamw_step_bounds(p, g, m, v, ema, mask, gnorm_sq, step, max_norm, grad_scale, hp=ADAM_HP):
-    """One step of the header's formula in float64 from the GIVEN fp32 state (p, m, v, ema before the step; gnorm_sq as given or None) -> (ref dict
-    p, m, v, ema, bounds dict).  adamw_kernel, with the hyper-parameters as the fp32 values the entry point receives (1 - beta is exact in fp32):
-    clip (:280-286):  sqrtf 2, times grad_scale 1, + 1e-6 1, the division 2, clip *= c 1: 7;  g' = g * clip (:290): 8 u |g'|
-    m (:293):  beta1 m 1, (1 - beta1) g' 1 + the 8 of g', the add 1 on |m'|:      u (|beta1 m| + 9 |(1 - beta1) g'|) + u |m'|
-    v (:294):  beta2 v 1, (1 - beta2) g' g' 2 + 16, the add 1:                    u (|beta2 v| + 18 |(1 - beta2) g'^2|) + u |v'|
-    p (:292, :296):  decay p *= (1 - lr wd): lr wd 1, 1 - 1, the product 1: 3 u |p|;   s = sqrtf(v') / sqrtf(bc2): e_v / (2 v') + 2, 2, 2;
-               denom = s + eps 1;  upd = ((lr / bc1) m') / denom: 2, e_m, 1, e_denom, 2;  the subtraction 1 on |p'|
-    ema (:302): ema d 1, (1 - d) p' 1 + e_p, the add 1 on |ema'|"""
-    b1, b2, eps, wd, d, lr = _f(hp["beta1"]), _f(hp["beta2"]), _f(hp["eps"]), _f(hp["wd"]), _f(hp["ema_decay"]), _f(hp["lr"])
-    bc1, bc2 = _f(1 - hp["beta1"] ** step), _f(1 - hp["beta2"] ** step)
-    ob1, ob2, od = _f(1.0 - b1), _f(1.0 - b2), _f(1.0 - d)
-    p, g, m, v = (t.to(F64) for t in (p, g, m, v))
-    max_norm, grad_scale = _f(max_norm), _f(grad_scale)
-    clip = grad_scale
-    if gnorm_sq is not None:
-        c = max_norm / (math.sqrt(float(gnorm_sq)) * grad_scale + _f(1e-6))
-        clip = grad_scale * min(1.0, c)
-    g2 = g * clip
-    fac = 1.0 - lr * wd
-    decay = torch.full_like(p, fac) if mask is None else torch.where(mask.repeat_interleave(4).bool(), torch.ones_like(p), torch.full_like(p, fac))
-    pd = p * decay
-    m2 = b1 * m + ob1 * g2
-    v2 = b2 * v + ob2 * g2 * g2
-    e_m = U * ((b1 * m).abs() + 9 * (ob1 * g2).abs()) + U * m2.abs()
-    e_v = U * ((b2 * v).abs() + 18 * (ob2 * g2 * g2)) + U * v2.abs()
-    s = v2.sqrt() / math.sqrt(bc2)
-    denom = s + eps
-    rel_v = torch.where(v2 > 0, e_v / (2 * v2.clamp_min(1e-300)), torch.zeros_like(v2))
-    e_denom = s * (rel_v + 6 * U) + U * denom
-    upd = (lr / bc1) * m2 / denom
-    e_upd = upd.abs() * (5 * U + e_denom / denom) + (lr / bc1) * e_m / denom
-    p2 = pd - upd
-    e_p = 3 * U * p.abs() + e_upd + U * p2.abs()
-    ref, bnd = dict(p=p2, m=m2, v=v2), dict(p=e_p, m=e_m, v=e_v)
-    if ema is not None:
-        e = ema.to(F64)
-        ref["ema"] = e * d + od * p2
-        bnd["ema"] = U * ((e * d).abs() + (od * p2).abs()) + od * e_p + U * ref["ema"].abs()
-    return ref, bnd
-
-
-def adamw_step_emulate(p, g, m, v, ema, mask, gnorm_sq, step, max_norm, grad_scale, hp=ADAM_HP, mutate=None):
-    """fp32 torch; mutations: clip_without_grad_scale (the norm is not scaled, :283), decay_on_exempt_granule (the mask is ignored, :292),
-    granule_index_per_element (no_decay4 is indexed by the element, not by the granule of four)"""
-    assert mutate is None or mutate in ADAMW_MUTATIONS
-    f = lambda x: torch.tensor(x, dtype=F32)
-    b1, b2, eps, wd, d, lr = (f(hp[k]) for k in ("beta1", "beta2", "eps", "wd", "ema_decay", "lr"))
-    bc1, bc2 = f(1 - hp["beta1"] ** step), f(1 - hp["beta2"] ** step)
-    p, g, m, v = (t.to(F32) for t in (p, g, m, v))
-    clip = f(grad_scale)
-    if gnorm_sq is not None:
-        nrm = torch.sqrt(gnorm_sq.to(F32).reshape(())) * (f(1.0) if mutate == "clip_without_grad_scale" else f(grad_scale))
-        c = f(max_norm) / (nrm + f(1e-6))
-        clip = clip * torch.minimum(c, f(1.0))
-    g2 = g * clip
-    n = p.numel()
-    if mask is None or mutate == "decay_on_exempt_granule":
-        exempt = torch.zeros(n, dtype=torch.bool)
-    elif mutate == "granule_index_per_element":
-        exempt = mask[torch.arange(n) % mask.numel()].bool()
-    else:
-        exempt = mask.repeat_interleave(4).bool()
-    pd = torch.where(exempt, p, p * (f(1.0) - lr * wd))
-    m2 = b1 * m + (f(1.0) - b1) * g2
-    v2 = b2 * v + (f(1.0) - b2) * g2 * g2
-    p2 = pd - (lr / bc1) * m2 / (torch.sqrt(v2) / torch.sqrt(bc2) + eps)
-    out = dict(p=p2, m=m2, v=v2)
-    if ema is not None:
-        out["ema"] = ema.to(F32) * d + (f(1.0) - d) * p2
-    return out
 
 
 # ============================================================================================ exact-fp32 companions (sgemm.hip)

@@ -1,6 +1,6 @@
 """The ensemble stage on the flat fused path, on a real MI355X: the token KL kernel per element against float64 (tests/_ens_model.py), EnsLoss
 loss_type='kldiv' against torch's own nn.KLDivLoss in float64 and against the reference's golden step, the optimizer tail of the two clip groups
-(all backbones under one norm, the fusion head under its own) against the float64 statements of tests/_tail_model.py on REAL gradients, the closed
+(all backbones under one norm, the fusion head under its own) against the float64 statements of tests/_optim_model.py on REAL gradients, the closed
 loop through engine.train_1epoch_ens_disjoint with ensemble.EnsStepRunner, and the CLI."""
 import argparse
 import json
@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import _ens_model as E
+import _optim_model as M
 import _tail_model as T
 from _tail_model import BF16, F32, F64, U
 from conftest import chk
@@ -238,10 +239,10 @@ def test_fused_tail_two_clip_groups(setup, dev):
     per_bb = [sum(float((p.grad.double() ** 2).sum()) for p in m.parameters()) for m in multi.backbones]
     assert min(per_bb) > 0 and abs(float(opt.gnorm_sq) - sum(per_bb)) < 1e-4 * sum(per_bb)
     for name, f, o, s in (("backbones", flat, opt, snaps[0]), ("ens_mlp", ens_flat, ens_opt, snaps[1])):
-        ref, bnd = T.sumsq_bounds(s["g"])
+        ref, bnd = M.sumsq_bounds(s["g"])
         hold(f"ens_tail/{name}/gnorm_sq", o.gnorm_sq[0], ref, bnd)
         assert float(o.gnorm_sq) > 0
-        ref, bnd = T.adamw_step_bounds(s["p"], s["g"], s["m"], s["v"], s["ema"], o.no_decay4, o.gnorm_sq.cpu(), 1, 1.0, 1.0, hp=HP)
+        ref, bnd = M.adamw_step_bounds(s["p"], s["g"], s["m"], s["v"], s["ema"], o.no_decay4, o.gnorm_sq.cpu(), 1, 1.0, 1.0, hp=HP)
         got = dict(p=f.flat, m=o.m, v=o.v, ema=o.ema)
         for k in ("p", "m", "v", "ema"):
             r = _ratio_dev(got[k], ref[k], bnd[k])

@@ -1,5 +1,5 @@
-"""The optimizer tails of csrc/optim.hip on a real MI355X against the float64 statements of tests/_optim_model.py, on the inputs tests/test_optim_model.py
-holds the model itself to: devit_sgd_step (momentum, nesterov), devit_adam_l2_step and devit_lamb_step (lamb, lambc) at the kernel level -- three chained
+"""The optimizer of csrc/optim.hip on a real MI355X against the float64 statements of tests/_optim_model.py, on the inputs tests/test_optim_model.py
+holds the model itself to: devit_sumsq_f32, then devit_adamw_step, devit_sgd_step (momentum, nesterov), devit_adam_l2_step and devit_lamb_step (lamb, lambc) at the kernel level -- three chained
 steps, each held element by element against the statement applied to the fp32 state the kernel itself left behind, the bf16 copy bit-exact, guard
 elements behind every buffer -- then FlatSGD / FlatAdam / FlatLamb behind one real backward of a two-block dedeit, and the CLIs with --opt."""
 import argparse
@@ -13,7 +13,7 @@ import _optim_model as M
 import _tail_model as T
 from _tail_model import BF16, F32, F64, ratio
 from conftest import chk
-from test_gpu_tail import Out, call, refused, same_bits
+from test_gpu_tail import Out, call, hold, refused, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -40,6 +40,67 @@ def _report(tag, worst):
 
 def _cid(c):
     return f"n{c['n']}-mn{c['max_norm']}-gs{c['grad_scale']}-gn{int(c['gnorm'])}-e{int(c['ema'])}"
+
+
+# ============================================================================================ devit_sumsq_f32, devit_adamw_step
+@pytest.mark.parametrize("n", M.SUMSQ_NS)
+def test_sumsq_f32(dev, n):
+    L = _L()
+    nws = L.load().devit_sumsq_workspace()
+    for ints in (True, False):
+        gv = M.sumsq_inputs(n, ints)
+        ref, bnd = M.sumsq_bounds(gv)
+        out, ws = Out(dev, 1, 1), Out(dev, 1, nws // 4)
+        call("devit_sumsq_f32", gv.to(dev), n, out.t, ws.t, nws)
+        assert out.intact() and ws.intact()
+        if ints:
+            assert float(out.v[0, 0]) == float(ref), "integers in [-2, 2]: every partial sum is exact"
+        else:
+            hold(f"sumsq_f32/n{n}/out", out.v[0, 0], ref, bnd)
+
+
+def test_sumsq_f32_refuses_n6(dev):
+    t = torch.zeros(1024, device=dev)
+    refused("devit_sumsq_f32", t, 6, t, t, 4096)
+
+
+@pytest.mark.parametrize("c", M.step_cases(), ids=lambda c: f"n{c['n']}-mn{c['max_norm']}-gs{c['grad_scale']}-gn{int(c['gnorm'])}-e{int(c['ema'])}")
+def test_adamw_step(dev, c):
+    """three chained steps; each is held against the float64 statement applied to the fp32 state the kernel itself left behind"""
+    L = _L()
+    i = M.step_inputs(c)
+    n, hp = c["n"], M.ADAM_HP
+    p, m, v = Out(dev, 1, n, init=i["p"]), Out(dev, 1, n, init=torch.zeros(n)), Out(dev, 1, n, init=torch.zeros(n))
+    ema = Out(dev, 1, n, init=i["p"]) if c["ema"] else None
+    p16 = Out(dev, 1, n, BF16) if c["p16"] else None
+    mask = None if i["mask"] is None else i["mask"].to(dev)
+    nws = L.load().devit_sumsq_workspace()
+    ws, gsq = torch.empty(nws, dtype=torch.uint8, device=dev), torch.empty(1, device=dev)
+    tag = f"adamw_step/n{n}_mn{c['max_norm']}_gs{c['grad_scale']}_gn{int(c['gnorm'])}_mask{int(c['mask'])}"
+    worst = {}
+    for step in (1, 2, 3):
+        g = i["grads"][step - 1]
+        gd = g.to(dev)
+        before = [t.v[0].cpu().clone() if t is not None else None for t in (p, m, v, ema)]
+        if c["gnorm"]:
+            call("devit_sumsq_f32", gd, n, gsq, ws, nws)
+        dyn = torch.tensor([hp["lr"], 1 - hp["beta1"] ** step, 1 - hp["beta2"] ** step], dtype=F32, device=dev)
+        call("devit_adamw_step", p.t, gd, m.t, v.t, ema.t if ema else None, p16.t if p16 else None, mask, gsq if c["gnorm"] else None, dyn, n,
+             hp["beta1"], hp["beta2"], hp["eps"], hp["wd"], c["max_norm"], hp["ema_decay"], c["grad_scale"])
+        ref, bnd = M.adamw_step_bounds(before[0], g, before[1], before[2], before[3], i["mask"], gsq.cpu() if c["gnorm"] else None, step,
+                                       c["max_norm"], c["grad_scale"])
+        got = dict(p=p, m=m, v=v, ema=ema)
+        for k in ref:
+            assert got[k].intact()
+            worst[k] = max(worst.get(k, 0.0), ratio(got[k].v[0], ref[k], bnd[k]))
+        if p16:
+            assert p16.intact() and same_bits(p16.v, p.v.to(BF16)), "p_bf16 == bf16(p)"
+        if step == 1:
+            z = g == 0
+            assert bool((m.v[0].cpu()[z] == 0).all()) and bool((v.v[0].cpu()[z] == 0).all()), "a zero gradient leaves zero moments at step 1"
+    for k, r in worst.items():
+        print(f"tail/{tag}/{k} {r:.3f}")
+        assert chk(r, 1.0, name=f"tail/{tag}/{k}"), (tag, k, r)
 
 
 # ============================================================================================ devit_sgd_step, devit_adam_l2_step
@@ -225,7 +286,7 @@ def test_flat_optimizers_behind_a_real_backward(dev, backward, kind):
     opt.step()
     torch.cuda.synchronize()
     gsq = opt.gnorm_sq.cpu()
-    ref, bnd = T.sumsq_bounds(s["g"])
+    ref, bnd = M.sumsq_bounds(s["g"])
     assert chk(ratio(gsq[0], ref, bnd), 1.0, name=f"tail/optim_model/{kind}/gnorm_sq")
     if kind == "nesterov":
         ref, bnd = M.sgd_step_bounds(s["p"], s["g"], s["buf"], s["ema"], opt.no_decay4, gsq, 1, 1.0, 1.0, True, hp=HP)

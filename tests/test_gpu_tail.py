@@ -1,5 +1,5 @@
-"""The kernels behind the C ABI that are neither GEMM, attention, dropout nor HSIC -- LayerNorm, the elementwise helpers, the losses, the optimizer
-tail, the index copies and the exact-fp32 companions -- on a real MI355X against the float64 statements of tests/_tail_model.py, on the inputs
+"""The kernels behind the C ABI that are neither GEMM, attention, dropout, HSIC nor the optimizer (tests/test_gpu_optim.py) -- LayerNorm, the
+elementwise helpers, the losses, the index copies and the exact-fp32 companions -- on a real MI355X against the float64 statements of tests/_tail_model.py, on the inputs
 tests/test_tail_model.py holds the model itself to.  Three kinds of assertion, the strongest that applies:
     bit-exact   (torch.equal) where the op is a copy or one correctly rounded operation, against the same operation in torch fp32;
     exact ints  small-integer inputs whose every partial sum is representable, against int64 / float64 arithmetic;
@@ -466,67 +466,6 @@ def test_relation_stats_and_grad(dev, B, N, hd_t, hd_s, scale):
         got = S.v.cpu().view(B, 256, 256)
         hold(f"{tag}/grad/up{up}_{'f32' if f32_out else 'bf16'}/S", got[:, :N, :N], want, eS)
         assert not bool(got[:, ~inside].any()), "S is exactly 0 outside N x N"
-
-
-# ============================================================================================ optimizer tail
-@pytest.mark.parametrize("n", T.SUMSQ_NS)
-def test_sumsq_f32(dev, n):
-    L = _L()
-    nws = L.load().devit_sumsq_workspace()
-    for ints in (True, False):
-        gv = T.sumsq_inputs(n, ints)
-        ref, bnd = T.sumsq_bounds(gv)
-        out, ws = Out(dev, 1, 1), Out(dev, 1, nws // 4)
-        call("devit_sumsq_f32", gv.to(dev), n, out.t, ws.t, nws)
-        assert out.intact() and ws.intact()
-        if ints:
-            assert float(out.v[0, 0]) == float(ref), "integers in [-2, 2]: every partial sum is exact"
-        else:
-            hold(f"sumsq_f32/n{n}/out", out.v[0, 0], ref, bnd)
-
-
-def test_sumsq_f32_refuses_n6(dev):
-    t = torch.zeros(1024, device=dev)
-    refused("devit_sumsq_f32", t, 6, t, t, 4096)
-
-
-@pytest.mark.parametrize("c", T.adamw_cases(), ids=lambda c: f"n{c['n']}-mn{c['max_norm']}-gs{c['grad_scale']}-gn{int(c['gnorm'])}-e{int(c['ema'])}")
-def test_adamw_step(dev, c):
-    """three chained steps; each is held against the float64 statement applied to the fp32 state the kernel itself left behind"""
-    L = _L()
-    i = T.adamw_inputs(c)
-    n, hp = c["n"], T.ADAM_HP
-    p, m, v = Out(dev, 1, n, init=i["p"]), Out(dev, 1, n, init=torch.zeros(n)), Out(dev, 1, n, init=torch.zeros(n))
-    ema = Out(dev, 1, n, init=i["p"]) if c["ema"] else None
-    p16 = Out(dev, 1, n, BF16) if c["p16"] else None
-    mask = None if i["mask"] is None else i["mask"].to(dev)
-    nws = L.load().devit_sumsq_workspace()
-    ws, gsq = torch.empty(nws, dtype=torch.uint8, device=dev), torch.empty(1, device=dev)
-    tag = f"adamw_step/n{n}_mn{c['max_norm']}_gs{c['grad_scale']}_gn{int(c['gnorm'])}_mask{int(c['mask'])}"
-    worst = {}
-    for step in (1, 2, 3):
-        g = i["grads"][step - 1]
-        gd = g.to(dev)
-        before = [t.v[0].cpu().clone() if t is not None else None for t in (p, m, v, ema)]
-        if c["gnorm"]:
-            call("devit_sumsq_f32", gd, n, gsq, ws, nws)
-        dyn = torch.tensor([hp["lr"], 1 - hp["beta1"] ** step, 1 - hp["beta2"] ** step], dtype=F32, device=dev)
-        call("devit_adamw_step", p.t, gd, m.t, v.t, ema.t if ema else None, p16.t if p16 else None, mask, gsq if c["gnorm"] else None, dyn, n,
-             hp["beta1"], hp["beta2"], hp["eps"], hp["wd"], c["max_norm"], hp["ema_decay"], c["grad_scale"])
-        ref, bnd = T.adamw_step_bounds(before[0], g, before[1], before[2], before[3], i["mask"], gsq.cpu() if c["gnorm"] else None, step,
-                                       c["max_norm"], c["grad_scale"])
-        got = dict(p=p, m=m, v=v, ema=ema)
-        for k in ref:
-            assert got[k].intact()
-            worst[k] = max(worst.get(k, 0.0), ratio(got[k].v[0], ref[k], bnd[k]))
-        if p16:
-            assert p16.intact() and same_bits(p16.v, p.v.to(BF16)), "p_bf16 == bf16(p)"
-        if step == 1:
-            z = g == 0
-            assert bool((m.v[0].cpu()[z] == 0).all()) and bool((v.v[0].cpu()[z] == 0).all()), "a zero gradient leaves zero moments at step 1"
-    for k, r in worst.items():
-        print(f"tail/{tag}/{k} {r:.3f}")
-        assert chk(r, 1.0, name=f"tail/{tag}/{k}"), (tag, k, r)
 
 
 # ============================================================================================ index copies (shrink.hip)

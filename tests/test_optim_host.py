@@ -1,5 +1,6 @@
-"""Host logic of the optimizer tails besides AdamW, no GPU: the factory that maps the command line to a class, the support check of the three training
-CLIs, FlatLamb's chunk table over a CPU ddp.FlatParams of dedeit and its validation, and the state dicts with their kind check."""
+"""Host logic of the optimizer tails, no GPU: the factory that maps the command line to a class, the support check of the three training CLIs,
+FlatLamb's chunk table over a CPU ddp.FlatParams of dedeit and its validation, the state dicts with their kind check, and the C calls of one
+FlatAdamW.step in their order."""
 import importlib
 
 import pytest
@@ -144,3 +145,25 @@ def test_state_dict_of_another_kind_is_refused(small):
             with pytest.raises(ValueError) as e:
                 b.load_state_dict(a.state_dict())
             assert src in str(e.value) and dst in str(e.value)
+
+
+def test_adamw_step_host_sequence(small, monkeypatch):
+    """the C calls of FlatAdamW.step: the norm only when the step clips, then exactly one devit_adamw_step that finds lr and the two bias
+    corrections of ITS step in `dyn`; the device check comes first, grad_scale is consumed once"""
+    _, flat = small
+    log = []
+    monkeypatch.setattr(_lib, "require_device", lambda t: log.append(("require_device", None)))
+    monkeypatch.setattr(optim, "stream_ptr", lambda: None)
+    for max_norm in (None, 0.0, 2.0):
+        opt = optim.FlatAdamW(flat, lr=0.25, betas=(0.5, 0.75), max_norm=max_norm)
+        monkeypatch.setattr(optim, "call", lambda name, *a: log.append((name, (opt.step_count, opt._dyn.tolist(), flat.grad_scale, a))))
+        for t in (1, 2):
+            del log[:]
+            flat.grad_scale = 0.5
+            opt.param_groups[0]["lr"] = 0.25 / t
+            opt.step()
+            assert [n for n, _ in log] == ["require_device"] + (["devit_sumsq_f32"] if max_norm else []) + ["devit_adamw_step"]
+            count, dyn, scale, args = log[-1][1]
+            assert count == t and dyn == [0.25 / t, 1 - 0.5 ** t, 1 - 0.75 ** t]          # all exact in fp32
+            assert scale == 0.5 and args[16] == 0.5 and flat.grad_scale == 1.0
+            assert (args[7] is None) == (not max_norm) and args[9] == flat.numel and args[10:13] == (0.5, 0.75, opt.eps)

@@ -1,7 +1,7 @@
-"""tests/_optim_model.py under test, on the CPU: the fp32 emulation of every optimizer tail of csrc/optim.hip stays inside its bounds over three chained
-steps (<= 0.5, below 1 on the short paths), every planted bug leaves them on a named output of a named case, the float64 statements of momentum,
-nesterov and adam agree with torch.optim.SGD / torch.optim.Adam (two parameter groups, three steps, 1e-12 relative), and the LAMB statement agrees
-with a naive per-tensor loop and has the properties timm's Lamb has."""
+"""tests/_optim_model.py under test, on the CPU: the fp32 emulation of the norm and of every optimizer tail of csrc/optim.hip stays inside its bounds
+over three chained steps (<= 0.5, below 1 on the short paths), every planted bug leaves them on a named output of a named case, the float64
+statements of adamw, momentum, nesterov and adam agree with torch.optim.AdamW / SGD / Adam (three steps, 1e-12 relative where the hyper-parameters
+are exact in fp32), and the LAMB statement agrees with a naive per-tensor loop and has the properties timm's Lamb has."""
 import math
 
 import pytest
@@ -31,6 +31,80 @@ def _ids(c):
     return f"n{c['n']}-mn{c['max_norm']}-gs{c['grad_scale']}-gn{int(c['gnorm'])}"
 
 
+# ------------------------------------------------------------------------------------------ the norm, AdamW
+@pytest.mark.parametrize("n", M.SUMSQ_NS)
+def test_sumsq(n):
+    gi = M.sumsq_inputs(n, True)
+    ref, _ = M.sumsq_bounds(gi)
+    assert float(ref) < 2 ** 24 and float((gi * gi).sum()) == float(ref)          # every partial sum is an integer below 2^24
+    gr = M.sumsq_inputs(n, False)
+    ref, bnd = M.sumsq_bounds(gr)
+    _hold(f"sumsq n{n}", dict(out=ratio((gr * gr).sum(), ref, bnd)))
+
+
+def _adam_chain(c, mutate=None):
+    """three chained steps of the emulation, each held against the float64 statement applied to the state it started from -> worst ratios"""
+    i = M.step_inputs(c)
+    n = c["n"]
+    p, m, v = i["p"].clone(), torch.zeros(n), torch.zeros(n)
+    ema = i["p"].clone() if c["ema"] else None
+    worst = {}
+    for step in (1, 2, 3):
+        g = i["grads"][step - 1]
+        gsq = (g * g).sum().reshape(1) if c["gnorm"] else None
+        ref, bnd = M.adamw_step_bounds(p, g, m, v, ema, i["mask"], gsq, step, c["max_norm"], c["grad_scale"])
+        e = M.adamw_step_emulate(p, g, m, v, ema, i["mask"], gsq, step, c["max_norm"], c["grad_scale"], mutate=mutate)
+        for k in ref:
+            worst[k] = max(worst.get(k, 0.0), ratio(e[k], ref[k], bnd[k]))
+        p, m, v, ema = e["p"], e["m"], e["v"], e.get("ema")
+    return worst
+
+
+@pytest.mark.parametrize("c", M.step_cases(), ids=lambda c: f"n{c['n']}-mn{c['max_norm']}-gs{c['grad_scale']}-gn{int(c['gnorm'])}")
+def test_adamw_emulation_within_bounds(c):
+    _hold(f"adamw {c}", _adam_chain(c))
+
+
+@pytest.mark.parametrize("bug", M.ADAMW_MUTATIONS)
+def test_adamw_planted_bugs(bug):
+    hits = []
+    for c in M.step_cases():
+        if c["n"] > 100000:
+            continue
+        hits += [((c["n"], c["max_norm"], c["grad_scale"], c["mask"]), k, rt) for k, rt in _adam_chain(c, mutate=bug).items()]
+    _caught(bug, hits)
+
+
+def test_adamw_statement_agrees_with_torch():
+    n = 64
+    c = dict(n=n, max_norm=0.05, gnorm=True, grad_scale=1.0, mask=False, ema=False, p16=False)
+    i = M.step_inputs(c)
+    hp = {k: T._f(v) for k, v in M.ADAM_HP.items()}          # the statement takes the hyper-parameters as fp32 values
+    rp = i["p"].to(F64).clone().requires_grad_(True)
+    opt = torch.optim.AdamW([rp], lr=hp["lr"], betas=(hp["beta1"], hp["beta2"]), eps=hp["eps"], weight_decay=hp["wd"])
+    p, m, v = i["p"].to(F64), torch.zeros(n, dtype=F64), torch.zeros(n, dtype=F64)
+    for step in (1, 2, 3):
+        g = i["grads"][step - 1].to(F64)
+        rp.grad = g.clone()
+        torch.nn.utils.clip_grad_norm_([rp], 0.05)
+        opt.step()
+        ref, _ = M.adamw_step_bounds(p, g, m, v, None, None, (g * g).sum(), step, 0.05, 1.0)
+        p, m, v = ref["p"], ref["m"], ref["v"]
+        # the kernel takes the bias corrections as fp32 values (dyn): the statement rounds them, torch does not -> compare with them unrounded
+        bc1, bc2 = 1 - hp["beta1"] ** step, 1 - hp["beta2"] ** step
+        assert abs(T._f(1 - M.ADAM_HP["beta1"] ** step) - bc1) < 1e-6 and abs(T._f(1 - M.ADAM_HP["beta2"] ** step) - bc2) < 1e-6
+    assert float((p - rp.detach()).abs().max()) <= 1e-6          # fp32-rounded bias corrections (1e-7 relative) times three updates of 1e-3
+    # with the corrections passed through unrounded the statement IS torch's: one step from zero state
+    rp2 = i["p"].to(F64).clone().requires_grad_(True)
+    opt2 = torch.optim.AdamW([rp2], lr=hp["lr"], betas=(0.5, 0.75), eps=hp["eps"], weight_decay=hp["wd"])
+    rp2.grad = i["grads"][1].to(F64).clone()
+    opt2.step()
+    ref, _ = M.adamw_step_bounds(i["p"].to(F64), i["grads"][1], torch.zeros(n), torch.zeros(n), None, None, None, 1, 1e9, 1.0,
+                                 hp=dict(M.ADAM_HP, beta1=0.5, beta2=0.75))
+    assert float((ref["p"] - rp2.detach()).abs().max()) <= 1e-12
+
+
+# ------------------------------------------------------------------------------------------ momentum, nesterov, adam
 def _chain(kind, c, mutate=None, nesterov=False):
     """three chained steps of the emulation, each held against the float64 statement applied to the state it started from -> worst ratios"""
     i = M.step_inputs(c)
