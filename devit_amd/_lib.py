@@ -188,6 +188,8 @@ SIGNATURES = {
     "devit_token_kldiv": (_I, [_P, _P, _Z, _I, _P, _P, _I, _P]),
     "devit_relation_stats": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "devit_relation_grad": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "devit_relation_fused_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "devit_relation_fused_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "devit_add_scale_cast_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "devit_hid_normalize": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "devit_hid_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),

@@ -1453,17 +1453,42 @@ class ClsDistillLossFn(torch.autograd.Function):
         return dlo * g, dlk * g, None, None, None, None, None
 
 
+def relation_fused_selected(s_qkv, t_qkv, B, N):
+    """Does RelationLossFn run csrc/relation.hip's two launches for these packed buffers?  N <= 208, both widths multiples of 64 up to 1024, a bf16
+    student and a bf16 or f16 teacher buffer holding the B N rows, and DEVIT_RELFUSE (read per call) not 0."""
+    if os.environ.get("DEVIT_RELFUSE", "") == "0":
+        return False
+    Ds, Dt = s_qkv.shape[1] // 3, t_qkv.shape[1] // 3
+    return (s_qkv.dtype == BF16 and t_qkv.dtype in (BF16, F16) and 0 < N <= 208 and B > 0
+            and all(0 < D <= 1024 and D % 64 == 0 for D in (Ds, Dt))
+            and all(b.dim() == 2 and b.shape[1] == 3 * D and b.stride(1) == 1 and b.stride(0) % 8 == 0 and b.shape[0] >= B * N
+                    and b.data_ptr() % 16 == 0 for b, D in ((s_qkv, Ds), (t_qkv, Dt))))
+
+
 class RelationLossFn(torch.autograd.Function):
     """q/k/v feature-relation losses (utils/losses.py:307-328) on PACKED qkv buffers.
 
     t_qkv: bf16 [>= B*N + 58 rows, 3*Dt], s_qkv likewise with Ds; component j lives in columns [j*D, (j+1)*D).
-    Returns fp32 [3] = (q, k, v) losses.  Gradient flows to the student buffer only."""
+    Returns fp32 [3] = (q, k, v) losses.  Gradient flows to the student buffer only.
+
+    Where relation_fused_selected() says so the two launches of csrc/relation.hip run (Grams on chip; the context keeps the bf16 S_unit of the
+    three components and nothing else); otherwise the batched GEMMs around devit_relation_stats / devit_relation_grad."""
 
     @staticmethod
     def forward(ctx, s_qkv, t_qkv, B, N, hd_s, hd_t):
         L.require_device(s_qkv)
         dev = s_qkv.device
         Ds, Dt = s_qkv.shape[1] // 3, t_qkv.shape[1] // 3
+        ctx.fused = relation_fused_selected(s_qkv, t_qkv, B, N)
+        if ctx.fused:
+            losses = torch.empty(3, dtype=F32, device=dev)
+            stats = torch.empty((3, 3, B * N), dtype=F32, device=dev)      # lse_t, lse_s, row_kl: dead after the reduce
+            S = torch.empty((3, B, 208, 224), dtype=BF16, device=dev)
+            call("devit_relation_fused_fwd", ptr(s_qkv), ptr(t_qkv), B, N, Ds, Dt, s_qkv.stride(0), t_qkv.stride(0), hd_t, hd_s,
+                 int(t_qkv.dtype == F16), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(S), ptr(losses), stream_ptr())
+            ctx.S, ctx.s_qkv = S, s_qkv
+            ctx.meta = (B, N, hd_s, hd_t, Ds)
+            return losses
         assert s_qkv.shape[0] >= (B - 1) * N + 256 and t_qkv.shape[0] >= (B - 1) * N + 256, "packed qkv needs pad rows"
         losses = torch.empty(3, dtype=F32, device=dev)
         grams, stats = [], []
@@ -1492,6 +1517,10 @@ class RelationLossFn(torch.autograd.Function):
         dev = s_qkv.device
         g = g.contiguous().float()
         d = torch.empty_like(s_qkv)       # rows < B*N are all written below (N rows per image x 3 components)
+        if ctx.fused:
+            call("devit_relation_fused_bwd", ptr(ctx.S), ptr(s_qkv), ptr(g), B, N, Ds, s_qkv.stride(0), ptr(d), d.stride(0), stream_ptr())
+            ctx.S = None
+            return d, None, None, None, None, None
         S = torch.empty((B, 256, 256), dtype=BF16, device=dev)
         for j in range(3):
             gt, gs = ctx.grams[j]

@@ -633,6 +633,22 @@ DEVIT_API int devit_relation_stats(const float* gram_t, const float* gram_s, int
 DEVIT_API int devit_relation_grad(const float* gram_t, const float* gram_s, const float* lse_t, const float* lse_s,
                         const float* upstream, int B, int N, int ldr, int head_dim_t, int head_dim_s, void* S_out,
                         int out_is_f32, void* stream);
+/* The same loss with both Grams kept on chip (csrc/relation.hip): two launches for all three components, no fp32 Gram in memory.
+ * The packed 16-bit qkv buffers are read in place: component j in columns [j D, (j + 1) D), image b in rows [b N, (b + 1) N), row strides
+ * ld_s / ld_t elements.  Rows >= N of an image's window are never read.  N <= 208, Ds and Dt multiples of 64 up to 1024, ld multiples of 8
+ * and >= 3 D (DEVIT_ERR_SHAPE otherwise); teacher_f16: the teacher buffer holds IEEE f16 instead of bf16.
+ *   fwd : lse_t, lse_s, row_kl: fp32 [3][B N] (row log-sum-exps of gram / sqrt(head_dim) and the rows' KL terms, as devit_relation_stats);
+ *         loss3[j] = sum(row_kl[j]) / B in a fixed order;
+ *         S_out: bf16 [3][B][208][224], every element written:
+ *             S_unit = (softmax_s + softmax_s^T - softmax_t - softmax_t^T) / (B sqrt(hd_s)), rounded once, zero outside N x N
+ *   bwd : d[b N + i][j Ds + c] = bf16(upstream3[j] * sum_k S_unit[j][b][i][k] F_s[b N + k][j Ds + c]): fp32 sum, the device scalar applied in
+ *         fp32, one rounding.  Rows >= B N of d and columns >= 3 Ds are not touched; rows < B N are all written.
+ * No atomics: both give the same bits on every run. */
+DEVIT_API int devit_relation_fused_fwd(const void* s_qkv, const void* t_qkv, int B, int N, int Ds, int Dt, int ld_s, int ld_t,
+                             int head_dim_t, int head_dim_s, int teacher_f16, float* lse_t, float* lse_s, float* row_kl,
+                             void* S_out, float* loss3, void* stream);
+DEVIT_API int devit_relation_fused_bwd(const void* S, const void* s_qkv, const float* upstream3, int B, int N, int Ds, int ld_s, void* d,
+                             int ld_d, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Hidden-state distillation (csrc/hid.hip).
