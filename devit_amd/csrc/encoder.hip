@@ -267,11 +267,11 @@ int encoder_fwd(int nblocks, const devit_block_weights* w, const devit_block_act
                 float eps, void* stream) {
   DEVIT_CHECK(nblocks > 0 && w && acts, DEVIT_ERR_ARG, "devit_encoder_fwd: bad argument");
   Ctx c{B * N, pad_rows(B * N), B, N, D, eps, stream};
-  for (int i = 0; i < nblocks; ++i) {
-    DEVIT_CHECK(i == 0 || acts[i].x == (const float*)acts[i - 1].buf[DEVIT_ACT_X2], DEVIT_ERR_ARG,
+  // (the chain is checked whole before the first block is enqueued: a refused call has launched nothing)
+  for (int i = 1; i < nblocks; ++i)
+    DEVIT_CHECK(acts[i].x == (const float*)acts[i - 1].buf[DEVIT_ACT_X2], DEVIT_ERR_ARG,
                 "devit_encoder_fwd: block %d does not read block %d's output", i, i - 1);
-    TRY(block_fwd(c, w[i], acts[i], drop ? drop + i : nullptr));
-  }
+  for (int i = 0; i < nblocks; ++i) TRY(block_fwd(c, w[i], acts[i], drop ? drop + i : nullptr));
   return DEVIT_OK;
 }
 }  // namespace

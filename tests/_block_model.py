@@ -1,0 +1,612 @@
+"""The host sequence of the 16-bit encoder block (csrc/encoder.hip: devit_encoder_fwd, devit_block_bwd) audited STAGE BY STAGE: every buffer a block
+leaves in memory is compared with the float64 statement of the ONE operation that produced it, evaluated on that operation's inputs exactly as
+they were left in memory, under the per-element bound the project already holds that kernel to:
+    LayerNorm forward / backward and their column sums   _tail_model.ln_fwd_bounds, ln_bwd_bounds, ln_colsum_bounds
+    the GEMM launches                                    _gemm_model.statement (per epilogue kind), wgrad_reference (the grouped weight gradients)
+    attention forward / backward                         _attn_model.bounds
+A wrong wire -- another buffer, flag, row scale or bias pointer, a pad row left with junk, a bias gradient counted twice -- is an error of the size
+of the signal on ONE named stage; no tolerance is made up for the composition (whose end-to-end accuracy stays with tests/test_gpu_model.py).
+Plain torch: everything runs where its inputs live.  Shared by tests/test_block_model.py (this model under test, no GPU: emulate() and its
+planted wiring bugs) and tests/test_gpu_block.py (the sequence under test).
+
+Two bounds are not in the sibling models and are counted here by their convention (u per rounding on the sum of the absolute terms):
+    g = bf16(rowscale * dx) of the LayerNorm backward (ln_rows.h: one fp32 product, one rounding to bf16): stored16(u |ref|, ref); the project's
+        own test of that kernel (tests/test_gpu_tail.py) holds it to the same bits as torch's product of the RETURNED dx, which is stricter
+    devit_colsum_bf16 (elementwise.hip: colsum_bf16_kernel + sum_partials_kernel) on non-integer data: colsum_pass_roundings() below.
+
+Cases (B, N, D, heads, hidden): the smallest shapes at which each branch of the sequence is taken; every M = B N is off the 256-row grid.
+    student     2 x 198, 384 / 6 / 1536   default routes: grouped weight gradients (D == 384), the column-sum pass for fc2's bias, QKV_PAD (128), ATT
+    student_fr  the same under DEVIT_GEMMFR=1 with fc2_w16t: fc2 forward on the k-major copy, both dgrad + LayerNorm sites fused
+    compacted   3 x 51, 384 / 4 (attn_width 256) / 640: qkv_pad_rows = 205, one row tile; default, DEVIT_GEMMFR=1, DEVIT_WGRADFR=0.  Its LayerNorm
+                workspace (20 workgroups) is smaller than the column-sum pass needs, so fc2's bias gradient comes from fc2's own split-K launch
+    wide        2 x 197, 256 / 4 / 512: wmode == 0, four split-K launches on the side stream (and on the caller's with DEVIT_WGRAD_STREAM=0)
+    short       4 x 17, 384 / 6 / 768: many images per tile
+    f16_fwd     1 x 208, 256 / 4 / 512, f16, no DEVIT_BLK_SAVE: forward only (one image: dp1 and dp2 are single values, 1.25 and 0.5)
+(devit_gemm_bf16 accepts every product of these shapes: none had to be moved.)"""
+import ctypes as C
+import math
+
+import torch
+
+import _attn_model as A
+import _gemm_model as G
+import _tail_model as T
+from _tail_model import BF16, F16, F32, F64, U, gen, ratio, stored16   # noqa: F401
+
+EPS = 1e-6
+SAVE, QKV_PAD, ATT = 1, 2, 4
+ACT_NAMES = ("ln1", "mean1", "rstd1", "qkv", "attn_o", "lse", "x1", "att", "ln2", "mean2", "rstd2", "h", "h_pre", "x2")
+BWD_NAMES = ("dh_pre", "dln2", "dx1", "g1", "dattn", "dqkv", "dln1", "lnws")
+ACC_NAMES = ("n1w", "n1b", "qkv_w", "qkv_b", "proj_w", "proj_b", "n2w", "n2b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")
+ENV_SWITCHES = ("DEVIT_GEMMFR", "DEVIT_WGRADFR", "DEVIT_WGRAD_STREAM", "DEVIT_LNFUSE", "DEVIT_GEMM4", "DEVIT_WGRAD_GROUP")
+ERR_SHAPE, ERR_ARG = -1, -2
+
+MUTATIONS = {  # planted wiring bug -> the stage (or untouched-bytes check) that must see it
+    "ln2_reads_x": "ln2", "x2_residual_from_x": "x2", "dp2_for_dp1": "x1", "h_pre_after_gate": "h_pre", "proj_bias_twice": "x1",
+    "pad_rows_left": "pad_rows", "fc2_bias_twice": "fc2_b", "proj_b_from_dx1": "proj_b", "g_prev_unscaled": "g_prev",
+    "dqkv_add_dropped": "dqkv", "lse_not_saved_per_head": "lse", "dx_pingpong_stale": "inputs"}
+
+
+def _case(name, B, N, D, heads, hidden, flags, dtype16=0, fc2t=False, envs=(("", {}),)):
+    return dict(name=name, B=B, N=N, D=D, heads=heads, hidden=hidden, flags=flags, dtype16=dtype16, fc2t=fc2t, envs=envs)
+
+
+CASES = [
+    _case("student", 2, 198, 384, 6, 1536, SAVE | QKV_PAD | ATT),
+    _case("student_fr", 2, 198, 384, 6, 1536, SAVE | QKV_PAD | ATT, fc2t=True, envs=(("", {"DEVIT_GEMMFR": "1"}),)),
+    _case("compacted", 3, 51, 384, 4, 640, SAVE | QKV_PAD,
+          envs=(("", {}), ("gemmfr", {"DEVIT_GEMMFR": "1"}), ("wgradfr0", {"DEVIT_WGRADFR": "0"}))),
+    _case("wide", 2, 197, 256, 4, 512, SAVE | ATT, envs=(("", {}), ("wgrad_stream0", {"DEVIT_WGRAD_STREAM": "0"}))),
+    _case("short", 4, 17, 384, 6, 768, SAVE | QKV_PAD),
+    _case("f16_fwd", 1, 208, 256, 4, 512, QKV_PAD | ATT, dtype16=1),
+]
+
+
+def case_named(name):
+    return next(c for c in CASES if c["name"] == name)
+
+
+def variants(backward_only=False):
+    """(id, case, environment) of every run of the table"""
+    out = []
+    for c in CASES:
+        if backward_only and not c["flags"] & SAVE:
+            continue
+        for tag, env in c["envs"]:
+            out.append((c["name"] + ("/" + tag if tag else ""), c, env))
+    return out
+
+
+def set_env(monkeypatch, env):
+    """every per-call switch of the sequence cleared, then the variant's own set"""
+    for k in ENV_SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+def pad_rows(m):
+    return (m + 255) // 256 * 256
+
+
+def qkv_extra(c):
+    return (128 if c["N"] >= 128 else 256 - c["N"]) if c["flags"] & QKV_PAD else 0
+
+
+def dims(c):
+    M = c["B"] * c["N"]
+    return dict(B=c["B"], N=c["N"], D=c["D"], H=c["heads"], Da=64 * c["heads"], Hd=c["hidden"], M=M, Mp=pad_rows(M))
+
+
+# ============================================================================================ buffer extents as include/devit_hip.h words them
+def act_extents(c):
+    """bytes per DEVIT_ACT_* buffer: "bf16 row buffers have pad_rows(M) rows (qkv: + the overhang when flagged)"; mean / rstd [M], lse [B][H][N] and
+    the fc1 pre-activation only with DEVIT_BLK_SAVE; x1 / x2 fp32 [M][D]; att bf16 [M][D] only with DEVIT_BLK_ATT"""
+    d = dims(c)
+    M, Mp, D, Da, Hd = d["M"], d["Mp"], d["D"], d["Da"], d["Hd"]
+    save, att = bool(c["flags"] & SAVE), bool(c["flags"] & ATT)
+    stat = M * 4 if save else 0
+    return dict(ln1=Mp * D * 2, mean1=stat, rstd1=stat, qkv=(Mp + qkv_extra(c)) * 3 * Da * 2, attn_o=Mp * Da * 2,
+                lse=d["B"] * d["H"] * d["N"] * 4 if save else 0, x1=M * D * 4, att=M * D * 2 if att else 0, ln2=Mp * D * 2, mean2=stat, rstd2=stat,
+                h=Mp * Hd * 2, h_pre=Mp * Hd * 2 if save else 0, x2=M * D * 4)
+
+
+def bwd_extents(c):
+    """bytes per DEVIT_BWD_* buffer; the LayerNorm workspace is devit_layernorm_bwd_workspace(M, D) = grid x 3 x D floats (layernorm.hip:208)"""
+    d = dims(c)
+    M, Mp, D, Da, Hd = d["M"], d["Mp"], d["D"], d["Da"], d["Hd"]
+    return dict(dh_pre=Mp * Hd * 2, dln2=Mp * D * 2, dx1=M * D * 4, g1=Mp * D * 2, dattn=Mp * Da * 2, dqkv=Mp * 3 * Da * 2, dln1=Mp * D * 2,
+                lnws=T.ln_bwd_grid(M) * 3 * D * 4)
+
+
+def buffer_shapes(c):
+    """name -> (rows, cols, 16-bit?) of every buffer a block forward / backward writes, as the sequence addresses them"""
+    d = dims(c)
+    M, Mp, D, Da, Hd = d["M"], d["Mp"], d["D"], d["Da"], d["Hd"]
+    return dict(ln1=(Mp, D, 1), mean1=(1, M, 0), rstd1=(1, M, 0), qkv=(Mp + qkv_extra(c), 3 * Da, 1), attn_o=(Mp, Da, 1),
+                lse=(d["B"] * d["H"], d["N"], 0), x1=(M, D, 0), att=(M, D, 1), ln2=(Mp, D, 1), mean2=(1, M, 0), rstd2=(1, M, 0), h=(Mp, Hd, 1),
+                h_pre=(Mp, Hd, 1), x2=(M, D, 0), dh_pre=(Mp, Hd, 1), dln2=(Mp, D, 1), dx1=(M, D, 0), g1=(Mp, D, 1), dattn=(Mp, Da, 1),
+                dqkv=(Mp, 3 * Da, 1), dln1=(Mp, D, 1))
+
+
+PADDED = ("ln1", "qkv", "attn_o", "ln2", "h", "h_pre", "dh_pre", "dln2", "g1", "dattn", "dqkv", "dln1", "g_prev")     # 16-bit, rows >= M zeroed
+
+
+# ============================================================================================ inputs
+def _mix(vals, n, shift):
+    return torch.tensor([vals[(i + shift) % len(vals)] for i in range(n)], dtype=F32)
+
+
+def dp_scales(B, shift=0):
+    """(dp1, dp2) [B]: different per-image vectors from the existing mixes, each with a 0 and a value above 1 where B >= 2"""
+    if B == 1:
+        return torch.tensor([1.25]), torch.tensor([0.5])
+    return _mix((1.25, 0.0, 1.0 / 0.9, 1.0), B, shift), _mix((0.0, 2.0, 0.5, 1.0), B, shift)
+
+
+def block_weights(c, key=0):
+    """seeded parameters of one block: 16-bit GEMM weights (bf16 / f16 values), nonzero fp32 biases, gammas off 1, betas off 0, gates from the
+    existing mixes (head: 0.5, 2, 0, 1; neuron: 0, 1, 0.5, -1.5, 3)"""
+    d = dims(c)
+    D, Da, Hd, H = d["D"], d["Da"], d["Hd"], d["H"]
+    g = gen("block", c["name"], "w", key)
+    dt = F16 if c["dtype16"] else BF16
+    rn = lambda *s: T.randn(g, *s)                                                              # noqa: E731
+    w = dict(n1w=1 + 0.1 * rn(D), n1b=0.1 * rn(D), n2w=1 + 0.1 * rn(D), n2b=0.1 * rn(D),
+             qkv_w16=(rn(3 * Da, D) / math.sqrt(D) * 2).to(dt), qkv_b=0.2 * rn(3 * Da), proj_w16=(rn(D, Da) / math.sqrt(Da)).to(dt), proj_b=0.2 * rn(D),
+             fc1_w16=(rn(Hd, D) / math.sqrt(D) * 2).to(dt), fc1_b=0.3 * rn(Hd), fc2_w16=(rn(D, Hd) / math.sqrt(Hd)).to(dt), fc2_b=0.2 * rn(D))
+    w["head_gate"] = _mix(A.GATE_MIX, H, key)
+    w["neuron_gate"] = torch.tensor(G.COLSCALES)[torch.randint(0, 5, (Hd,), generator=g)]
+    w["dp1"], w["dp2"] = dp_scales(d["B"], key)
+    if c["fc2t"]:
+        w["fc2_w16t"] = w["fc2_w16"].t().contiguous()
+    return w
+
+
+def inputs(c, key=0, dqkv_add=True):
+    """seeded CPU tensors of one block forward + backward: w (block_weights), x with a per-row offset, dx, g2 = bf16(dp2 dx), dqkv_add (or None),
+    prev_dp2, and acc0: what every gradient accumulator (prev_fc2_b included) holds before the call -- the sequence accumulates"""
+    d = dims(c)
+    M, D, Da, Hd, B = d["M"], d["D"], d["Da"], d["Hd"], d["B"]
+    g = gen("block", c["name"], "x", key)
+    w = block_weights(c, key)
+    x = T.randn(g, M, D) + 2 * T.randn(g, M, 1)
+    dx = T.randn(g, M, D)
+    inp = dict(w=w, x=x, dx=dx, g2=(dx * w["dp2"].repeat_interleave(d["N"])[:, None]).to(BF16),
+               dqkv_add=(0.5 * T.randn(g, M, 3 * Da)).to(BF16) if dqkv_add else None, prev_dp2=_mix(T.ROWSCALE_MIX, B, key + 1))
+    shapes = dict(n1w=(D,), n1b=(D,), qkv_w=(3 * Da, D), qkv_b=(3 * Da,), proj_w=(D, Da), proj_b=(D,), n2w=(D,), n2b=(D,), fc1_w=(Hd, D),
+                  fc1_b=(Hd,), fc2_w=(D, Hd), fc2_b=(D,), prev_fc2_b=(D,))
+    inp["acc0"] = {k: 3 * T.randn(g, *s) for k, s in shapes.items()}
+    return inp
+
+
+def to_device(inp, dev):
+    mv = lambda v: v.to(dev) if isinstance(v, torch.Tensor) else ({k: mv(x) for k, x in v.items()} if isinstance(v, dict) else v)   # noqa: E731
+    return mv(inp)
+
+
+# ============================================================================================ which launch produced what
+def colsum_pass_roundings(rows):
+    """devit_colsum_bf16 on `rows` rows (elementwise.hip): 64 chunks from 512 rows on, else 1 (:462); a thread adds every 8th row of its chunk in
+    sequence (:220-233), 8 partials of the workgroup (:242); sum_partials_kernel: every 8th chunk in sequence (:254), 8 groups (:260), the
+    accumulate (:261)"""
+    nchunk = 64 if rows >= 512 else 1
+    per = -(-rows // nchunk)
+    return -(-per // 8) + 8 + -(-nchunk // 8) + 8 + 1
+
+
+def colsum_pass_bounds(y16, rows, out0):
+    """column sums of the live rows of a bf16 matrix as the column-sum pass over `rows` (padded) rows adds them -> (float64 sums + out0, bound)"""
+    v = y16.to(F64)
+    ref = T.colsum_ref(v, v.shape[0], v.shape[1], 0, 0).to(v.device) + out0.to(F64)
+    return ref, U * colsum_pass_roundings(rows) * (v.abs().sum(0) + out0.to(F64).abs())
+
+
+def routes(c, env, lnws_bytes, colsum_ws, fused=(False, False), g2_bias_done=False, prev=True):
+    """The decisions of block_bwd (csrc/encoder.hip) that change WHICH kernel an output comes from, hence how many roundings its bound counts:
+    wmode (the grouped launch: D == 384, three K-steps, DEVIT_WGRADFR != 0) and who owns fc2's bias gradient: 'handed' (g2_bias_done: not this
+    call's), 'colsum' (the pass over g2, when the LayerNorm workspace is large enough for it) or 'launch' (the row sums of fc2's own split-K
+    launch).  fused: devit_dgrad_layernorm_bwd_fused at the LN2 and LN1 sites, asked of the library by the caller.  prev: g_prev / prev_fc2_b given."""
+    d = dims(c)
+    wmode = d["D"] == 384 and d["Mp"] // 64 >= 3 and env.get("DEVIT_WGRADFR", "1") != "0"
+    fb = "handed" if g2_bias_done else "colsum" if (wmode and d["Hd"] % 128 == 0 and lnws_bytes >= colsum_ws) else "launch"
+    return dict(wmode=wmode, fc2_bias=fb, fused=tuple(fused), prev=prev)
+
+
+def default_routes(c, env=None, **kw):
+    """routes() from the restated extents (no library needed: the CPU tests)"""
+    return routes(c, env or {}, bwd_extents(c)["lnws"], 64 * c["D"] * 4, **kw)
+
+
+def fused_chain(tiles):
+    """longest chain of additions of the fused launch's column sums (tests/test_gpu_lnfuse.py, chain_length)"""
+    return 32 + 1 + 3 + -(-tiles // 32) + 32 + 1
+
+
+# ============================================================================================ the stages
+def _rs(v, N):
+    return v.to(F64).repeat_interleave(N)[:, None]
+
+
+def _d(t):
+    return t.to(F64)
+
+
+def _ln_fwd_stage(tag, x, gamma, beta, y16, mean, rstd, f16, save):
+    r, b = T.ln_fwd_bounds(x, gamma, beta, EPS)
+    yield "ln" + tag, y16, r["y"], stored16(b["y"], r["y"], f16)
+    if save:
+        yield "mean" + tag, mean, r["mean"], b["mean"]
+        yield "rstd" + tag, rstd, r["rstd"], b["rstd"]
+
+
+def forward_stages(c, inp, bufs):
+    """yields (stage, got, float64 reference, bound) for what devit_encoder_fwd left of one block, read off block_fwd"""
+    d, w = dims(c), inp["w"]
+    B, N, H, M = d["B"], d["N"], d["H"], d["M"]
+    f16, save, att = bool(c["dtype16"]), bool(c["flags"] & SAVE), bool(c["flags"] & ATT)
+    x = bufs["x"]
+    yield from _ln_fwd_stage("1", x, w["n1w"], w["n1b"], bufs["ln1"][:M], bufs.get("mean1"), bufs.get("rstd1"), f16, save)
+    ref, bnd = G.statement(G.STORE_BF16, _d(bufs["ln1"][:M]), _d(w["qkv_w16"]), bias=_d(w["qkv_b"]), f16=f16)
+    yield "qkv", bufs["qkv"][:M], ref["out"], bnd["out"]
+    q, k, v, _, _ = A.split_packed(bufs["qkv"], B, N, H)
+    r, b = A.bounds(q, k, v, w["head_gate"], 0.125, u=A.U_F16 if f16 else A.U_BF16, f16=f16)
+    yield "attn_o", A.heads(bufs["attn_o"], B, N, H), r["O"], b["O"]
+    if save:
+        yield "lse", bufs["lse"].view(B, H, N), r["lse"], b["lse"]
+    ref, bnd = G.statement(G.RESIDUAL, _d(bufs["attn_o"][:M]), _d(w["proj_w16"]), bias=_d(w["proj_b"]), res=_d(x), rowscale=_rs(w["dp1"], N), aux=att,
+                           f16=f16)
+    yield "x1", bufs["x1"], ref["out"], bnd["out"]
+    if att:
+        yield "att", bufs["att"], ref["aux"], bnd["aux"]
+    yield from _ln_fwd_stage("2", bufs["x1"], w["n2w"], w["n2b"], bufs["ln2"][:M], bufs.get("mean2"), bufs.get("rstd2"), f16, save)
+    ref, bnd = G.statement(G.GELU, _d(bufs["ln2"][:M]), _d(w["fc1_w16"]), bias=_d(w["fc1_b"]), colscale=_d(w["neuron_gate"]), aux=save, f16=f16)
+    yield "h", bufs["h"][:M], ref["out"], bnd["out"]
+    if save:
+        yield "h_pre", bufs["h_pre"][:M], ref["aux"], bnd["aux"]
+    ref, bnd = G.statement(G.RESIDUAL, _d(bufs["h"][:M]), _d(w["fc2_w16"]), bias=_d(w["fc2_b"]), res=_d(bufs["x1"]), rowscale=_rs(w["dp2"], N), f16=f16)
+    yield "x2", bufs["x2"], ref["out"], bnd["out"]
+
+
+def _live(buf, M, Mp):
+    """the [Mp][cols] operand a weight-gradient reduction is STATED on: the live rows, zero below -- junk the sequence left in a pad row is then in
+    what the launch summed and not in the reference"""
+    out = torch.zeros((Mp, buf.shape[1]), dtype=F64, device=buf.device)
+    out[:M] = buf[:M].to(F64)
+    return out
+
+
+def _wgrad_stage(name, bname, dy, x, w0, b0, M, Mp, route):
+    """w_grad [Nw][Kf] += dy^T x (+ b_grad += column sums of dy from the same launch when b0 is given), by the launch wgrad_job / linear_wgrad
+    (csrc/encoder.hip) send it to: a job of the grouped launch (the most slices split_k == 0 can choose), else the split-K launch"""
+    from devit_amd import ops
+    Nw, Kf = w0.shape
+    dyl, xl = _live(dy, M, Mp), _live(x, M, Mp)
+    job = None
+    if route["wmode"] and Kf == 384 and Nw % 128 == 0:
+        job = dict(a=dyl, b=xl, a_cols=Nw, transposed=0)
+    elif route["wmode"] and Nw == 384 and Kf % 128 == 0 and b0 is None:
+        job = dict(a=xl, b=dyl, a_cols=Kf, transposed=1)
+    if job is not None:
+        dd = dict(job=dict(a_cols=job["a_cols"], transposed=job["transposed"]), a=job["a"], b=job["b"], out0=w0.reshape(-1), ldc=Kf, orows=Nw, ocols=Kf)
+        if b0 is not None:
+            dd["colsum0"] = b0
+        ref, bnd = G.wgrad_reference(dd, Mp, G.wgrad_max_split(Mp))
+        return [(name, ref["out"], bnd["out"])] + ([(bname, ref["colsum"], bnd["colsum"])] if b0 is not None else [])
+    ref, bnd = G.statement(G.ATOMIC, dyl.t(), xl.t(), out0=_d(w0), aux0=None if b0 is None else _d(b0), aux=b0 is not None,
+                           split_k=ops.split_k_for(Nw, Kf, Mp // 64), tiles_n=Kf // 128)
+    return [(name, ref["out"], bnd["out"])] + ([(bname, ref["aux"], bnd["aux"])] if b0 is not None else [])
+
+
+def _ln_bwd_stage(tag, x, mean, rstd, gamma, dln, dres, g0, b0, M, fused, tiles):
+    r, b = T.ln_bwd_bounds(x, mean, rstd, gamma, dln, dres, g0, b0)
+    if fused:        # the same terms in the fused launch's order: the longer chain of the two (tests/test_gpu_lnfuse.py)
+        nc, nf = T.ln_col_roundings(M), max(T.ln_col_roundings(M), fused_chain(tiles))
+        b = dict(b, dgamma=b["dgamma"] * (nf + 3) / (nc + 3), dbeta=b["dbeta"] * nf / nc)
+    return r, b
+
+
+def backward_stages(c, inp, bufs, route, dln=None):
+    """yields (stage, got, float64 reference, bound) for what devit_block_bwd left, read off block_bwd.  route: routes().  dln: {'dln2': .., 'dln1': ..}
+    the LayerNorm backward's input where the fused launch kept it on chip (from a run of the two launches on bit-identical dh_pre / dqkv)."""
+    d, w, a0 = dims(c), inp["w"], inp["acc0"]
+    B, N, H, M, Mp, Da = d["B"], d["N"], d["H"], d["M"], d["Mp"], d["Da"]
+    tiles = Mp // 256
+    acc = bufs["acc"]
+    g2, dx = bufs["g2"], bufs["dx"]
+    # 1, 2: fc2's weight gradient and who owns its bias gradient
+    own = route["fc2_bias"] == "launch"
+    st = _wgrad_stage("fc2_w", "fc2_b", g2, bufs["h"], a0["fc2_w"], a0["fc2_b"] if own else None, M, Mp, route)
+    if route["fc2_bias"] == "colsum":
+        ref, bnd = colsum_pass_bounds(g2[:M], Mp, a0["fc2_b"])
+        yield "fc2_b", acc["fc2_b"], ref, bnd
+    elif route["fc2_bias"] == "handed":
+        yield "fc2_b", acc["fc2_b"], _d(a0["fc2_b"]), torch.zeros_like(_d(a0["fc2_b"]))
+    for name, ref, bnd in st[::-1]:
+        yield name, acc[name], ref, bnd
+    # 3
+    ref, bnd = G.statement(G.DGELU, _d(g2[:M]), _d(w["fc2_w16"]).t(), colscale=_d(w["neuron_gate"]), aux_in=_d(bufs["h_pre"][:M]))
+    yield "dh_pre", bufs["dh_pre"][:M], ref["out"], bnd["out"]
+    # 4
+    if not route["fused"][0]:
+        ref, bnd = G.statement(G.STORE_BF16, _d(bufs["dh_pre"][:M]), _d(w["fc1_w16"]).t())
+        yield "dln2", bufs["dln2"][:M], ref["out"], bnd["out"]
+    # 5
+    for name, ref, bnd in _wgrad_stage("fc1_w", "fc1_b", bufs["dh_pre"], bufs["ln2"], a0["fc1_w"], a0["fc1_b"], M, Mp, route):
+        yield name, acc[name], ref, bnd
+    # 6
+    dln2 = (dln or bufs)["dln2"] if route["fused"][0] else bufs["dln2"]
+    r, b = _ln_bwd_stage("2", bufs["x1"], bufs["mean2"], bufs["rstd2"], w["n2w"], dln2[:M], dx, a0["n2w"], a0["n2b"], M, route["fused"][0], tiles)
+    yield "dx1", bufs["dx1"], r["dx"], b["dx"]
+    ref = _rs(w["dp1"], N) * _d(bufs["dx1"])
+    yield "g1", bufs["g1"][:M], ref, stored16(U * ref.abs(), ref)
+    yield "n2w", acc["n2w"], r["dgamma"], b["dgamma"]
+    yield "n2b", acc["n2b"], r["dbeta"], b["dbeta"]
+    ref, bnd = T.ln_colsum_bounds(bufs["g1"][:M], a0["proj_b"])
+    if route["fused"][0]:
+        bnd = bnd * max(T.ln_col_roundings(M), fused_chain(tiles)) / T.ln_col_roundings(M)
+    yield "proj_b", acc["proj_b"], ref, bnd
+    # 7
+    ref, bnd = G.statement(G.STORE_BF16, _d(bufs["g1"][:M]), _d(w["proj_w16"]).t())
+    yield "dattn", bufs["dattn"][:M], ref["out"], bnd["out"]
+    # 8
+    for name, ref, bnd in _wgrad_stage("proj_w", None, bufs["g1"], bufs["attn_o"], a0["proj_w"], None, M, Mp, route):
+        yield name, acc[name], ref, bnd
+    # 9
+    add = bufs.get("dqkv_add")
+    q, k, v, do, ad = A.split_packed(bufs["qkv"], B, N, H, bufs["dattn"], add)
+    r, b = A.bounds(q, k, v, w["head_gate"], 0.125, do, ad)
+    got = torch.stack([A.heads(bufs["dqkv"], B, N, H, j * Da) for j in range(3)])
+    yield "dqkv", got, torch.stack([r["dQ"], r["dK"], r["dV"]]), torch.stack([b["dQ"], b["dK"], b["dV"]])
+    # 10
+    if not route["fused"][1]:
+        ref, bnd = G.statement(G.STORE_BF16, _d(bufs["dqkv"][:M]), _d(w["qkv_w16"]).t())
+        yield "dln1", bufs["dln1"][:M], ref["out"], bnd["out"]
+    # 11
+    for name, ref, bnd in _wgrad_stage("qkv_w", "qkv_b", bufs["dqkv"], bufs["ln1"], a0["qkv_w"], a0["qkv_b"], M, Mp, route):
+        yield name, acc[name], ref, bnd
+    # 12
+    dln1 = (dln or bufs)["dln1"] if route["fused"][1] else bufs["dln1"]
+    r, b = _ln_bwd_stage("1", bufs["x"], bufs["mean1"], bufs["rstd1"], w["n1w"], dln1[:M], bufs["dx1"], a0["n1w"], a0["n1b"], M, route["fused"][1], tiles)
+    yield "dx_in", bufs["dx_in"], r["dx"], b["dx"]
+    yield "n1w", acc["n1w"], r["dgamma"], b["dgamma"]
+    yield "n1b", acc["n1b"], r["dbeta"], b["dbeta"]
+    if route["prev"]:
+        ref = _rs(inp["prev_dp2"], N) * _d(bufs["dx_in"])
+        yield "g_prev", bufs["g_prev"][:M], ref, stored16(U * ref.abs(), ref)
+        if "prev_fc2_b" in acc:
+            ref, bnd = T.ln_colsum_bounds(bufs["g_prev"][:M], a0["prev_fc2_b"])
+            if route["fused"][1]:
+                bnd = bnd * max(T.ln_col_roundings(M), fused_chain(tiles)) / T.ln_col_roundings(M)
+            yield "prev_fc2_b", acc["prev_fc2_b"], ref, bnd
+
+
+def audit(c, inp, bufs, route=None, dln=None):
+    """-> ({stage: worst |err| / bound over every live element}, problems): problems names every untouched-bytes statement that does not hold --
+    'pad_rows/<buffer>' (a 16-bit buffer whose rows >= M are not zero, the qkv overhang included), 'inputs/<name>' (an input of the call that
+    did not come back bit for bit).  route None: the forward alone."""
+    M = dims(c)["M"]
+    rt = {}
+    for name, got, ref, bnd in forward_stages(c, inp, bufs):
+        rt[name] = ratio(got, ref, bnd)
+    if route is not None:
+        for name, got, ref, bnd in backward_stages(c, inp, bufs, route, dln):
+            rt[name] = ratio(got, ref, bnd)
+    problems = []
+    for name in PADDED:
+        t = bufs.get(name)
+        if t is not None and t.shape[0] > M and bool((t[M:].view(torch.int16) != 0).any()):
+            problems.append("pad_rows/" + name)
+    for name in ("x", "dx", "g2", "dqkv_add"):
+        if bufs.get(name) is not None and inp.get(name) is not None and not torch.equal(bufs[name][:inp[name].shape[0]].cpu(), inp[name].cpu()):
+            problems.append("inputs/" + name)
+    return rt, problems
+
+
+# ============================================================================================ emulation
+def emulate(c, inp, mutate=None, route=None):
+    """One block forward (and, with DEVIT_BLK_SAVE, backward) in fp32 torch, every buffer of the sequence as it would be left -> bufs as audit()
+    takes them.  The GEMMs are plain fp32 products (another order than the kernels'), LayerNorm and attention are the sibling models' emulations,
+    16-bit stores one rounding.  `mutate`: one of MUTATIONS, a planted WIRING bug -- every kernel stays correct."""
+    assert mutate is None or mutate in MUTATIONS
+    d, w, a0 = dims(c), inp["w"], inp["acc0"]
+    B, N, H, M, Mp, Da = d["B"], d["N"], d["H"], d["M"], d["Mp"], d["Da"]
+    f16, save, att = bool(c["dtype16"]), bool(c["flags"] & SAVE), bool(c["flags"] & ATT)
+    dt = F16 if f16 else BF16
+    route = route or default_routes(c)
+    f = lambda t: t.to(F32)                                                                     # noqa: E731
+
+    def padded(v, extra=0, t=dt):
+        out = torch.zeros((Mp + extra, v.shape[1]), dtype=t)
+        out[:M] = v.to(t)
+        return out
+
+    x = inp["x"]
+    dp1 = (w["dp2"] if mutate == "dp2_for_dp1" else w["dp1"]).repeat_interleave(N)[:, None]
+    dp2 = w["dp2"].repeat_interleave(N)[:, None]
+    bufs = dict(x=x.clone())
+    e = T.ln_fwd_emulate(x, w["n1w"], w["n1b"], EPS)
+    bufs.update(ln1=padded(e["y"]), mean1=e["mean"], rstd1=e["rstd"])
+    bufs["qkv"] = padded(f(bufs["ln1"][:M]) @ f(w["qkv_w16"]).t() + w["qkv_b"], qkv_extra(c))
+    q, k, v, _, _ = A.split_packed(bufs["qkv"], B, N, H)
+    ae = A.emulate(q, k, v, w["head_gate"], 0.125, f16=f16)
+    bufs["attn_o"] = padded(A.rows(ae["O"]))
+    lse = ae["lse"].to(F32)
+    if mutate == "lse_not_saved_per_head":
+        lse = lse[:, :1].expand(B, H, N).contiguous()
+    bufs["lse"] = lse
+    pre = f(bufs["attn_o"][:M]) @ f(w["proj_w16"]).t() + w["proj_b"]
+    if mutate == "proj_bias_twice":
+        pre = pre + w["proj_b"]
+    bufs["x1"] = x + dp1 * pre
+    if att:
+        bufs["att"] = pre.to(dt)
+    e = T.ln_fwd_emulate(x if mutate == "ln2_reads_x" else bufs["x1"], w["n2w"], w["n2b"], EPS)
+    bufs.update(ln2=padded(e["y"]), mean2=e["mean"], rstd2=e["rstd"])
+    pre = f(bufs["ln2"][:M]) @ f(w["fc1_w16"]).t() + w["fc1_b"]
+    bufs["h"] = padded(G.gelu_fit32(pre) * w["neuron_gate"])
+    bufs["h_pre"] = padded(pre * w["neuron_gate"] if mutate == "h_pre_after_gate" else pre)
+    bufs["x2"] = (x if mutate == "x2_residual_from_x" else bufs["x1"]) + dp2 * (f(bufs["h"][:M]) @ f(w["fc2_w16"]).t() + w["fc2_b"])
+    if not save:
+        for k_ in ("mean1", "rstd1", "lse", "mean2", "rstd2", "h_pre"):
+            del bufs[k_]
+        return bufs
+    # ---- backward
+    dx, g2 = inp["dx"], padded(inp["g2"], t=BF16)
+    bufs.update(dx=dx.clone(), g2=inp["g2"].clone(), dqkv_add=inp["dqkv_add"])
+    acc = {}
+    if mutate == "pad_rows_left":
+        bufs["h"][Mp - 2] = 0.375
+    if route["fc2_bias"] == "handed":
+        acc["fc2_b"] = a0["fc2_b"].clone()
+    else:
+        acc["fc2_b"] = a0["fc2_b"] + f(g2).sum(0) * (2 if mutate == "fc2_bias_twice" else 1)
+    acc["fc2_w"] = a0["fc2_w"] + f(g2).t() @ f(bufs["h"])
+    dh = (f(g2[:M]) @ f(w["fc2_w16"])) * w["neuron_gate"] * G.dgelu_fit32(f(bufs["h_pre"][:M]))
+    bufs["dh_pre"] = padded(dh, t=BF16)
+    bufs["dln2"] = padded(f(bufs["dh_pre"][:M]) @ f(w["fc1_w16"]), t=BF16)
+    acc["fc1_w"] = a0["fc1_w"] + f(bufs["dh_pre"]).t() @ f(bufs["ln2"])
+    acc["fc1_b"] = a0["fc1_b"] + f(bufs["dh_pre"]).sum(0)
+    e = T.ln_bwd_emulate(bufs["x1"], bufs["mean2"], bufs["rstd2"], w["n2w"], bufs["dln2"][:M], dx, a0["n2w"], a0["n2b"])
+    bufs["dx1"], acc["n2w"], acc["n2b"] = e["dx"], e["dgamma"], e["dbeta"]
+    bufs["g1"] = padded(dp1 * bufs["dx1"], t=BF16)
+    acc["proj_b"] = a0["proj_b"] + (bufs["dx1"] if mutate == "proj_b_from_dx1" else f(bufs["g1"][:M])).sum(0)
+    if mutate == "pad_rows_left":
+        bufs["g1"][M] = -0.75
+    bufs["dattn"] = padded(f(bufs["g1"][:M]) @ f(w["proj_w16"]), t=BF16)
+    acc["proj_w"] = a0["proj_w"] + f(bufs["g1"]).t() @ f(bufs["attn_o"])
+    add = None if (inp["dqkv_add"] is None or mutate == "dqkv_add_dropped") else inp["dqkv_add"]
+    q, k, v, do, ad = A.split_packed(bufs["qkv"], B, N, H, bufs["dattn"], add)
+    ae = A.emulate(q, k, v, w["head_gate"], 0.125, do, ad)
+    bufs["dqkv"] = padded(torch.cat([A.rows(ae[n]) for n in ("dQ", "dK", "dV")], 1), t=BF16)
+    bufs["dln1"] = padded(f(bufs["dqkv"][:M]) @ f(w["qkv_w16"]), t=BF16)
+    acc["qkv_w"] = a0["qkv_w"] + f(bufs["dqkv"]).t() @ f(bufs["ln1"])
+    acc["qkv_b"] = a0["qkv_b"] + f(bufs["dqkv"]).sum(0)
+    e = T.ln_bwd_emulate(x, bufs["mean1"], bufs["rstd1"], w["n1w"], bufs["dln1"][:M], bufs["dx1"], a0["n1w"], a0["n1b"])
+    bufs["dx_in"], acc["n1w"], acc["n1b"] = e["dx"], e["dgamma"], e["dbeta"]
+    if route["prev"]:
+        pdp = 1.0 if mutate == "g_prev_unscaled" else inp["prev_dp2"].repeat_interleave(N)[:, None]
+        bufs["g_prev"] = padded(pdp * bufs["dx_in"], t=BF16)
+        acc["prev_fc2_b"] = a0["prev_fc2_b"] + f(bufs["g_prev"][:M]).sum(0)
+    if mutate == "dx_pingpong_stale":       # dx_in written over the dx the block was given: every output is right, the caller's buffer is not
+        bufs["dx"] = bufs["dx_in"].clone()
+    bufs["acc"] = acc
+    return bufs
+
+
+# ============================================================================================ the C structs of a call
+def structs(c, adr, flags=None):
+    """(devit_block_weights, devit_block_acts, devit_block_wgrads, devit_block_bwd_io) of a case.  adr(name) -> the address that stands for the named
+    buffer or None: weights by their field name, 'x', 'dp1', 'dp2', the DEVIT_ACT_* / DEVIT_BWD_* buffers by ACT_NAMES / BWD_NAMES,
+    'g_<accumulator>', 'dx', 'g2', 'dx_in', 'g_prev', 'prev_dp2', 'g_prev_fc2_b', 'dqkv_add'"""
+    from devit_amd import _lib as L
+    d = dims(c)
+    w = L.BlockWeights()
+    for n in ("n1w", "n1b", "qkv_b", "proj_b", "n2w", "n2b", "fc1_b", "fc2_b", "qkv_w16", "proj_w16", "fc1_w16", "fc2_w16", "head_gate", "neuron_gate"):
+        setattr(w, n, adr(n))
+    w.num_heads, w.attn_width, w.hidden, w.dtype16 = d["H"], d["Da"], d["Hd"], c["dtype16"]
+    w.fc2_w16t = adr("fc2_w16t") if c["fc2t"] else None
+    a = L.BlockActs()
+    a.x, a.dp1, a.dp2, a.flags = adr("x"), adr("dp1"), adr("dp2"), c["flags"] if flags is None else flags
+    for i, n in enumerate(ACT_NAMES):
+        a.buf[i] = adr(n)
+    g = L.BlockWgrads()
+    for n in ACC_NAMES:
+        setattr(g, n, adr("g_" + n))
+    io = L.BlockBwdIO()
+    io.dx, io.g2, io.dx_in, io.g_prev = adr("dx"), adr("g2"), adr("dx_in"), adr("g_prev")
+    io.prev_dp2, io.prev_fc2_b_grad, io.g2_bias_done, io.dqkv_add = adr("prev_dp2"), adr("g_prev_fc2_b"), 0, adr("dqkv_add")
+    for i, n in enumerate(BWD_NAMES):
+        io.ws[i] = adr(n)
+    io.lnws_bytes = 0
+    io.defer_jobs = io.defer_count = None
+    return w, a, g, io
+
+
+def call_fwd(nblocks, w, a, c, stream=None):
+    """devit_encoder_fwd itself (no raise) -> (return code, message)"""
+    from devit_amd import _lib as L
+    lib = L.load()
+    rc = lib.devit_encoder_fwd(nblocks, w, a, c["B"], c["N"], c["D"], EPS, stream)
+    return rc, lib.devit_last_error().decode() if rc else ""
+
+
+def call_bwd(w, a, g, io, c, stream=None):
+    from devit_amd import _lib as L
+    lib = L.load()
+    ref = lambda s: None if s is None else C.byref(s)                                           # noqa: E731
+    rc = lib.devit_block_bwd(ref(w), ref(a), ref(g), ref(io), c["B"], c["N"], c["D"], EPS, stream)
+    return rc, lib.devit_last_error().decode() if rc else ""
+
+
+def _set(obj, **kw):
+    for k, v in kw.items():
+        setattr(obj, k, v)
+
+
+def _null_buf(arr, i):
+    arr[i] = None
+
+
+# (name, case, what to change in (case copy, w, a, g, io) before the call, which entry point, DEVIT_ERR_*, words the message must hold).  'fwd2': two
+# blocks, `change` sees the second block's acts.  Every one is an argument check in front of the first launch (csrc/encoder.hip).
+REFUSALS = [
+    ("N_209", "student", lambda c, w, a, g, io: c.update(N=209), "fwd", ERR_SHAPE, "N=209"),
+    ("D_320", "student", lambda c, w, a, g, io: c.update(D=320), "fwd", ERR_SHAPE, "D=320"),
+    ("N_209_bwd", "student", lambda c, w, a, g, io: c.update(N=209), "bwd", ERR_SHAPE, "N=209"),
+    ("attn_width_not_64_heads", "student", lambda c, w, a, g, io: _set(w, num_heads=5), "fwd", ERR_SHAPE, "heads 5 * 64"),
+    ("attn_width_not_64_heads_bwd", "student", lambda c, w, a, g, io: _set(w, num_heads=5), "bwd", ERR_SHAPE, "heads 5 * 64"),
+    ("f16_with_save", "f16_fwd", lambda c, w, a, g, io: _set(a, flags=a.flags | SAVE), "fwd", ERR_ARG, "f16 is the frozen-teacher forward"),
+    ("null_activation_buffer", "student", lambda c, w, a, g, io: _null_buf(a.buf, ACT_NAMES.index("ln2")), "fwd", ERR_ARG, "null activation buffer"),
+    ("null_saved_buffer", "student", lambda c, w, a, g, io: _null_buf(a.buf, ACT_NAMES.index("lse")), "fwd", ERR_ARG, "DEVIT_BLK_SAVE needs"),
+    ("att_flag_without_att", "student", lambda c, w, a, g, io: _null_buf(a.buf, ACT_NAMES.index("att")), "fwd", ERR_ARG, "DEVIT_BLK_ATT needs att"),
+    ("second_block_reads_another_x", "student", lambda c, w, a, g, io: None, "fwd2", ERR_ARG, "block 1 does not read block 0's output"),
+    ("backward_without_save", "student", lambda c, w, a, g, io: _set(a, flags=a.flags & ~SAVE), "bwd", ERR_ARG, "without DEVIT_BLK_SAVE"),
+    ("f16_backward", "f16_fwd", lambda c, w, a, g, io: _set(a, flags=a.flags | SAVE), "bwd", ERR_ARG, "f16 blocks have no backward"),
+    ("null_workspace_entry", "student", lambda c, w, a, g, io: _null_buf(io.ws, BWD_NAMES.index("dattn")), "bwd", ERR_ARG, "workspace 4 is null"),
+    ("null_accumulator", "student", lambda c, w, a, g, io: _set(g, proj_b=None), "bwd", ERR_ARG, "null gradient accumulator"),
+    ("null_g2", "student", lambda c, w, a, g, io: _set(io, g2=None), "bwd", ERR_ARG, "dx / g2 / dx_in"),
+    ("null_io", "student", lambda c, w, a, g, io: None, "bwd_null_io", ERR_ARG, "null argument"),
+]
+
+
+def refused(case_name, change, entry, adr):
+    """run one REFUSALS row with the addresses adr() gives -> (return code, message)"""
+    from devit_amd import _lib as L
+    c = dict(case_named(case_name))
+    w, a, g, io = structs(c, adr)
+    change(c, w, a, g, io)
+    if entry == "fwd":
+        return call_fwd(1, C.byref(w), C.byref(a), c)
+    if entry == "fwd2":
+        ws, as_ = (L.BlockWeights * 2)(w, w), (L.BlockActs * 2)(a, a)        # the second block reads the first's x, not its x2
+        return call_fwd(2, ws, as_, c)
+    if entry == "bwd_null_io":
+        return call_bwd(w, a, g, None, c)
+    return call_bwd(w, a, g, io, c)
+
+
+def sizes_refusals():
+    """the two sizes functions: a null `sizes` pointer, N = 209, D = 320 -> [(name, return code, message, expected code, words)]"""
+    from devit_amd import _lib as L
+    lib = L.load()
+    out = []
+    sa, sb = (C.c_size_t * len(ACT_NAMES))(), (C.c_size_t * len(BWD_NAMES))()
+    for name, args, sz_a, sz_b, code, words in (("null_sizes", (2, 198, 384, 384, 1536), None, None, ERR_ARG, "null"),
+                                               ("N_209", (2, 209, 384, 384, 1536), sa, sb, ERR_SHAPE, "N=209"),
+                                               ("D_320", (2, 198, 320, 384, 1536), sa, sb, ERR_SHAPE, "D=320")):
+        rc = lib.devit_block_acts_sizes(*args, SAVE, sz_a)
+        out.append(("acts_sizes/" + name, rc, lib.devit_last_error().decode(), code, words))
+        rc = lib.devit_block_bwd_sizes(*args, sz_b)
+        out.append(("bwd_sizes/" + name, rc, lib.devit_last_error().decode(), code, words))
+    return out
+
+
+def library_sizes(c):
+    """(devit_block_acts_sizes, devit_block_bwd_sizes) of the case as dicts by buffer name (host functions: no GPU needed)"""
+    from devit_amd import _lib as L
+    d = dims(c)
+    sa, sb = (C.c_size_t * len(ACT_NAMES))(), (C.c_size_t * len(BWD_NAMES))()
+    L.call("devit_block_acts_sizes", d["B"], d["N"], d["D"], d["Da"], d["Hd"], c["flags"], sa)
+    L.call("devit_block_bwd_sizes", d["B"], d["N"], d["D"], d["Da"], d["Hd"], sb)
+    return dict(zip(ACT_NAMES, sa)), dict(zip(BWD_NAMES, sb))

@@ -429,35 +429,33 @@ def _live(inp, c, name):
     return inp["bufs"][name][live_index(c, inp["geo"]).to(inp["bufs"][name].device)]
 
 
-def reference(c, inp, with_bounds=True):
-    """-> (ref, bnd): float64 [batch][m_lim][N] per output name ('out', 'aux'; ATOMIC aux: [m_lim]), exactly as include/devit_hip.h words each kind."""
-    geo, kind, K, N = inp["geo"], c["kind"], c["K"], c["N"]
-    m_lim, f16 = geo["m_lim"], bool(c["dtype16"])
-    a = logical(inp, inp["A"], m_lim, K, c["batch"]).to(F64)
-    b = logical(inp, inp["B"], N, K, c["batch"]).to(F64)
-    acc = a @ b.transpose(1, 2)
-    absacc = a.abs() @ b.abs().transpose(1, 2)
-    bufs = inp["bufs"]
-    vec = lambda n: bufs[n][:N].to(F64) if n in bufs else None                                 # noqa: E731
-    bias, cs = vec("bias"), vec("colscale")
+def statement(kind, a, b, *, bias=None, colscale=None, rowscale=None, res=None, aux_in=None, pos=None, f16=False, aux=False, out0=None,
+              aux0=None, split_k=1, tiles_n=1):
+    """One launch of devit_gemm_bf16 on LOGICAL float64 matrices, exactly as include/devit_hip.h words each kind -> (ref, bnd): dicts over 'out' and,
+    where the launch writes one, 'aux'.  a [..][m][K] and b [..][N][K] hold the 16-bit operands exactly; bias / colscale [N]; rowscale broadcastable
+    to the output with the scale of every row already looked up (None: 1); res / aux_in / pos in the output's shape; ATOMIC: out0 / aux0 what the
+    accumulators held, split_k the slices, tiles_n the n-tiles that each add a share of a row sum.  reference() gathers these from a case's
+    physical buffers; tests/_block_model.py feeds it the buffers an encoder block left behind."""
+    K = a.shape[-1]
+    acc = a @ b.transpose(-1, -2)
+    absacc = a.abs() @ b.abs().transpose(-1, -2)
+    cs = colscale
     ref, bnd = {}, {}
     if kind == ATOMIC:
         # out += acc; aux[m] += sum_k A[m][k].  s: one atomic per slice (gemm_tile.h:385), the preloaded value is a term of the sum
-        out0 = _live(inp, c, "out0").to(F64)
         ref["out"] = out0 + acc
-        bnd["out"] = E32 * (K + c["split_k"]) * (absacc + out0.abs())
-        if c["aux"]:
+        bnd["out"] = E32 * (K + split_k) * (absacc + out0.abs())
+        if aux:
             # sum8_bf16 (gemm_tile.h:9-16): K additions; the folds 2 (:397-398); one atomic per (slice, n-tile) that took a K-step (:305,400)
-            aux0 = bufs["aux0"][:m_lim].to(F64)
-            tiles_n = (N + tiles_of(c)[1] - 1) // tiles_of(c)[1]
-            ref["aux"] = aux0 + a[0].sum(1)
-            bnd["aux"] = E32 * (K + 2 + c["split_k"] * tiles_n) * (a[0].abs().sum(1) + aux0.abs())
+            a0 = a[0] if a.dim() == 3 else a
+            ref["aux"] = aux0 + a0.sum(1)
+            bnd["aux"] = E32 * (K + 2 + split_k * tiles_n) * (a0.abs().sum(1) + aux0.abs())
         return ref, bnd
     e_acc = E32 * K * absacc                               # s = 0: the accumulators start at zero and one workgroup owns the whole K
     if kind == DGELU:
         # out = acc * colscale * gelu'(aux_in) (gemm_device.h:360,367): acc + 0 is exact; acc * cs 1; gelu_bwd's arithmetic E_g; the product 1.
         # gelu_bwd (devit_common.h:100-104): q 3 on Qabs; w = fma(-s, s, s) carries |1 - 2 s| E_s and 1; x * w 1; fma(x w, q, s) 1 on the result
-        z = _live(inp, c, "aux_in").to(F64)
+        z = aux_in
         e_s, s, q, qabs = _fit_arith(z)
         w = s * (1 - s)
         e_w = (1 - 2 * s).abs() * e_s + U * w
@@ -479,28 +477,48 @@ def reference(c, inp, with_bounds=True):
         ref["out"] = gelu_exact(pre) * cs
         e = cs.abs() * (dgelu_exact(pre).abs() * e_pre + GELU_FIT_ERR + pre.abs() * e_s + U * (pre * s).abs()) + U * ref["out"].abs()
         bnd["out"] = stored16(e, ref["out"], f16)
-        if c["aux"]:
+        if aux:
             ref["aux"], bnd["aux"] = pre, stored16(e_pre, pre, f16)
     elif kind == RESIDUAL:
         # out = res + rowscale[m / rows_per_scale] * (acc + bias) (gemm_device.h:316): the product 1, the sum 1; aux = cvt(acc + bias) (:305)
-        res = _live(inp, c, "out0" if c["alias"] else "res").to(F64)
-        if c["rowscale"]:
-            m = torch.arange(m_lim, device=res.device)
-            rs = bufs["rowscale"].to(F64)[torch.div(m, geo["rows_per_scale"], rounding_mode="floor")][None, :, None]
-        else:
-            rs = torch.ones((), dtype=F64, device=res.device)
+        rs = rowscale if rowscale is not None else torch.ones((), dtype=F64, device=res.device)
         ref["out"] = res + rs * pre
         bnd["out"] = rs.abs() * e_pre + U * (rs * pre).abs() + U * ref["out"].abs()
-        if c["aux"]:
+        if aux:
             ref["aux"], bnd["aux"] = pre, stored16(e_pre, pre, f16)
     elif kind == PATCH:
         # row m = (b, t): out[b (T + tok) + tok + t] = acc + bias + pos[tok + t] (gemm_device.h:286,315): one more sum
-        T, tok = c["patch_tokens"], c["extra_tokens"]
-        t = torch.arange(m_lim, device=acc.device) % T
-        pos = bufs["pos"].view(tok + T, geo["ldc"])[tok + t, :N].to(F64)[None]
         ref["out"] = pre + pos
         bnd["out"] = e_pre + U * ref["out"].abs()
     return ref, bnd
+
+
+def reference(c, inp, with_bounds=True):
+    """-> (ref, bnd): float64 [batch][m_lim][N] per output name ('out', 'aux'; ATOMIC aux: [m_lim]): statement() on the logical matrices that the
+    case's operand descriptions name."""
+    geo, kind, K, N = inp["geo"], c["kind"], c["K"], c["N"]
+    m_lim = geo["m_lim"]
+    a = logical(inp, inp["A"], m_lim, K, c["batch"]).to(F64)
+    b = logical(inp, inp["B"], N, K, c["batch"]).to(F64)
+    bufs = inp["bufs"]
+    vec = lambda n: bufs[n][:N].to(F64) if n in bufs else None                                 # noqa: E731
+    kw = dict(bias=vec("bias"), colscale=vec("colscale"), f16=bool(c["dtype16"]), aux=bool(c["aux"]))
+    if kind == ATOMIC:
+        kw.update(out0=_live(inp, c, "out0").to(F64), split_k=c["split_k"], tiles_n=(N + tiles_of(c)[1] - 1) // tiles_of(c)[1])
+        if c["aux"]:
+            kw["aux0"] = bufs["aux0"][:m_lim].to(F64)
+    elif kind == DGELU:
+        kw["aux_in"] = _live(inp, c, "aux_in").to(F64)
+    elif kind == RESIDUAL:
+        kw["res"] = _live(inp, c, "out0" if c["alias"] else "res").to(F64)
+        if c["rowscale"]:
+            m = torch.arange(m_lim, device=kw["res"].device)
+            kw["rowscale"] = bufs["rowscale"].to(F64)[torch.div(m, geo["rows_per_scale"], rounding_mode="floor")][None, :, None]
+    elif kind == PATCH:
+        T, tok = c["patch_tokens"], c["extra_tokens"]
+        t = torch.arange(m_lim, device=a.device) % T
+        kw["pos"] = bufs["pos"].view(tok + T, geo["ldc"])[tok + t, :N].to(F64)[None]
+    return statement(kind, a, b, **kw)
 
 
 # ============================================================================================ emulation

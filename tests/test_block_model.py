@@ -1,0 +1,128 @@
+"""tests/_block_model.py under test, without a GPU: the fp32 emulation of one encoder block passes the stage audit, every planted wiring bug is seen
+on the stage it is named for (or by the untouched-bytes statement it breaks), the buffer extents include/devit_hip.h words are what
+devit_block_acts_sizes / devit_block_bwd_sizes report, and the entry points' refusals -- argument checks in front of the first launch, so they
+need no device -- return their DEVIT_ERR_* with the cause in the message.  tests/test_gpu_block.py runs the same audit on the sequence itself."""
+import functools
+
+import pytest
+import torch
+
+import _block_model as K
+
+BWD_CASES = [c for c in K.CASES if c["flags"] & K.SAVE]
+# stages that are 16-bit stores (held below 1 like every 16-bit store of the sibling models: a correct round-to-nearest store comes arbitrarily close
+# to its own term of the bound); every fp32 stage stays at <= 0.5
+STORES16 = {"ln1", "qkv", "attn_o", "att", "ln2", "h", "h_pre", "dh_pre", "dln2", "g1", "dattn", "dqkv", "dln1", "g_prev"}
+
+
+@functools.lru_cache(maxsize=None)
+def clean(name):
+    """(inputs, unmutated emulation, its audit) of a case: computed once, shared, left unchanged"""
+    c = K.case_named(name)
+    inp = K.inputs(c)
+    bufs = K.emulate(c, inp)
+    return inp, bufs, K.audit(c, inp, bufs, K.default_routes(c) if c["flags"] & K.SAVE else None)
+
+
+@pytest.mark.parametrize("c", K.CASES, ids=[c["name"] for c in K.CASES])
+def test_emulation_passes_the_stage_audit(c):
+    _, _, (rt, problems) = clean(c["name"])
+    print(" ".join(f"{k} {v:.3f}" for k, v in rt.items()))
+    assert not problems, problems
+    for name, r in rt.items():
+        assert r < 1.0 if name in STORES16 else r <= 0.5, (c["name"], name, r)
+    if c["flags"] & K.SAVE:       # the whole list of the sequence: nothing the block leaves in memory is unaudited
+        want = {"ln1", "mean1", "rstd1", "qkv", "attn_o", "lse", "x1", "ln2", "mean2", "rstd2", "h", "h_pre", "x2", "fc2_b", "fc2_w", "dh_pre", "dln2",
+                "fc1_w", "fc1_b", "dx1", "g1", "n2w", "n2b", "proj_b", "dattn", "proj_w", "dqkv", "dln1", "qkv_w", "qkv_b", "dx_in", "n1w", "n1b", "g_prev",
+                "prev_fc2_b"} | ({"att"} if c["flags"] & K.ATT else set())
+        assert set(rt) == want, set(rt) ^ want
+
+
+@pytest.mark.parametrize("mutate", sorted(K.MUTATIONS))
+@pytest.mark.parametrize("c", BWD_CASES, ids=[c["name"] for c in BWD_CASES])
+def test_planted_wiring_bug_is_seen(c, mutate):
+    inp, _, _ = clean(c["name"])
+    rt, problems = K.audit(c, inp, K.emulate(c, inp, mutate=mutate), K.default_routes(c))
+    where = K.MUTATIONS[mutate]
+    if where in ("pad_rows", "inputs"):
+        assert any(p.startswith(where + "/") for p in problems), (mutate, problems)
+        if where == "pad_rows":
+            assert {"pad_rows/h", "pad_rows/g1"} <= set(problems)
+    else:
+        assert rt[where] >= 1.0, (c["name"], mutate, where, rt[where])
+
+
+def test_inputs_make_a_swapped_wire_visible():
+    """what the issue asks of the inputs, stated once"""
+    for c in BWD_CASES:
+        w, inp = K.block_weights(c), clean(c["name"])[0]
+        assert not torch.equal(w["dp1"], w["dp2"])
+        for v in (w["dp1"], w["dp2"]):
+            assert bool((v == 0).any()) and bool((v > 1).any())
+        assert bool((w["head_gate"] == 0).any()) and bool((w["head_gate"] > 1).any())
+        assert bool((w["neuron_gate"] == 0).any()) and bool((w["neuron_gate"] < 0).any()) and bool((w["neuron_gate"] > 1).any())
+        for b in ("qkv_b", "proj_b", "fc1_b", "fc2_b", "n1b", "n2b"):
+            assert bool((w[b] != 0).all())
+        assert float((w["n1w"] - 1).abs().min()) > 0 and float((w["n2w"] - 1).abs().min()) > 0
+        assert float(inp["x"].mean(1).std()) > 1.0, "a per-row offset"
+        assert all(bool((v != 0).all()) for v in inp["acc0"].values()), "every accumulator is preloaded"
+        assert K.dims(c)["M"] % 256 != 0
+    assert K.inputs(K.case_named("student"), dqkv_add=False)["dqkv_add"] is None
+
+
+@pytest.mark.parametrize("c", BWD_CASES, ids=[c["name"] for c in BWD_CASES])
+def test_without_dqkv_add_and_without_a_block_below(c):
+    """the other variant of the inputs: no dqkv_add, no g_prev (block 0), fc2's bias gradient handed down by the block above"""
+    inp = K.inputs(c, key=1, dqkv_add=False)
+    route = K.default_routes(c, g2_bias_done=True, prev=False)
+    rt, problems = K.audit(c, inp, K.emulate(c, inp, route=route), route)
+    assert not problems and "g_prev" not in rt and rt["fc2_b"] == 0.0
+    for name, r in rt.items():
+        assert r < 1.0 if name in STORES16 else r <= 0.5, (c["name"], name, r)
+    rt, _ = K.audit(c, inp, K.emulate(c, inp, route=K.default_routes(c, prev=False)), route)
+    assert rt["fc2_b"] == float("inf"), "a bias gradient formed twice (handed down AND taken here) is seen"
+
+
+# ---- host-only statements about the library
+@pytest.mark.parametrize("c", K.CASES, ids=[c["name"] for c in K.CASES])
+def test_reported_sizes_hold_the_stated_extents(c):
+    """devit_block_acts_sizes / devit_block_bwd_sizes against the extents the header words: at least the extent, 256-aligned, exactly 0 for what
+    the flags leave out"""
+    acts, bwd = K.library_sizes(c)
+    for got, want in ((acts, K.act_extents(c)), (bwd, K.bwd_extents(c))):
+        assert set(got) == set(want)
+        for name, n in want.items():
+            assert got[name] % 256 == 0 and got[name] >= n, (c["name"], name, got[name], n)
+            assert (got[name] == 0) == (n == 0), (c["name"], name, got[name], n)
+            assert got[name] < n + 256, (c["name"], name, "more than one alignment step over the stated extent")
+    from devit_amd import _lib as L
+    d = K.dims(c)
+    assert L.load().devit_layernorm_bwd_workspace(d["M"], d["D"]) == K.bwd_extents(c)["lnws"]
+    assert L.load().devit_colsum_workspace(d["Mp"], d["D"]) == 64 * d["D"] * 4, "the figure default_routes() restates"
+
+
+def test_routes_of_the_table():
+    """the branches the table is there for, from the restated rule"""
+    r = {c["name"]: K.default_routes(c) for c in BWD_CASES}
+    assert r["student"]["wmode"] and r["student"]["fc2_bias"] == "colsum"
+    assert r["compacted"]["wmode"] and r["compacted"]["fc2_bias"] == "launch"
+    assert not r["wide"]["wmode"] and r["wide"]["fc2_bias"] == "launch"
+    assert r["short"]["wmode"] and r["short"]["fc2_bias"] == "launch"
+    assert not K.default_routes(K.case_named("compacted"), {"DEVIT_WGRADFR": "0"})["wmode"]
+    assert K.qkv_extra(K.case_named("compacted")) == 205 and K.qkv_extra(K.case_named("student")) == 128
+
+
+def fake(name):
+    return 0x100000 * (1 + sum(ord(ch) for ch in name) % 97)
+
+
+@pytest.mark.parametrize("name,case,change,entry,code,words", K.REFUSALS, ids=[r[0] for r in K.REFUSALS])
+def test_entry_points_refuse_before_anything_is_launched(name, case, change, entry, code, words):
+    """with addresses that are not memory: a check that came after a launch (or a dereference) could not return its own code here"""
+    rc, msg = K.refused(case, change, entry, fake)
+    assert rc == code and words in msg, (name, rc, msg)
+
+
+def test_sizes_functions_refuse():
+    for name, rc, msg, code, words in K.sizes_refusals():
+        assert rc == code and words in msg, (name, rc, msg)
