@@ -293,6 +293,8 @@ int block_bwd(const devit_block_weights* wp, const devit_block_acts* ap, const d
   const bool drop = d && d->thr > 0, drop_attn = d && d->thr_attn > 0;
   DEVIT_CHECK(!drop || !io->g2_bias_done, DEVIT_ERR_ARG,
               "devit_block_bwd_drop: with p > 0 a block forms its own fc2 bias gradient from its masked g2 (g2_bias_done must be 0)");
+  // (refused here, in front of the first launch: the dropout kernels' own check of `block` would stop a backward that is half enqueued)
+  DEVIT_CHECK(!(drop || drop_attn) || d->block >= 0, DEVIT_ERR_ARG, "devit_block_bwd_drop: block %d (the block's index in the model, >= 0)", d->block);
   const devit_block_weights& w = *wp;
   const devit_block_acts& a = *ap;
   const devit_block_wgrads& g = *gp;

@@ -22,13 +22,27 @@ Cases (B, N, D, heads, hidden): the smallest shapes at which each branch of the 
     wide        2 x 197, 256 / 4 / 512: wmode == 0, four split-K launches on the side stream (and on the caller's with DEVIT_WGRAD_STREAM=0)
     short       4 x 17, 384 / 6 / 768: many images per tile
     f16_fwd     1 x 208, 256 / 4 / 512, f16, no DEVIT_BLK_SAVE: forward only (one image: dp1 and dp2 are single values, 1.25 and 0.5)
-(devit_gemm_bf16 accepts every product of these shapes: none had to be moved.)"""
+(devit_gemm_bf16 accepts every product of these shapes: none had to be moved.)
+
+The dropped sequence (devit_encoder_fwd_drop / devit_block_bwd_drop) is the same audit with a per-block description (drop_of(): seed, block index,
+p, p_attn).  thr / s come from _drop_model.thr_s and every mask from the numpy mirror (tests/_philox.py through _drop_model._keep and
+_attn_model.attn_keep), never from devit_dropout_mask.  No bound is new: the attention stages take _attn_model.bounds(..., keep, s); `tmp` is fc2's
+STORE_F32 statement; x2 _drop_model.residual_statement with judge_residual's bound; fc2_b / proj_b the column sums of the masked g2 / g1 under
+apply_statement's bound.  Where a pass rewrites or loses a stage's buffer two statements compose (x1: residual_stage(e_y); h, dh_pre:
+masked_in_place()); g1 and the caller's g2 are held bit for bit.  DROP_CASES (no DEVIT_BLK_ATT: refused under p > 0), rates (p, p_attn):
+    student_drop     2 x 198, 384 / 6 / 1536, block 5, (0.1, 0.1): grouped weight gradients, NO column-sum pass for fc2's bias, ceil4(198) = 200
+    student_fr_drop  the same under DEVIT_GEMMFR=1 with fc2_w16t, block 0, (0.5, 0): both fused sites with a NULL column-sum pointer, fc2_w16t not taken
+    compacted_drop   3 x 51, 384 / 4 / 640, block 11; default and DEVIT_WGRADFR=0; (0, 0.25): attention-only dropout on the plain sequence,
+                     ceil4(51) = 52, and (0.1, 0.1)
+    wide_drop        2 x 197, 256 / 4 / 512, block 5, (0.1, 0.1): split-K weight gradients on the side stream (and DEVIT_WGRAD_STREAM=0) reading
+                     buffers masked in place on the caller's stream"""
 import ctypes as C
 import math
 
 import torch
 
 import _attn_model as A
+import _drop_model as DM
 import _gemm_model as G
 import _tail_model as T
 from _tail_model import BF16, F16, F32, F64, U, gen, ratio, stored16   # noqa: F401
@@ -45,6 +59,13 @@ MUTATIONS = {  # planted wiring bug -> the stage (or untouched-bytes check) that
     "ln2_reads_x": "ln2", "x2_residual_from_x": "x2", "dp2_for_dp1": "x1", "h_pre_after_gate": "h_pre", "proj_bias_twice": "x1",
     "pad_rows_left": "pad_rows", "fc2_bias_twice": "fc2_b", "proj_b_from_dx1": "proj_b", "g_prev_unscaled": "g_prev",
     "dqkv_add_dropped": "dqkv", "lse_not_saved_per_head": "lse", "dx_pingpong_stale": "inputs"}
+# the dropped sequence's planted wiring bugs -> (stage, what the rates must be for the bug to change anything: 'p', 'p_attn' or 'p != p_attn')
+DROP_MUTATIONS = {
+    "site2_mask_at_site4": ("x2", "p"), "bwd_site3_left_out": ("dh_pre", "p"), "attn_scale_at_site2": ("x1", "p != p_attn"),
+    "attn_pitch_N": ("attn_o", "p_attn"), "bwd_mask_of_next_block": ("g1", "p"), "fc2_b_from_unmasked_g2": ("fc2_b", "p"),
+    "proj_b_by_layernorm_too": ("proj_b", "p"), "x2_from_proj_tmp": ("x2", "p"), "h_pre_masked_too": ("h_pre", "p"),
+    "g2_masked_out_of_place": ("inputs/g2", "p"), "fc2_w_reads_unmasked_h": ("fc2_w", "p")}
+MUTATIONS.update({k: v[0] for k, v in DROP_MUTATIONS.items()})
 
 
 def _case(name, B, N, D, heads, hidden, flags, dtype16=0, fc2t=False, envs=(("", {}),)):
@@ -62,8 +83,34 @@ CASES = [
 ]
 
 
+# ---- the dropped sequence (devit_encoder_fwd_drop / devit_block_bwd_drop: block_fwd / block_bwd with d != NULL).  A case names the block index its
+# masks are generated for; a run is (tag, environment, (p, p_attn)).  DEVIT_BLK_ATT is refused under p > 0, so no case carries it.
+DROP_SEED = (0x9E3779B9 << 32) | 20240807
+
+
+def drop_of(block, p, p_attn, seed=DROP_SEED):
+    """the per-block dropout description of the audit and of emulate(): what devit_block_dropout carries, as rates"""
+    return dict(seed=seed, block=block, p=p, p_attn=p_attn)
+
+
+DROP_CASES = [
+    dict(_case("student_drop", 2, 198, 384, 6, 1536, SAVE | QKV_PAD), block=5, runs=(("", {}, (0.1, 0.1)),)),
+    dict(_case("student_fr_drop", 2, 198, 384, 6, 1536, SAVE | QKV_PAD, fc2t=True), block=0, runs=(("", {"DEVIT_GEMMFR": "1"}, (0.5, 0.0)),)),
+    dict(_case("compacted_drop", 3, 51, 384, 4, 640, SAVE | QKV_PAD), block=11,
+         runs=(("attn", {}, (0.0, 0.25)), ("attn/wgradfr0", {"DEVIT_WGRADFR": "0"}, (0.0, 0.25)), ("both", {}, (0.1, 0.1)),
+               ("both/wgradfr0", {"DEVIT_WGRADFR": "0"}, (0.1, 0.1)))),
+    dict(_case("wide_drop", 2, 197, 256, 4, 512, SAVE), block=5,
+         runs=(("", {}, (0.1, 0.1)), ("wgrad_stream0", {"DEVIT_WGRAD_STREAM": "0"}, (0.1, 0.1)))),
+]
+
+
+def drop_variants():
+    """(id, case, environment, dropout description) of every run of the dropped table"""
+    return [(c["name"] + ("/" + tag if tag else ""), c, env, drop_of(c["block"], *rates)) for c in DROP_CASES for tag, env, rates in c["runs"]]
+
+
 def case_named(name):
-    return next(c for c in CASES if c["name"] == name)
+    return next(c for c in CASES + DROP_CASES if c["name"] == name)
 
 
 def variants(backward_only=False):
@@ -202,14 +249,18 @@ def colsum_pass_bounds(y16, rows, out0):
     return ref, U * colsum_pass_roundings(rows) * (v.abs().sum(0) + out0.to(F64).abs())
 
 
-def routes(c, env, lnws_bytes, colsum_ws, fused=(False, False), g2_bias_done=False, prev=True):
+def routes(c, env, lnws_bytes, colsum_ws, fused=(False, False), g2_bias_done=False, prev=True, drop=None):
     """The decisions of block_bwd (csrc/encoder.hip) that change WHICH kernel an output comes from, hence how many roundings its bound counts:
     wmode (the grouped launch: D == 384, three K-steps, DEVIT_WGRADFR != 0) and who owns fc2's bias gradient: 'handed' (g2_bias_done: not this
     call's), 'colsum' (the pass over g2, when the LayerNorm workspace is large enough for it) or 'launch' (the row sums of fc2's own split-K
-    launch).  fused: devit_dgrad_layernorm_bwd_fused at the LN2 and LN1 sites, asked of the library by the caller.  prev: g_prev / prev_fc2_b given."""
+    launch).  fused: devit_dgrad_layernorm_bwd_fused at the LN2 and LN1 sites, asked of the library by the caller.  prev: g_prev / prev_fc2_b given.
+    drop with p > 0: 'masked' -- the column sums of the site-4 pass over g2, whatever the other rules would say (block_bwd: fc2_bias_here = false)."""
     d = dims(c)
     wmode = d["D"] == 384 and d["Mp"] // 64 >= 3 and env.get("DEVIT_WGRADFR", "1") != "0"
     fb = "handed" if g2_bias_done else "colsum" if (wmode and d["Hd"] % 128 == 0 and lnws_bytes >= colsum_ws) else "launch"
+    if drop is not None and drop["p"] > 0:
+        assert not g2_bias_done, "devit_block_bwd_drop refuses g2_bias_done with p > 0"
+        fb = "masked"
     return dict(wmode=wmode, fc2_bias=fb, fused=tuple(fused), prev=prev)
 
 
@@ -240,30 +291,127 @@ def _ln_fwd_stage(tag, x, gamma, beta, y16, mean, rstd, f16, save):
         yield "rstd" + tag, rstd, r["rstd"], b["rstd"]
 
 
-def forward_stages(c, inp, bufs):
-    """yields (stage, got, float64 reference, bound) for what devit_encoder_fwd left of one block, read off block_fwd"""
+# ---- the dropout passes.  Masks come from the numpy mirror alone (tests/_philox.py through _drop_model._keep and _attn_model.attn_keep), thr / s
+# from _drop_model.thr_s; every bound is one the sibling models already state, composed where a pass rewrites a stage's buffer in place.
+SITE_ATTN, SITE_PROJ, SITE_HIDDEN, SITE_FC2 = 1, 2, 3, 4
+_ATTN_KEEP = {}
+
+
+def is_dropped(drop):
+    """(drop, drop_attn) of block_fwd / block_bwd: thr > 0, thr_attn > 0"""
+    return (False, False) if drop is None else (DM.thr_s(drop["p"])[0] > 0, DM.thr_s(drop["p_attn"])[0] > 0)
+
+
+def site_keep(c, drop, site, cols, dev="cpu", block=None):
+    """bool [M][cols], pitch cols: the keep mask of sites 2, 3, 4 of the block (another block's with `block`)"""
+    blk = drop["block"] if block is None else block
+    return DM._keep(drop["seed"], site, blk, DM.thr_s(drop["p"])[0], dims(c)["M"], cols, cols).to(dev)
+
+
+def attn_site_keep(c, drop, dev="cpu", pitch=None):
+    """bool [B][H][N][N] at pitch ceil4(N) (or the pitch a wrong kernel would take), and scale_keep_attn"""
+    d = dims(c)
+    key = (drop["seed"], drop["block"], drop["p_attn"], d["B"], d["H"], d["N"], pitch)
+    if key not in _ATTN_KEEP:
+        _ATTN_KEEP[key] = A.attn_keep(drop["seed"], drop["block"], DM.thr_s(drop["p_attn"])[0], d["B"], d["H"], d["N"], pitch=pitch)
+    return _ATTN_KEEP[key].to(dev), DM.thr_s(drop["p_attn"])[1]
+
+
+def _apply_case(drop, site, rows, cols, p=None, colsum=False):
+    return dict(kernel="apply", dtype=BF16, rows=rows, cols=cols, ld=cols, pitch=cols, colsum=colsum, site=site, block=drop["block"],
+                p=drop["p"] if p is None else p, seed=drop["seed"])
+
+
+def masked16(drop, site, pre16, keep):
+    """_drop_model.apply_statement of a bf16 buffer's live rows: what devit_dropout_apply must leave of them, to the bit"""
+    z = torch.zeros(pre16.shape[1], dtype=F32, device=pre16.device)
+    return DM.apply_statement(_apply_case(drop, site, *pre16.shape), dict(x=pre16, colsum0=z), keep)[0]
+
+
+def masked_colsum_bounds(drop, site, stored16_, out0):
+    """the column sums devit_dropout_apply adds to its `colsum` while it masks, stated on the buffer AS STORED (apply_statement at p = 0 keeps every
+    element's bits, so its sums and its bound -- strip + 3 + gy additions, _drop_model's docstring -- are those of the stored values) + the preload"""
+    keep = torch.ones(stored16_.shape, dtype=torch.bool, device=stored16_.device)
+    _, colsum, bound = DM.apply_statement(_apply_case(drop, site, *stored16_.shape, p=0.0, colsum=True), dict(x=stored16_, colsum0=out0), keep)
+    return colsum, bound
+
+
+def masked_in_place(drop, ref, e, keep):
+    """A 16-bit buffer a launch wrote and devit_dropout_apply then rewrote in place: the launch's statement gives (ref, e), its 16-bit store included.
+    A dropped element is the zero apply_statement states (bound 0).  A kept one is bf16(fp32(v) * s) of the stored v, |v - ref| <= e
+    (dropout_apply_kernel.inc:32: one fp32 product, one rounding to bf16; :21 is the fp32 buffers' line): around s ref it lies within
+        s e  +  stored16(U s (|ref| + e), s (|ref| + e))
+    -- the producer's error scaled, plus apply's own two roundings on an input of magnitude |ref| + e."""
+    s = DM.thr_s(drop["p"])[1]
+    mag = s * (ref.abs() + e)
+    zero = torch.zeros((), dtype=F64, device=ref.device)
+    return torch.where(keep, s * ref, zero), torch.where(keep, s * e + stored16(U * mag, mag), zero)
+
+
+def residual_stage(c, drop, site, x, y, rowscale, keep, got, e_y=None):
+    """devit_dropout_residual (x_out = x + rowscale y s where kept) -> (float64 reference, bound): _drop_model.residual_statement and judge_residual's
+    bound 2^-24 (|rs y s| + |out|); bound 0 (x's value exactly) where the element is dropped or its row scale is 0.  e_y: y is itself a float64
+    statement with this bound, of a temporary that is gone -- its error reaches the output times |rs| s"""
+    d = dims(c)
+    rc = dict(kernel="residual", rows=d["M"], cols=x.shape[1], rps=d["N"], p=drop["p"], site=site)
+    want, branch, exact = DM.residual_statement(rc, dict(x=x, y=y, rowscale=rowscale), keep)
+    bound = DM.U24 * (branch.abs() + got.to(F64).abs())
+    if e_y is not None:
+        bound = bound + _rs(rowscale, d["N"]).abs() * DM.thr_s(drop["p"])[1] * e_y
+    return want, torch.where(exact, torch.zeros((), dtype=F64, device=bound.device), bound)
+
+
+def _attn_drop_kw(c, drop, dev, pitch=None):
+    if not is_dropped(drop)[1]:
+        return {}
+    keep, s = attn_site_keep(c, drop, dev, pitch)
+    return dict(keep=keep, s=s)
+
+
+def forward_stages(c, inp, bufs, drop=None):
+    """yields (stage, got, float64 reference, bound) for what devit_encoder_fwd (with `drop`: devit_encoder_fwd_drop) left of one block, read off
+    block_fwd"""
     d, w = dims(c), inp["w"]
-    B, N, H, M = d["B"], d["N"], d["H"], d["M"]
+    B, N, H, M, D, Hd = d["B"], d["N"], d["H"], d["M"], d["D"], d["Hd"]
     f16, save, att = bool(c["dtype16"]), bool(c["flags"] & SAVE), bool(c["flags"] & ATT)
+    dropped, _ = is_dropped(drop)
     x = bufs["x"]
+    dev = x.device
     yield from _ln_fwd_stage("1", x, w["n1w"], w["n1b"], bufs["ln1"][:M], bufs.get("mean1"), bufs.get("rstd1"), f16, save)
     ref, bnd = G.statement(G.STORE_BF16, _d(bufs["ln1"][:M]), _d(w["qkv_w16"]), bias=_d(w["qkv_b"]), f16=f16)
     yield "qkv", bufs["qkv"][:M], ref["out"], bnd["out"]
     q, k, v, _, _ = A.split_packed(bufs["qkv"], B, N, H)
-    r, b = A.bounds(q, k, v, w["head_gate"], 0.125, u=A.U_F16 if f16 else A.U_BF16, f16=f16)
+    r, b = A.bounds(q, k, v, w["head_gate"], 0.125, u=A.U_F16 if f16 else A.U_BF16, f16=f16, **_attn_drop_kw(c, drop, dev))
     yield "attn_o", A.heads(bufs["attn_o"], B, N, H), r["O"], b["O"]
     if save:
         yield "lse", bufs["lse"].view(B, H, N), r["lse"], b["lse"]
-    ref, bnd = G.statement(G.RESIDUAL, _d(bufs["attn_o"][:M]), _d(w["proj_w16"]), bias=_d(w["proj_b"]), res=_d(x), rowscale=_rs(w["dp1"], N), aux=att,
-                           f16=f16)
-    yield "x1", bufs["x1"], ref["out"], bnd["out"]
-    if att:
-        yield "att", bufs["att"], ref["aux"], bnd["aux"]
+    if dropped:      # proj stores fp32 into the temporary fc2 then overwrites: its statement and the residual pass's (site 2) compose
+        ref, bnd = G.statement(G.STORE_F32, _d(bufs["attn_o"][:M]), _d(w["proj_w16"]), bias=_d(w["proj_b"]))
+        yield ("x1", bufs["x1"]) + residual_stage(c, drop, SITE_PROJ, bufs["x"], ref["out"], w["dp1"], site_keep(c, drop, SITE_PROJ, D, dev), bufs["x1"],
+                                                  bnd["out"])
+    else:
+        ref, bnd = G.statement(G.RESIDUAL, _d(bufs["attn_o"][:M]), _d(w["proj_w16"]), bias=_d(w["proj_b"]), res=_d(x), rowscale=_rs(w["dp1"], N), aux=att,
+                               f16=f16)
+        yield "x1", bufs["x1"], ref["out"], bnd["out"]
+        if att:
+            yield "att", bufs["att"], ref["aux"], bnd["aux"]
     yield from _ln_fwd_stage("2", bufs["x1"], w["n2w"], w["n2b"], bufs["ln2"][:M], bufs.get("mean2"), bufs.get("rstd2"), f16, save)
     ref, bnd = G.statement(G.GELU, _d(bufs["ln2"][:M]), _d(w["fc1_w16"]), bias=_d(w["fc1_b"]), colscale=_d(w["neuron_gate"]), aux=save, f16=f16)
-    yield "h", bufs["h"][:M], ref["out"], bnd["out"]
+    if dropped:      # masked in place after the GELU launch (site 3); the saved pre-activation stays as the launch left it
+        yield ("h", bufs["h"][:M]) + masked_in_place(drop, ref["out"], bnd["out"], site_keep(c, drop, SITE_HIDDEN, Hd, dev))
+    else:
+        yield "h", bufs["h"][:M], ref["out"], bnd["out"]
     if save:
         yield "h_pre", bufs["h_pre"][:M], ref["aux"], bnd["aux"]
+    if dropped:      # fc2 stores fp32 into the temporary (as the call leaves it), the residual pass forms x2 from the stored x1 and tmp (site 4)
+        ref, bnd = G.statement(G.STORE_F32, _d(bufs["h"][:M]), _d(w["fc2_w16"]), bias=_d(w["fc2_b"]))
+        keep4 = site_keep(c, drop, SITE_FC2, D, dev)
+        if bufs.get("tmp") is not None:
+            yield "tmp", bufs["tmp"][:M], ref["out"], bnd["out"]
+            yield ("x2", bufs["x2"]) + residual_stage(c, drop, SITE_FC2, bufs["x1"], bufs["tmp"][:M], w["dp2"], keep4, bufs["x2"])
+        else:        # a block of a chain whose successor has written the shared temporary since: composed as x1 is
+            yield ("x2", bufs["x2"]) + residual_stage(c, drop, SITE_FC2, bufs["x1"], ref["out"], w["dp2"], keep4, bufs["x2"], bnd["out"])
+        return
     ref, bnd = G.statement(G.RESIDUAL, _d(bufs["h"][:M]), _d(w["fc2_w16"]), bias=_d(w["fc2_b"]), res=_d(bufs["x1"]), rowscale=_rs(w["dp2"], N), f16=f16)
     yield "x2", bufs["x2"], ref["out"], bnd["out"]
 
@@ -306,14 +454,18 @@ def _ln_bwd_stage(tag, x, mean, rstd, gamma, dln, dres, g0, b0, M, fused, tiles)
     return r, b
 
 
-def backward_stages(c, inp, bufs, route, dln=None):
-    """yields (stage, got, float64 reference, bound) for what devit_block_bwd left, read off block_bwd.  route: routes().  dln: {'dln2': .., 'dln1': ..}
-    the LayerNorm backward's input where the fused launch kept it on chip (from a run of the two launches on bit-identical dh_pre / dqkv)."""
+def backward_stages(c, inp, bufs, route, dln=None, drop=None):
+    """yields (stage, got, float64 reference, bound) for what devit_block_bwd (with `drop`: devit_block_bwd_drop) left, read off block_bwd.  route:
+    routes().  dln: {'dln2': .., 'dln1': ..} the LayerNorm backward's input where the fused launch kept it on chip (from a run of the two launches on
+    bit-identical dh_pre / dqkv).  Under p > 0 bufs['g2'] is the caller's buffer as the call left it: masked (audit() holds it to the pre-mask value)."""
     d, w, a0 = dims(c), inp["w"], inp["acc0"]
-    B, N, H, M, Mp, Da = d["B"], d["N"], d["H"], d["M"], d["Mp"], d["Da"]
+    B, N, H, M, Mp, Da, D, Hd = d["B"], d["N"], d["H"], d["M"], d["Mp"], d["Da"], d["D"], d["Hd"]
     tiles = Mp // 256
     acc = bufs["acc"]
     g2, dx = bufs["g2"], bufs["dx"]
+    dropped, _ = is_dropped(drop)
+    dev = dx.device
+    assert dropped == (route["fc2_bias"] == "masked")
     # 1, 2: fc2's weight gradient and who owns its bias gradient
     own = route["fc2_bias"] == "launch"
     st = _wgrad_stage("fc2_w", "fc2_b", g2, bufs["h"], a0["fc2_w"], a0["fc2_b"] if own else None, M, Mp, route)
@@ -322,11 +474,16 @@ def backward_stages(c, inp, bufs, route, dln=None):
         yield "fc2_b", acc["fc2_b"], ref, bnd
     elif route["fc2_bias"] == "handed":
         yield "fc2_b", acc["fc2_b"], _d(a0["fc2_b"]), torch.zeros_like(_d(a0["fc2_b"]))
+    elif route["fc2_bias"] == "masked":      # the site-4 pass's own column sums of what it stored, and nothing else
+        yield ("fc2_b", acc["fc2_b"]) + masked_colsum_bounds(drop, SITE_FC2, g2[:M], a0["fc2_b"])
     for name, ref, bnd in st[::-1]:
         yield name, acc[name], ref, bnd
     # 3
     ref, bnd = G.statement(G.DGELU, _d(g2[:M]), _d(w["fc2_w16"]).t(), colscale=_d(w["neuron_gate"]), aux_in=_d(bufs["h_pre"][:M]))
-    yield "dh_pre", bufs["dh_pre"][:M], ref["out"], bnd["out"]
+    if dropped:      # masked in place after the dGELU launch (site 3)
+        yield ("dh_pre", bufs["dh_pre"][:M]) + masked_in_place(drop, ref["out"], bnd["out"], site_keep(c, drop, SITE_HIDDEN, Hd, dev))
+    else:
+        yield "dh_pre", bufs["dh_pre"][:M], ref["out"], bnd["out"]
     # 4
     if not route["fused"][0]:
         ref, bnd = G.statement(G.STORE_BF16, _d(bufs["dh_pre"][:M]), _d(w["fc1_w16"]).t())
@@ -338,13 +495,24 @@ def backward_stages(c, inp, bufs, route, dln=None):
     dln2 = (dln or bufs)["dln2"] if route["fused"][0] else bufs["dln2"]
     r, b = _ln_bwd_stage("2", bufs["x1"], bufs["mean2"], bufs["rstd2"], w["n2w"], dln2[:M], dx, a0["n2w"], a0["n2b"], M, route["fused"][0], tiles)
     yield "dx1", bufs["dx1"], r["dx"], b["dx"]
-    ref = _rs(w["dp1"], N) * _d(bufs["dx1"])
-    yield "g1", bufs["g1"][:M], ref, stored16(U * ref.abs(), ref)
+    if dropped:
+        # The pre-mask value is bf16(dp1 * dx1) of the STORED dx1: one fp32 product, one rounding -- torch's product, to which tests/test_gpu_tail.py
+        # (the LayerNorm backward) and tests/test_gpu_lnfuse.py (the fused launch) hold this output bit for bit.  The equality carries over on both
+        # routes, so the masked g1 is held to apply_statement of it (site 2) bit for bit: the bound is 0.
+        pre = (w["dp1"].to(F32).repeat_interleave(N)[:, None] * bufs["dx1"]).to(BF16)
+        want = masked16(drop, SITE_PROJ, pre, site_keep(c, drop, SITE_PROJ, D, dev)).to(F64)
+        yield "g1", bufs["g1"][:M], want, torch.zeros_like(want)
+    else:
+        ref = _rs(w["dp1"], N) * _d(bufs["dx1"])
+        yield "g1", bufs["g1"][:M], ref, stored16(U * ref.abs(), ref)
     yield "n2w", acc["n2w"], r["dgamma"], b["dgamma"]
     yield "n2b", acc["n2b"], r["dbeta"], b["dbeta"]
-    ref, bnd = T.ln_colsum_bounds(bufs["g1"][:M], a0["proj_b"])
-    if route["fused"][0]:
-        bnd = bnd * max(T.ln_col_roundings(M), fused_chain(tiles)) / T.ln_col_roundings(M)
+    if dropped:      # the LayerNorm backward ran with a NULL column-sum pointer: the site-2 pass's sums of the masked g1, and nothing else
+        ref, bnd = masked_colsum_bounds(drop, SITE_PROJ, bufs["g1"][:M], a0["proj_b"])
+    else:
+        ref, bnd = T.ln_colsum_bounds(bufs["g1"][:M], a0["proj_b"])
+        if route["fused"][0]:
+            bnd = bnd * max(T.ln_col_roundings(M), fused_chain(tiles)) / T.ln_col_roundings(M)
     yield "proj_b", acc["proj_b"], ref, bnd
     # 7
     ref, bnd = G.statement(G.STORE_BF16, _d(bufs["g1"][:M]), _d(w["proj_w16"]).t())
@@ -355,7 +523,7 @@ def backward_stages(c, inp, bufs, route, dln=None):
     # 9
     add = bufs.get("dqkv_add")
     q, k, v, do, ad = A.split_packed(bufs["qkv"], B, N, H, bufs["dattn"], add)
-    r, b = A.bounds(q, k, v, w["head_gate"], 0.125, do, ad)
+    r, b = A.bounds(q, k, v, w["head_gate"], 0.125, do, ad, **_attn_drop_kw(c, drop, dev))
     got = torch.stack([A.heads(bufs["dqkv"], B, N, H, j * Da) for j in range(3)])
     yield "dqkv", got, torch.stack([r["dQ"], r["dK"], r["dV"]]), torch.stack([b["dQ"], b["dK"], b["dV"]])
     # 10
@@ -381,16 +549,17 @@ def backward_stages(c, inp, bufs, route, dln=None):
             yield "prev_fc2_b", acc["prev_fc2_b"], ref, bnd
 
 
-def audit(c, inp, bufs, route=None, dln=None):
+def audit(c, inp, bufs, route=None, dln=None, drop=None):
     """-> ({stage: worst |err| / bound over every live element}, problems): problems names every untouched-bytes statement that does not hold --
     'pad_rows/<buffer>' (a 16-bit buffer whose rows >= M are not zero, the qkv overhang included), 'inputs/<name>' (an input of the call that
-    did not come back bit for bit).  route None: the forward alone."""
-    M = dims(c)["M"]
+    did not come back bit for bit).  route None: the forward alone.  drop (drop_of()): the dropped sequence; with p > 0 the caller's g2 is the one
+    input that must NOT come back as it was: it must be torch.equal to apply_statement of the value the test handed in (site 4)."""
+    M, D = dims(c)["M"], dims(c)["D"]
     rt = {}
-    for name, got, ref, bnd in forward_stages(c, inp, bufs):
+    for name, got, ref, bnd in forward_stages(c, inp, bufs, drop):
         rt[name] = ratio(got, ref, bnd)
     if route is not None:
-        for name, got, ref, bnd in backward_stages(c, inp, bufs, route, dln):
+        for name, got, ref, bnd in backward_stages(c, inp, bufs, route, dln, drop):
             rt[name] = ratio(got, ref, bnd)
     problems = []
     for name in PADDED:
@@ -398,17 +567,41 @@ def audit(c, inp, bufs, route=None, dln=None):
         if t is not None and t.shape[0] > M and bool((t[M:].view(torch.int16) != 0).any()):
             problems.append("pad_rows/" + name)
     for name in ("x", "dx", "g2", "dqkv_add"):
-        if bufs.get(name) is not None and inp.get(name) is not None and not torch.equal(bufs[name][:inp[name].shape[0]].cpu(), inp[name].cpu()):
+        if bufs.get(name) is None or inp.get(name) is None:
+            continue
+        want = inp[name]
+        if name == "g2" and route is not None and is_dropped(drop)[0]:
+            want = masked16(drop, SITE_FC2, want, site_keep(c, drop, SITE_FC2, D, want.device))
+        if not torch.equal(bufs[name][:want.shape[0]].cpu(), want.cpu()):
             problems.append("inputs/" + name)
     return rt, problems
 
 
 # ============================================================================================ emulation
-def emulate(c, inp, mutate=None, route=None):
+def _emu_apply(t16, keep, s):
+    """devit_dropout_apply on a bf16 buffer's live rows: bf16(fp32(x) * s) where kept, +0 where dropped"""
+    return torch.where(keep, (t16.to(F32) * torch.tensor(s, dtype=F32)).to(BF16), torch.zeros((), dtype=BF16))
+
+
+def _emu_residual(x, y, rs, keep, s):
+    """devit_dropout_residual as _drop_model.emulate_residual words it: t = y * s rounded, out = fmaf(rs, t, x) where kept, x's bits where dropped"""
+    t = y * torch.tensor(s, dtype=F32)
+    return torch.where(keep, (rs.to(F64) * t.to(F64) + x.to(F64)).to(F32), x)
+
+
+def emulate(c, inp, mutate=None, route=None, drop=None):
     """One block forward (and, with DEVIT_BLK_SAVE, backward) in fp32 torch, every buffer of the sequence as it would be left -> bufs as audit()
     takes them.  The GEMMs are plain fp32 products (another order than the kernels'), LayerNorm and attention are the sibling models' emulations,
-    16-bit stores one rounding.  `mutate`: one of MUTATIONS, a planted WIRING bug -- every kernel stays correct."""
+    16-bit stores one rounding.  `mutate`: one of MUTATIONS, a planted WIRING bug -- every kernel stays correct.  drop (drop_of()): the dropped
+    sequence, with bufs['tmp'] as fc2 leaves it and bufs['g2'] masked in place."""
     assert mutate is None or mutate in MUTATIONS
+    assert mutate not in DROP_MUTATIONS or drop is not None
+    dropped, dropped_attn = is_dropped(drop)
+    D_, Hd_ = c["D"], c["hidden"]
+    if dropped:
+        s_keep = DM.thr_s(drop["p"])[1]
+        keep2, keep3, keep4 = (site_keep(c, drop, site, cols) for site, cols in ((SITE_PROJ, D_), (SITE_HIDDEN, Hd_), (SITE_FC2, D_)))
+    akw = _attn_drop_kw(c, drop, "cpu", pitch=c["N"] if mutate == "attn_pitch_N" else None)
     d, w, a0 = dims(c), inp["w"], inp["acc0"]
     B, N, H, M, Mp, Da = d["B"], d["N"], d["H"], d["M"], d["Mp"], d["Da"]
     f16, save, att = bool(c["dtype16"]), bool(c["flags"] & SAVE), bool(c["flags"] & ATT)
@@ -429,7 +622,7 @@ def emulate(c, inp, mutate=None, route=None):
     bufs.update(ln1=padded(e["y"]), mean1=e["mean"], rstd1=e["rstd"])
     bufs["qkv"] = padded(f(bufs["ln1"][:M]) @ f(w["qkv_w16"]).t() + w["qkv_b"], qkv_extra(c))
     q, k, v, _, _ = A.split_packed(bufs["qkv"], B, N, H)
-    ae = A.emulate(q, k, v, w["head_gate"], 0.125, f16=f16)
+    ae = A.emulate(q, k, v, w["head_gate"], 0.125, f16=f16, **akw)
     bufs["attn_o"] = padded(A.rows(ae["O"]))
     lse = ae["lse"].to(F32)
     if mutate == "lse_not_saved_per_head":
@@ -438,7 +631,11 @@ def emulate(c, inp, mutate=None, route=None):
     pre = f(bufs["attn_o"][:M]) @ f(w["proj_w16"]).t() + w["proj_b"]
     if mutate == "proj_bias_twice":
         pre = pre + w["proj_b"]
-    bufs["x1"] = x + dp1 * pre
+    if dropped:
+        tmp_proj = pre
+        bufs["x1"] = _emu_residual(x, pre, dp1, keep2, DM.thr_s(drop["p_attn"])[1] if mutate == "attn_scale_at_site2" else s_keep)
+    else:
+        bufs["x1"] = x + dp1 * pre
     if att:
         bufs["att"] = pre.to(dt)
     e = T.ln_fwd_emulate(x if mutate == "ln2_reads_x" else bufs["x1"], w["n2w"], w["n2b"], EPS)
@@ -446,38 +643,62 @@ def emulate(c, inp, mutate=None, route=None):
     pre = f(bufs["ln2"][:M]) @ f(w["fc1_w16"]).t() + w["fc1_b"]
     bufs["h"] = padded(G.gelu_fit32(pre) * w["neuron_gate"])
     bufs["h_pre"] = padded(pre * w["neuron_gate"] if mutate == "h_pre_after_gate" else pre)
-    bufs["x2"] = (x if mutate == "x2_residual_from_x" else bufs["x1"]) + dp2 * (f(bufs["h"][:M]) @ f(w["fc2_w16"]).t() + w["fc2_b"])
+    if dropped:
+        h_unmasked = bufs["h"].clone()
+        bufs["h"][:M] = _emu_apply(bufs["h"][:M], keep3, s_keep)
+        if mutate == "h_pre_masked_too":
+            bufs["h_pre"][:M] = _emu_apply(bufs["h_pre"][:M], keep3, s_keep)
+        bufs["tmp"] = torch.full((Mp, D_), math.nan, dtype=F32)      # (rows >= M are never written: whatever the arena held)
+        bufs["tmp"][:M] = f(bufs["h"][:M]) @ f(w["fc2_w16"]).t() + w["fc2_b"]
+        bufs["x2"] = _emu_residual(x if mutate == "x2_residual_from_x" else bufs["x1"], tmp_proj if mutate == "x2_from_proj_tmp" else bufs["tmp"][:M],
+                                   dp2, keep2 if mutate == "site2_mask_at_site4" else keep4, s_keep)
+    else:
+        bufs["x2"] = (x if mutate == "x2_residual_from_x" else bufs["x1"]) + dp2 * (f(bufs["h"][:M]) @ f(w["fc2_w16"]).t() + w["fc2_b"])
     if not save:
         for k_ in ("mean1", "rstd1", "lse", "mean2", "rstd2", "h_pre"):
             del bufs[k_]
         return bufs
     # ---- backward
     dx, g2 = inp["dx"], padded(inp["g2"], t=BF16)
-    bufs.update(dx=dx.clone(), g2=inp["g2"].clone(), dqkv_add=inp["dqkv_add"])
+    if dropped:      # site 4: the caller's g2 masked in place, its column sums are fc2's bias gradient
+        assert route["fc2_bias"] == "masked", "routes(..., drop=...)"
+        g2_unmasked = g2
+        g2 = padded(_emu_apply(inp["g2"], keep4, s_keep), t=BF16)
+    bufs.update(dx=dx.clone(), g2=inp["g2"].clone() if (not dropped or mutate == "g2_masked_out_of_place") else g2[:M].clone(), dqkv_add=inp["dqkv_add"])
     acc = {}
     if mutate == "pad_rows_left":
         bufs["h"][Mp - 2] = 0.375
     if route["fc2_bias"] == "handed":
         acc["fc2_b"] = a0["fc2_b"].clone()
+    elif mutate == "fc2_b_from_unmasked_g2":
+        acc["fc2_b"] = a0["fc2_b"] + f(g2_unmasked).sum(0)
     else:
         acc["fc2_b"] = a0["fc2_b"] + f(g2).sum(0) * (2 if mutate == "fc2_bias_twice" else 1)
-    acc["fc2_w"] = a0["fc2_w"] + f(g2).t() @ f(bufs["h"])
+    acc["fc2_w"] = a0["fc2_w"] + f(g2).t() @ f(h_unmasked if mutate == "fc2_w_reads_unmasked_h" else bufs["h"])
     dh = (f(g2[:M]) @ f(w["fc2_w16"])) * w["neuron_gate"] * G.dgelu_fit32(f(bufs["h_pre"][:M]))
     bufs["dh_pre"] = padded(dh, t=BF16)
+    if dropped and mutate != "bwd_site3_left_out":
+        bufs["dh_pre"][:M] = _emu_apply(bufs["dh_pre"][:M], keep3, s_keep)
     bufs["dln2"] = padded(f(bufs["dh_pre"][:M]) @ f(w["fc1_w16"]), t=BF16)
     acc["fc1_w"] = a0["fc1_w"] + f(bufs["dh_pre"]).t() @ f(bufs["ln2"])
     acc["fc1_b"] = a0["fc1_b"] + f(bufs["dh_pre"]).sum(0)
     e = T.ln_bwd_emulate(bufs["x1"], bufs["mean2"], bufs["rstd2"], w["n2w"], bufs["dln2"][:M], dx, a0["n2w"], a0["n2b"])
     bufs["dx1"], acc["n2w"], acc["n2b"] = e["dx"], e["dgamma"], e["dbeta"]
     bufs["g1"] = padded(dp1 * bufs["dx1"], t=BF16)
+    ln_sums = f(bufs["g1"][:M]).sum(0)       # what the LayerNorm backward would add, given a column-sum pointer
+    if dropped:      # site 2
+        kb = site_keep(c, drop, SITE_PROJ, D_, block=drop["block"] + 1) if mutate == "bwd_mask_of_next_block" else keep2
+        bufs["g1"][:M] = _emu_apply(bufs["g1"][:M], kb, s_keep)
     acc["proj_b"] = a0["proj_b"] + (bufs["dx1"] if mutate == "proj_b_from_dx1" else f(bufs["g1"][:M])).sum(0)
+    if mutate == "proj_b_by_layernorm_too":
+        acc["proj_b"] = acc["proj_b"] + ln_sums
     if mutate == "pad_rows_left":
         bufs["g1"][M] = -0.75
     bufs["dattn"] = padded(f(bufs["g1"][:M]) @ f(w["proj_w16"]), t=BF16)
     acc["proj_w"] = a0["proj_w"] + f(bufs["g1"]).t() @ f(bufs["attn_o"])
     add = None if (inp["dqkv_add"] is None or mutate == "dqkv_add_dropped") else inp["dqkv_add"]
     q, k, v, do, ad = A.split_packed(bufs["qkv"], B, N, H, bufs["dattn"], add)
-    ae = A.emulate(q, k, v, w["head_gate"], 0.125, do, ad)
+    ae = A.emulate(q, k, v, w["head_gate"], 0.125, do, ad, **akw)
     bufs["dqkv"] = padded(torch.cat([A.rows(ae[n]) for n in ("dQ", "dK", "dV")], 1), t=BF16)
     bufs["dln1"] = padded(f(bufs["dqkv"][:M]) @ f(w["qkv_w16"]), t=BF16)
     acc["qkv_w"] = a0["qkv_w"] + f(bufs["dqkv"]).t() @ f(bufs["ln1"])
@@ -498,7 +719,7 @@ def emulate(c, inp, mutate=None, route=None):
 def structs(c, adr, flags=None):
     """(devit_block_weights, devit_block_acts, devit_block_wgrads, devit_block_bwd_io) of a case.  adr(name) -> the address that stands for the named
     buffer or None: weights by their field name, 'x', 'dp1', 'dp2', the DEVIT_ACT_* / DEVIT_BWD_* buffers by ACT_NAMES / BWD_NAMES,
-    'g_<accumulator>', 'dx', 'g2', 'dx_in', 'g_prev', 'prev_dp2', 'g_prev_fc2_b', 'dqkv_add'"""
+    'g_<accumulator>', 'dx', 'g2', 'dx_in', 'g_prev', 'prev_dp2', 'g_prev_fc2_b', 'dqkv_add' (and 'tmp', the dropped sequence's fp32 temporary: refused())"""
     from devit_amd import _lib as L
     d = dims(c)
     w = L.BlockWeights()
@@ -539,6 +760,31 @@ def call_bwd(w, a, g, io, c, stream=None):
     return rc, lib.devit_last_error().decode() if rc else ""
 
 
+def drop_struct(drop, tmp):
+    """devit_block_dropout of a description: thr / s of both rates from _drop_model.thr_s, `tmp` the address of the shared fp32 temporary or None"""
+    from devit_amd import _lib as L
+    s = L.BlockDropout()
+    (thr, sk), (thr_a, sk_a) = DM.thr_s(drop["p"]), DM.thr_s(drop["p_attn"])
+    s.seed, s.block, s.thr, s.thr_attn, s.scale_keep, s.scale_keep_attn, s.tmp = drop["seed"], drop["block"], thr, thr_a, sk, sk_a, tmp
+    return s
+
+
+def call_fwd_drop(nblocks, w, a, dr, c, stream=None):
+    """devit_encoder_fwd_drop itself (no raise) -> (return code, message); dr: the devit_block_dropout array (or one struct by reference) or None"""
+    from devit_amd import _lib as L
+    lib = L.load()
+    rc = lib.devit_encoder_fwd_drop(nblocks, w, a, dr, c["B"], c["N"], c["D"], EPS, stream)
+    return rc, lib.devit_last_error().decode() if rc else ""
+
+
+def call_bwd_drop(w, a, g, io, dr, c, stream=None):
+    from devit_amd import _lib as L
+    lib = L.load()
+    ref = lambda s: None if s is None else C.byref(s)                                           # noqa: E731
+    rc = lib.devit_block_bwd_drop(ref(w), ref(a), ref(g), ref(io), ref(dr), c["B"], c["N"], c["D"], EPS, stream)
+    return rc, lib.devit_last_error().decode() if rc else ""
+
+
 def _set(obj, **kw):
     for k, v in kw.items():
         setattr(obj, k, v)
@@ -567,6 +813,18 @@ REFUSALS = [
     ("null_accumulator", "student", lambda c, w, a, g, io: _set(g, proj_b=None), "bwd", ERR_ARG, "null gradient accumulator"),
     ("null_g2", "student", lambda c, w, a, g, io: _set(io, g2=None), "bwd", ERR_ARG, "dx / g2 / dx_in"),
     ("null_io", "student", lambda c, w, a, g, io: None, "bwd_null_io", ERR_ARG, "null argument"),
+    # the _drop entry points ('fwd_drop' / 'bwd_drop'): c["dr"] is the call's devit_block_dropout, (0.1, 0.1) at the case's block, tmp given
+    ("null_dropout_array", "student_drop", lambda c, w, a, g, io: c.update(dr=None), "fwd_drop", ERR_ARG, "null dropout array"),
+    ("null_dropout_bwd", "student_drop", lambda c, w, a, g, io: c.update(dr=None), "bwd_drop", ERR_ARG, "null dropout"),
+    ("drop_without_tmp", "student_drop", lambda c, w, a, g, io: _set(c["dr"], tmp=None), "fwd_drop", ERR_ARG, "p > 0 needs the fp32 temporary"),
+    ("drop_with_att", "student", lambda c, w, a, g, io: None, "fwd_drop", ERR_ARG, "cannot also store the attention-branch output (DEVIT_BLK_ATT)"),
+    ("drop_on_f16", "f16_fwd", lambda c, w, a, g, io: None, "fwd_drop", ERR_ARG, "dropout runs on bf16 blocks"),
+    ("attn_drop_on_f16", "f16_fwd", lambda c, w, a, g, io: _set(c["dr"], thr=0), "fwd_drop", ERR_ARG, "dropout runs on bf16 blocks"),
+    ("drop_block_negative", "student_drop", lambda c, w, a, g, io: _set(c["dr"], block=-1), "fwd_drop", ERR_ARG, "dropout runs on bf16 blocks"),
+    ("drop_block_negative_bwd", "student_drop", lambda c, w, a, g, io: _set(c["dr"], block=-1), "bwd_drop", ERR_ARG, "block -1"),
+    ("attn_drop_block_negative_bwd", "student_drop", lambda c, w, a, g, io: _set(c["dr"], block=-1, thr=0), "bwd_drop", ERR_ARG, "block -1"),
+    ("g2_bias_done_with_drop", "student_drop", lambda c, w, a, g, io: _set(io, g2_bias_done=1), "bwd_drop", ERR_ARG, "g2_bias_done must be 0"),
+    ("drop_on_f16_bwd", "f16_fwd", lambda c, w, a, g, io: _set(a, flags=a.flags | SAVE), "bwd_drop", ERR_ARG, "f16 blocks have no backward"),
 ]
 
 
@@ -575,7 +833,12 @@ def refused(case_name, change, entry, adr):
     from devit_amd import _lib as L
     c = dict(case_named(case_name))
     w, a, g, io = structs(c, adr)
+    c["dr"] = drop_struct(drop_of(c.get("block", 0), 0.1, 0.1), adr("tmp"))
     change(c, w, a, g, io)
+    if entry == "fwd_drop":
+        return call_fwd_drop(1, C.byref(w), C.byref(a), None if c["dr"] is None else C.byref(c["dr"]), c)
+    if entry == "bwd_drop":
+        return call_bwd_drop(w, a, g, io, c["dr"], c)
     if entry == "fwd":
         return call_fwd(1, C.byref(w), C.byref(a), c)
     if entry == "fwd2":
