@@ -32,6 +32,9 @@ ACT_LN1, ACT_MEAN1, ACT_RSTD1, ACT_QKV, ACT_ATTN_O, ACT_LSE, ACT_X1, ACT_ATT, AC
     ACT_X2, ACT_COUNT = range(15)
 BLK_SAVE, BLK_QKV_PAD, BLK_ATT = 1, 2, 4
 BWD_DH_PRE, BWD_DLN2, BWD_DX1, BWD_G1, BWD_DATTN, BWD_DQKV, BWD_DLN1, BWD_LNWS, BWD_COUNT = range(9)
+# the lean last block (devit_tail_*): what it has and the block lacks, behind the block's indices
+TAIL_LN1_TOK, TAIL_Q, TAIL_X_TOK, TAIL_ACT_COUNT = range(ACT_COUNT, ACT_COUNT + 4)
+TAIL_BWD_DKV, TAIL_BWD_DLN1_TOK, TAIL_BWD_COUNT = range(BWD_COUNT, BWD_COUNT + 3)
 
 
 class BlockWeights(C.Structure):
@@ -53,6 +56,15 @@ class BlockBwdIO(C.Structure):
     _fields_ = [("dx", C.c_void_p), ("g2", C.c_void_p), ("dx_in", C.c_void_p), ("g_prev", C.c_void_p),
                 ("prev_dp2", C.c_void_p), ("prev_fc2_b_grad", C.c_void_p), ("g2_bias_done", C.c_int),
                 ("dqkv_add", C.c_void_p), ("ws", C.c_void_p * 8), ("lnws_bytes", C.c_size_t),
+                ("defer_jobs", C.c_void_p), ("defer_count", C.c_void_p)]
+
+
+class TailActs(C.Structure):
+    _fields_ = [("acts", BlockActs), ("ln1_tok", C.c_void_p), ("q", C.c_void_p), ("x_tok", C.c_void_p), ("ntok", C.c_int)]
+
+
+class TailBwdIO(C.Structure):
+    _fields_ = [("dx", C.c_void_p), ("g2", C.c_void_p), ("dx_in", C.c_void_p), ("ws", C.c_void_p * 10), ("lnws_bytes", C.c_size_t),
                 ("defer_jobs", C.c_void_p), ("defer_count", C.c_void_p)]
 
 
@@ -105,10 +117,10 @@ DROP_POS, DROP_ATTN, DROP_PROJ, DROP_HIDDEN, DROP_FC2 = range(5)
 ROUTE_TILE128, ROUTE_TILE256, ROUTE_FULL_ROW, ROUTE_GEMM4 = 1, 3, 4, 5
 
 WGRAD_MAX_JOBS = 48
-ABI_VERSION = 3
+ABI_VERSION = 4
 # devit_abi_struct_size(which) -> the mirror it must equal (checked at load time: an array of stale mirrors is misread silently)
 ABI_STRUCTS = {0: Epilogue, 1: Operand, 2: BlockWeights, 3: BlockWgrads, 4: BlockActs, 5: BlockBwdIO, 6: IndexJob, 7: WgradJob, 8: LaunchInfo, 9: BlockDropout,
-               10: MixSample, 11: OptChunk}
+               10: MixSample, 11: OptChunk, 12: TailActs, 13: TailBwdIO}
 
 
 class DevitError(RuntimeError):
@@ -145,6 +157,11 @@ SIGNATURES = {
     "devit_encoder_fwd": (_I, [_I, C.POINTER(BlockWeights), C.POINTER(BlockActs), _I, _I, _I, _F, _P]),
     "devit_block_bwd": (_I, [C.POINTER(BlockWeights), C.POINTER(BlockActs), C.POINTER(BlockWgrads), C.POINTER(BlockBwdIO),
                              _I, _I, _I, _F, _P]),
+    "devit_tail_acts_sizes": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]),
+    "devit_tail_bwd_sizes": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]),
+    "devit_tail_fwd": (_I, [C.POINTER(BlockWeights), C.POINTER(TailActs), _I, _I, _I, _F, _P]),
+    "devit_tail_bwd": (_I, [C.POINTER(BlockWeights), C.POINTER(TailActs), C.POINTER(BlockWgrads), C.POINTER(TailBwdIO), _I, _I, _I, _F, _P]),
+    "devit_token_rows_copy": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "devit_encoder_fwd_drop": (_I, [_I, C.POINTER(BlockWeights), C.POINTER(BlockActs), C.POINTER(BlockDropout), _I, _I, _I, _F, _P]),
     "devit_block_bwd_drop": (_I, [C.POINTER(BlockWeights), C.POINTER(BlockActs), C.POINTER(BlockWgrads), C.POINTER(BlockBwdIO),
                                   C.POINTER(BlockDropout), _I, _I, _I, _F, _P]),

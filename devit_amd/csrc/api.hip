@@ -38,6 +38,8 @@ extern "C" size_t devit_abi_struct_size(int which) {
     case 9: return sizeof(devit_block_dropout);
     case 10: return sizeof(devit_mix_sample);
     case 11: return sizeof(devit_opt_chunk);
+    case 12: return sizeof(devit_tail_acts);
+    case 13: return sizeof(devit_tail_bwd_io);
     default: return 0;
   }
 }

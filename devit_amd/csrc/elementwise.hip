@@ -205,6 +205,25 @@ __global__ __launch_bounds__(256) void scale_cast_kernel(const float* src, __bf1
   }
 }
 
+// ---- the first ntok rows of every image from one strided matrix into another (devit_token_rows_copy): 16-byte vectors, strides in bytes ----
+struct TokenRowsArgs {
+  const char* src;
+  char* dst;
+  size_t src_image, src_row, dst_image, dst_row;
+  int ntok, vecs;           // vectors per row
+  size_t total;             // B * ntok * vecs
+};
+template <bool ADD>
+__global__ __launch_bounds__(256) void token_rows_copy_kernel(const TokenRowsArgs a) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < a.total; i += (size_t)gridDim.x * 256) {
+    const size_t r = i / a.vecs, b = r / a.ntok;
+    const size_t v = i - r * a.vecs, t = r - b * a.ntok;
+    const f32x4 s = *(const f32x4*)(a.src + b * a.src_image + t * a.src_row + v * 16);
+    f32x4* d = (f32x4*)(a.dst + b * a.dst_image + t * a.dst_row + v * 16);
+    *d = ADD ? *d + s : s;
+  }
+}
+
 // ---- column sums of a bf16 [M][ld] matrix (bias gradients): partial[chunk][N] -------------------------
 __global__ __launch_bounds__(256) void colsum_bf16_kernel(const __bf16* y, int M, int N, int ld, int row_group,
                                                           int row_skip, float* partial) {
@@ -446,6 +465,26 @@ extern "C" int devit_scale_cast_bf16(const float* src, void* dst, const float* r
   DEVIT_CHECK(D % 4 == 0 && M > 0, DEVIT_ERR_SHAPE, "devit_scale_cast_bf16: D %% 4");
   hipLaunchKernelGGL(scale_cast_kernel, dim3(grid_for((size_t)M * D / 4, 4096)), dim3(256), 0, (hipStream_t)stream, src,
                      (__bf16*)dst, rowscale, rows_per_scale, M, D);
+  DEVIT_LAUNCH_CHECK();
+  return DEVIT_OK;
+}
+
+extern "C" int devit_token_rows_copy(const void* src, int src_rows_per_image, int src_ld, void* dst, int dst_rows_per_image, int dst_ld, int B,
+                                     int ntok, int cols, int elem, int add, void* stream) {
+  DEVIT_CHECK(src && dst && (elem == 2 || elem == 4) && (!add || elem == 4), DEVIT_ERR_ARG,
+              "devit_token_rows_copy: null pointer / elem=%d not 2 or 4 / add=%d on 16-bit elements", elem, add);
+  DEVIT_CHECK(B > 0 && ntok > 0 && ntok <= src_rows_per_image && ntok <= dst_rows_per_image && cols > 0 && cols <= src_ld && cols <= dst_ld,
+              DEVIT_ERR_SHAPE, "devit_token_rows_copy: B=%d ntok=%d of %d / %d rows per image, cols=%d of ld %d / %d", B, ntok, src_rows_per_image,
+              dst_rows_per_image, cols, src_ld, dst_ld);
+  const size_t e = (size_t)elem;
+  DEVIT_CHECK((((uintptr_t)src) & 15) == 0 && (((uintptr_t)dst) & 15) == 0 && (src_ld * e) % 16 == 0 && (dst_ld * e) % 16 == 0 && (cols * e) % 16 == 0,
+              DEVIT_ERR_ARG, "devit_token_rows_copy: pointers, leading dimensions (%d, %d) and cols=%d must be whole 16-byte vectors", src_ld, dst_ld, cols);
+  TokenRowsArgs a{(const char*)src, (char*)dst, src_rows_per_image * src_ld * e, src_ld * e, dst_rows_per_image * dst_ld * e, dst_ld * e,
+                  ntok, (int)(cols * e / 16), (size_t)B * ntok * (cols * e / 16)};
+  if (add)
+    hipLaunchKernelGGL(token_rows_copy_kernel<true>, dim3(grid_for(a.total)), dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(token_rows_copy_kernel<false>, dim3(grid_for(a.total)), dim3(256), 0, (hipStream_t)stream, a);
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
 }

@@ -271,7 +271,7 @@ def lean_tail(*models):
     """Forwards of `models` inside this context promise that the caller reads nothing of the LAST block but the class /
     distillation tokens of its output (through 'output' / 'last_tokens'): not its q/k/v (the 'qkv' entry of the last block
     is None; DEKD reads the middle block's, engine.py:91-92), not `head_output` / `neuron_output` of its modules.  The
-    model then runs that block on the token rows only (ops._tail_forward): the reference computes all 198 rows and
+    model then runs that block on the token rows only (devit_tail_fwd): the reference computes all 198 rows and
     keeps two (models/de_vit.py:286-288).  Logits are bit-identical.  engine.distill_forward / evaluate enter it."""
     vits = [m.module if hasattr(m, "module") else m for m in models]
     prev = [getattr(v, "_lean_tail", False) for v in vits]

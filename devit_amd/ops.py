@@ -12,9 +12,9 @@ Layout conventions
     padded to a multiple of 128 with ZERO pad rows (`rows_alloc`): the GEMM tiles are 128 rows tall and
     the weight-gradient GEMMs reduce over the padded row count.
   * residual stream: fp32 [B, N, D]; branch activations / branch gradients: bf16.
-  * the encoder blocks' launch sequence lives in C (csrc/encoder.hip: devit_encoder_fwd / devit_block_bwd) and nowhere else; EncoderFn is
-    that call, the lean tail of the last block and the grouping of the weight gradients.  bench.py's instruments see the launches
-    through the library's launch observer (`observing`), so the instrumented step is the step that runs.
+  * the encoder blocks' launch sequence lives in C (csrc/encoder.hip: devit_encoder_fwd / devit_block_bwd, and devit_tail_fwd / devit_tail_bwd
+    for the lean last block) and nowhere else; EncoderFn is those calls and the grouping of the weight gradients.  bench.py's instruments see
+    the launches through the library's launch observer (`observing`), so the instrumented step is the step that runs.
   * weight gradients are ACCUMULATED straight into `param.grad` (fp32, allocated zero on first use), the
     way DDP "main_grad" fusions do; `backward` returns None for parameters and reports finished blocks
     through `grad_ready` callbacks (devit_amd/ddp.py hooks its bucket all-reduce there).
@@ -514,149 +514,17 @@ class EncoderCfg:
         # blocks whose packed qkv output gets the zeroed overhang rows RelationLossFn reads (None: every block)
         self.qkv_pad_layers = qkv_pad_layers
         # > 0: the caller reads only the first `lean_tokens` rows of every image of the encoder output (the class /
-        # distillation tokens, models/de_vit.py:286-288) and nothing of the last block besides: that block then runs as
-        # _tail_forward / _tail_backward and the output is [B, lean_tokens, D]
+        # distillation tokens, models/de_vit.py:286-288) and nothing of the last block besides: that block then runs on its token rows
+        # (devit_tail_fwd / devit_tail_bwd) and the output is [B, lean_tokens, D]
         self.lean_tokens = lean_tokens
         # dropout p > 0 of a TRAINING forward: None, or (seed, [(p, p_attn) per block]) -- the masks are functions of the seed (dropout.py), so
         # this is all a backward needs to regenerate them
         self.drop = None
 
 
-def scale_cast(dx, rowscale, N):
-    B, _, D = dx.shape
-    M = B * N
-    g = rows_alloc(M, D, BF16, dx.device)
-    call("devit_scale_cast_bf16", ptr(dx), ptr(g), ptr(rowscale), N, M, D, stream_ptr())
-    return g
-
-
 # ----------------------------------------------------------------------------------------------
-# The LAST block when only the class / distillation tokens of its output are read (models/de_vit.py:286-288 takes
-# x[:, 0], x[:, 1] after the final norm, and engine.py:91-92 takes q/k/v of the middle block only): of the last block
-# only K and V are needed on all rows; the Q projection, attention, proj, LN2, fc1 and fc2 run on the B * ntok token
-# rows.  Same kernels and per-row arithmetic as the full block (csrc/encoder.hip), so the token rows -- and the logits -- are bit-identical
-# to the full block's; the reference computes (and then drops) the other 196 rows per image.
-# ----------------------------------------------------------------------------------------------
-def _gather_tok(src2d, B, N, ntok, cols, dtype, dev, pad=True):
-    """Rows (b, t < ntok) of a [B*N (+pad), cols] matrix as a dense [pad_rows(B*ntok), cols] matrix (zero pad rows)."""
-    T = B * ntok
-    out = rows_alloc(T, cols, dtype, dev) if pad else torch.empty((T, cols), dtype=dtype, device=dev)
-    out[:T].view(B, ntok, cols).copy_(src2d[:B * N].view(B, N, cols)[:, :ntok])
-    return out
-
-
-def _tail_forward(x, bp, dp, cfg, need_grad, ntok):
-    """x: fp32 [B, N, D] contiguous (output of the block before the last).  Returns (x2_tok fp32 [B, ntok, D], saved)."""
-    B, N, D = x.shape
-    M, T, H, dev = B * N, B * ntok, bp.num_heads, x.device
-    Da = H * 64                           # attention width (< D when heads were compacted away, shrink.compact)
-    qkv_b = getattr(bp.qkv_b, "value", bp.qkv_b)
-    t16 = 1 if bp.qkv_w16.dtype == F16 else 0
-    dt = F16 if t16 else BF16
-    if t16 and need_grad:
-        raise L.DevitError('precision="f16" is forward-only (frozen teacher): run it under torch.no_grad()')
-    x2 = x.view(M, D)
-    ln1 = rows_alloc(M, D, dt, dev)
-    mean1 = torch.empty(M, dtype=F32, device=dev) if need_grad else None
-    rstd1 = torch.empty(M, dtype=F32, device=dev) if need_grad else None
-    layernorm_fwd(x2, M, D, bp.n1w, bp.n1b, cfg.eps, y_bf16=ln1, mean=mean1, rstd=rstd1, dtype16=t16)
-    kv = rows_alloc(M, 2 * Da, dt, dev)                                  # (K | V) of every row
-    linear_fwd(ln1, bp.qkv_w16[Da:], qkv_b[Da:], M, out=kv, dtype16=t16)
-    ln1_tok = _gather_tok(ln1, B, N, ntok, D, dt, dev)
-    q_tok = rows_alloc(T, Da, dt, dev)                                   # Q of the token rows
-    linear_fwd(ln1_tok, bp.qkv_w16[:Da], qkv_b[:Da], T, out=q_tok, dtype16=t16)
-    attn_o = rows_alloc(T, Da, dt, dev)
-    lse = torch.empty((B, H, ntok), dtype=F32, device=dev) if need_grad else None
-    call("devit_attn_fwd_rows", ptr(q_tok), Da, ptr(kv), 2 * Da, ptr(attn_o), ptr(lse), ptr(bp.head_gate), B, ntok, N, H,
-         64, 0.125, t16, stream_ptr())
-    x_tok = _gather_tok(x2, B, N, ntok, D, F32, dev, pad=False)
-    dp1, dp2 = dp if dp is not None else (None, None)
-    x1 = torch.empty((B, ntok, D), dtype=F32, device=dev)
-    linear_fwd(attn_o, bp.proj_w16, bp.proj_b, T, out=x1.view(T, D), kind=L.EPI_RESIDUAL_F32, res=x_tok, rowscale=dp1,
-               rows_per_scale=ntok, dtype16=t16)
-    ln2 = rows_alloc(T, D, dt, dev)
-    mean2 = torch.empty(T, dtype=F32, device=dev) if need_grad else None
-    rstd2 = torch.empty(T, dtype=F32, device=dev) if need_grad else None
-    layernorm_fwd(x1.view(T, D), T, D, bp.n2w, bp.n2b, cfg.eps, y_bf16=ln2, mean=mean2, rstd=rstd2, dtype16=t16)
-    Hd = bp.fc1_w16.shape[0]
-    h = rows_alloc(T, Hd, dt, dev)
-    h_pre = rows_alloc(T, Hd, dt, dev) if need_grad else None
-    linear_fwd(ln2, bp.fc1_w16, bp.fc1_b, T, out=h, kind=L.EPI_GELU_BF16, colscale=bp.neuron_gate, aux=h_pre,
-               exact_gelu=cfg.exact_gelu, dtype16=t16)
-    x2o = torch.empty((B, ntok, D), dtype=F32, device=dev)
-    linear_fwd(h, bp.fc2_w16, bp.fc2_b, T, out=x2o.view(T, D), kind=L.EPI_RESIDUAL_F32, res=x1.view(T, D), rowscale=dp2,
-               rows_per_scale=ntok, dtype16=t16)
-    if getattr(bp, "module", None) is not None:
-        # the shrink contract's debug views (models/de_vit.py:41,77) of THIS block are not produced on the lean path: drop the ones an
-        # earlier full forward left, so a ranking pass run inside lean_tail fails loudly instead of reading stale activations (and the
-        # arena they kept alive is released)
-        bp.module.mlp.neuron_output = None
-        bp.module.attn.head_output = None
-    s = None
-    if need_grad:
-        s = dict(x=x, ln1=ln1, mean1=mean1, rstd1=rstd1, kv=kv, ln1_tok=ln1_tok, q_tok=q_tok, attn_o=attn_o, lse=lse,
-                 x1=x1, ln2=ln2, mean2=mean2, rstd2=rstd2, h=h, h_pre=h_pre, dp1=dp1, dp2=dp2, ntok=ntok)
-    return x2o, s
-
-
-def _tail_backward(dx, s, bp, cfg, defer=None):
-    """dx: fp32 [B, ntok, D] gradient of _tail_forward's output.  Returns the fp32 [B, N, D] gradient of its input.
-    Every product that the full block's backward forms from the 196 untouched rows per image is an exact zero there (their
-    output gradient is zero), so the sums here hold the same terms; the token rows of dln1 are produced by one K = 3D GEMM
-    like the full path's (one rounding), the other rows by the K = 2D GEMM over (dK | dV) -- the same sum without its zeros."""
-    ntok = s["ntok"]
-    x = s["x"]
-    B, N, D = x.shape
-    M, T, H, dev = B * N, B * ntok, bp.num_heads, x.device
-    Hd = bp.fc1_w.shape[0]
-    Da = H * 64
-    dx = dx.contiguous()
-    g2 = scale_cast(dx, s["dp2"], ntok)
-    # ---- MLP branch on the token rows
-    linear_wgrad(g2, s["h"], grad_buf(bp.fc2_w), grad_buf(bp.fc2_b), T)
-    dh_pre = rows_alloc(T, Hd, BF16, dev)
-    linear_dgrad(g2, bp.fc2_w16, T, out=dh_pre, kind=L.EPI_DGELU_BF16, colscale=bp.neuron_gate, aux_in=s["h_pre"],
-                 exact_gelu=cfg.exact_gelu)
-    dln2 = rows_alloc(T, D, BF16, dev)
-    linear_dgrad(dh_pre, bp.fc1_w16, T, out=dln2)
-    linear_wgrad(dh_pre, s["ln2"], grad_buf(bp.fc1_w), grad_buf(bp.fc1_b), T)
-    dx1 = torch.empty((B, ntok, D), dtype=F32, device=dev)
-    g1 = rows_alloc(T, D, BF16, dev)
-    layernorm_bwd(dln2, False, s["x1"].view(T, D), T, D, s["mean2"], s["rstd2"], bp.n2w, dx.view(T, D), dx1.view(T, D),
-                  g1, s["dp1"], ntok, grad_buf(bp.n2w), grad_buf(bp.n2b), gsum=grad_buf(bp.proj_b))
-    # ---- attention branch: dO on the token rows; dQ there, dK / dV on every row
-    dattn = rows_alloc(T, Da, BF16, dev)
-    linear_dgrad(g1, bp.proj_w16, T, out=dattn)
-    linear_wgrad(g1, s["attn_o"], grad_buf(bp.proj_w), None, T)
-    dqkv_tok = rows_alloc(T, 3 * Da, BF16, dev)                          # (dQ | dK | dV) of the token rows
-    dkv = rows_alloc(M, 2 * Da, BF16, dev)
-    call("devit_attn_bwd_rows", ptr(s["q_tok"]), Da, ptr(s["kv"]), 2 * Da, ptr(s["attn_o"]), ptr(dattn), ptr(s["lse"]),
-         ptr(bp.head_gate), ptr(dqkv_tok), 3 * Da, ptr(dkv), 2 * Da, B, ntok, N, H, 64, 0.125, stream_ptr())
-    dqkv_tok[:T].view(B, ntok, 3 * Da)[:, :, Da:].copy_(dkv[:M].view(B, N, 2 * Da)[:, :ntok])
-    dln1 = rows_alloc(M, D, BF16, dev)
-    linear_dgrad(dkv, bp.qkv_w16[Da:], M, out=dln1)
-    dln1_tok = rows_alloc(T, D, BF16, dev)
-    linear_dgrad(dqkv_tok, bp.qkv_w16, T, out=dln1_tok)
-    dln1[:M].view(B, N, D)[:, :ntok].copy_(dln1_tok[:T].view(B, ntok, D))
-    gw, gb = grad_buf(bp.qkv_w), grad_buf(bp.qkv_b)
-    # the one product of this block that reduces over ALL rows (dK | dV against ln1) can ride the encoder's grouped weight-gradient launch
-    # (defer: a DeferredWgrads whose single group is launched behind block 0 -- the caller then reports this block with that group)
-    j = wgrad_job_struct(dkv, s["ln1"], gw[Da:], gb[Da:]) if (defer is not None and wgrad_enabled(pad_rows(M))) else None
-    if j is None:
-        linear_wgrad(dkv, s["ln1"], gw[Da:], gb[Da:], M)
-    linear_wgrad(dqkv_tok[:, :Da], s["ln1_tok"], gw[:Da], gb[:Da], T)
-    if defer is not None:
-        defer.add(bp, [j] if j is not None else [], (dkv, s["ln1"], gw, gb))
-    dx0 = torch.empty((B, N, D), dtype=F32, device=dev)
-    layernorm_bwd(dln1, False, x.view(M, D), M, D, s["mean1"], s["rstd1"], bp.n1w, None, dx0.view(M, D), None, None, 0,
-                  grad_buf(bp.n1w), grad_buf(bp.n1b))
-    dx0[:, :ntok] += dx1                                                   # the residual path exists on the token rows only
-    return dx0
-
-
-# ----------------------------------------------------------------------------------------------
-# whole blocks per ctypes call (devit_encoder_fwd / devit_block_bwd, csrc/encoder.hip): the ONE host sequence of the 16-bit block --
-# there is no restatement of it here.  One arena per block of an encoder call holds its activations; the instruments above see its
+# whole blocks per ctypes call (devit_encoder_fwd / devit_block_bwd, devit_tail_fwd / devit_tail_bwd; csrc/encoder.hip): the ONE host sequence
+# of the 16-bit block -- there is no restatement of it here.  One arena per block of an encoder call holds its activations; the instruments above see its
 # launches through the library's observer.
 # ----------------------------------------------------------------------------------------------
 # Stream whose allocator pool the encoder arenas come from (None: the current stream).  A forward that runs on a side
@@ -678,18 +546,23 @@ _ACT_DT = {L.ACT_LN1: BF16, L.ACT_QKV: BF16, L.ACT_ATTN_O: BF16, L.ACT_ATT: BF16
            L.ACT_H_PRE: BF16}
 
 
-def _act_sizes(B, N, D, Da, Hd, flags):
-    key = ("a", B, N, D, Da, Hd, flags)
+def _sizes(name, count, *args):
+    """One of the library's sizes functions -> (sizes, their byte offsets in one allocation, total), cached."""
+    key = (name,) + args
     v = _sizes_cache.get(key)
     if v is None:
-        sz = (C.c_size_t * L.ACT_COUNT)()
-        call("devit_block_acts_sizes", B, N, D, Da, Hd, flags, sz)
+        sz = (C.c_size_t * count)()
+        call(name, *args, sz)
         offs, off = [], 0
         for n in sz:
             offs.append(off)
             off += n
         v = _sizes_cache[key] = (list(sz), offs, off)
     return v
+
+
+def _act_sizes(B, N, D, Da, Hd, flags):
+    return _sizes("devit_block_acts_sizes", L.ACT_COUNT, B, N, D, Da, Hd, flags)
 
 
 def _bwd_sizes(B, N, D, widths):
@@ -910,6 +783,76 @@ def _encoder_backward_composite(run, cfg, dx, dqkvs, defer, dencs=None):
     return ws[o:o + dxb].view(F32).view(B, N, D)
 
 
+# ----------------------------------------------------------------------------------------------
+# The LAST block when only the class / distillation tokens of its output are read (models/de_vit.py:286-288 takes x[:, 0], x[:, 1] after the
+# final norm, and engine.py:91-92 takes q/k/v of the middle block only): one call each way (devit_tail_fwd / devit_tail_bwd, include/devit_hip.h).
+# Of the last block only K and V are needed on all rows; everything else runs on the B * ntok token rows, the branch half through the block's own
+# host sequence -- so the token rows, and the logits, are bit-identical to the full block's; the reference computes (and then drops) the other
+# 196 rows per image.
+# ----------------------------------------------------------------------------------------------
+class _TailRun:
+    """What the lean last block's forward leaves behind for its backward: the structs and the arena they point into."""
+    __slots__ = ("weights", "acts", "arena", "x", "dims")
+
+
+def _tail_forward_composite(x, bp, dp, cfg, need_grad, ntok):
+    """x: fp32 [B, N, D] contiguous (output of the block before the last).  Returns (x2_tok fp32 [B, ntok, D], a view of the call's arena; the
+    _TailRun).  One arena from _arena(): in a side-stream forward it lives in the consumer's pool like the body blocks' (ARENA_ALLOC_STREAM) and
+    must stay referenced until the consumer has joined (EncoderFn.forward hangs it on the last body block's qkv view)."""
+    B, N, D = x.shape
+    run = _TailRun()
+    w = run.weights = _weights_struct(bp)
+    if w.dtype16 and need_grad:
+        raise L.DevitError('precision="f16" is forward-only (frozen teacher): run it under torch.no_grad()')
+    flags = L.BLK_SAVE if need_grad else 0
+    sz, offs, tot = _sizes("devit_tail_acts_sizes", L.TAIL_ACT_COUNT, B, N, ntok, D, w.attn_width, w.hidden, flags)
+    run.arena, run.x, run.dims = _arena(tot, x.device), x, (B, N, D)
+    base = run.arena.data_ptr()
+    t = run.acts = L.TailActs()
+    t.acts.x, t.acts.flags, t.ntok = x.data_ptr(), flags, ntok
+    for j in range(L.ACT_COUNT):
+        t.acts.buf[j] = base + offs[j] if sz[j] else None
+    t.ln1_tok, t.q, t.x_tok = (base + offs[j] for j in (L.TAIL_LN1_TOK, L.TAIL_Q, L.TAIL_X_TOK))
+    t.acts.dp1, t.acts.dp2 = (_p(dp[0]), _p(dp[1])) if dp is not None else (None, None)
+    call("devit_tail_fwd", C.byref(w), C.byref(t), B, N, D, cfg.eps, stream_ptr())
+    if getattr(bp, "module", None) is not None:
+        # the shrink contract's debug views (models/de_vit.py:41,77) of THIS block are not produced on the lean path: drop the ones an
+        # earlier full forward left, so a ranking pass run inside lean_tail fails loudly instead of reading stale activations (and the
+        # arena they kept alive is released)
+        bp.module.mlp.neuron_output = None
+        bp.module.attn.head_output = None
+    o = offs[L.ACT_X2]
+    return run.arena[o:o + B * ntok * D * 4].view(F32).view(B, ntok, D), run
+
+
+def _tail_backward_composite(run, bp, cfg, dx, defer=None):
+    """dx: fp32 [B, ntok, D] gradient of _tail_forward_composite's output.  Returns the fp32 [B, N, D] gradient of its input, a view of the call's
+    workspace.  defer: a DeferredWgrads whose single group is launched behind block 0 -- the one product of this block that reduces over ALL rows
+    (dK | dV against ln1) then rides that launch as a job, and the caller reports this block with that group."""
+    B, N, D = run.dims
+    w, ntok = run.weights, run.acts.ntok
+    T, M = B * ntok, B * N
+    sz, offs, tot = _sizes("devit_tail_bwd_sizes", L.TAIL_BWD_COUNT, B, N, ntok, D, w.attn_width, w.hidden)
+    gb = (pad_rows(T) * D * 2 + 255) // 256 * 256
+    ws = torch.empty(tot + gb + M * D * 4, dtype=torch.uint8, device=dx.device)        # transients, g2 = bf16(dp2 * dx), dx_in
+    base = ws.data_ptr()
+    dx = dx.contiguous()
+    call("devit_scale_cast_bf16", ptr(dx), C.c_void_p(base + tot), C.c_void_p(run.acts.acts.dp2), ntok, T, D, stream_ptr())
+    io = L.TailBwdIO()
+    io.dx, io.g2, io.dx_in, io.lnws_bytes = dx.data_ptr(), base + tot, base + tot + gb, sz[L.BWD_LNWS]
+    for j in range(L.TAIL_BWD_COUNT):
+        io.ws[j] = base + offs[j]
+    got, ngot = L.WgradJob(), C.c_int(0)
+    if defer is not None:
+        io.defer_jobs, io.defer_count = C.addressof(got), C.addressof(ngot)
+    wg = _wgrads_struct(bp)
+    call("devit_tail_bwd", C.byref(w), C.byref(run.acts), C.byref(wg), C.byref(io), B, N, D, cfg.eps, stream_ptr())
+    if defer is not None:      # (the job reads DKV of the workspace and LN1 of the arena: both stay until the group is launched)
+        defer.add(bp, [L.WgradJob.from_buffer_copy(got)] if ngot.value else [], (ws, run.arena, grad_buf(bp.qkv_w), grad_buf(bp.qkv_b)))
+    o = tot + gb
+    return ws[o:o + M * D * 4].view(F32).view(B, N, D)
+
+
 class EncoderFn(torch.autograd.Function):
     """x -> blocks[0..n) -> (x_out, [qkv_i bf16 packed ...], [att_i ...], [enc_i ...])."""
 
@@ -945,7 +888,10 @@ class EncoderFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         xo = run.views[-1]["x2"]
         if lean:
-            xo, ctx.tail = _tail_forward(xo, cfg.blocks[-1], dp_last, cfg, need_grad, lean)
+            xo, tail = _tail_forward_composite(xo, cfg.blocks[-1], dp_last, cfg, need_grad, lean)
+            ctx.tail = tail if need_grad else None
+            if ARENA_ALLOC_STREAM is not None and qkvs:      # a side-stream forward's arenas stay referenced by the returned dict until the consumer
+                qkvs[-1]._devit_tail_arena = tail.arena       # has joined: this block hands out no view of its own to hold its arena
         return (xo,) + tuple(qkvs) + tuple(atts) + tuple(encs)
 
     @staticmethod
@@ -964,13 +910,13 @@ class EncoderFn(torch.autograd.Function):
             tail, ctx.tail = ctx.tail, None
             last = cfg.blocks[-1]
             if dx is None:
-                dx = torch.zeros_like(tail["x1"])
+                dx = torch.zeros((tail.dims[0], tail.acts.ntok, tail.dims[2]), dtype=F32, device=tail.x.device)
             nb -= 1
             defer = DeferredWgrads(cfg, nb)
             if defer.policy == "all":          # (no exchange to overlap: the last block is reported with the one group)
-                dx = _tail_backward(dx, tail, last, cfg, defer)
+                dx = _tail_backward_composite(tail, last, cfg, dx, defer)
             else:
-                dx = _tail_backward(dx, tail, last, cfg)
+                dx = _tail_backward_composite(tail, last, cfg, dx)
                 last.finish_grads()
                 if cfg.grad_ready is not None:
                     cfg.grad_ready(last.all_params())
@@ -1323,7 +1269,9 @@ class HeadsFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dtok, dlo=None, dlk=None):
-        x, tok, mean, rstd = ctx.save
+        # (released here, like EncoderFn's: `tok` is an output of this node, so ctx.save is a reference cycle that only the garbage collector would
+        # free -- and x, a view of the lean last block's arena, would keep that arena allocated until then)
+        (x, tok, mean, rstd), ctx.save = ctx.save, None
         norm_w, norm_b, head_w, head_b, headd_w, headd_b = ctx.params
         B, T, D, ntok, eps, grad_ready = ctx.meta
         dev = x.device

@@ -27,7 +27,9 @@ extern "C" {
  * only (the library is built with -fvisibility=hidden).  A binding asks devit_version() AND checks its struct sizes against
  * devit_abi_struct_size() before it passes arrays of structs (devit_encoder_fwd strides by sizeof(devit_block_weights)). */
 /* 3: devit_set_launch_observer. */
-#define DEVIT_ABI_VERSION 3
+/* 4: the lean last block per call (devit_tail_fwd / devit_tail_bwd, their two sizes functions, devit_tail_acts, devit_tail_bwd_io) and
+ * devit_token_rows_copy. */
+#define DEVIT_ABI_VERSION 4
 #define DEVIT_API __attribute__((visibility("default")))
 
 enum {
@@ -44,7 +46,7 @@ DEVIT_API const char* devit_last_error(void); /* host string, thread-local, vali
 DEVIT_API int devit_check_device(int dev);
 /* sizeof() of the ABI's structs as THIS library was compiled (which: 0 devit_epilogue, 1 devit_operand, 2 devit_block_weights,
  * 3 devit_block_wgrads, 4 devit_block_acts, 5 devit_block_bwd_io, 6 devit_index_job, 7 devit_wgrad_job, 8 devit_launch_info, 9 devit_block_dropout,
- * 10 devit_mix_sample, 11 devit_opt_chunk; anything else: 0).  A binding
+ * 10 devit_mix_sample, 11 devit_opt_chunk, 12 devit_tail_acts, 13 devit_tail_bwd_io; anything else: 0).  A binding
  * compares them with its own mirrors once at load time: a stale mirror of a struct that is passed as an ARRAY would otherwise be misread
  * from its second element on, with no error. */
 DEVIT_API size_t devit_abi_struct_size(int which);
@@ -406,6 +408,61 @@ DEVIT_API int devit_encoder_fwd(int nblocks, const devit_block_weights* w, const
  * (read per call) keeps every launch on `stream`; a device index >= 16 does the same.  Worth +0.9 % on the DEKD step (profiles/r04_h_*). */
 DEVIT_API int devit_block_bwd(const devit_block_weights* w, const devit_block_acts* acts, const devit_block_wgrads* grads,
                     const devit_block_bwd_io* io, int B, int N, int D, float eps, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The lean last block per call: the caller reads only the first ntok rows of every image of the block's output (the class / distillation
+ * tokens, models/de_vit.py:286-288).  LN1 and the K and V projections run on all M = B * N rows; the Q projection, attention
+ * (devit_attn_fwd_rows) and everything from proj on -- the SAME host sequence as the block's, csrc/encoder.hip: branch_fwd / branch_bwd -- on
+ * the T = B * ntok token rows, ntok rows per DropPath scale.  Same kernels and per-row arithmetic as devit_encoder_fwd, so the token rows of
+ * the output are bit-identical to the block's.  All launches go to `stream`; nothing is allocated, nothing synchronises.
+ *
+ *   devit_tail_acts  : acts.x is the block's fp32 [M][D] input and acts.buf[] the block's buffers with these extents (sizes from
+ *                      devit_tail_acts_sizes, index DEVIT_ACT_* / DEVIT_TAIL_*; Mp = pad_rows(M), Tp = pad_rows(T)):
+ *                        LN1 16-bit [Mp][D], MEAN1 / RSTD1 [M]        QKV: (K | V) 16-bit [Mp][2 attn_width]
+ *                        ATTN_O 16-bit [Tp][attn_width], LSE [B][heads][ntok]      X1, X2 fp32 [T][D]     LN2 16-bit [Tp][D], MEAN2 / RSTD2 [T]
+ *                        H, H_PRE 16-bit [Tp][hidden]                 ATT: unused (size 0)
+ *                      and what the block has no place for: ln1_tok 16-bit [Tp][D] (the token rows of LN1), q 16-bit [Tp][attn_width],
+ *                      x_tok fp32 [T][D] (the token rows of x).  acts.flags: DEVIT_BLK_SAVE or 0.  The output is buf[DEVIT_ACT_X2].
+ *                      Pad rows of every 16-bit row buffer are zeroed by the forward.
+ *   devit_tail_bwd   : io->dx = d loss / d x2 fp32 [T][D], io->g2 = bf16(dp2 * dx) in the first T of its Tp rows; produces io->dx_in fp32 [M][D].
+ *                      Transients from devit_tail_bwd_sizes (index DEVIT_BWD_* / DEVIT_TAIL_BWD_*): the block's on Tp rows -- DQKV is
+ *                      (dQ | dK | dV) of the token rows -- except DLN1 [Mp][D] and LNWS (for M rows); DKV 16-bit [Mp][2 attn_width],
+ *                      DLN1_TOK 16-bit [Tp][D].  Weight gradients are accumulated by split-K launches on `stream`.  io->defer_jobs (a HOST
+ *                      array of >= 1 entry) not NULL: the one product that reduces over all rows, (dK | dV)^T ln1, is written there as a job
+ *                      for a later devit_wgrad_grouped(..., K = Mp, ...) call where the full-row weight-gradient kernel takes it (D == 384,
+ *                      DEVIT_WGRADFR not 0) instead of being launched; the caller then keeps DKV and LN1 alive until that launch.
+ * ---------------------------------------------------------------------------------------- */
+enum { DEVIT_TAIL_LN1_TOK = DEVIT_ACT_COUNT, DEVIT_TAIL_Q, DEVIT_TAIL_X_TOK, DEVIT_TAIL_ACT_COUNT };
+typedef struct {
+  devit_block_acts acts;
+  void *ln1_tok, *q;
+  float* x_tok;
+  int ntok;                /* 0 < ntok <= N */
+} devit_tail_acts;
+
+enum { DEVIT_TAIL_BWD_DKV = DEVIT_BWD_COUNT, DEVIT_TAIL_BWD_DLN1_TOK, DEVIT_TAIL_BWD_COUNT };
+typedef struct {
+  const float* dx;         /* in: fp32 [T][D] */
+  void* g2;                /* in: bf16 [pad_rows(T)][D]; its rows >= T are zeroed by the call */
+  float* dx_in;            /* out: fp32 [M][D] */
+  void* ws[DEVIT_TAIL_BWD_COUNT];
+  size_t lnws_bytes;
+  devit_wgrad_job* defer_jobs;
+  int* defer_count;        /* out: jobs written (0 or 1) */
+} devit_tail_bwd_io;
+
+DEVIT_API int devit_tail_acts_sizes(int B, int N, int ntok, int D, int attn_width, int hidden, int flags, size_t* sizes /* [DEVIT_TAIL_ACT_COUNT] */);
+DEVIT_API int devit_tail_bwd_sizes(int B, int N, int ntok, int D, int attn_width, int hidden, size_t* sizes /* [DEVIT_TAIL_BWD_COUNT] */);
+DEVIT_API int devit_tail_fwd(const devit_block_weights* w, const devit_tail_acts* acts, int B, int N, int D, float eps, void* stream);
+DEVIT_API int devit_tail_bwd(const devit_block_weights* w, const devit_tail_acts* acts, const devit_block_wgrads* grads,
+                   const devit_tail_bwd_io* io, int B, int N, int D, float eps, void* stream);
+
+/* The first ntok rows of every image, from one strided matrix into another (the lean last block's gathers and scatters):
+ *   dst[(b * dst_rows_per_image + t) * dst_ld + c]  =  (or, add != 0, +=)  src[(b * src_rows_per_image + t) * src_ld + c],   b < B, t < ntok, c < cols
+ * elem: bytes per element, 2 or 4; add needs 4 (fp32).  Leading dimensions in elements.  Moves 16-byte vectors: pointers, leading dimensions and
+ * cols must be whole multiples of 16 bytes (DEVIT_ERR_ARG otherwise).  Source and destination must not overlap. */
+DEVIT_API int devit_token_rows_copy(const void* src, int src_rows_per_image, int src_ld, void* dst, int dst_rows_per_image, int dst_ld, int B,
+                          int ntok, int cols, int elem, int add, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Index copies of physically shrunk (compacted) blocks that are being TRAINED (distill_sub.py:384-401 trains the gated

@@ -828,10 +828,117 @@ REFUSALS = [
 ]
 
 
+# ---- the lean last block (devit_tail_fwd / devit_tail_bwd, include/devit_hip.h): the block's buffers on T = B ntok rows from the attention output
+# on, (K | V) in the qkv slot, and three buffers of its own; the backward's transients likewise, with two of its own
+TAIL_ACT_NAMES = ACT_NAMES + ("ln1_tok", "q", "x_tok")
+TAIL_BWD_NAMES = BWD_NAMES + ("dkv", "dln1_tok")
+# (B, N, ntok, D, attn_width, hidden): one row tile, the student's last block, a compacted one
+TAIL_SIZE_CASES = ((3, 5, 1, 128, 128, 128), (2, 198, 2, 384, 384, 1536), (2, 198, 2, 384, 256, 1024))
+
+
+def tail_extents(B, N, ntok, D, Da, Hd, save):
+    """(bytes per devit_tail_acts buffer, bytes per devit_tail_bwd transient) as the header words them"""
+    M, Tr = B * N, B * ntok
+    Mp, Tp = pad_rows(M), pad_rows(Tr)
+    acts = dict(ln1=Mp * D * 2, mean1=M * 4 * save, rstd1=M * 4 * save, qkv=Mp * 2 * Da * 2, attn_o=Tp * Da * 2, lse=B * (Da // 64) * ntok * 4 * save,
+                x1=Tr * D * 4, att=0, ln2=Tp * D * 2, mean2=Tr * 4 * save, rstd2=Tr * 4 * save, h=Tp * Hd * 2, h_pre=Tp * Hd * 2 * save, x2=Tr * D * 4,
+                ln1_tok=Tp * D * 2, q=Tp * Da * 2, x_tok=Tr * D * 4)
+    bwd = dict(dh_pre=Tp * Hd * 2, dln2=Tp * D * 2, dx1=Tr * D * 4, g1=Tp * D * 2, dattn=Tp * Da * 2, dqkv=Tp * 3 * Da * 2, dln1=Mp * D * 2,
+               lnws=T.ln_bwd_grid(M) * 3 * D * 4, dkv=Mp * 2 * Da * 2, dln1_tok=Tp * D * 2)
+    return acts, bwd
+
+
+def tail_library_sizes(B, N, ntok, D, Da, Hd, flags):
+    from devit_amd import _lib as L
+    sa, sb = (C.c_size_t * len(TAIL_ACT_NAMES))(), (C.c_size_t * len(TAIL_BWD_NAMES))()
+    L.call("devit_tail_acts_sizes", B, N, ntok, D, Da, Hd, flags, sa)
+    L.call("devit_tail_bwd_sizes", B, N, ntok, D, Da, Hd, sb)
+    return dict(zip(TAIL_ACT_NAMES, sa)), dict(zip(TAIL_BWD_NAMES, sb))
+
+
+def tail_structs(c, adr, ntok=2):
+    """(devit_block_weights, devit_tail_acts, devit_block_wgrads, devit_tail_bwd_io) of a case, addresses as for structs()"""
+    from devit_amd import _lib as L
+    w, a, g, _ = structs(c, adr, flags=c["flags"] & SAVE)
+    t = L.TailActs()
+    t.acts = a
+    t.acts.buf[ACT_NAMES.index("att")] = None
+    t.ln1_tok, t.q, t.x_tok, t.ntok = adr("ln1_tok"), adr("q"), adr("x_tok"), ntok
+    io = L.TailBwdIO()
+    io.dx, io.g2, io.dx_in, io.lnws_bytes = adr("dx"), adr("g2"), adr("dx_in"), 0
+    for i, n in enumerate(TAIL_BWD_NAMES):
+        io.ws[i] = adr(n)
+    io.defer_jobs = io.defer_count = None
+    return w, t, g, io
+
+
+# as REFUSALS, for 'tail_fwd' / 'tail_bwd' (`a` is the devit_tail_acts, `io` the devit_tail_bwd_io) and 'copy' (c["copy"]: the arguments of
+# devit_token_rows_copy behind the two pointers, by name).  Every one in front of the first launch, the memsets included.
+TAIL_REFUSALS = [
+    ("tail_null_acts", "student", lambda c, w, a, g, io: c.update(null="a"), "tail_fwd", ERR_ARG, "null argument"),
+    ("tail_N_209", "student", lambda c, w, a, g, io: c.update(N=209), "tail_fwd", ERR_SHAPE, "N=209"),
+    ("tail_D_320", "student", lambda c, w, a, g, io: c.update(D=320), "tail_fwd", ERR_SHAPE, "D=320"),
+    ("tail_heads", "student", lambda c, w, a, g, io: _set(w, num_heads=5), "tail_fwd", ERR_SHAPE, "heads 5 * 64"),
+    ("tail_ntok_0", "student", lambda c, w, a, g, io: _set(a, ntok=0), "tail_fwd", ERR_SHAPE, "ntok=0"),
+    ("tail_ntok_above_N", "student", lambda c, w, a, g, io: _set(a, ntok=199), "tail_fwd", ERR_SHAPE, "ntok=199 of N=198"),
+    ("tail_flag_att", "student", lambda c, w, a, g, io: _set(a.acts, flags=SAVE | ATT), "tail_fwd", ERR_ARG, "DEVIT_BLK_SAVE is the only one"),
+    ("tail_f16_with_save", "f16_fwd", lambda c, w, a, g, io: _set(a.acts, flags=SAVE), "tail_fwd", ERR_ARG, "f16 is the frozen-teacher forward"),
+    ("tail_null_block_buffer", "student", lambda c, w, a, g, io: _null_buf(a.acts.buf, ACT_NAMES.index("ln2")), "tail_fwd", ERR_ARG, "null activation buffer"),
+    ("tail_null_q", "student", lambda c, w, a, g, io: _set(a, q=None), "tail_fwd", ERR_ARG, "null activation buffer"),
+    ("tail_null_x_tok", "student", lambda c, w, a, g, io: _set(a, x_tok=None), "tail_fwd", ERR_ARG, "null activation buffer"),
+    ("tail_null_saved_buffer", "student", lambda c, w, a, g, io: _null_buf(a.acts.buf, ACT_NAMES.index("rstd2")), "tail_fwd", ERR_ARG, "DEVIT_BLK_SAVE needs"),
+    ("tail_bwd_null_io", "student", lambda c, w, a, g, io: c.update(null="io"), "tail_bwd", ERR_ARG, "null argument"),
+    ("tail_bwd_N_209", "student", lambda c, w, a, g, io: c.update(N=209), "tail_bwd", ERR_SHAPE, "N=209"),
+    ("tail_bwd_heads", "student", lambda c, w, a, g, io: _set(w, num_heads=5), "tail_bwd", ERR_SHAPE, "heads 5 * 64"),
+    ("tail_bwd_ntok_above_N", "student", lambda c, w, a, g, io: _set(a, ntok=199), "tail_bwd", ERR_SHAPE, "ntok=199 of N=198"),
+    ("tail_bwd_without_save", "student", lambda c, w, a, g, io: _set(a.acts, flags=0), "tail_bwd", ERR_ARG, "without DEVIT_BLK_SAVE"),
+    ("tail_bwd_f16", "f16_fwd", lambda c, w, a, g, io: _set(a.acts, flags=SAVE), "tail_bwd", ERR_ARG, "f16 blocks have no backward"),
+    ("tail_bwd_null_accumulator", "student", lambda c, w, a, g, io: _set(g, qkv_b=None), "tail_bwd", ERR_ARG, "null gradient accumulator"),
+    ("tail_bwd_null_dx_in", "student", lambda c, w, a, g, io: _set(io, dx_in=None), "tail_bwd", ERR_ARG, "dx / g2 / dx_in"),
+    ("tail_bwd_null_dkv", "student", lambda c, w, a, g, io: _null_buf(io.ws, TAIL_BWD_NAMES.index("dkv")), "tail_bwd", ERR_ARG, "workspace 8 is null"),
+    ("tail_bwd_null_dattn", "student", lambda c, w, a, g, io: _null_buf(io.ws, TAIL_BWD_NAMES.index("dattn")), "tail_bwd", ERR_ARG, "workspace 4 is null"),
+    ("copy_null_src", "student", lambda c, w, a, g, io: c["copy"].update(src=None), "copy", ERR_ARG, "null pointer"),
+    ("copy_elem_3", "student", lambda c, w, a, g, io: c["copy"].update(elem=3), "copy", ERR_ARG, "elem=3"),
+    ("copy_add_16_bit", "student", lambda c, w, a, g, io: c["copy"].update(add=1), "copy", ERR_ARG, "add=1 on 16-bit"),
+    ("copy_unaligned_src", "student", lambda c, w, a, g, io: c["copy"].update(src=c["copy"]["src"] + 8), "copy", ERR_ARG, "whole 16-byte vectors"),
+    ("copy_unaligned_dst", "student", lambda c, w, a, g, io: c["copy"].update(dst=c["copy"]["dst"] + 2), "copy", ERR_ARG, "whole 16-byte vectors"),
+    ("copy_unaligned_src_ld", "student", lambda c, w, a, g, io: c["copy"].update(src_ld=388), "copy", ERR_ARG, "whole 16-byte vectors"),
+    ("copy_unaligned_dst_ld", "student", lambda c, w, a, g, io: c["copy"].update(dst_ld=1156), "copy", ERR_ARG, "whole 16-byte vectors"),
+    ("copy_cols_not_whole_vectors", "student", lambda c, w, a, g, io: c["copy"].update(cols=380), "copy", ERR_ARG, "whole 16-byte vectors"),
+    ("copy_ntok_above_rows", "student", lambda c, w, a, g, io: c["copy"].update(ntok=3), "copy", ERR_SHAPE, "ntok=3"),
+    ("copy_cols_above_ld", "student", lambda c, w, a, g, io: c["copy"].update(cols=392), "copy", ERR_SHAPE, "cols=392"),
+]
+REFUSALS += TAIL_REFUSALS
+
+
+def _refused_tail(c, change, entry, adr0):
+    from devit_amd import _lib as L
+    lib = L.load()
+    # (the lean block's own buffers stand at block buffers of the same kind: a refused call touches none of them)
+    stand_in = dict(ln1_tok="ln2", q="attn_o", x_tok="x1", dkv="dqkv", dln1_tok="dln2")
+    adr = lambda n: adr0(stand_in.get(n, n))                                                    # noqa: E731
+    w, t, g, io = tail_structs(c, adr)
+    c["copy"] = dict(src=adr("x"), src_rows_per_image=198, src_ld=384, dst=adr("x_tok"), dst_rows_per_image=2, dst_ld=1152, B=2, ntok=2, cols=384,
+                     elem=2, add=0)
+    change(c, w, t, g, io)
+    ref = lambda s, n: None if c.get("null") == n else C.byref(s)                               # noqa: E731
+    if entry == "tail_fwd":
+        rc = lib.devit_tail_fwd(ref(w, "w"), ref(t, "a"), c["B"], c["N"], c["D"], EPS, None)
+    elif entry == "tail_bwd":
+        rc = lib.devit_tail_bwd(ref(w, "w"), ref(t, "a"), ref(g, "g"), ref(io, "io"), c["B"], c["N"], c["D"], EPS, None)
+    else:
+        k = c["copy"]
+        rc = lib.devit_token_rows_copy(k["src"], k["src_rows_per_image"], k["src_ld"], k["dst"], k["dst_rows_per_image"], k["dst_ld"], k["B"],
+                                       k["ntok"], k["cols"], k["elem"], k["add"], None)
+    return rc, lib.devit_last_error().decode() if rc else ""
+
+
 def refused(case_name, change, entry, adr):
     """run one REFUSALS row with the addresses adr() gives -> (return code, message)"""
     from devit_amd import _lib as L
     c = dict(case_named(case_name))
+    if entry in ("tail_fwd", "tail_bwd", "copy"):
+        return _refused_tail(c, change, entry, adr)
     w, a, g, io = structs(c, adr)
     c["dr"] = drop_struct(drop_of(c.get("block", 0), 0.1, 0.1), adr("tmp"))
     change(c, w, a, g, io)
@@ -862,6 +969,15 @@ def sizes_refusals():
         out.append(("acts_sizes/" + name, rc, lib.devit_last_error().decode(), code, words))
         rc = lib.devit_block_bwd_sizes(*args, sz_b)
         out.append(("bwd_sizes/" + name, rc, lib.devit_last_error().decode(), code, words))
+    ta, tb = (C.c_size_t * len(TAIL_ACT_NAMES))(), (C.c_size_t * len(TAIL_BWD_NAMES))()
+    for name, args, sz_a, sz_b, code, words in (("null_sizes", (2, 198, 2, 384, 384, 1536), None, None, ERR_ARG, "null"),
+                                               ("N_209", (2, 209, 2, 384, 384, 1536), ta, tb, ERR_SHAPE, "N=209"),
+                                               ("ntok_0", (2, 198, 0, 384, 384, 1536), ta, tb, ERR_SHAPE, "ntok=0"),
+                                               ("ntok_above_N", (2, 5, 6, 384, 384, 1536), ta, tb, ERR_SHAPE, "ntok=6 of N=5")):
+        rc = lib.devit_tail_acts_sizes(*args, SAVE, sz_a)
+        out.append(("tail_acts_sizes/" + name, rc, lib.devit_last_error().decode(), code, words))
+        rc = lib.devit_tail_bwd_sizes(*args, sz_b)
+        out.append(("tail_bwd_sizes/" + name, rc, lib.devit_last_error().decode(), code, words))
     return out
 
 

@@ -42,7 +42,7 @@ def test_header_symbols_exported(lib):
 
 
 def test_version_and_error_string(lib):
-    assert lib.devit_version() == 3
+    assert lib.devit_version() == 4
     assert isinstance(lib.devit_last_error(), bytes)
 
 

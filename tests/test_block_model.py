@@ -164,6 +164,22 @@ def test_reported_sizes_hold_the_stated_extents(c):
     assert L.load().devit_colsum_workspace(d["Mp"], d["D"]) == 64 * d["D"] * 4, "the figure default_routes() restates"
 
 
+@pytest.mark.parametrize("dims", K.TAIL_SIZE_CASES, ids=["x".join(map(str, d)) for d in K.TAIL_SIZE_CASES])
+@pytest.mark.parametrize("save", (1, 0))
+def test_reported_tail_sizes_hold_the_stated_extents(dims, save):
+    """devit_tail_acts_sizes / devit_tail_bwd_sizes, as for the block: at least the extent the header words (pad rows of T = B ntok and of M counted),
+    256-aligned, less than one alignment step over, exactly 0 for what the flags leave out (and for `att`, which the lean block never has)"""
+    acts, bwd = K.tail_library_sizes(*dims, K.SAVE if save else 0)
+    want_a, want_b = K.tail_extents(*dims, save)
+    B, N, ntok, D, Da, Hd = dims
+    assert want_a["ln2"] == K.pad_rows(B * ntok) * D * 2 and want_a["qkv"] == K.pad_rows(B * N) * 2 * Da * 2
+    for got, want in ((acts, want_a), (bwd, want_b)):
+        assert set(got) == set(want)
+        for name, n in want.items():
+            assert got[name] % 256 == 0 and n <= got[name] < n + 256, (dims, name, got[name], n)
+            assert (got[name] == 0) == (n == 0), (dims, name, got[name], n)
+
+
 def test_routes_of_the_table():
     """the branches the table is there for, from the restated rule"""
     r = {c["name"]: K.default_routes(c) for c in BWD_CASES}

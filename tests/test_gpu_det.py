@@ -450,7 +450,7 @@ def test_ensemble_step_twice(dev):
 
 def contributors(name, shape, seen, B):
     """How many partial sums the step's launches add per address of parameter `name` (depth-2 `dedeit`: block 0 through devit_block_bwd, block 1 the
-    lean tail of ops._tail_backward), read off the launches the library reported (`seen`):
+    lean tail of devit_tail_bwd, csrc/encoder.hip), read off the launches the library reported (`seen`):
       block 0's qkv / proj / fc1 weights and biases and its fc2 weight: the K slices of the grouped launch that holds its jobs (the one with >= 4 jobs);
       block 0's fc2 bias: a fixed-order column-sum pass, or -- if devit_block_bwd had to take the split-K launch for it -- that launch's row sums:
         counted as the largest [384 x 1536] launch's split_k * tiles_n;

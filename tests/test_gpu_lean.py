@@ -1,4 +1,4 @@
-"""The last block on its token rows only (devit_amd.de_vit.lean_tail, ops._tail_forward / _tail_backward, the
+"""The last block on its token rows only (devit_amd.de_vit.lean_tail, devit_tail_fwd / devit_tail_bwd in csrc/encoder.hip, the
 devit_attn_*_rows entry points) against the full block: the reference computes all 198 rows of the last block and reads
 two of them (models/de_vit.py:286-288; q/k/v of the middle block only, engine.py:91-92).
 
