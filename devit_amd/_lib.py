@@ -94,6 +94,17 @@ class OptChunk(C.Structure):
 
 OPT_CHUNK_GRANULES, OPT_CHUNK_NO_DECAY = 1024, 1
 
+
+class AugmentSample(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("y0", "x0", "h", "w", "Rh", "Rw", "oy", "ox", "filter", "flip", "n_erase", "erase_mode")] + \
+               [("erase", C.c_int * 4 * 4), ("noise_base", C.c_ulonglong)]
+
+
+# include/devit_hip.h, "Input augmentation"
+AUGMENT_TAPS, AUGMENT_MAX_ERASE, AUGMENT_SITE = 12, 4, 0x100
+AUG_NONE, AUG_BILINEAR, AUG_BICUBIC = range(3)
+AUG_ERASE_CONST, AUG_ERASE_RAND, AUG_ERASE_PIXEL = range(3)
+
 # devit_launch_info.has
 HAS_Y_BF16, HAS_Y_F32, HAS_DY_F32, HAS_DRES, HAS_DX, HAS_DX_BF16, HAS_DQKV_ADD = 1, 2, 4, 8, 16, 32, 64
 
@@ -120,7 +131,7 @@ WGRAD_MAX_JOBS = 48
 ABI_VERSION = 4
 # devit_abi_struct_size(which) -> the mirror it must equal (checked at load time: an array of stale mirrors is misread silently)
 ABI_STRUCTS = {0: Epilogue, 1: Operand, 2: BlockWeights, 3: BlockWgrads, 4: BlockActs, 5: BlockBwdIO, 6: IndexJob, 7: WgradJob, 8: LaunchInfo, 9: BlockDropout,
-               10: MixSample, 11: OptChunk, 12: TailActs, 13: TailBwdIO}
+               10: MixSample, 11: OptChunk, 12: TailActs, 13: TailBwdIO, 14: AugmentSample}
 
 
 class DevitError(RuntimeError):
@@ -220,6 +231,9 @@ SIGNATURES = {
     "devit_im2row_f32_sized": (_I, [_P, _P, _I, _I, _I, _P]),
     "devit_scale_rows_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "devit_colsum_f32": (_I, [_P, _I, _I, _I, _P, _I, _P]),
+    "devit_augment_workspace": (_Z, [_I, _I]),
+    "devit_augment_coeffs": (_I, [_P, _I, _I, _P, _Z, _P]),
+    "devit_augment_batch": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _U64, _P, _P, _Z, _P]),
     "devit_comm_unique_id": (_I, [_P]),
     "devit_comm_init": (_I, [_P, _I, _I, C.POINTER(C.c_void_p)]),
     "devit_comm_allreduce_f32": (_I, [_P, _P, _Z, _P]),

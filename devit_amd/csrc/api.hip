@@ -40,6 +40,7 @@ extern "C" size_t devit_abi_struct_size(int which) {
     case 11: return sizeof(devit_opt_chunk);
     case 12: return sizeof(devit_tail_acts);
     case 13: return sizeof(devit_tail_bwd_io);
+    case 14: return sizeof(devit_augment_sample);
     default: return 0;
   }
 }

@@ -1,0 +1,382 @@
+"""Device-resident datasets ("Device-resident datasets"): the whole uint8 image set lives in HBM, the host draws one small
+parameter row per sample, and one HIP stage (csrc/augment.hip: devit_augment_batch) turns a batch of indices into the normalized fp32
+batch [B,3,S,S] that Mixup and the patch-row kernels consume.  It stands where the reference has a DataLoader over
+timm.data.transforms_factory.transforms_imagenet_train / the Resize + CenterCrop eval stack (data/get_dataset.py:71-109): crop and resize
+(or the padded crop at 32 pixels), horizontal flip, ToTensor, Normalize, RandomErasing.  RandAugment and ColorJitter are not built.
+
+The draws are timm 0.5.4's own scalar formulas on a private random.Random; the arithmetic is the header's ("Input augmentation").
+Nothing here imports torchvision or timm; PIL only to read an image folder."""
+import math
+import os
+import pickle
+import random
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import ops
+from ._lib import ptr, stream_ptr
+
+IMAGENET_DEFAULT_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_DEFAULT_STD = (0.229, 0.224, 0.225)
+
+# host mirror of devit_augment_sample (120 bytes, _lib.AugmentSample)
+AUG_SAMPLE_DTYPE = np.dtype([(n, "<i4") for n in ("y0", "x0", "h", "w", "Rh", "Rw", "oy", "ox", "filter", "flip", "n_erase", "erase_mode")] +
+                            [("erase", "<i4", (4, 4)), ("noise_base", "<u8")])
+FILTERS = {"bilinear": L.AUG_BILINEAR, "bicubic": L.AUG_BICUBIC}
+ERASE_MODES = {"const": L.AUG_ERASE_CONST, "rand": L.AUG_ERASE_RAND, "pixel": L.AUG_ERASE_PIXEL}
+IMG_EXTENSIONS = ('.jpg', '.jpeg', '.png', '.ppm', '.bmp', '.pgm', '.tif', '.tiff', '.webp')      # torchvision's ImageFolder list
+
+
+def taps_needed(length, R, filt):
+    """The most taps one output index of an axis uses when `length` source pixels are resized to R (the header's xmax - xmin)."""
+    if filt == L.AUG_NONE:
+        return 1
+    scale = length / R
+    support = (2.0 if filt == L.AUG_BICUBIC else 1.0) * max(scale, 1.0)
+    most = 0
+    for xx in range(R):
+        center = (xx + 0.5) * scale
+        most = max(most, min(int(center + support + 0.5), length) - max(int(center - support + 0.5), 0))
+    return most
+
+
+def _check_taps(length, R, filt, what):
+    n = taps_needed(length, R, filt)
+    if n > L.AUGMENT_TAPS:
+        name = {v: k for k, v in FILTERS.items()}[filt]
+        raise ValueError(f"{what}: resizing {length} source pixels to {R} with the {name} filter needs {n} taps per output pixel, the resampling "
+                         f"kernel holds {L.AUGMENT_TAPS} (a crop side up to 3 x the output side for bicubic, 6 x for bilinear)")
+
+
+# ---- the resident set ------------------------------------------------------------------------------------------------------------------------
+class DeviceImageSet:
+    """images uint8 [n,H0,W0,3] and labels int64 [n] on the device, classes: the class names.  Every image has the same H0 x W0."""
+
+    def __init__(self, images, labels, classes):
+        self.images, self.labels, self.classes = images, labels, list(classes)
+
+    def __len__(self):
+        return self.images.shape[0]
+
+    @property
+    def size(self):
+        return int(self.images.shape[1]), int(self.images.shape[2])
+
+    @classmethod
+    def from_arrays(cls, images, labels, classes=None, device="cuda"):
+        if isinstance(images, (list, tuple)):
+            shapes = sorted({tuple(np.shape(a)) for a in images})
+            if len(shapes) > 1:
+                raise ValueError(f"DeviceImageSet: images of shapes {shapes[:4]}: resident sets are uniform (one H x W for every image)")
+            images = np.stack([np.asarray(a) for a in images])
+        images = images if isinstance(images, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images))
+        labels = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.asarray(labels, dtype=np.int64))
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+            raise ValueError(f"DeviceImageSet: images must be uint8 [n,H,W,3], got {images.dtype} {tuple(images.shape)}")
+        if labels.dim() != 1 or labels.shape[0] != images.shape[0] or images.shape[0] < 1:
+            raise ValueError(f"DeviceImageSet: {images.shape[0]} images, labels of shape {tuple(labels.shape)}")
+        if classes is None:
+            classes = [str(i) for i in range(int(labels.max()) + 1)]
+        return cls(images.contiguous().to(device), labels.long().to(device), classes)
+
+    @classmethod
+    def from_cifar100(cls, root, train, device="cuda"):
+        """The `cifar-100-python` pickles under root (what torchvision's CIFAR100 unpacks), read with pickle and numpy."""
+        path = os.path.join(root, "cifar-100-python", "train" if train else "test")
+        if not os.path.exists(path):
+            raise SystemExit(f"--device-data: {path} not found (the cifar-100-python pickles under --data-path)")
+        with open(path, "rb") as f:
+            d = pickle.load(f, encoding="latin1")
+        images = np.ascontiguousarray(np.asarray(d["data"], dtype=np.uint8).reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1))
+        meta = os.path.join(root, "cifar-100-python", "meta")
+        classes = None
+        if os.path.exists(meta):
+            with open(meta, "rb") as f:
+                classes = list(pickle.load(f, encoding="latin1")["fine_label_names"])
+        return cls.from_arrays(images, np.asarray(d["fine_labels"], dtype=np.int64), classes or [str(i) for i in range(100)], device)
+
+    @classmethod
+    def from_folder(cls, root, device="cuda"):
+        """An ImageFolder tree root/<class>/<file>: classes are the sorted directory names, files sorted within a class, read with PIL
+        and convert('RGB')."""
+        try:
+            from PIL import Image
+        except ImportError as e:
+            raise SystemExit("DeviceImageSet.from_folder reads images with PIL, which is not installed: " + repr(e))
+        if not os.path.isdir(root):
+            raise SystemExit(f"--device-data: {root} is not a directory (an ImageFolder tree, as splite_dataset.py writes)")
+        classes = sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d)))
+        images, labels, size = [], [], None
+        for ci, c in enumerate(classes):
+            for dirpath, _, files in sorted(os.walk(os.path.join(root, c), followlinks=True)):
+                for fn in sorted(files):
+                    if not fn.lower().endswith(IMG_EXTENSIONS):
+                        continue
+                    with Image.open(os.path.join(dirpath, fn)) as im:
+                        a = np.asarray(im.convert('RGB'), dtype=np.uint8)
+                    if size is None:
+                        size = a.shape[:2]
+                    if a.shape[:2] != size:
+                        raise ValueError(f"{os.path.join(dirpath, fn)} is {a.shape[0]} x {a.shape[1]}, the images before it {size[0]} x {size[1]}: "
+                                         "resident sets are uniform (one H x W for every image)")
+                    images.append(a)
+                    labels.append(ci)
+        if not images:
+            raise SystemExit(f"--device-data: no images under {root}")
+        return cls.from_arrays(np.stack(images), np.asarray(labels, dtype=np.int64), classes, device)
+
+
+# ---- the per-sample draws --------------------------------------------------------------------------------------------------------------------
+class TrainAugment:
+    """One devit_augment_sample per sample, drawn as timm 0.5.4 draws (transforms_imagenet_train: RandomResizedCropAndInterpolation.get_params,
+    the interpolation when 'random', RandomHorizontalFlip, RandomErasing._erase), in that order, on a private random.Random seeded by
+    (seed, rank) and carried across epochs.  S == 32: the crop is RandomCrop(S, padding=4) at unit scale (data/get_dataset.py:92-96)."""
+
+    def __init__(self, S, scale=(0.08, 1.0), ratio=(3. / 4., 4. / 3.), interpolation='bicubic', hflip=0.5, re_prob=0., re_mode='const',
+                 re_count=1, seed=0, rank=0, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD):
+        self.S = ops.check_img_size(S, exc=ValueError)
+        if interpolation != 'random' and interpolation not in FILTERS:
+            raise ValueError(f"TrainAugment: interpolation {interpolation!r}: bicubic, bilinear or random")
+        re_mode = re_mode or 'const'
+        if re_mode not in ERASE_MODES:
+            raise ValueError(f"TrainAugment: re_mode {re_mode!r}: const, rand or pixel")
+        if not 1 <= re_count <= L.AUGMENT_MAX_ERASE:
+            raise ValueError(f"TrainAugment: re_count {re_count}: the erase stage holds 1 .. {L.AUGMENT_MAX_ERASE} boxes per sample")
+        self.scale, self.ratio, self.interpolation, self.hflip = tuple(scale), tuple(ratio), interpolation, hflip
+        self.re_prob, self.re_mode, self.re_count = re_prob, re_mode, re_count
+        self.seed, self.rank, self.mean, self.std = int(seed), int(rank), tuple(mean), tuple(std)
+        self.rng = random.Random(self.seed * 65536 + self.rank)
+        self.drawn = 0            # samples drawn so far: the noise counter base of the next batch
+
+    def check_set(self, H0, W0):
+        """Refuse a set this transform cannot serve (the tap limit of the resampling kernel), before anything is drawn."""
+        if self.S == 32:
+            if H0 + 8 < self.S or W0 + 8 < self.S:
+                raise ValueError(f"TrainAugment: a padded {self.S} x {self.S} crop does not fit {H0} x {W0} images")
+            return
+        for f in (FILTERS.values() if self.interpolation == 'random' else (FILTERS[self.interpolation],)):
+            _check_taps(H0, self.S, f, f"TrainAugment on {H0} x {W0} images")      # the largest crop is the whole side
+            _check_taps(W0, self.S, f, f"TrainAugment on {H0} x {W0} images")
+
+    def _crop(self, H0, W0):
+        rng = self.rng
+        area = W0 * H0
+        for _ in range(10):
+            target_area = rng.uniform(*self.scale) * area
+            aspect_ratio = math.exp(rng.uniform(math.log(self.ratio[0]), math.log(self.ratio[1])))
+            w = int(round(math.sqrt(target_area * aspect_ratio)))
+            h = int(round(math.sqrt(target_area / aspect_ratio)))
+            if w <= W0 and h <= H0:
+                i = rng.randint(0, H0 - h)
+                j = rng.randint(0, W0 - w)
+                return i, j, h, w
+        in_ratio = W0 / H0                    # fallback: the central crop with the ratio clamped
+        if in_ratio < min(self.ratio):
+            w = W0
+            h = int(round(w / min(self.ratio)))
+        elif in_ratio > max(self.ratio):
+            h = H0
+            w = int(round(h * max(self.ratio)))
+        else:
+            w, h = W0, H0
+        return (H0 - h) // 2, (W0 - w) // 2, h, w
+
+    def _erase(self):
+        rng, S, boxes = self.rng, self.S, []
+        if rng.random() > self.re_prob:
+            return boxes
+        count = 1 if self.re_count == 1 else rng.randint(1, self.re_count)
+        for _ in range(count):
+            for _ in range(10):
+                target_area = rng.uniform(0.02, 1 / 3) * (S * S) / count
+                aspect_ratio = math.exp(rng.uniform(math.log(0.3), math.log(1 / 0.3)))
+                h = int(round(math.sqrt(target_area * aspect_ratio)))
+                w = int(round(math.sqrt(target_area / aspect_ratio)))
+                if w < S and h < S:
+                    boxes.append((rng.randint(0, S - h), rng.randint(0, S - w), h, w))
+                    break
+        return boxes
+
+    def draw(self, B, H0, W0):
+        """-> AUG_SAMPLE_DTYPE [B]: crop, interpolation if random, flip, erasing per sample"""
+        S, rng = self.S, self.rng
+        cols, erase = [], np.zeros((B, 4, 4), dtype=np.int32)      # (columns are filled at once: a field store per sample costs more than its draw)
+        for b in range(B):
+            if S == 32:
+                y0, x0, h, w, filt = rng.randint(0, H0 + 8 - S) - 4, rng.randint(0, W0 + 8 - S) - 4, S, S, L.AUG_NONE
+            else:
+                y0, x0, h, w = self._crop(H0, W0)
+                if h < 1 or w < 1:
+                    raise ValueError(f"TrainAugment: drew an empty {h} x {w} crop on {H0} x {W0} images (scale {self.scale})")
+                filt = rng.choice((L.AUG_BILINEAR, L.AUG_BICUBIC)) if self.interpolation == 'random' else FILTERS[self.interpolation]
+            flip = int(rng.random() < self.hflip) if self.hflip > 0. else 0
+            boxes = self._erase() if self.re_prob > 0. else ()
+            if boxes:
+                erase[b, :len(boxes)] = boxes
+            cols.append((y0, x0, h, w, filt, flip, len(boxes)))
+        tab = np.zeros(B, dtype=AUG_SAMPLE_DTYPE)
+        cols = np.asarray(cols, dtype=np.int32)
+        for k, name in enumerate(("y0", "x0", "h", "w", "filter", "flip", "n_erase")):
+            tab[name] = cols[:, k]
+        tab["Rh"], tab["Rw"], tab["erase_mode"], tab["erase"] = S, S, ERASE_MODES[self.re_mode], erase
+        tab["noise_base"] = (self.rank << 48) + self.drawn
+        self.drawn += B
+        return tab
+
+    def state_dict(self):
+        return {"rng": self.rng.getstate(), "drawn": self.drawn}
+
+    def load_state_dict(self, state):
+        v, words, gauss = state["rng"]
+        self.rng.setstate((v, tuple(words), gauss))
+        self.drawn = int(state["drawn"])
+
+
+class EvalTransform:
+    """The reference's eval stack (data/get_dataset.py:99-109).  S > 32: torchvision Resize(int(256 / 224 * S)) -- the shorter side to R, the other to
+    int(R * long / short), bicubic -- and CenterCrop(S) with offsets int(round((side - S) / 2.)).  S == 32: the image as it is."""
+
+    def __init__(self, S, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD):
+        self.S, self.seed, self.mean, self.std = ops.check_img_size(S, exc=ValueError), 0, tuple(mean), tuple(std)
+
+    def geometry(self, H0, W0):
+        """(Rh, Rw, oy, ox, filter)"""
+        S = self.S
+        if S == 32:
+            return S, S, 0, 0, L.AUG_NONE
+        R = int((256 / 224) * S)
+        Rh, Rw = (R, int(R * W0 / H0)) if H0 <= W0 else (int(R * H0 / W0), R)
+        return Rh, Rw, int(round((Rh - S) / 2.)), int(round((Rw - S) / 2.)), L.AUG_BICUBIC
+
+    def check_set(self, H0, W0):
+        Rh, Rw, _, _, filt = self.geometry(H0, W0)
+        if filt == L.AUG_NONE:
+            if (H0, W0) != (self.S, self.S):
+                raise ValueError(f"EvalTransform: at {self.S} pixels the images are used as they are, and the set's are {H0} x {W0}")
+            return
+        _check_taps(H0, Rh, filt, f"EvalTransform on {H0} x {W0} images")
+        _check_taps(W0, Rw, filt, f"EvalTransform on {H0} x {W0} images")
+
+    def draw(self, B, H0, W0):
+        tab = np.zeros(B, dtype=AUG_SAMPLE_DTYPE)
+        tab["h"], tab["w"] = H0, W0
+        tab["Rh"], tab["Rw"], tab["oy"], tab["ox"], tab["filter"] = self.geometry(H0, W0)
+        return tab
+
+    def state_dict(self):
+        return {}
+
+    def load_state_dict(self, state):
+        pass
+
+
+# ---- the device stage ------------------------------------------------------------------------------------------------------------------------
+UPLOAD_RING_SLOTS = 256
+_upload_ring = {}     # device -> [pinned uint8 [UPLOAD_RING_SLOTS, bytes per slot], uploads so far] (as ops.mix_table's ring, and for its reason)
+
+
+def upload(host_bytes, device):
+    """numpy uint8 [nbytes] -> a fresh device uint8 tensor through a pinned ring slot of its own, by a copy that never waits for the stream."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    nbytes = host_bytes.shape[0]
+    ring = _upload_ring.get(device)
+    if ring is None or ring[0].shape[1] < nbytes:
+        ring = _upload_ring[device] = [torch.zeros((UPLOAD_RING_SLOTS, max(nbytes, 65536)), dtype=torch.uint8).pin_memory(), 0]
+    slot = ring[0][ring[1] % UPLOAD_RING_SLOTS, :nbytes]
+    ring[1] += 1
+    slot.copy_(torch.from_numpy(host_bytes))
+    dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    dev.copy_(slot, non_blocking=True)
+    return dev
+
+
+def check_table(tab, H0, W0, S):
+    """ValueError for a table the header's definition does not cover (the kernels are memory-safe for any bytes; this is where values are checked)."""
+    if tab.dtype != AUG_SAMPLE_DTYPE or tab.ndim != 1 or tab.shape[0] < 1:
+        raise ValueError("augment_batch: the table is a 1-d numpy array of AUG_SAMPLE_DTYPE")
+    filt = tab["filter"]
+    if not np.isin(filt, (0, 1, 2)).all() or not np.isin(tab["erase_mode"], (0, 1, 2)).all():
+        raise ValueError("augment_batch: filter and erase_mode are 0, 1 or 2")
+    if ((tab["n_erase"] < 0) | (tab["n_erase"] > L.AUGMENT_MAX_ERASE)).any():
+        raise ValueError(f"augment_batch: n_erase must lie in 0 .. {L.AUGMENT_MAX_ERASE}")
+    if ((tab["h"] < 1) | (tab["w"] < 1) | (tab["Rh"] < 1) | (tab["Rw"] < 1)).any():
+        raise ValueError("augment_batch: empty box or virtual size")
+    if ((tab["oy"] < 0) | (tab["ox"] < 0) | (tab["oy"] + S > tab["Rh"]) | (tab["ox"] + S > tab["Rw"])).any():
+        raise ValueError(f"augment_batch: the {S} x {S} window must lie inside the virtual output")
+    res = filt != 0
+    if (res & ((tab["y0"] < 0) | (tab["x0"] < 0) | (tab["y0"] + tab["h"] > H0) | (tab["x0"] + tab["w"] > W0))).any():
+        raise ValueError(f"augment_batch: a resized box must lie inside the {H0} x {W0} image")
+    if (~res & ((tab["h"] != tab["Rh"]) | (tab["w"] != tab["Rw"]))).any():
+        raise ValueError("augment_batch: filter 0 is unit scale: the box has the virtual output's size")
+    for key in {(int(a), int(b), int(c)) for a, b, c in zip(tab["h"][res], tab["Rh"][res], filt[res])} | \
+            {(int(a), int(b), int(c)) for a, b, c in zip(tab["w"][res], tab["Rw"][res], filt[res])}:
+        _check_taps(*key, "augment_batch")
+
+
+def augment_batch(src, idx, table, S, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD, seed=0, out=None, table_dev=None):
+    """src uint8 [n,H0,W0,3] and idx int32 [B] on the device, table: AUG_SAMPLE_DTYPE [B] on the host (validated here, then uploaded)
+    -> fp32 [B,3,S,S] (devit_augment_batch).  table_dev: the table's bytes already on the device (the caller validated and uploaded them)."""
+    L.require_device(src)
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3 or not src.is_contiguous():
+        raise ValueError(f"augment_batch: src must be a contiguous uint8 [n,H0,W0,3] tensor, got {src.dtype} {tuple(src.shape)}")
+    if idx.dtype != torch.int32 or idx.dim() != 1 or idx.device != src.device or not idx.is_contiguous():
+        raise ValueError("augment_batch: idx must be a contiguous int32 [B] tensor on the set's device")
+    S = ops.check_img_size(S, exc=ValueError)
+    n, H0, W0 = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    B = idx.shape[0]
+    if table.shape[0] != B:
+        raise ValueError(f"augment_batch: the table has {table.shape[0]} rows, the batch {B} samples")
+    if table_dev is None:
+        check_table(table, H0, W0, S)
+        table_dev = upload(np.ascontiguousarray(table).view(np.uint8).reshape(-1), src.device)
+    if out is None:
+        out = torch.empty((B, 3, S, S), dtype=torch.float32, device=src.device)
+    elif out.dtype != torch.float32 or out.shape[1:] != (3, S, S) or out.shape[0] < B or not out.is_contiguous() or out.device != src.device:
+        raise ValueError("augment_batch: out must be a contiguous fp32 [>=B,3,S,S] tensor on the set's device")
+    nbytes = L.load().devit_augment_workspace(B, S)
+    ws = ops.workspace(src.device, nbytes)
+    m3, s3 = (L.C.c_float * 3)(*mean), (L.C.c_float * 3)(*std)
+    ops.call("devit_augment_batch", ptr(src), n, H0, W0, ptr(idx), ptr(table_dev), B, S, m3, s3, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out),
+             ptr(ws), nbytes, stream_ptr())
+    return out
+
+
+class DeviceLoader:
+    """Batches of a DeviceImageSet: (images fp32 [B,3,S,S], labels int64 [B]) device tensors, fresh per step as SyntheticLoader's and for its
+    reason.  sampler: any iterable of indices with a length (RASampler, DistributedSampler, SequentialSampler); `.sampler` is what
+    distill_sub.set_epoch reshuffles.  The index batch and the parameter table go up together by one pinned, non-blocking copy."""
+
+    def __init__(self, dataset, sampler, batch_size, transform, drop_last):
+        self.dataset, self.sampler, self.batch_size, self.transform, self.drop_last = dataset, sampler, int(batch_size), transform, drop_last
+        transform.check_set(*dataset.size)        # refuses a set that needs more taps than the kernel holds
+
+    def __len__(self):
+        n = len(self.sampler)
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def _batch(self, indices):
+        ds, tf = self.dataset, self.transform
+        B, (H0, W0) = len(indices), ds.size
+        table = tf.draw(B, H0, W0)
+        idx = np.asarray(indices, dtype=np.int32)
+        if idx.min() < 0 or idx.max() >= len(ds):
+            raise IndexError(f"DeviceLoader: the sampler yields indices outside 0 .. {len(ds) - 1}")
+        pad = (-idx.nbytes) % 8                   # the table's 64-bit field stays aligned behind the indices
+        both = upload(np.concatenate([idx.view(np.uint8), np.zeros(pad, np.uint8), table.view(np.uint8).reshape(-1)]), ds.images.device)
+        idx_dev = both[:idx.nbytes].view(torch.int32)
+        images = augment_batch(ds.images, idx_dev, table, tf.S, tf.mean, tf.std, tf.seed, table_dev=both[idx.nbytes + pad:])
+        return images, ds.labels.index_select(0, idx_dev.long())
+
+    def __iter__(self):
+        batch = []
+        for i in self.sampler:
+            batch.append(int(i))
+            if len(batch) == self.batch_size:
+                yield self._batch(batch)
+                batch = []
+        if batch and not self.drop_last:
+            yield self._batch(batch)

@@ -11,7 +11,8 @@ Same flags, defaults, output-directory naming, checkpoint files and per-epoch lo
 Differences, all host-side: (1) `--synthetic N` trains/evaluates on N on-device random batches per epoch (the image
 has no torchvision / datasets; the JPEG pipeline of data/ is outside the hot path) -- without it the
 reference's dataset package must be importable as `data.get_dataset` (its `build_division_dataset` / `build_dataset`);
-samplers and loaders are then built as the reference builds them (`build_loaders`);
+samplers and loaders are then built as the reference builds them (`build_loaders`); `--device-data` reads the division's image folders (or the
+CIFAR-100 pickles) itself, keeps them on the device as uint8 and runs the reference's crop / flip / normalize / erase stack in one HIP stage;
 (2) bf16 needs no loss scaling: `scaler` in checkpoints is an empty dict; (3) Mixup/CutMix run as device-side
 tensor ops (SURVEY §8f-4 "next").
 """
@@ -81,6 +82,9 @@ def get_args_parser():
       help='train the gated student MASKED at the dense cost, as the reference does (default: through compacted blocks, '
            'devit_amd.shrink.compact(trainable=True): same function and gradients, the shrunk model\'s FLOPs)')
     a('--synthetic', type=int, default=0, metavar='STEPS', help='train on STEPS random on-device batches per epoch')
+    a('--device-data', action='store_true', default=False,
+      help='keep the uint8 dataset resident on the device and crop, resize, flip, normalize and erase there (devit_amd.data; DESIGN.md section 15): '
+           'needs no torchvision / timm.  RandAugment and ColorJitter are not built: give --aa none --color-jitter 0')
     a('--deterministic', action='store_true', default=False,
       help='fixed-order reductions instead of fp32 atomics in arrival order (devit_amd.ops.set_deterministic; DESIGN.md section 14): the same '
            '--seed, inputs and launch configuration give the same bits on every run at world size 1; +0.2 %% on the bs-256 DEKD step, 256 MiB of workspace')
@@ -154,6 +158,8 @@ def build_loaders(args, num_classes, device, provider="division", plain_sampler_
     drop_last.  `plain_sampler_over`: with --no-repeated-aug distill_sub.py:281-283 and train_subdata.py:347-349 build the
     TRAIN sampler over the TEST set (its length sets the epoch length, and with it the LR schedule); kept, ensemble.py:271-273
     uses the train set."""
+    if getattr(args, 'device_data', False):
+        return build_device_loaders(args, num_classes, device, provider, plain_sampler_over)
     if args.synthetic > 0:
         size = getattr(args, 'input_size', 224)
         return (SyntheticLoader(args.synthetic, args.batch_size, num_classes, device, 1234 + utils.get_rank(), size),
@@ -187,6 +193,78 @@ def build_loaders(args, num_classes, device, provider="division", plain_sampler_
     val_loader = torch.utils.data.DataLoader(test_ds, sampler=sampler_val, batch_size=args.eval_batch_size,
                                              num_workers=args.num_workers, pin_memory=args.pin_mem, drop_last=False)
     return train_loader, val_loader, num_classes
+
+
+def check_device_data(args):
+    """--device-data builds the reference's transform stack without RandAugment and ColorJitter: refuse the flags that ask for them (and --no_aug,
+    whose stack is timm's default one with both) instead of silently training on something else."""
+    if not getattr(args, 'device_data', False):
+        return
+    if args.synthetic > 0:
+        raise SystemExit("--device-data and --synthetic are two sources of batches: give one")
+    missing = []
+    if (args.aa or 'none').lower() != 'none':
+        missing.append(f"--aa {args.aa} (RandAugment / AutoAugment is not built: --aa none)")
+    if args.color_jitter:
+        missing.append(f"--color-jitter {args.color_jitter} (ColorJitter is not built: --color-jitter 0)")
+    if getattr(args, 'no_aug', False):
+        missing.append("--no_aug (timm's default training stack, which includes ColorJitter, is not built)")
+    if missing:
+        raise SystemExit("--device-data: " + "; ".join(missing))
+    if args.train_interpolation not in ('bicubic', 'bilinear', 'random'):
+        raise SystemExit(f"--device-data --train-interpolation {args.train_interpolation}: bicubic, bilinear or random")
+    if (args.remode or 'const') not in ('const', 'rand', 'pixel'):
+        raise SystemExit(f"--device-data --remode {args.remode}: const, rand or pixel")
+    if args.reprob > 0 and not 1 <= args.recount <= 4:
+        raise SystemExit(f"--device-data --recount {args.recount}: the erase stage holds 1 .. 4 boxes per sample")
+
+
+def build_device_loaders(args, num_classes, device, provider, plain_sampler_over):
+    """build_loaders with --device-data: the same samplers, drop_last and --no-repeated-aug quirk over devit_amd.data.DeviceImageSet."""
+    from devit_amd import data
+    check_device_data(args)
+    if provider == "division":
+        root = os.path.join(args.data_path, f"sub-dataset{args.start_division}")
+        train_ds = data.DeviceImageSet.from_folder(os.path.join(root, 'train_dataset'), device)
+        test_ds = data.DeviceImageSet.from_folder(os.path.join(root, 'test_dataset'), device)
+        num_classes = len(train_ds.classes)
+    elif args.dataset == 'cifar100':
+        train_ds = data.DeviceImageSet.from_cifar100(args.data_path, True, device)
+        test_ds = data.DeviceImageSet.from_cifar100(args.data_path, False, device)
+        num_classes = 100
+    else:
+        raise SystemExit(f"--device-data --dataset {args.dataset}: only cifar100 is read whole (its pickles under --data-path); the other sets "
+                         "have images of mixed sizes, and resident sets are uniform")
+    world, rank = utils.get_world_size(), utils.get_rank()
+    if args.repeated_aug:
+        sampler_train = RASampler(train_ds, num_replicas=world, rank=rank, shuffle=True)
+    else:
+        sampler_train = torch.utils.data.DistributedSampler(test_ds if plain_sampler_over == "test" else train_ds,
+                                                            num_replicas=world, rank=rank, shuffle=True)
+    if args.dist_eval:
+        sampler_val = torch.utils.data.DistributedSampler(test_ds, num_replicas=world, rank=rank, shuffle=False)
+    else:
+        sampler_val = torch.utils.data.SequentialSampler(test_ds)
+    try:
+        train_tf = data.TrainAugment(args.input_size, interpolation=args.train_interpolation, re_prob=args.reprob, re_mode=args.remode or 'const',
+                                     re_count=args.recount if args.reprob > 0 else 1, seed=args.seed, rank=rank)
+        train_loader = data.DeviceLoader(train_ds, sampler_train, args.batch_size, train_tf, drop_last=True)
+        val_loader = data.DeviceLoader(test_ds, sampler_val, args.eval_batch_size, data.EvalTransform(args.input_size), drop_last=False)
+    except ValueError as e:
+        raise SystemExit("--device-data: " + str(e))
+    return train_loader, val_loader, num_classes
+
+
+def loader_state(loader):
+    """What a checkpoint keeps of the train loader (a DeviceLoader's draw stream; nothing for the others)."""
+    tf = getattr(loader, "transform", None)
+    return tf.state_dict() if hasattr(tf, "state_dict") else {}
+
+
+def load_loader_state(loader, state):
+    tf = getattr(loader, "transform", None)
+    if state and hasattr(tf, "load_state_dict"):
+        tf.load_state_dict(state)
 
 
 def set_epoch(loader, epoch):
@@ -409,6 +487,7 @@ def check_supported(args):
     optim.OPT_NAMES; --sched: cosine): refuse the others instead of silently training something else (create_optimizer /
     create_scheduler, distill_sub.py:340-343)."""
     check_input_size(args)
+    check_device_data(args)
     apply_deterministic(args)
     if args.opt.lower() == 'sgd':
         raise SystemExit("--opt sgd: use nesterov: timm's sgd is Nesterov SGD (or momentum for the plain form)")
@@ -491,6 +570,7 @@ def main(args):
             optimizer.load_state_dict(ck['optimizer'])
             lr_scheduler.load_state_dict(ck['lr_scheduler'])
             args.start_epoch = ck['epoch'] + 1
+            load_loader_state(train_loader, ck.get('data'))
     if args.eval:
         print(engine.evaluate(val_loader, model, device))
         return
@@ -522,7 +602,8 @@ def main(args):
         utils.save_on_master({'model': model.state_dict(), 'optimizer': optimizer.state_dict(),
                               'lr_scheduler': lr_scheduler.state_dict(), 'epoch': epoch,
                               'model_ema': optimizer.ema_state_dict(model), 'scaler': loss_scaler.state_dict(),
-                              'args': args}, output_dir / 'checkpoint_temp.pth')
+                              'args': args, **({'data': loader_state(train_loader)} if loader_state(train_loader) else {})},   # (--device-data only)
+                             output_dir / 'checkpoint_temp.pth')
         test_stats = engine.evaluate(val_loader, model, device)
         print(f"Epoch: {epoch}/{args.epochs}  [Train] Loss: {train_stats.get('loss', float('nan')):.4f}  "
               f"[Eval] Top-1: {test_stats['acc1']:.4f} Top-5: {test_stats['acc5']:.4f} Loss: {test_stats['loss']:.4f}")

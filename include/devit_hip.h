@@ -46,7 +46,7 @@ DEVIT_API const char* devit_last_error(void); /* host string, thread-local, vali
 DEVIT_API int devit_check_device(int dev);
 /* sizeof() of the ABI's structs as THIS library was compiled (which: 0 devit_epilogue, 1 devit_operand, 2 devit_block_weights,
  * 3 devit_block_wgrads, 4 devit_block_acts, 5 devit_block_bwd_io, 6 devit_index_job, 7 devit_wgrad_job, 8 devit_launch_info, 9 devit_block_dropout,
- * 10 devit_mix_sample, 11 devit_opt_chunk, 12 devit_tail_acts, 13 devit_tail_bwd_io; anything else: 0).  A binding
+ * 10 devit_mix_sample, 11 devit_opt_chunk, 12 devit_tail_acts, 13 devit_tail_bwd_io, 14 devit_augment_sample; anything else: 0).  A binding
  * compares them with its own mirrors once at load time: a stale mirror of a struct that is passed as an ARRAY would otherwise be misread
  * from its second element on, with no error. */
 DEVIT_API size_t devit_abi_struct_size(int which);
@@ -799,6 +799,66 @@ DEVIT_API int devit_encoder_fwd_drop(int nblocks, const devit_block_weights* w, 
                            int B, int N, int D, float eps, void* stream);
 DEVIT_API int devit_block_bwd_drop(const devit_block_weights* w, const devit_block_acts* acts, const devit_block_wgrads* grads,
                          const devit_block_bwd_io* io, const devit_block_dropout* drop, int B, int N, int D, float eps, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Input augmentation: a resident uint8 image set -> the normalized fp32 batch [B,3,S,S] that Mixup and the patch-row kernels consume.
+ * It replaces, per sample, timm's transforms_imagenet_train as data/get_dataset.py:71-97 configures it (RandomResizedCrop / RandomCrop with
+ * padding, horizontal flip, ToTensor, Normalize, RandomErasing) and the eval stack (Resize, CenterCrop, ToTensor, Normalize); every random
+ * draw is the host's and arrives in a device table of B devit_augment_sample (struct id 14 of devit_abi_struct_size, 120 bytes).
+ *   src    uint8 [n][H0][W0][3] (HWC), idx int32 [B] on the device: out[b] is made from image idx[b] (clamped to 0 .. n-1)
+ *   out    fp32 [B][3][S][S], S one of the patch-cutting kernels' sizes (a multiple of 16 from 32 to 224), 16-byte aligned
+ * Per output pixel (y, x) of sample b, in this order:
+ *  1 crop, then resize -- PIL's Image.crop((x0, y0, x0 + w, y0 + h)).resize((Rw, Rh), filter) on the uint8 values, of which the
+ *    window [oy, oy + S) x [ox, ox + S) is produced (train: Rh = Rw = S, oy = ox = 0; eval: the resized side with a centred window).
+ *    Per axis, with len the box side and R the virtual side: scale = len / R, fs = max(scale, 1), support = (1 bilinear | 2 bicubic) * fs;
+ *    for the virtual index xx: center = (xx + 0.5) * scale, xmin = max(int(center - support + 0.5), 0), xmax = min(int(center + support
+ *    + 0.5), len); tap k (0 <= k < xmax - xmin) weighs f((k + xmin - center + 0.5) * (1 / fs)), f the triangle or the Keys cubic with
+ *    a = -0.5 ( ((a+2)|t| - (a+3)) t^2 + 1 below 1, (((|t| - 5)|t| + 8)|t| - 4) a below 2 ); the weights are divided by their sequential
+ *    sum and become integers int(w * 2^22 +- 0.5) (half away from zero).  All of this in IEEE double, uncontracted, in this operation
+ *    order (devit_augment_coeffs, a kernel of its own; it is PIL's precompute_coeffs + normalize_coeffs_8bpc).  The horizontal pass runs
+ *    first; each pass is clamp((2^21 + sum pixel * weight) >> 22, 0, 255) in int32, and the uint8 between the passes is part of the
+ *    definition.  Taps never leave the box.  At most DEVIT_AUGMENT_TAPS taps per axis: a caller refuses sets that would need more.
+ *    filter 0 (unit scale): the pixel (y0 + oy + y, x0 + ox + x) itself; the box may then lie partly outside the image (RandomCrop's padding).
+ *    A pixel outside the image reads 0 in every mode.
+ *  2 horizontal flip of the window (flip != 0): output x takes window column S - 1 - x.
+ *  3 ToTensor and Normalize in fp32: v = ((float)u8 / 255.0f - mean[c]) / std[c]  (two correctly rounded divisions, one subtraction).
+ *  4 RandomErasing, after Normalize as in timm: inside any of the first n_erase boxes (top, left, h, w) of the OUTPUT the value becomes
+ *      erase_mode 0 const: 0;  1 rand: one normal per box and channel;  2 pixel: one normal per channel and pixel
+ *    (boxes later in the list win where they overlap; in mode 2 a pixel's normal does not depend on the box).
+ *    Normals: Philox4x32-10 as in section "Dropout", key = (seed & 0xffffffff, seed >> 32), counter = (N & 0xffffffff, N >> 32,
+ *    DEVIT_AUGMENT_SITE + c, g) with N = noise_base + b and c the channel; mode 2: g = (y * S + x) >> 2 and the pixel takes normal
+ *    (y * S + x) & 3 of the call; mode 1: g = 0x80000000 + box index, normal 0.  The four normals of a call's words w0 .. w3 are
+ *      z0 = r(w0) cos(2 pi u(w1)), z1 = r(w0) sin(2 pi u(w1)), z2 = r(w2) cos(2 pi u(w3)), z3 = r(w2) sin(2 pi u(w3)),
+ *      u(w) = ((w >> 8) + 0.5) * 2^-24, r(w) = sqrt(-2 ln u(w))   (Box-Muller)
+ *    evaluated in fp32.  u(w) is exact in fp32 for w >> 8 < 2^23; above, 1 - u(w) is (it is u of the complemented word), and the kernel
+ *    goes through it: ln u = log1p(-(1 - u)), cos(2 pi u) = cos(2 pi (1 - u)), sin(2 pi u) = -sin(2 pi (1 - u)).  So the inputs of the
+ *    four library functions (logf / log1pf, sqrtf, sincospif) carry no rounding error of their own.
+ * devit_augment_workspace(B, S): bytes of the coefficient workspace (int32 [B][2 axes][2 + DEVIT_AUGMENT_TAPS][S]: xmin, count, weights).
+ * devit_augment_coeffs fills it from the table; devit_augment_batch runs devit_augment_coeffs and then the resampling kernel, which is
+ * integer arithmetic up to step 3.  mean / std are HOST arrays of 3 floats.  No address in either kernel depends on the table's or idx's contents
+ * without a clamp, so both are memory-safe for any table bytes; rows of `out` beyond B and bytes outside `out` are never written.
+ * ---------------------------------------------------------------------------------------- */
+#define DEVIT_AUGMENT_TAPS 12
+#define DEVIT_AUGMENT_MAX_ERASE 4
+#define DEVIT_AUGMENT_SITE 0x100u /* word 2 of the noise counter is this + channel: no dropout site (0 .. 4) shares a counter with it */
+enum devit_augment_filter { DEVIT_AUG_NONE = 0, DEVIT_AUG_BILINEAR = 1, DEVIT_AUG_BICUBIC = 2 };
+enum devit_augment_erase { DEVIT_AUG_ERASE_CONST = 0, DEVIT_AUG_ERASE_RAND = 1, DEVIT_AUG_ERASE_PIXEL = 2 };
+typedef struct {
+  int y0, x0, h, w;     /* source box; y0 / x0 may be negative with filter 0 */
+  int Rh, Rw, oy, ox;   /* virtual output size and the window's offset in it */
+  int filter;           /* devit_augment_filter */
+  int flip;
+  int n_erase;          /* 0 .. DEVIT_AUGMENT_MAX_ERASE */
+  int erase_mode;       /* devit_augment_erase */
+  int erase[DEVIT_AUGMENT_MAX_ERASE][4]; /* top, left, h, w in the output */
+  unsigned long long noise_base;
+} devit_augment_sample;
+DEVIT_API size_t devit_augment_workspace(int B, int S);
+DEVIT_API int devit_augment_coeffs(const devit_augment_sample* table /* device, B entries */, int B, int S, void* workspace,
+                         size_t workspace_bytes, void* stream);
+DEVIT_API int devit_augment_batch(const unsigned char* src, int n, int H0, int W0, const int* idx, const devit_augment_sample* table, int B,
+                        int S, const float* mean /* host [3] */, const float* std /* host [3] */, unsigned long long seed, float* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
