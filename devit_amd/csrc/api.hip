@@ -41,6 +41,7 @@ extern "C" size_t devit_abi_struct_size(int which) {
     case 12: return sizeof(devit_tail_acts);
     case 13: return sizeof(devit_tail_bwd_io);
     case 14: return sizeof(devit_augment_sample);
+    case 15: return sizeof(devit_augment_ops);
     default: return 0;
   }
 }

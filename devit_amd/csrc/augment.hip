@@ -5,6 +5,9 @@
 //                           LDS as the uint8 intermediate (thread x keeps column x's taps in registers), then the vertical pass, flip,
 //                           normalize (a table of the 256 levels per channel, made with the header's two divisions) and erasing out of
 //                           LDS into 16-byte stores.  Integer arithmetic up to the normalization.
+//   augment_u8_kernel       augment_kernel's two passes and flip, with the uint8 window [B][S][S][3] as the result
+//   image_ops_kernel        (header, "Image ops") one workgroup per sample: that window into LDS whole, RandAugment's / ColorJitter's layers applied
+//                           there bit for bit as PIL computes them, then normalize and erasing out of LDS; or uint8 to uint8 (devit_image_ops)
 // Every source address is clamped and the value masked afterwards (as attention.hip's fetch_rows: no load under a per-element
 // condition), every LDS row index is clamped, idx is clamped: no table or index bytes can send an access out of bounds.
 #include "devit_common.h"
@@ -243,6 +246,415 @@ __global__ __launch_bounds__(THREADS) void augment_kernel(const unsigned char* _
   }
 }
 
+// augment_kernel's two passes and flip with the uint8 window [B][S][S][3] as the result (what image_ops_kernel loads): steps 3 and 4 are that kernel's
+__global__ __launch_bounds__(THREADS) void augment_u8_kernel(const unsigned char* __restrict__ src, int n_img, int H0, int W0,
+                                                             const int* __restrict__ idx, const devit_augment_sample* __restrict__ table,
+                                                             int S, const int* __restrict__ ws, unsigned char* __restrict__ out8) {
+  __shared__ __attribute__((aligned(16))) unsigned char inter[3][NROWS][PITCH];
+  __shared__ int s_ymin[BAND], s_yn[BAND], s_wy[BAND][TAPS];
+  const int tid = threadIdx.x, b = blockIdx.y, r0 = blockIdx.x * BAND, r1 = min(r0 + BAND, S);
+  const devit_augment_sample* sp = table + b;
+  const int y0 = sp->y0, x0 = sp->x0, flip = sp->flip;
+  const int img = clampi(idx[b], 0, n_img - 1);
+  const unsigned char* image = src + (size_t)img * H0 * W0 * 3;
+  const int* wsy = ws + (size_t)(b * 2) * PLANES * S;
+  const int* wsx = wsy + (size_t)PLANES * S;
+
+  // the band's vertical coefficients -> LDS; column tid's horizontal ones -> registers
+  for (int i = tid; i < BAND * PLANES; i += THREADS) {
+    const int r = i / PLANES, q = i % PLANES;
+    const int v = wsy[(size_t)q * S + min(r0 + r, S - 1)];
+    if (q == 0) s_ymin[r] = v;
+    else if (q == 1) s_yn[r] = clampi(v, 0, TAPS);
+    else s_wy[r][q - 2] = v;
+  }
+  const int xc = min(tid, S - 1);
+  const int xmin_x = wsx[xc];
+  int wx[TAPS];
+#pragma unroll
+  for (int k = 0; k < TAPS; ++k) wx[k] = wsx[(size_t)(2 + k) * S + xc];
+  // vertical pass: a wave takes 64 / nq (row, channel) pairs at a time, lane -> (pair, quad of four output pixels); the divisions are per thread, not per item
+  const int nq = S >> 2, lane = tid & 63, per = 64 / nq, sub = lane / nq, xq = lane - sub * nq;
+  const int x = xq * 4, xs = flip ? S - 4 - x : x;
+  int r = r0;
+  while (r < r1) {
+    __syncthreads();      // the coefficients are staged; the previous run's intermediate has been read
+    const int lo = s_ymin[r - r0];
+    int e = r + 1;        // one output row needs at most TAPS <= NROWS source rows: every run advances
+    while (e < r1 && s_ymin[e - r0] + s_yn[e - r0] - lo <= NROWS) ++e;
+    const int nrows = clampi(s_ymin[e - 1 - r0] + s_yn[e - 1 - r0] - lo, 0, NROWS);
+
+    // horizontal pass: source rows lo .. lo + nrows of the box, output column tid
+    if (tid < S) {
+      for (int row = 0; row < nrows; ++row) {
+        const int sy = y0 + lo + row;
+        const bool in_y = sy >= 0 && sy < H0;
+        const unsigned char* line = image + (size_t)clampi(sy, 0, H0 - 1) * W0 * 3;
+        int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+#pragma unroll
+        for (int k = 0; k < TAPS; ++k) {
+          const int sx = x0 + xmin_x + k;
+          const bool ok = in_y && sx >= 0 && sx < W0;
+          const unsigned char* p = line + clampi(sx, 0, W0 - 1) * 3;
+          const int p0 = p[0], p1 = p[1], p2 = p[2];
+          const int w = ok ? wx[k] : 0;
+          a0 += p0 * w;
+          a1 += p1 * w;
+          a2 += p2 * w;
+        }
+        inter[0][row][tid] = (unsigned char)clampi(a0 >> 22, 0, 255);
+        inter[1][row][tid] = (unsigned char)clampi(a1 >> 22, 0, 255);
+        inter[2][row][tid] = (unsigned char)clampi(a2 >> 22, 0, 255);
+      }
+    }
+    __syncthreads();
+
+    // vertical pass and flip: four output pixels of one row and channel per item
+    const int pairs = (e - r) * 3;
+    for (int t = (tid >> 6) * per + sub; sub < per && t < pairs; t += (THREADS / 64) * per) {
+      const int c = t % 3, yy = r + t / 3;
+      const int ymin = s_ymin[yy - r0] - lo, yn = s_yn[yy - r0];
+      int acc[4] = {1 << 21, 1 << 21, 1 << 21, 1 << 21};
+      for (int k = 0; k < yn; ++k) {
+        const unsigned q = *(const unsigned*)&inter[c][clampi(ymin + k, 0, NROWS - 1)][xs];
+        const int w = s_wy[yy - r0][k];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] += (int)((q >> (8 * j)) & 255u) * w;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        out8[(((size_t)b * S + yy) * S + x + j) * 3 + c] = (unsigned char)clampi((flip ? acc[3 - j] : acc[j]) >> 22, 0, 255);
+    }
+    r = e;
+  }
+}
+
+
+// ---- image ops (include/devit_hip.h, "Image ops"): one workgroup per sample, the sample's S x S x 3 uint8 image in LDS through every layer --------
+constexpr int OPS_THREADS = 512;                                                // 8 waves: 256 VGPRs each, the staged pixels and the fp64 cubic fit without spills
+constexpr int OPS_PIX = (224 * 224 + OPS_THREADS - 1) / OPS_THREADS;            // 98 pixels per thread at the largest S, staged as one dword each
+constexpr int OPS_FIXED_LDS = 3 * 256 * 4 + 3 * 256 * 4 + 3 * 256 + 3 * 4 * 4 + DEVIT_AUGMENT_MAX_ERASE * 3 * 4 + 16;      // behind the image
+static_assert(224 * 224 * 3 + OPS_FIXED_LDS <= 163840, "the image and its tables fit one CU's LDS");
+
+__device__ __forceinline__ int blend8(int d, int u, float f) {
+#pragma clang fp contract(off)
+  const float df = (float)d;
+  const float r = df + f * ((float)u - df);
+  if (f >= 0.f && f <= 1.f) return clampi((int)r, 0, 255);
+  return r <= 0.f ? 0 : (r >= 255.f ? 255 : clampi((int)r, 0, 255));
+}
+
+__device__ __forceinline__ int luma8(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
+
+// ImageFilter.SMOOTH at an inner pixel, channel c
+__device__ __forceinline__ int smooth8(const unsigned char* img, int S, int y, int x, int c) {
+#pragma clang fp contract(off)
+  const float k1 = 1.0f / 13.0f, k5 = 5.0f / 13.0f;
+  float acc = 0.f;
+#pragma unroll
+  for (int j = -1; j <= 1; ++j)
+#pragma unroll
+    for (int i = -1; i <= 1; ++i) acc = acc + (float)img[((y + j) * S + x + i) * 3 + c] * ((i == 0 && j == 0) ? k5 : k1);
+  acc = acc + 0.5f;
+  return acc <= 0.f ? 0 : (acc >= 255.f ? 255 : (int)acc);
+}
+
+__device__ __forceinline__ double cubic4(double v1, double v2, double v3, double v4, double d) {
+#pragma clang fp contract(off)
+  const double p1 = v2, p2 = -v1 + v3, p3 = 2 * (v1 - v2) + v3 - v4, p4 = -v1 + v2 - v3 + v4;
+  return p1 + d * (p2 + d * (p3 + d * p4));
+}
+
+// one output pixel of Image.transform(AFFINE): r | g << 8 | b << 16
+__device__ __forceinline__ unsigned affine_pixel(const unsigned char* img, int S, int yo, int xo, const double (&m)[6], bool cubic, unsigned fill) {
+#pragma clang fp contract(off)
+  const double X = xo + 0.5, Y = yo + 0.5;
+  double xin = m[0] * X + m[1] * Y + m[2], yin = m[3] * X + m[4] * Y + m[5];
+  if (!(xin >= 0.0 && xin < (double)S && yin >= 0.0 && yin < (double)S)) return fill;      // (a NaN lands here)
+  xin -= 0.5;
+  yin -= 0.5;
+  const double fx = floor(xin), fy = floor(yin);
+  const double dx = xin - fx, dy = yin - fy;
+  const int x = (int)fx, y = (int)fy;      // -1 .. S - 1
+  unsigned px = 0;
+  if (cubic) {
+    int xc[4], row[4];
+    bool ok[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      xc[k] = clampi(x - 1 + k, 0, S - 1) * 3;
+      row[k] = clampi(y - 1 + k, 0, S - 1) * S * 3;
+      ok[k] = k == 0 || (y - 1 + k >= 0 && y - 1 + k < S);
+    }
+#pragma unroll 1
+    for (int c = 0; c < 3; ++c) {      // (one channel's sixteen taps at a time: the registers belong to the staged pixels)
+      double r[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const unsigned char* p = img + row[k] + c;
+        const double v = cubic4((double)p[xc[0]], (double)p[xc[1]], (double)p[xc[2]], (double)p[xc[3]], dx);
+        r[k] = (k == 0 || ok[k]) ? v : r[k > 0 ? k - 1 : 0];
+      }
+      const double v = cubic4(r[0], r[1], r[2], r[3], dy);
+      px |= (unsigned)(v <= 0.0 ? 0 : (v >= 255.0 ? 255 : (int)v)) << (8 * c);
+    }
+  } else {
+    const int x0 = clampi(x, 0, S - 1) * 3, x1 = clampi(x + 1, 0, S - 1) * 3;
+    const int r0 = clampi(y, 0, S - 1) * S * 3, r1 = clampi(y + 1, 0, S - 1) * S * 3;
+    const bool ok1 = y + 1 >= 0 && y + 1 < S;
+#pragma unroll 1
+    for (int c = 0; c < 3; ++c) {
+      const double a0 = (double)img[r0 + x0 + c], a1 = (double)img[r0 + x1 + c];
+      const double b0 = (double)img[r1 + x0 + c], b1 = (double)img[r1 + x1 + c];
+      const double v1 = a0 + (a1 - a0) * dx;
+      const double v2 = ok1 ? b0 + (b1 - b0) * dx : v1;
+      const double v = v1 + (v2 - v1) * dy;
+      px |= (unsigned)clampi((int)v, 0, 255) << (8 * c);
+    }
+  }
+  return px;
+}
+
+// One output pixel p of a neighbour op (Sharpness, the affine family) of layer l, read from the image at the start of LDS: r | g << 8 | b << 16
+__device__ __forceinline__ unsigned neighbour_pixel(int p, int S, const devit_augment_ops* __restrict__ op, int l) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const unsigned char* img = smem;
+  const int y = p / S, x = p - y * S;
+  if (op->op[l] == DEVIT_OP_SHARPNESS) {
+    const float f = op->factor[l];
+    const unsigned char* q = img + p * 3;
+    const bool inner = y > 0 && y < S - 1 && x > 0 && x < S - 1;
+    const int yc = clampi(y, 1, S - 2), xc = clampi(x, 1, S - 2);
+    unsigned v = 0;
+#pragma unroll 1
+    for (int c = 0; c < 3; ++c) {
+      const int u = q[c], s = inner ? smooth8(img, S, yc, xc, c) : u;
+      v |= (unsigned)blend8(s, u, f) << (8 * c);
+    }
+    return v;
+  }
+  double m[6];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) m[j] = op->matrix[l][j];
+  const unsigned fill = (unsigned)(op->fill[l][0] & 255) | (unsigned)(op->fill[l][1] & 255) << 8 | (unsigned)(op->fill[l][2] & 255) << 16;
+  return affine_pixel(img, S, y, x, m, op->filter[l] == DEVIT_AUG_BICUBIC, fill);
+}
+
+// FINISH: steps 3 and 4 of "Input augmentation" out of LDS into `out`; else the uint8 image into out8
+template <bool FINISH>
+__global__ __launch_bounds__(OPS_THREADS) void image_ops_kernel(const unsigned char* __restrict__ in, const devit_augment_ops* __restrict__ ops,
+                                                                int S, unsigned char* __restrict__ out8,
+                                                                const devit_augment_sample* __restrict__ table, Norm3 norm, unsigned k0,
+                                                                unsigned k1, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x, b = blockIdx.x, SS = S * S, n4 = SS * 3 / 4;      // S is a multiple of 16
+  unsigned char* img = smem;
+  unsigned* img32 = (unsigned*)smem;
+  int* s_hist = (int*)(smem + SS * 3);                     // [3][256]: counts, then their exclusive prefix sums
+  float* s_norm = (float*)(s_hist + 3 * 256);              // [3][256]
+  unsigned char* s_lut = (unsigned char*)(s_norm + 3 * 256);      // [3][256]
+  int* s_stat = (int*)(s_lut + 3 * 256);                   // [3][4]: lo, hi, non-empty bins, step
+  float* s_rand = (float*)(s_stat + 12);                   // [MAX_ERASE][3]
+  int* s_sum = (int*)(s_rand + DEVIT_AUGMENT_MAX_ERASE * 3);
+  const devit_augment_ops* op = ops + b;
+  const int n_ops = clampi(op->n_ops, 0, DEVIT_AUGMENT_MAX_OPS);
+  const int kmax = (SS + OPS_THREADS - 1) / OPS_THREADS;   // <= OPS_PIX
+
+  {
+    const unsigned* g = (const unsigned*)(in + (size_t)b * SS * 3);
+    for (int i = tid; i < n4; i += OPS_THREADS) img32[i] = g[i];
+  }
+  __syncthreads();
+
+#pragma unroll 1
+  for (int l = 0; l < n_ops; ++l) {
+    const int id = op->op[l];
+    const float f = op->factor[l];
+    const int arg = op->arg[l];
+    if (id == DEVIT_OP_COLOR) {                             // pointwise per pixel, in place
+      for (int p = tid; p < SS; p += OPS_THREADS) {
+        unsigned char* q = img + p * 3;
+        const int r = q[0], g = q[1], bl = q[2], L = luma8(r, g, bl);
+        q[0] = (unsigned char)blend8(L, r, f);
+        q[1] = (unsigned char)blend8(L, g, f);
+        q[2] = (unsigned char)blend8(L, bl, f);
+      }
+      __syncthreads();
+    } else if (id == DEVIT_OP_SHARPNESS || id == DEVIT_OP_ROTATE || (id >= DEVIT_OP_SHEAR_X && id <= DEVIT_OP_TRANSLATE_Y)) {
+      // neighbour ops: every output pixel of this thread into registers, a barrier, then back into the image
+      unsigned stage[OPS_PIX];
+#pragma unroll
+      for (int j = 0; j < OPS_PIX; ++j) stage[j] = 0;
+      int tl = tid;      // opaque per layer: the 98 write-back addresses are otherwise computed once before the layer loop and held in 98 registers
+      asm volatile("" : "+v"(tl));
+      // A shift register: the newest pixel enters at index 0 and everything moves up one, so every index is static and the array stays in
+      // registers (indexed by k it would live in scratch).  Pixels are taken last to first: pixel k ends at stage[k].
+#pragma unroll 1
+      for (int k = kmax - 1; k >= 0; --k) {
+        const unsigned v = neighbour_pixel(min(tl + k * OPS_THREADS, SS - 1), S, op, l);
+#pragma unroll
+        for (int j = OPS_PIX - 1; j > 0; --j) stage[j] = stage[j - 1];
+        stage[0] = v;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < OPS_PIX; ++j) {
+        const int p = min(tl + j * OPS_THREADS, SS - 1);      // (threads past the end staged the last pixel's own value: they store it once more)
+        if (j < kmax) {
+          unsigned char* q = img + p * 3;
+          q[0] = (unsigned char)stage[j];
+          q[1] = (unsigned char)(stage[j] >> 8);
+          q[2] = (unsigned char)(stage[j] >> 16);
+        }
+      }
+      __syncthreads();
+    } else if (id >= 0 && id < DEVIT_OP_COUNT) {           // a 3 x 256 table, applied in place
+      if (id == DEVIT_OP_AUTOCONTRAST || id == DEVIT_OP_EQUALIZE) {
+        for (int i = tid; i < 3 * 256; i += OPS_THREADS) s_hist[i] = 0;
+        __syncthreads();
+        for (int i = tid; i < n4; i += OPS_THREADS) {
+          const unsigned q = img32[i];
+          const int c0 = i % 3;                            // channel of byte 4 i
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int c = (c0 + j) % 3;
+            atomicAdd(&s_hist[c * 256 + ((q >> (8 * j)) & 255u)], 1);
+          }
+        }
+        __syncthreads();
+        if (tid < 3) {
+          int* h = s_hist + tid * 256;
+          int lo = 256, hi = -1, bins = 0, last = 0, total = 0;
+          for (int i = 0; i < 256; ++i) {
+            const int n = h[i];
+            if (n) {
+              if (lo == 256) lo = i;
+              hi = i;
+              ++bins;
+              last = n;
+            }
+            h[i] = total;
+            total += n;
+          }
+          s_stat[tid * 4 + 0] = lo;
+          s_stat[tid * 4 + 1] = hi;
+          s_stat[tid * 4 + 2] = bins;
+          s_stat[tid * 4 + 3] = (total - last) / 255;
+        }
+      } else if (id == DEVIT_OP_CONTRAST) {
+        if (tid == 0) *s_sum = 0;
+        __syncthreads();
+        int sum = 0;
+        for (int p = tid; p < SS; p += OPS_THREADS) sum += luma8(img[p * 3], img[p * 3 + 1], img[p * 3 + 2]);
+        atomicAdd(s_sum, sum);                             // integers: any order gives the same sum
+      }
+      __syncthreads();
+      for (int i = tid; i < 3 * 256; i += OPS_THREADS) {
+        const int c = i >> 8, u = i & 255;
+        int v = u;
+        if (id == DEVIT_OP_AUTOCONTRAST) {
+#pragma clang fp contract(off)
+          const int lo = s_stat[c * 4], hi = s_stat[c * 4 + 1];
+          if (hi > lo) {
+            const double scale = 255.0 / (double)(hi - lo), off = (double)(-lo) * scale;
+            v = clampi((int)((double)u * scale + off), 0, 255);
+          }
+        } else if (id == DEVIT_OP_EQUALIZE) {
+          const int step = s_stat[c * 4 + 3];
+          if (s_stat[c * 4 + 2] > 1 && step > 0) v = min(255, (step / 2 + s_hist[c * 256 + u]) / step);
+        } else if (id == DEVIT_OP_INVERT) {
+          v = 255 - u;
+        } else if (id == DEVIT_OP_POSTERIZE) {
+          v = u & ~((1 << (8 - clampi(arg, 0, 8))) - 1);
+        } else if (id == DEVIT_OP_SOLARIZE) {
+          v = u < arg ? u : 255 - u;
+        } else if (id == DEVIT_OP_SOLARIZE_ADD) {
+          v = u < 128 ? min(255, u + clampi(arg, 0, 255)) : u;
+        } else if (id == DEVIT_OP_BRIGHTNESS) {
+          v = blend8(0, u, f);
+        } else {                                           // DEVIT_OP_CONTRAST
+#pragma clang fp contract(off)
+          v = blend8(clampi((int)((double)*s_sum / (double)SS + 0.5), 0, 255), u, f);
+        }
+        s_lut[i] = (unsigned char)v;
+      }
+      __syncthreads();
+      for (int i = tid; i < n4; i += OPS_THREADS) {
+        const unsigned q = img32[i];
+        const int c0 = i % 3;
+        unsigned o = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o |= (unsigned)s_lut[((c0 + j) % 3) * 256 + ((q >> (8 * j)) & 255u)] << (8 * j);
+        img32[i] = o;
+      }
+      __syncthreads();
+    }
+  }
+
+  if constexpr (!FINISH) {
+    unsigned* g = (unsigned*)(out8 + (size_t)b * SS * 3);
+    for (int i = tid; i < n4; i += OPS_THREADS) g[i] = img32[i];
+  } else {
+    const devit_augment_sample* sp = table + b;
+    const int n_erase = clampi(sp->n_erase, 0, DEVIT_AUGMENT_MAX_ERASE), erase_mode = sp->erase_mode;
+    const unsigned long long N = sp->noise_base + (unsigned long long)b;
+    if (erase_mode == DEVIT_AUG_ERASE_RAND && tid < n_erase * 3) {
+      const int e = tid / 3, c = tid % 3;
+      s_rand[e * 3 + c] = normals4(noise_words(N, c, 0x80000000u + (unsigned)e, k0, k1))[0];
+    }
+    for (int i = tid; i < 3 * 256; i += OPS_THREADS) {
+      const int c = i >> 8;
+      s_norm[i] = ((float)(i & 255) / 255.0f - norm.mean[c]) / norm.std[c];
+    }
+    __syncthreads();
+    const int nq = S >> 2, items = 3 * S * nq;
+    for (int t = tid; t < items; t += OPS_THREADS) {
+      const int xq = t % nq, rest = t / nq, yy = rest % S, c = rest / S, x = xq * 4;
+      const unsigned char* q = img + (yy * S + x) * 3 + c;
+      f32x4 v;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = s_norm[c * 256 + q[3 * j]];
+      unsigned inside = 0;      // bit 4 e + j: pixel j lies in box e
+      for (int eb = 0; eb < n_erase; ++eb) {
+        const int top = sp->erase[eb][0], left = sp->erase[eb][1], eh = sp->erase[eb][2], ew = sp->erase[eb][3];
+        if (yy >= top && yy - top < eh) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (x + j >= left && x + j - left < ew) inside |= 1u << (4 * eb + j);
+        }
+      }
+      if (inside) {
+        f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        if (erase_mode == DEVIT_AUG_ERASE_PIXEL) z = normals4(noise_words(N, c, (unsigned)(yy * S + x) >> 2, k0, k1));
+#pragma unroll
+        for (int eb = 0; eb < DEVIT_AUGMENT_MAX_ERASE; ++eb) {      // later boxes win
+          const float zr = erase_mode == DEVIT_AUG_ERASE_RAND ? s_rand[eb * 3 + c] : 0.f;
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (inside >> (4 * eb + j) & 1u) v[j] = erase_mode == DEVIT_AUG_ERASE_PIXEL ? z[j] : zr;
+        }
+      }
+      store16_stream(out + (((size_t)b * 3 + c) * S + yy) * S + x, v);
+    }
+  }
+}
+
+template <bool FINISH>
+int launch_image_ops(const char* who, const unsigned char* in, const devit_augment_ops* ops, int B, int S, unsigned char* out8,
+                     const devit_augment_sample* table, Norm3 norm, unsigned long long seed, float* out, void* stream) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute((const void*)image_ops_kernel<FINISH>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       224 * 224 * 3 + OPS_FIXED_LDS);
+    DEVIT_CHECK(e == hipSuccess, DEVIT_ERR_LAUNCH, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(image_ops_kernel<FINISH>, dim3(B), dim3(OPS_THREADS), S * S * 3 + OPS_FIXED_LDS, (hipStream_t)stream, in, ops, S, out8,
+                     table, norm, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), out);
+  DEVIT_LAUNCH_CHECK();
+  return DEVIT_OK;
+}
+
 int check_geometry(const char* who, int B, int S) {
   DEVIT_CHECK(B > 0 && B <= 65535, DEVIT_ERR_ARG, "%s: B = %d, 1 .. 65535 samples per call", who, B);
   DEVIT_CHECK(devit_patch_grid(3, S, S, 16) != 0, DEVIT_ERR_SHAPE, "%s: output side %d: " DEVIT_PATCH_SIZES_MSG, who, S);
@@ -289,4 +701,42 @@ extern "C" int devit_augment_batch(const unsigned char* src, int n, int H0, int 
                      S, (const int*)workspace, norm, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), out);
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
+}
+
+extern "C" int devit_image_ops(const unsigned char* in, const devit_augment_ops* ops, int B, int S, unsigned char* out, void* stream) {
+  if (int rc = check_geometry("devit_image_ops", B, S)) return rc;
+  DEVIT_CHECK(in && ops && out, DEVIT_ERR_ARG, "devit_image_ops: null pointer");
+  DEVIT_CHECK((((uintptr_t)in | (uintptr_t)out) & 3) == 0, DEVIT_ERR_ARG, "devit_image_ops: in and out must be 4-byte aligned");
+  return launch_image_ops<false>("devit_image_ops", in, ops, B, S, out, nullptr, Norm3{}, 0ull, nullptr, stream);
+}
+
+extern "C" size_t devit_augment_ops_workspace(int B, int S) {
+  if (B <= 0 || S <= 0) return 0;
+  return ((devit_augment_workspace(B, S) + 15) & ~(size_t)15) + (size_t)B * S * S * 3;
+}
+
+extern "C" int devit_augment_batch_ops(const unsigned char* src, int n, int H0, int W0, const int* idx, const devit_augment_sample* table,
+                                       const devit_augment_ops* ops, int B, int S, const float* mean, const float* std,
+                                       unsigned long long seed, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_geometry("devit_augment_batch_ops", B, S)) return rc;
+  DEVIT_CHECK(src && idx && table && ops && mean && std && out && workspace, DEVIT_ERR_ARG, "devit_augment_batch_ops: null pointer");
+  DEVIT_CHECK(n > 0 && H0 > 0 && W0 > 0 && H0 <= 4096 && W0 <= 4096, DEVIT_ERR_ARG,
+              "devit_augment_batch_ops: a set of %d images of %d x %d (sides 1 .. 4096)", n, H0, W0);
+  DEVIT_CHECK((((uintptr_t)out | (uintptr_t)workspace) & 15) == 0, DEVIT_ERR_ARG,
+              "devit_augment_batch_ops: out and the workspace must be 16-byte aligned");
+  DEVIT_CHECK(workspace_bytes >= devit_augment_ops_workspace(B, S), DEVIT_ERR_ARG,
+              "devit_augment_batch_ops: the workspace holds %zu bytes, devit_augment_ops_workspace(B, S) is %zu", workspace_bytes,
+              devit_augment_ops_workspace(B, S));
+  Norm3 norm;
+  for (int c = 0; c < 3; ++c) {
+    DEVIT_CHECK(std[c] > 0.f, DEVIT_ERR_ARG, "devit_augment_batch_ops: std[%d] = %g must be positive", c, (double)std[c]);
+    norm.mean[c] = mean[c];
+    norm.std[c] = std[c];
+  }
+  unsigned char* window = (unsigned char*)workspace + ((devit_augment_workspace(B, S) + 15) & ~(size_t)15);
+  if (int rc = devit_augment_coeffs(table, B, S, workspace, workspace_bytes, stream)) return rc;
+  hipLaunchKernelGGL(augment_u8_kernel, dim3((S + BAND - 1) / BAND, B), dim3(THREADS), 0, (hipStream_t)stream, src, n, H0, W0, idx, table, S,
+                     (const int*)workspace, window);
+  DEVIT_LAUNCH_CHECK();
+  return launch_image_ops<true>("devit_augment_batch_ops", window, ops, B, S, nullptr, table, norm, seed, out, stream);
 }

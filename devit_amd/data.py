@@ -2,7 +2,8 @@
 parameter row per sample, and one HIP stage (csrc/augment.hip: devit_augment_batch) turns a batch of indices into the normalized fp32
 batch [B,3,S,S] that Mixup and the patch-row kernels consume.  It stands where the reference has a DataLoader over
 timm.data.transforms_factory.transforms_imagenet_train / the Resize + CenterCrop eval stack (data/get_dataset.py:71-109): crop and resize
-(or the padded crop at 32 pixels), horizontal flip, ToTensor, Normalize, RandomErasing.  RandAugment and ColorJitter are not built.
+(or the padded crop at 32 pixels), horizontal flip, RandAugment's `rand-...-inc1` layers or ColorJitter without hue on the uint8 window
+(devit_augment_batch_ops; the header's "Image ops"), ToTensor, Normalize, RandomErasing.
 
 The draws are timm 0.5.4's own scalar formulas on a private random.Random; the arithmetic is the header's ("Input augmentation").
 Nothing here imports torchvision or timm; PIL only to read an image folder."""
@@ -24,6 +25,9 @@ IMAGENET_DEFAULT_STD = (0.229, 0.224, 0.225)
 # host mirror of devit_augment_sample (120 bytes, _lib.AugmentSample)
 AUG_SAMPLE_DTYPE = np.dtype([(n, "<i4") for n in ("y0", "x0", "h", "w", "Rh", "Rw", "oy", "ox", "filter", "flip", "n_erase", "erase_mode")] +
                             [("erase", "<i4", (4, 4)), ("noise_base", "<u8")])
+# host mirror of devit_augment_ops (328 bytes, _lib.AugmentOps): a sample's image-op layers
+AUG_OPS_DTYPE = np.dtype([("n_ops", "<i4"), ("reserved", "<i4"), ("op", "<i4", (4,)), ("filter", "<i4", (4,)), ("factor", "<f4", (4,)),
+                          ("arg", "<i4", (4,)), ("fill", "<i4", (4, 4)), ("matrix", "<f8", (4, 6))])
 FILTERS = {"bilinear": L.AUG_BILINEAR, "bicubic": L.AUG_BICUBIC}
 ERASE_MODES = {"const": L.AUG_ERASE_CONST, "rand": L.AUG_ERASE_RAND, "pixel": L.AUG_ERASE_PIXEL}
 IMG_EXTENSIONS = ('.jpg', '.jpeg', '.png', '.ppm', '.bmp', '.pgm', '.tif', '.tiff', '.webp')      # torchvision's ImageFolder list
@@ -48,6 +52,52 @@ def _check_taps(length, R, filt, what):
         name = {v: k for k, v in FILTERS.items()}[filt]
         raise ValueError(f"{what}: resizing {length} source pixels to {R} with the {name} filter needs {n} taps per output pixel, the resampling "
                          f"kernel holds {L.AUGMENT_TAPS} (a crop side up to 3 x the output side for bicubic, 6 x for bilinear)")
+
+
+def parse_auto_augment(config):
+    """timm's RandAugment config string 'rand-m<int>-mstd<float>-inc<0|1>-n<int>' -> dict(m, n, mstd) (defaults m 10, n 2, mstd 0).  Only the
+    `inc1` operation set is built; ValueError names what a string asks for beyond that."""
+    parts = str(config).split("-")
+    if parts[0] != "rand":
+        what = {"augmix": "AugMix", "original": "the AutoAugment policy 'original'", "originalr": "the AutoAugment policy 'originalr'",
+                "v0": "the AutoAugment policy 'v0'", "v0r": "the AutoAugment policy 'v0r'"}.get(parts[0], f"the policy {parts[0]!r}")
+        raise ValueError(f"auto_augment {config!r}: {what} is not built, only RandAugment's rand-m<M>-mstd<F>-inc1-n<N>")
+    out, inc = {"m": 10, "n": 2, "mstd": 0.0}, 0
+    for part in parts[1:]:
+        try:
+            if part.startswith("mstd"):
+                out["mstd"] = float(part[4:])
+            elif part.startswith("inc"):
+                inc = int(bool(int(part[3:])))
+            elif part.startswith("m"):
+                out["m"] = int(part[1:])
+            elif part.startswith("n"):
+                out["n"] = int(part[1:])
+            elif part.startswith("w"):
+                raise ValueError(f"auto_augment {config!r}: the weighted op choice ({part}) is not built")
+            else:
+                raise ValueError(f"auto_augment {config!r}: unknown section {part!r} (m<int>, mstd<float>, inc1, n<int>)")
+        except ValueError as e:
+            if "auto_augment" in str(e):
+                raise
+            raise ValueError(f"auto_augment {config!r}: section {part!r} does not parse (m<int>, mstd<float>, inc1, n<int>)")
+    if not inc:
+        raise ValueError(f"auto_augment {config!r}: the non-increasing op set (inc0, timm's default) is not built: add -inc1")
+    if not 1 <= out["n"] <= L.AUGMENT_MAX_OPS:
+        raise ValueError(f"auto_augment {config!r}: n = {out['n']}: the op stage holds 1 .. {L.AUGMENT_MAX_OPS} layers per sample")
+    if out["m"] < 0 or not out["mstd"] >= 0:
+        raise ValueError(f"auto_augment {config!r}: m and mstd must not be negative")
+    return out
+
+
+def rotate_matrix(deg, S):
+    """PIL's Image.rotate(deg) about the centre of an S x S image, as the six doubles of Image.transform(AFFINE)"""
+    t = -math.radians(deg % 360.0)
+    m = [round(math.cos(t), 15), round(math.sin(t), 15), 0.0, round(-math.sin(t), 15), round(math.cos(t), 15), 0.0]
+    c = S / 2.0
+    m[2] = m[0] * (-c) + m[1] * (-c) + m[2] + c
+    m[5] = m[3] * (-c) + m[4] * (-c) + m[5] + c
+    return m
 
 
 # ---- the resident set ------------------------------------------------------------------------------------------------------------------------
@@ -135,8 +185,12 @@ class TrainAugment:
     (seed, rank) and carried across epochs.  S == 32: the crop is RandomCrop(S, padding=4) at unit scale (data/get_dataset.py:92-96)."""
 
     def __init__(self, S, scale=(0.08, 1.0), ratio=(3. / 4., 4. / 3.), interpolation='bicubic', hflip=0.5, re_prob=0., re_mode='const',
-                 re_count=1, seed=0, rank=0, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD):
+                 re_count=1, seed=0, rank=0, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD, auto_augment=None, color_jitter=None):
         self.S = ops.check_img_size(S, exc=ValueError)
+        self.rand = parse_auto_augment(auto_augment) if auto_augment and auto_augment != 'none' else None
+        self.color_jitter = float(color_jitter) if color_jitter and self.rand is None else 0.      # timm: if auto_augment ... elif color_jitter
+        if self.color_jitter < 0:
+            raise ValueError(f"TrainAugment: color_jitter {color_jitter} must not be negative")
         if interpolation != 'random' and interpolation not in FILTERS:
             raise ValueError(f"TrainAugment: interpolation {interpolation!r}: bicubic, bilinear or random")
         re_mode = re_mode or 'const'
@@ -147,8 +201,13 @@ class TrainAugment:
         self.scale, self.ratio, self.interpolation, self.hflip = tuple(scale), tuple(ratio), interpolation, hflip
         self.re_prob, self.re_mode, self.re_count = re_prob, re_mode, re_count
         self.seed, self.rank, self.mean, self.std = int(seed), int(rank), tuple(mean), tuple(std)
+        self.fill = tuple(min(255, round(255 * m)) for m in self.mean)
         self.rng = random.Random(self.seed * 65536 + self.rank)
         self.drawn = 0            # samples drawn so far: the noise counter base of the next batch
+
+    @property
+    def has_ops(self):
+        return self.rand is not None or self.color_jitter > 0
 
     def check_set(self, H0, W0):
         """Refuse a set this transform cannot serve (the tap limit of the resampling kernel), before anything is drawn."""
@@ -199,9 +258,67 @@ class TrainAugment:
                     break
         return boxes
 
+    def _layers(self):
+        """the image-op layers of one sample [(op, filter, factor, arg, matrix)]: RandAugment's n draws (op, applied?, magnitude, sign, filter)
+        or ColorJitter's order and factors"""
+        rng, S, out = self.rng, self.S, []
+        if self.rand is None:
+            order = [0, 1, 2]
+            rng.shuffle(order)
+            cj = self.color_jitter
+            f = [rng.uniform(max(0., 1. - cj), 1. + cj) for _ in range(3)]            # brightness, contrast, saturation: timm's argument order
+            return [((L.OP_BRIGHTNESS, L.OP_CONTRAST, L.OP_COLOR)[k], L.AUG_BILINEAR, f[k], 0, None) for k in order]
+        m, mstd = self.rand["m"], self.rand["mstd"]
+        for _ in range(self.rand["n"]):
+            op = rng.randrange(L.OP_COUNT)
+            if rng.random() > 0.5:
+                continue
+            mag = float(m)
+            if mstd > 0:
+                mag = rng.uniform(0, mag) if mstd == float('inf') else rng.gauss(mag, mstd)
+            lvl = min(10., max(0., mag)) / 10.
+            factor, arg, matrix, filt = 1., 0, None, L.AUG_BILINEAR
+            if op in (L.OP_ROTATE, L.OP_SHEAR_X, L.OP_SHEAR_Y, L.OP_TRANSLATE_X, L.OP_TRANSLATE_Y, L.OP_COLOR, L.OP_CONTRAST, L.OP_BRIGHTNESS,
+                      L.OP_SHARPNESS):
+                v = lvl * {L.OP_ROTATE: 30., L.OP_SHEAR_X: 0.3, L.OP_SHEAR_Y: 0.3, L.OP_TRANSLATE_X: 0.45, L.OP_TRANSLATE_Y: 0.45}.get(op, 0.9)
+                if rng.random() > 0.5:
+                    v = -v
+                if op == L.OP_ROTATE:
+                    matrix = rotate_matrix(v, S)
+                elif op == L.OP_SHEAR_X:
+                    matrix = (1., v, 0., 0., 1., 0.)
+                elif op == L.OP_SHEAR_Y:
+                    matrix = (1., 0., 0., v, 1., 0.)
+                elif op == L.OP_TRANSLATE_X:
+                    matrix = (1., 0., v * S, 0., 1., 0.)
+                elif op == L.OP_TRANSLATE_Y:
+                    matrix = (1., 0., 0., 0., 1., v * S)
+                else:
+                    factor = 1. + v
+                if matrix is not None:
+                    filt = rng.choice((L.AUG_BILINEAR, L.AUG_BICUBIC)) if self.interpolation == 'random' else FILTERS[self.interpolation]
+            elif op == L.OP_POSTERIZE:
+                arg = 4 - int(lvl * 4)
+            elif op == L.OP_SOLARIZE:
+                arg = 256 - int(lvl * 256)
+            elif op == L.OP_SOLARIZE_ADD:
+                arg = int(lvl * 110)
+            out.append((op, filt, factor, arg, matrix))
+        return out
+
     def draw(self, B, H0, W0):
-        """-> AUG_SAMPLE_DTYPE [B]: crop, interpolation if random, flip, erasing per sample"""
+        """-> AUG_SAMPLE_DTYPE [B]: crop, interpolation if random, flip, erasing per sample (a transform without image-op layers)"""
+        if self.has_ops:
+            raise ValueError("TrainAugment.draw: this transform draws image-op layers too: draw_with_ops returns both tables")
+        return self.draw_with_ops(B, H0, W0)[0]
+
+    def draw_with_ops(self, B, H0, W0):
+        """-> (AUG_SAMPLE_DTYPE [B], AUG_OPS_DTYPE [B] or None): crop, interpolation if random, flip, the image-op layers, erasing per sample"""
         S, rng = self.S, self.rng
+        layers = np.zeros(B, dtype=AUG_OPS_DTYPE) if self.has_ops else None
+        if layers is not None:
+            layers["matrix"][:, :, 0] = layers["matrix"][:, :, 4] = 1.
+            layers["fill"][:, :, :3] = self.fill
         cols, erase = [], np.zeros((B, 4, 4), dtype=np.int32)      # (columns are filled at once: a field store per sample costs more than its draw)
         for b in range(B):
             if S == 32:
@@ -212,6 +329,13 @@ class TrainAugment:
                     raise ValueError(f"TrainAugment: drew an empty {h} x {w} crop on {H0} x {W0} images (scale {self.scale})")
                 filt = rng.choice((L.AUG_BILINEAR, L.AUG_BICUBIC)) if self.interpolation == 'random' else FILTERS[self.interpolation]
             flip = int(rng.random() < self.hflip) if self.hflip > 0. else 0
+            if layers is not None:
+                row = layers[b]
+                for k, (op, lf, factor, arg, matrix) in enumerate(self._layers()):
+                    row["op"][k], row["filter"][k], row["factor"][k], row["arg"][k] = op, lf, factor, arg
+                    if matrix is not None:
+                        row["matrix"][k] = matrix
+                    row["n_ops"] = k + 1
             boxes = self._erase() if self.re_prob > 0. else ()
             if boxes:
                 erase[b, :len(boxes)] = boxes
@@ -223,7 +347,7 @@ class TrainAugment:
         tab["Rh"], tab["Rw"], tab["erase_mode"], tab["erase"] = S, S, ERASE_MODES[self.re_mode], erase
         tab["noise_base"] = (self.rank << 48) + self.drawn
         self.drawn += B
-        return tab
+        return tab, layers
 
     def state_dict(self):
         return {"rng": self.rng.getstate(), "drawn": self.drawn}
@@ -317,9 +441,45 @@ def check_table(tab, H0, W0, S):
         _check_taps(*key, "augment_batch")
 
 
-def augment_batch(src, idx, table, S, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD, seed=0, out=None, table_dev=None):
+def check_ops_table(layers, B):
+    """ValueError for an image-op table the header's definition does not cover (the kernel is memory-safe for any bytes, as above)."""
+    if layers.dtype != AUG_OPS_DTYPE or layers.ndim != 1 or layers.shape[0] != B:
+        raise ValueError(f"image ops: the table is a 1-d numpy array of {B} AUG_OPS_DTYPE rows")
+    n = layers["n_ops"]
+    if ((n < 0) | (n > L.AUGMENT_MAX_OPS)).any():
+        raise ValueError(f"image ops: n_ops must lie in 0 .. {L.AUGMENT_MAX_OPS}")
+    live = np.arange(L.AUGMENT_MAX_OPS)[None, :] < n[:, None]
+    if (live & ((layers["op"] < 0) | (layers["op"] >= L.OP_COUNT))).any():
+        raise ValueError(f"image ops: op ids are 0 .. {L.OP_COUNT - 1}")
+    affine = live & np.isin(layers["op"], (L.OP_ROTATE, L.OP_SHEAR_X, L.OP_SHEAR_Y, L.OP_TRANSLATE_X, L.OP_TRANSLATE_Y))
+    if (affine & ~np.isin(layers["filter"], (L.AUG_BILINEAR, L.AUG_BICUBIC))).any():
+        raise ValueError("image ops: the filter of an affine op is 1 (bilinear) or 2 (bicubic)")
+    if (affine & ~np.isfinite(layers["matrix"]).all(axis=2)).any():
+        raise ValueError("image ops: the matrix of an affine op must be finite")
+    if (live & ~np.isfinite(layers["factor"])).any():
+        raise ValueError("image ops: the blend factor must be finite")
+    if (live & ((layers["fill"] < 0) | (layers["fill"] > 255)).any(axis=2)).any():
+        raise ValueError("image ops: fill levels are 0 .. 255")
+
+
+def image_ops(images, layers):
+    """uint8 [B,S,S,3] on the device, AUG_OPS_DTYPE [B] on the host -> uint8 [B,S,S,3]: the layers alone (devit_image_ops)"""
+    L.require_device(images)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or images.shape[1] != images.shape[2] or not images.is_contiguous():
+        raise ValueError(f"image_ops: images must be a contiguous uint8 [B,S,S,3] tensor, got {images.dtype} {tuple(images.shape)}")
+    B, S = int(images.shape[0]), ops.check_img_size(int(images.shape[1]), exc=ValueError)
+    check_ops_table(layers, B)
+    ops_dev = upload(np.ascontiguousarray(layers).view(np.uint8).reshape(-1), images.device)
+    out = torch.empty_like(images)
+    ops.call("devit_image_ops", ptr(images), ptr(ops_dev), B, S, ptr(out), stream_ptr())
+    return out
+
+
+def augment_batch(src, idx, table, S, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD, seed=0, out=None, table_dev=None, layers=None,
+                  layers_dev=None):
     """src uint8 [n,H0,W0,3] and idx int32 [B] on the device, table: AUG_SAMPLE_DTYPE [B] on the host (validated here, then uploaded)
-    -> fp32 [B,3,S,S] (devit_augment_batch).  table_dev: the table's bytes already on the device (the caller validated and uploaded them)."""
+    -> fp32 [B,3,S,S] (devit_augment_batch).  table_dev: the table's bytes already on the device (the caller validated and uploaded them).
+    layers: AUG_OPS_DTYPE [B], the image-op layers between flip and ToTensor (devit_augment_batch_ops; layers_dev as table_dev)."""
     L.require_device(src)
     if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3 or not src.is_contiguous():
         raise ValueError(f"augment_batch: src must be a contiguous uint8 [n,H0,W0,3] tensor, got {src.dtype} {tuple(src.shape)}")
@@ -337,9 +497,18 @@ def augment_batch(src, idx, table, S, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_D
         out = torch.empty((B, 3, S, S), dtype=torch.float32, device=src.device)
     elif out.dtype != torch.float32 or out.shape[1:] != (3, S, S) or out.shape[0] < B or not out.is_contiguous() or out.device != src.device:
         raise ValueError("augment_batch: out must be a contiguous fp32 [>=B,3,S,S] tensor on the set's device")
+    m3, s3 = (L.C.c_float * 3)(*mean), (L.C.c_float * 3)(*std)
+    if layers is not None:
+        if layers_dev is None:
+            check_ops_table(layers, B)
+            layers_dev = upload(np.ascontiguousarray(layers).view(np.uint8).reshape(-1), src.device)
+        nbytes = L.load().devit_augment_ops_workspace(B, S)
+        ws = ops.workspace(src.device, nbytes)
+        ops.call("devit_augment_batch_ops", ptr(src), n, H0, W0, ptr(idx), ptr(table_dev), ptr(layers_dev), B, S, m3, s3,
+                 int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out), ptr(ws), nbytes, stream_ptr())
+        return out
     nbytes = L.load().devit_augment_workspace(B, S)
     ws = ops.workspace(src.device, nbytes)
-    m3, s3 = (L.C.c_float * 3)(*mean), (L.C.c_float * 3)(*std)
     ops.call("devit_augment_batch", ptr(src), n, H0, W0, ptr(idx), ptr(table_dev), B, S, m3, s3, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out),
              ptr(ws), nbytes, stream_ptr())
     return out
@@ -361,14 +530,19 @@ class DeviceLoader:
     def _batch(self, indices):
         ds, tf = self.dataset, self.transform
         B, (H0, W0) = len(indices), ds.size
-        table = tf.draw(B, H0, W0)
+        table, layers = tf.draw_with_ops(B, H0, W0) if getattr(tf, "has_ops", False) else (tf.draw(B, H0, W0), None)
         idx = np.asarray(indices, dtype=np.int32)
         if idx.min() < 0 or idx.max() >= len(ds):
             raise IndexError(f"DeviceLoader: the sampler yields indices outside 0 .. {len(ds) - 1}")
         pad = (-idx.nbytes) % 8                   # the table's 64-bit field stays aligned behind the indices
-        both = upload(np.concatenate([idx.view(np.uint8), np.zeros(pad, np.uint8), table.view(np.uint8).reshape(-1)]), ds.images.device)
-        idx_dev = both[:idx.nbytes].view(torch.int32)
-        images = augment_batch(ds.images, idx_dev, table, tf.S, tf.mean, tf.std, tf.seed, table_dev=both[idx.nbytes + pad:])
+        parts = [idx.view(np.uint8), np.zeros(pad, np.uint8), table.view(np.uint8).reshape(-1)]
+        if layers is not None:
+            check_ops_table(layers, B)
+            parts.append(layers.view(np.uint8).reshape(-1))       # (120-byte rows: the layers' doubles stay 8-byte aligned behind them)
+        both = upload(np.concatenate(parts), ds.images.device)
+        idx_dev, at = both[:idx.nbytes].view(torch.int32), idx.nbytes + pad
+        images = augment_batch(ds.images, idx_dev, table, tf.S, tf.mean, tf.std, tf.seed, table_dev=both[at:at + table.nbytes], layers=layers,
+                               layers_dev=both[at + table.nbytes:] if layers is not None else None)
         return images, ds.labels.index_select(0, idx_dev.long())
 
     def __iter__(self):

@@ -84,7 +84,10 @@ def get_args_parser():
     a('--synthetic', type=int, default=0, metavar='STEPS', help='train on STEPS random on-device batches per epoch')
     a('--device-data', action='store_true', default=False,
       help='keep the uint8 dataset resident on the device and crop, resize, flip, normalize and erase there (devit_amd.data; DESIGN.md section 15): '
-           'needs no torchvision / timm.  RandAugment and ColorJitter are not built: give --aa none --color-jitter 0')
+           'needs no torchvision / timm.  RandAugment and ColorJitter need --device-aug; without it give --aa none --color-jitter 0')
+    a('--device-aug', action='store_true', default=False,
+      help='with --device-data: run --aa rand-m<M>-mstd<F>-inc1-n<N> (RandAugment) or --color-jitter (no hue), and --no_aug\'s stack, on the device too, '
+           'on the uint8 image held in LDS between flip and ToTensor (DESIGN.md section 16)')
     a('--deterministic', action='store_true', default=False,
       help='fixed-order reductions instead of fp32 atomics in arrival order (devit_amd.ops.set_deterministic; DESIGN.md section 14): the same '
            '--seed, inputs and launch configuration give the same bits on every run at world size 1; +0.2 %% on the bs-256 DEKD step, 256 MiB of workspace')
@@ -196,19 +199,31 @@ def build_loaders(args, num_classes, device, provider="division", plain_sampler_
 
 
 def check_device_data(args):
-    """--device-data builds the reference's transform stack without RandAugment and ColorJitter: refuse the flags that ask for them (and --no_aug,
-    whose stack is timm's default one with both) instead of silently training on something else."""
+    """--device-data builds the reference's transform stack; RandAugment and ColorJitter (and --no_aug, whose stack is timm's default one with
+    ColorJitter) only with --device-aug: without it, refuse the flags that ask for them instead of silently training on something else."""
     if not getattr(args, 'device_data', False):
+        if getattr(args, 'device_aug', False):
+            raise SystemExit("--device-aug runs the image ops of the --device-data stage: give --device-data too")
         return
     if args.synthetic > 0:
         raise SystemExit("--device-data and --synthetic are two sources of batches: give one")
     missing = []
-    if (args.aa or 'none').lower() != 'none':
-        missing.append(f"--aa {args.aa} (RandAugment / AutoAugment is not built: --aa none)")
-    if args.color_jitter:
-        missing.append(f"--color-jitter {args.color_jitter} (ColorJitter is not built: --color-jitter 0)")
-    if getattr(args, 'no_aug', False):
-        missing.append("--no_aug (timm's default training stack, which includes ColorJitter, is not built)")
+    if getattr(args, 'device_aug', False):
+        if (args.aa or 'none').lower() != 'none' and not getattr(args, 'no_aug', False):
+            from devit_amd import data
+            try:
+                data.parse_auto_augment(args.aa)
+            except ValueError as e:
+                raise SystemExit("--device-data --device-aug: " + str(e))
+        if args.color_jitter < 0:
+            raise SystemExit(f"--device-data --device-aug --color-jitter {args.color_jitter}: must not be negative")
+    else:
+        if (args.aa or 'none').lower() != 'none':
+            missing.append(f"--aa {args.aa} (RandAugment runs on the device only with --device-aug; AutoAugment is not built: --aa none)")
+        if args.color_jitter:
+            missing.append(f"--color-jitter {args.color_jitter} (ColorJitter runs on the device only with --device-aug: --color-jitter 0)")
+        if getattr(args, 'no_aug', False):
+            missing.append("--no_aug (timm's default training stack, which includes ColorJitter, needs --device-aug)")
     if missing:
         raise SystemExit("--device-data: " + "; ".join(missing))
     if args.train_interpolation not in ('bicubic', 'bilinear', 'random'):
@@ -246,8 +261,13 @@ def build_device_loaders(args, num_classes, device, provider, plain_sampler_over
     else:
         sampler_val = torch.utils.data.SequentialSampler(test_ds)
     try:
-        train_tf = data.TrainAugment(args.input_size, interpolation=args.train_interpolation, re_prob=args.reprob, re_mode=args.remode or 'const',
-                                     re_count=args.recount if args.reprob > 0 else 1, seed=args.seed, rank=rank)
+        aa = args.aa if (args.aa or 'none').lower() != 'none' else None
+        if getattr(args, 'no_aug', False):      # timm's default training stack: ColorJitter 0.4, bilinear, no RandAugment, no erasing
+            train_tf = data.TrainAugment(args.input_size, interpolation='bilinear', seed=args.seed, rank=rank, color_jitter=0.4)
+        else:
+            train_tf = data.TrainAugment(args.input_size, interpolation=args.train_interpolation, re_prob=args.reprob, re_mode=args.remode or 'const',
+                                         re_count=args.recount if args.reprob > 0 else 1, seed=args.seed, rank=rank,
+                                         **(dict(auto_augment=aa, color_jitter=args.color_jitter) if getattr(args, 'device_aug', False) else {}))
         train_loader = data.DeviceLoader(train_ds, sampler_train, args.batch_size, train_tf, drop_last=True)
         val_loader = data.DeviceLoader(test_ds, sampler_val, args.eval_batch_size, data.EvalTransform(args.input_size), drop_last=False)
     except ValueError as e:

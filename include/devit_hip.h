@@ -46,7 +46,7 @@ DEVIT_API const char* devit_last_error(void); /* host string, thread-local, vali
 DEVIT_API int devit_check_device(int dev);
 /* sizeof() of the ABI's structs as THIS library was compiled (which: 0 devit_epilogue, 1 devit_operand, 2 devit_block_weights,
  * 3 devit_block_wgrads, 4 devit_block_acts, 5 devit_block_bwd_io, 6 devit_index_job, 7 devit_wgrad_job, 8 devit_launch_info, 9 devit_block_dropout,
- * 10 devit_mix_sample, 11 devit_opt_chunk, 12 devit_tail_acts, 13 devit_tail_bwd_io, 14 devit_augment_sample; anything else: 0).  A binding
+ * 10 devit_mix_sample, 11 devit_opt_chunk, 12 devit_tail_acts, 13 devit_tail_bwd_io, 14 devit_augment_sample, 15 devit_augment_ops; anything else: 0).  A binding
  * compares them with its own mirrors once at load time: a stale mirror of a struct that is passed as an ARRAY would otherwise be misread
  * from its second element on, with no error. */
 DEVIT_API size_t devit_abi_struct_size(int which);
@@ -859,6 +859,75 @@ DEVIT_API int devit_augment_coeffs(const devit_augment_sample* table /* device, 
 DEVIT_API int devit_augment_batch(const unsigned char* src, int n, int H0, int W0, const int* idx, const devit_augment_sample* table, int B,
                         int S, const float* mean /* host [3] */, const float* std /* host [3] */, unsigned long long seed, float* out,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Image ops: RandAugment's fifteen `rand-...-inc1` operations (timm 0.5.4 auto_augment.py, _RAND_INCREASING_TRANSFORMS) and the three
+ * enhancement steps of ColorJitter without hue, on the S x S uint8 window between step 2 (flip) and step 3 (ToTensor) above, bit for bit as
+ * PIL computes them.  Every draw is the host's: sample b applies layers 0 .. n_ops - 1 of entry b of a device table of devit_augment_ops
+ * (struct id 15 of devit_abi_struct_size, 328 bytes), each layer on the result of the one before.  A layer is (op, filter, factor, arg,
+ * matrix, fill); u is a uint8 level of the layer's input, all of the image is read before any of it is replaced.
+ *   Invert        255 - u
+ *   Posterize     u & ~(2^(8 - arg) - 1), arg = bits clamped to 0 .. 8 (0: black)
+ *   Solarize      u if u < arg else 255 - u
+ *   SolarizeAdd   min(255, u + arg) if u < 128 else u
+ *   AutoContrast  per channel, lo / hi the first / last non-empty bin of its histogram: unchanged if hi <= lo, else scale = 255.0 / (hi - lo),
+ *                 off = -lo * scale, u -> clamp(int(u * scale + off), 0, 255) in IEEE double, uncontracted (int truncates toward zero)
+ *   Equalize      per channel with histogram h: unchanged with at most one non-empty bin; step = (sum of the bins - the last non-empty
+ *                 bin) / 255 in integers, unchanged if 0; else u -> min(255, (step / 2 + sum of h[0 .. u-1]) / step) in integers
+ *   blend(d, u, f) = d + f * (u - d) in fp32: operands converted to float, f rounded to float, one multiply and one add, NOT fused;
+ *                 truncated toward zero for 0 <= f <= 1, else 0 if <= 0, 255 if >= 255, else truncated
+ *   Brightness    blend(0, u, factor)
+ *   Color         blend(L, u, factor), L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 of the pixel, for all three channels
+ *   Contrast      blend(m, u, factor), m = int(sum of L over the image / (S * S) + 0.5): integer sum, one double division
+ *   Sharpness     blend(s, u, factor), s = PIL's ImageFilter.SMOOTH: the one-pixel border is the image's; inside, a fp32 accumulation from 0,
+ *                 row-major over the 3 x 3 window, of pixel * (k / 13.0f) with k = 1 except 5 at the centre (each product rounded, then each
+ *                 sum), then + 0.5f; 0 if <= 0, 255 if >= 255, else truncated
+ *   Rotate, ShearX, ShearY, TranslateX, TranslateY   Image.transform(AFFINE, matrix, filter, fillcolor = fill): the matrix (a, b, c, d, e, f)
+ *                 is the host's (ShearX (1, v, 0, 0, 1, 0); ShearY (1, 0, 0, v, 1, 0); TranslateX (1, 0, px, 0, 1, 0); TranslateY (1, 0, 0, 0,
+ *                 1, px); Rotate as Image.rotate(deg): t = -radians(deg % 360), a = e = round(cos t, 15), b = round(sin t, 15), d = round(-sin t,
+ *                 15), c = a * (-S/2) + b * (-S/2) + S/2, f = d * (-S/2) + e * (-S/2) + S/2); the five op ids run the same code.
+ *                 Output pixel (xo, yo), in IEEE double, uncontracted: xin = a (xo + 0.5) + b (yo + 0.5) + c, yin = d (xo + 0.5) + e (yo +
+ *                 0.5) + f.  Unless 0 <= xin < S and 0 <= yin < S (a NaN is not) the pixel is the fill colour.  Else xin -= 0.5, x = floor(xin),
+ *                 dx = xin - x, the same for y; cl() clamps an index to 0 .. S - 1.
+ *                 bilinear: row(r) = p0 + (p1 - p0) * dx on columns cl(x), cl(x + 1) of row r; v1 = row(cl(y)); v2 = row(y + 1) if that row is
+ *                 in the image, else v1; result v1 + (v2 - v1) * dy, truncated.
+ *                 bicubic: cub(v1, v2, v3, v4, t) = p1 + t (p2 + t (p3 + t p4)), p1 = v2, p2 = -v1 + v3, p3 = 2 (v1 - v2) + v3 - v4,
+ *                 p4 = -v1 + v2 - v3 + v4; row(r) = cub over columns cl(x - 1) .. cl(x + 2) at dx; the four row values are row(cl(y - 1)),
+ *                 then row(y), row(y + 1), row(y + 2), each replaced by the value before it when its row is outside the image; result
+ *                 cub of them at dy: 0 if <= 0, 255 if >= 255, else truncated.
+ * Op ids outside 0 .. 14 leave the image as it is; n_ops is clamped to 0 .. DEVIT_AUGMENT_MAX_OPS; a filter other than bicubic is bilinear.
+ * The kernel (one workgroup per sample) holds the sample's whole image in LDS -- 150 528 bytes at S = 224 -- through every layer: the
+ * histograms and the luminance sum are integer LDS reductions (order-free: the result is deterministic), the pointwise ops run in place
+ * through a 3 x 256 table, Sharpness and the affine family compute every output pixel into registers before any is written back.
+ *   devit_image_ops          uint8 [B][S][S][3] -> uint8 [B][S][S][3] (in == out is allowed): the layers alone
+ *   devit_augment_batch_ops  devit_augment_batch with the layers between steps 2 and 3: steps 1 and 2 leave the uint8 window in the
+ *                            workspace, the op kernel loads it, applies the layers and does steps 3 and 4.  With n_ops == 0 for every
+ *                            sample its output has the bits of devit_augment_batch's.  devit_augment_ops_workspace(B, S) bytes of workspace
+ *                            (the coefficient workspace and the windows behind it).
+ * Both are memory-safe for any table bytes: ids, counts and every LDS address are clamped, a non-finite or huge matrix gives fill colour.
+ * ---------------------------------------------------------------------------------------- */
+#define DEVIT_AUGMENT_MAX_OPS 4
+enum devit_image_op {
+  DEVIT_OP_AUTOCONTRAST = 0, DEVIT_OP_EQUALIZE = 1, DEVIT_OP_INVERT = 2, DEVIT_OP_ROTATE = 3, DEVIT_OP_POSTERIZE = 4, DEVIT_OP_SOLARIZE = 5,
+  DEVIT_OP_SOLARIZE_ADD = 6, DEVIT_OP_COLOR = 7, DEVIT_OP_CONTRAST = 8, DEVIT_OP_BRIGHTNESS = 9, DEVIT_OP_SHARPNESS = 10,
+  DEVIT_OP_SHEAR_X = 11, DEVIT_OP_SHEAR_Y = 12, DEVIT_OP_TRANSLATE_X = 13, DEVIT_OP_TRANSLATE_Y = 14, DEVIT_OP_COUNT = 15
+};
+typedef struct {
+  int n_ops;                              /* 0 .. DEVIT_AUGMENT_MAX_OPS */
+  int reserved;
+  int op[DEVIT_AUGMENT_MAX_OPS];          /* devit_image_op */
+  int filter[DEVIT_AUGMENT_MAX_OPS];      /* devit_augment_filter of the affine family */
+  float factor[DEVIT_AUGMENT_MAX_OPS];    /* the blend ops */
+  int arg[DEVIT_AUGMENT_MAX_OPS];         /* Posterize: bits, Solarize: threshold, SolarizeAdd: addend */
+  int fill[DEVIT_AUGMENT_MAX_OPS][4];     /* r, g, b of the affine family's fill colour, one spare */
+  double matrix[DEVIT_AUGMENT_MAX_OPS][6];
+} devit_augment_ops;
+DEVIT_API int devit_image_ops(const unsigned char* in, const devit_augment_ops* ops /* device, B entries */, int B, int S, unsigned char* out,
+                    void* stream);
+DEVIT_API size_t devit_augment_ops_workspace(int B, int S);
+DEVIT_API int devit_augment_batch_ops(const unsigned char* src, int n, int H0, int W0, const int* idx, const devit_augment_sample* table,
+                            const devit_augment_ops* ops, int B, int S, const float* mean /* host [3] */, const float* std /* host [3] */,
+                            unsigned long long seed, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the device-resident input stage costs (results: profiles/augment_cost.json).
+"""What the device-resident input stage costs (DESIGN.md sections 15 and 16; results: profiles/augment_cost.json, profiles/randaug_cost.json).
 
     augment_cost.py kernels [--batch-size 256] [--reps 50]
         cold and warm time of devit_augment_coeffs and of devit_augment_batch (coefficients + resampling) for one batch of 32 x 32 images
@@ -9,6 +9,7 @@
         bench.py's DEKD step at bs 256 (same models, optimizer, look-ahead teacher, weights put back every step), fed through
         engine._PreparedBatches by a DeviceLoader over a 50 000-image random uint8 set (device) or by resident random batches (synthetic).
         The parent's own yardstick is its bench.py; this leg exists so that the two sources run the very same loop.
+    --aa rand-m9-mstd0.5-inc1 (either leg): the image-op layers on (devit_augment_batch_ops; section 16); default: none, the stage of section 15.
 One JSON line on stdout."""
 import argparse
 import json
@@ -30,8 +31,9 @@ def kernels(args):
     B, S = args.batch_size, 224
     g = torch.Generator().manual_seed(0)
     ds = data.DeviceImageSet.from_arrays(torch.randint(0, 256, (50000, 32, 32, 3), generator=g, dtype=torch.uint8), torch.zeros(50000, dtype=torch.long), device=dev)
-    tf = data.TrainAugment(S, interpolation='bicubic', re_prob=1.0, re_mode='pixel', seed=0)
-    tab = tf.draw(B, 32, 32)
+    tf = data.TrainAugment(S, interpolation='bicubic', re_prob=1.0, re_mode='pixel', seed=0, auto_augment=args.aa)
+    tab, layers = tf.draw_with_ops(B, 32, 32)
+    layers_dev = None if layers is None else data.upload(layers.view(np.uint8).reshape(-1), dev)
     idx = torch.randint(0, 50000, (B,), generator=g, dtype=torch.int32).to(dev)
     tab_dev = data.upload(tab.view(np.uint8).reshape(-1), dev)
     out = torch.empty((B, 3, S, S), device=dev)
@@ -43,7 +45,7 @@ def kernels(args):
         ops.call("devit_augment_coeffs", L.ptr(tab_dev), B, S, L.ptr(ws), nbytes, L.stream_ptr())
 
     def both():
-        data.augment_batch(ds.images, idx, tab, S, seed=0, out=out, table_dev=tab_dev)
+        data.augment_batch(ds.images, idx, tab, S, seed=0, out=out, table_dev=tab_dev, layers=layers, layers_dev=layers_dev)
 
     def timed(fn, cold):
         ms = []
@@ -61,14 +63,14 @@ def kernels(args):
         for _ in range(5):
             fn()
     torch.cuda.synchronize()
-    res = {"what": "kernels", "batch": B, "source": "32x32 uint8", "S": S, "filter": "bicubic", "erase": "pixel, re_prob 1", "reps": args.reps,
+    res = {"what": "kernels", "aa": args.aa or "none", "layers_applied": 0 if layers is None else int(layers["n_ops"].sum()), "batch": B, "source": "32x32 uint8", "S": S, "filter": "bicubic", "erase": "pixel, re_prob 1", "reps": args.reps,
            "erased_share": round(float(sum(int(t["erase"][0][2]) * int(t["erase"][0][3]) for t in tab if t["n_erase"])) / (B * S * S), 4),
            "out_bytes": out.numel() * 4, "workspace_bytes": nbytes,
            "coeffs": {"warm": timed(coeffs, False), "cold": timed(coeffs, True)},
            "coeffs_plus_resample": {"warm": timed(both, False), "cold": timed(both, True)}}
     t0 = time.perf_counter()
     for _ in range(20):
-        tf.draw(B, 32, 32)
+        tf.draw_with_ops(B, 32, 32)
     res["host_draw_ms_per_batch"] = round((time.perf_counter() - t0) / 20 * 1e3, 3)
     print(json.dumps(res))
 
@@ -114,7 +116,7 @@ def step(args):
         ds = data.DeviceImageSet.from_arrays(torch.randint(0, 256, (50000, 32, 32, 3), generator=gc, dtype=torch.uint8),
                                              torch.randint(0, C, (50000,), generator=gc), device=dev)
         sampler = torch.randint(0, 50000, (n * B,), generator=gc).tolist()
-        loader = data.DeviceLoader(ds, sampler, B, data.TrainAugment(224, re_prob=0.25, re_mode='pixel', seed=0), drop_last=True)
+        loader = data.DeviceLoader(ds, sampler, B, data.TrainAugment(224, re_prob=0.25, re_mode='pixel', seed=0, auto_augment=args.aa), drop_last=True)
     else:
         loader = distill_sub.SyntheticLoader(n, B, C, dev, 1234)
     look = engine.TeacherLookahead(teacher)
@@ -144,7 +146,7 @@ def step(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert bool(torch.isfinite(loss)), "non-finite loss"
-    print(json.dumps({"what": "step", "source": args.source, "batch": B, "steps": args.steps, "warmup": args.warmup,
+    print(json.dumps({"what": "step", "source": args.source, "aa": args.aa or "none", "batch": B, "steps": args.steps, "warmup": args.warmup,
                       "value": round(B * args.steps / dt, 1), "unit": "images/sec", "step_ms": round(dt / args.steps * 1e3, 3),
                       "host_enqueue_ms_per_step": round(t_enqueue / args.steps * 1e3, 3), "loss": float(loss)}))
 
@@ -157,5 +159,6 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--aa", default=None, help="a RandAugment config for the device stage, e.g. rand-m9-mstd0.5-inc1 (default: none)")
     a = ap.parse_args()
     (kernels if a.what == "kernels" else step)(a)
