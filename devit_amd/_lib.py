@@ -105,6 +105,10 @@ class AugmentOps(C.Structure):
                 ("arg", C.c_int * 4), ("fill", C.c_int * 4 * 4), ("matrix", C.c_double * 6 * 4)]
 
 
+class ImageEntry(C.Structure):
+    _fields_ = [("offset", C.c_ulonglong), ("H", C.c_int), ("W", C.c_int)]
+
+
 # include/devit_hip.h, "Image ops": devit_image_op
 AUGMENT_MAX_OPS, OP_COUNT = 4, 15
 OP_AUTOCONTRAST, OP_EQUALIZE, OP_INVERT, OP_ROTATE, OP_POSTERIZE, OP_SOLARIZE, OP_SOLARIZE_ADD, OP_COLOR, OP_CONTRAST, OP_BRIGHTNESS, \
@@ -112,6 +116,7 @@ OP_AUTOCONTRAST, OP_EQUALIZE, OP_INVERT, OP_ROTATE, OP_POSTERIZE, OP_SOLARIZE, O
 
 # include/devit_hip.h, "Input augmentation"
 AUGMENT_TAPS, AUGMENT_MAX_ERASE, AUGMENT_SITE = 12, 4, 0x100
+AUGMENT_TAPS_MAX, AUGMENT_FORCE_WIDE = 128, 1      # "Packed sets"
 AUG_NONE, AUG_BILINEAR, AUG_BICUBIC = range(3)
 AUG_ERASE_CONST, AUG_ERASE_RAND, AUG_ERASE_PIXEL = range(3)
 
@@ -141,7 +146,7 @@ WGRAD_MAX_JOBS = 48
 ABI_VERSION = 4
 # devit_abi_struct_size(which) -> the mirror it must equal (checked at load time: an array of stale mirrors is misread silently)
 ABI_STRUCTS = {0: Epilogue, 1: Operand, 2: BlockWeights, 3: BlockWgrads, 4: BlockActs, 5: BlockBwdIO, 6: IndexJob, 7: WgradJob, 8: LaunchInfo, 9: BlockDropout,
-               10: MixSample, 11: OptChunk, 12: TailActs, 13: TailBwdIO, 14: AugmentSample, 15: AugmentOps}
+               10: MixSample, 11: OptChunk, 12: TailActs, 13: TailBwdIO, 14: AugmentSample, 15: AugmentOps, 16: ImageEntry}
 
 
 class DevitError(RuntimeError):
@@ -247,6 +252,8 @@ SIGNATURES = {
     "devit_image_ops": (_I, [_P, _P, _I, _I, _P, _P]),
     "devit_augment_ops_workspace": (_Z, [_I, _I]),
     "devit_augment_batch_ops": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _U64, _P, _P, _Z, _P]),
+    "devit_augment_ragged_workspace": (_Z, [_I, _I, _I, _I]),
+    "devit_augment_ragged": (_I, [_P, _Z, _P, _I, _P, _P, _P, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _U64, _P, _P, _Z, _I, C.c_uint, _P]),
     "devit_comm_unique_id": (_I, [_P]),
     "devit_comm_init": (_I, [_P, _I, _I, C.POINTER(C.c_void_p)]),
     "devit_comm_allreduce_f32": (_I, [_P, _P, _Z, _P]),

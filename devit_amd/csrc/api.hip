@@ -42,6 +42,7 @@ extern "C" size_t devit_abi_struct_size(int which) {
     case 13: return sizeof(devit_tail_bwd_io);
     case 14: return sizeof(devit_augment_sample);
     case 15: return sizeof(devit_augment_ops);
+    case 16: return sizeof(devit_image_entry);
     default: return 0;
   }
 }

@@ -8,6 +8,9 @@
 //   augment_u8_kernel       augment_kernel's two passes and flip, with the uint8 window [B][S][S][3] as the result
 //   image_ops_kernel        (header, "Image ops") one workgroup per sample: that window into LDS whole, RandAugment's / ColorJitter's layers applied
 //                           there bit for bit as PIL computes them, then normalize and erasing out of LDS; or uint8 to uint8 (devit_image_ops)
+//   ragged_coeffs_kernel, ragged_narrow_kernel, ragged_wide_kernel   (header, "Packed sets") the same stage over a packed set of mixed image sizes:
+//                           the image's base, H0 and W0 from a directory entry; the narrow kernel is augment_kernel / augment_u8_kernel on that
+//                           image, the wide one serves 13 .. 128 taps per axis by streaming source rows into per-column accumulators
 // Every source address is clamped and the value masked afterwards (as attention.hip's fetch_rows: no load under a per-element
 // condition), every LDS row index is clamped, idx is clamped: no table or index bytes can send an access out of bounds.
 #include "devit_common.h"
@@ -661,6 +664,343 @@ int check_geometry(const char* who, int B, int S) {
   return DEVIT_OK;
 }
 
+// ---- packed sets of mixed image sizes (include/devit_hip.h, "Packed sets"): the image's base, H0 and W0 come from a directory entry --------
+constexpr int TAPS_MAX = DEVIT_AUGMENT_TAPS_MAX;
+constexpr int WBAND = 16;             // output rows per workgroup of the wide kernel: their accumulators are 48 registers of thread x
+
+// The closed-form bound on the taps an axis needs (the header states it): never below the exact count, so a sample it calls narrow is narrow.
+__device__ __forceinline__ int axis_taps(int len, int R, int filter) {
+#pragma clang fp contract(off)
+  if ((filter != DEVIT_AUG_BILINEAR && filter != DEVIT_AUG_BICUBIC) || len <= 0 || R <= 0) return 1;
+  const double scale = (double)len / (double)R;
+  const double support = (filter == DEVIT_AUG_BICUBIC ? 2.0 : 1.0) * (scale < 1.0 ? 1.0 : scale);
+  const double nd = floor(2.0 * support) + 1.0;
+  return nd >= (double)len ? len : (int)nd;
+}
+__device__ __forceinline__ bool sample_is_wide(const devit_augment_sample* s) {
+  return max(axis_taps(s->h, s->Rh, s->filter), axis_taps(s->w, s->Rw, s->filter)) > TAPS;
+}
+
+struct RaggedImage {
+  const unsigned char* base;
+  int H0, W0;
+  bool ok;      // false: the entry reaches outside the arena; every pixel then reads 0 (from the arena's first bytes, masked)
+};
+__device__ __forceinline__ RaggedImage ragged_image(const unsigned char* arena, size_t arena_bytes, const devit_image_entry* entries, int n_img,
+                                                    int i) {
+  const devit_image_entry e = entries[clampi(i, 0, n_img - 1)];
+  const bool dims = e.H >= 1 && e.W >= 1;
+  const unsigned long long extent = dims ? 3ull * (unsigned long long)e.H * (unsigned long long)e.W : 0ull;      // < 2^64 for 31-bit sides
+  const bool ok = dims && e.offset <= arena_bytes && extent <= arena_bytes - e.offset;
+  return RaggedImage{ok ? arena + e.offset : arena, ok ? e.H : 1, ok ? e.W : 1, ok};
+}
+
+// PIL's coefficients for T planes of weights: resample_coeffs' operations in its order (the same bits for counts up to TAPS), the weights
+// computed twice instead of held, since T of them do not fit registers
+__global__ __launch_bounds__(256) void ragged_coeffs_kernel(const devit_augment_sample* __restrict__ table, int B, int S, int T,
+                                                            int* __restrict__ ws) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= B * 2 * S) return;
+  const int j = t % S, axis = (t / S) & 1, b = t / (2 * S);
+  const devit_augment_sample* s = table + b;
+  const int len = axis ? s->w : s->h, R = axis ? s->Rw : s->Rh, xx = (axis ? s->ox : s->oy) + j, filter = s->filter;
+  int* p = ws + (size_t)(b * 2 + axis) * (2 + T) * S + j;
+  if (!((filter == DEVIT_AUG_BILINEAR || filter == DEVIT_AUG_BICUBIC) && len > 0 && R > 0)) {      // unit scale: the pixel itself
+    p[0] = xx;
+    p[S] = 1;
+    for (int k = 0; k < T; ++k) p[(size_t)(2 + k) * S] = k == 0 ? WEIGHT_ONE : 0;
+    return;
+  }
+  const int cubic = filter == DEVIT_AUG_BICUBIC;
+  const double scale = (double)len / (double)R;
+  const double fs = scale < 1.0 ? 1.0 : scale;
+  const double support = (cubic ? 2.0 : 1.0) * fs;
+  const double center = (xx + 0.5) * scale;
+  const double ss = 1.0 / fs;
+  int xmin = (int)(center - support + 0.5);
+  if (xmin < 0) xmin = 0;
+  if (xmin > len) xmin = len;
+  int xmax = (int)(center + support + 0.5);
+  if (xmax > len) xmax = len;
+  int n = xmax - xmin;
+  n = n < 0 ? 0 : (n > T ? T : n);
+  double ww = 0.0;
+  for (int k = 0; k < n; ++k) ww += filter_weight((k + xmin - center + 0.5) * ss, cubic);
+  p[0] = xmin;
+  p[S] = n;
+  for (int k = 0; k < T; ++k) {
+    double v = 0.0;
+    if (k < n) {
+      v = filter_weight((k + xmin - center + 0.5) * ss, cubic);
+      if (ww != 0.0) v /= ww;
+    }
+    p[(size_t)(2 + k) * S] = v < 0 ? (int)(-0.5 + v * (double)WEIGHT_ONE) : (int)(0.5 + v * (double)WEIGHT_ONE);
+  }
+}
+
+// what a ragged kernel needs of steps 3 and 4 (staged by stage_finish, read by finish_quad)
+struct FinishLds {
+  float rand[DEVIT_AUGMENT_MAX_ERASE][3];
+  float norm[3][256];
+};
+__device__ __forceinline__ void stage_finish(FinishLds& f, const devit_augment_sample* sp, int b, int tid, const Norm3& norm, unsigned k0, unsigned k1) {
+  const int n_erase = clampi(sp->n_erase, 0, DEVIT_AUGMENT_MAX_ERASE);
+  const unsigned long long N = sp->noise_base + (unsigned long long)b;
+  if (sp->erase_mode == DEVIT_AUG_ERASE_RAND && tid < n_erase * 3) {
+    const int e = tid / 3, c = tid % 3;
+    f.rand[e][c] = normals4(noise_words(N, c, 0x80000000u + (unsigned)e, k0, k1))[0];
+  }
+  for (int i = tid; i < 3 * 256; i += THREADS) {
+    const int c = i >> 8;
+    f.norm[c][i & 255] = ((float)(i & 255) / 255.0f - norm.mean[c]) / norm.std[c];
+  }
+}
+// steps 3 and 4 on output pixels (yy, x .. x + 3) of channel c, u their levels after the flip: augment_kernel's statements
+__device__ __forceinline__ void finish_quad(const FinishLds& f, const devit_augment_sample* sp, int b, int c, int yy, int x, int S,
+                                            const int (&u)[4], unsigned k0, unsigned k1, float* __restrict__ out) {
+  const int n_erase = clampi(sp->n_erase, 0, DEVIT_AUGMENT_MAX_ERASE), erase_mode = sp->erase_mode;
+  const unsigned long long N = sp->noise_base + (unsigned long long)b;
+  f32x4 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = f.norm[c][u[j]];
+  unsigned inside = 0;      // bit 4 e + j: pixel j lies in box e
+  for (int eb = 0; eb < n_erase; ++eb) {
+    const int top = sp->erase[eb][0], left = sp->erase[eb][1], eh = sp->erase[eb][2], ew = sp->erase[eb][3];
+    if (yy >= top && yy - top < eh) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (x + j >= left && x + j - left < ew) inside |= 1u << (4 * eb + j);
+    }
+  }
+  if (inside) {
+    f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    if (erase_mode == DEVIT_AUG_ERASE_PIXEL) z = normals4(noise_words(N, c, (unsigned)(yy * S + x) >> 2, k0, k1));
+#pragma unroll
+    for (int eb = 0; eb < DEVIT_AUGMENT_MAX_ERASE; ++eb) {      // later boxes win
+      const float zr = erase_mode == DEVIT_AUG_ERASE_RAND ? f.rand[eb][c] : 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (inside >> (4 * eb + j) & 1u) v[j] = erase_mode == DEVIT_AUG_ERASE_PIXEL ? z[j] : zr;
+    }
+  }
+  store16_stream(out + (((size_t)b * 3 + c) * S + yy) * S + x, v);
+}
+
+// The narrow kernel: augment_kernel (U8: augment_u8_kernel) with the image taken from the directory.  Samples the closed form calls wide are
+// the wide kernel's when it runs (wide_on): their workgroups leave at once.  The workspace has T weight planes; this kernel reads the first TAPS.
+template <bool U8>
+__global__ __launch_bounds__(THREADS) void ragged_narrow_kernel(const unsigned char* __restrict__ arena, size_t arena_bytes,
+                                                                const devit_image_entry* __restrict__ entries, int n_img,
+                                                                const int* __restrict__ idx, const devit_augment_sample* __restrict__ table,
+                                                                int S, int T, const int* __restrict__ ws, int wide_on, Norm3 norm, unsigned k0,
+                                                                unsigned k1, float* __restrict__ out, unsigned char* __restrict__ out8) {
+  __shared__ __attribute__((aligned(16))) unsigned char inter[3][NROWS][PITCH];
+  __shared__ int s_ymin[BAND], s_yn[BAND], s_wy[BAND][TAPS];
+  __shared__ FinishLds fin;
+  const int tid = threadIdx.x, b = blockIdx.y, r0 = blockIdx.x * BAND, r1 = min(r0 + BAND, S);
+  const devit_augment_sample* sp = table + b;
+  if (wide_on && sample_is_wide(sp)) return;      // the same for every thread of the workgroup
+  const int y0 = sp->y0, x0 = sp->x0, flip = sp->flip;
+  const RaggedImage im = ragged_image(arena, arena_bytes, entries, n_img, idx[b]);
+  const unsigned char* image = im.base;
+  const int H0 = im.H0, W0 = im.W0, planes = 2 + T;
+  const int* wsy = ws + (size_t)(b * 2) * planes * S;
+  const int* wsx = wsy + (size_t)planes * S;
+
+  // the band's vertical coefficients -> LDS; column tid's horizontal ones -> registers
+  for (int i = tid; i < BAND * PLANES; i += THREADS) {
+    const int r = i / PLANES, q = i % PLANES;
+    const int v = wsy[(size_t)min(q, planes - 1) * S + min(r0 + r, S - 1)];
+    if (q == 0) s_ymin[r] = v;
+    else if (q == 1) s_yn[r] = clampi(v, 0, min(T, TAPS));
+    else s_wy[r][q - 2] = q < planes ? v : 0;
+  }
+  const int xc = min(tid, S - 1);
+  const int xmin_x = wsx[xc];
+  int wx[TAPS];
+#pragma unroll
+  for (int k = 0; k < TAPS; ++k) {
+    const int v = wsx[(size_t)min(2 + k, planes - 1) * S + xc];
+    wx[k] = k < T ? v : 0;
+  }
+  if constexpr (!U8) stage_finish(fin, sp, b, tid, norm, k0, k1);
+
+  // vertical pass: a wave takes 64 / nq (row, channel) pairs at a time, lane -> (pair, quad of four output pixels)
+  const int nq = S >> 2, lane = tid & 63, per = 64 / nq, sub = lane / nq, xq = lane - sub * nq;
+  const int x = xq * 4, xs = flip ? S - 4 - x : x;
+  int r = r0;
+  while (r < r1) {
+    __syncthreads();      // the coefficients are staged; the previous run's intermediate has been read
+    const int lo = s_ymin[r - r0];
+    int e = r + 1;        // one output row needs at most TAPS <= NROWS source rows: every run advances
+    while (e < r1 && s_ymin[e - r0] + s_yn[e - r0] - lo <= NROWS) ++e;
+    const int nrows = clampi(s_ymin[e - 1 - r0] + s_yn[e - 1 - r0] - lo, 0, NROWS);
+
+    // horizontal pass: source rows lo .. lo + nrows of the box, output column tid
+    if (tid < S) {
+      for (int row = 0; row < nrows; ++row) {
+        const int sy = y0 + lo + row;
+        const bool in_y = im.ok && sy >= 0 && sy < H0;
+        const unsigned char* line = image + (size_t)clampi(sy, 0, H0 - 1) * W0 * 3;
+        int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+#pragma unroll
+        for (int k = 0; k < TAPS; ++k) {
+          const int sx = x0 + xmin_x + k;
+          const bool ok = in_y && sx >= 0 && sx < W0;
+          const unsigned char* p = line + (size_t)clampi(sx, 0, W0 - 1) * 3;
+          const int p0 = p[0], p1 = p[1], p2 = p[2];
+          const int w = ok ? wx[k] : 0;
+          a0 += p0 * w;
+          a1 += p1 * w;
+          a2 += p2 * w;
+        }
+        inter[0][row][tid] = (unsigned char)clampi(a0 >> 22, 0, 255);
+        inter[1][row][tid] = (unsigned char)clampi(a1 >> 22, 0, 255);
+        inter[2][row][tid] = (unsigned char)clampi(a2 >> 22, 0, 255);
+      }
+    }
+    __syncthreads();
+
+    // vertical pass, flip, then steps 3 and 4 or the uint8 window: four output pixels of one row and channel per item
+    const int pairs = (e - r) * 3;
+    for (int t = (tid >> 6) * per + sub; sub < per && t < pairs; t += (THREADS / 64) * per) {
+      const int c = t % 3, yy = r + t / 3;
+      const int ymin = s_ymin[yy - r0] - lo, yn = s_yn[yy - r0];
+      int acc[4] = {1 << 21, 1 << 21, 1 << 21, 1 << 21};
+      for (int k = 0; k < yn; ++k) {
+        const unsigned q = *(const unsigned*)&inter[c][clampi(ymin + k, 0, NROWS - 1)][xs];
+        const int w = s_wy[yy - r0][k];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] += (int)((q >> (8 * j)) & 255u) * w;
+      }
+      int u[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) u[j] = clampi((flip ? acc[3 - j] : acc[j]) >> 22, 0, 255);
+      if constexpr (U8) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out8[(((size_t)b * S + yy) * S + x + j) * 3 + c] = (unsigned char)u[j];
+      } else {
+        finish_quad(fin, sp, b, c, yy, x, S, u, k0, k1, out);
+      }
+    }
+    r = e;
+  }
+}
+
+// The wide kernel: up to TAPS_MAX taps per axis.  One workgroup per (sample, band of WBAND output rows); thread x owns output column x.  It walks
+// the band's source rows once: the row's horizontal result for its column (weights read [k][x] from the workspace, clamped to uint8 as PIL's
+// intermediate is), added at once, weighted, into the accumulators of the output rows whose vertical window holds that source row.  No
+// intermediate image, so no limit on the rows a band spans.  The finished rows go through LDS to the quad-wise finish of the narrow kernel.
+template <bool U8>
+__global__ __launch_bounds__(THREADS) void ragged_wide_kernel(const unsigned char* __restrict__ arena, size_t arena_bytes,
+                                                              const devit_image_entry* __restrict__ entries, int n_img,
+                                                              const int* __restrict__ idx, const devit_augment_sample* __restrict__ table,
+                                                              int S, int T, const int* __restrict__ ws, int force, Norm3 norm, unsigned k0,
+                                                              unsigned k1, float* __restrict__ out, unsigned char* __restrict__ out8) {
+  __shared__ __attribute__((aligned(16))) unsigned char tile[3][WBAND][PITCH];
+  __shared__ int s_ymin[WBAND], s_yn[WBAND], s_wy[WBAND][TAPS_MAX];
+  __shared__ FinishLds fin;
+  const int tid = threadIdx.x, b = blockIdx.y, r0 = blockIdx.x * WBAND, nb = min(WBAND, S - r0);
+  const devit_augment_sample* sp = table + b;
+  if (!force && !sample_is_wide(sp)) return;      // the same for every thread of the workgroup
+  const int y0 = sp->y0, x0 = sp->x0, flip = sp->flip;
+  const RaggedImage im = ragged_image(arena, arena_bytes, entries, n_img, idx[b]);
+  const int H0 = im.H0, W0 = im.W0, planes = 2 + T;
+  const int* wsy = ws + (size_t)(b * 2) * planes * S;
+  const int* wsx = wsy + (size_t)planes * S;
+
+  for (int i = tid; i < WBAND * planes; i += THREADS) {
+    const int r = i / planes, q = i - r * planes;
+    const int v = wsy[(size_t)q * S + min(r0 + r, S - 1)];
+    if (q == 0) s_ymin[r] = v;
+    else if (q == 1) s_yn[r] = r < nb ? clampi(v, 0, T) : 0;
+    else s_wy[r][q - 2] = v;
+  }
+  const int xc = min(tid, S - 1);
+  const int xmin_x = wsx[xc], nx = clampi(wsx[S + xc], 0, T);
+  const int* wcol = wsx + (size_t)2 * S + xc;
+  if constexpr (!U8) stage_finish(fin, sp, b, tid, norm, k0, k1);
+  __syncthreads();
+
+  int ym[WBAND], yn[WBAND], acc[WBAND][3];      // (uniform values: scalar registers)
+#pragma unroll
+  for (int r = 0; r < WBAND; ++r) {
+    ym[r] = __builtin_amdgcn_readfirstlane(s_ymin[r]);
+    yn[r] = __builtin_amdgcn_readfirstlane(s_yn[r]);
+    acc[r][0] = acc[r][1] = acc[r][2] = 1 << 21;
+  }
+  // the rows' windows abut or overlap (the centres advance by the scale, a window is at least twice that): their union is one run of at most
+  // WBAND * T source rows
+  const int lo = ym[0];
+  const int nrows = clampi(__builtin_amdgcn_readfirstlane(s_ymin[nb - 1] + s_yn[nb - 1]) - lo, 0, WBAND * TAPS_MAX);
+  if (tid < S) {
+    for (int row = 0; row < nrows; ++row) {
+      const int sy = y0 + lo + row;
+      const bool in_y = im.ok && sy >= 0 && sy < H0;
+      const unsigned char* line = im.base + (size_t)clampi(sy, 0, H0 - 1) * W0 * 3;
+      int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+      for (int k = 0; k < nx; ++k) {
+        const int sx = x0 + xmin_x + k;
+        const bool ok = in_y && sx >= 0 && sx < W0;
+        const unsigned char* p = line + (size_t)clampi(sx, 0, W0 - 1) * 3;
+        const int p0 = p[0], p1 = p[1], p2 = p[2];
+        const int w = ok ? wcol[(size_t)k * S] : 0;
+        a0 += p0 * w;
+        a1 += p1 * w;
+        a2 += p2 * w;
+      }
+      const int h0 = clampi(a0 >> 22, 0, 255), h1 = clampi(a1 >> 22, 0, 255), h2 = clampi(a2 >> 22, 0, 255);      // PIL's uint8 intermediate
+#pragma unroll
+      for (int r = 0; r < WBAND; ++r) {
+        const int k = lo + row - ym[r];
+        if (k >= 0 && k < yn[r]) {
+          const int w = s_wy[r][k];
+          acc[r][0] += h0 * w;
+          acc[r][1] += h1 * w;
+          acc[r][2] += h2 * w;
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < WBAND; ++r) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) tile[c][r][tid] = (unsigned char)clampi(acc[r][c] >> 22, 0, 255);
+    }
+  }
+  __syncthreads();
+
+  const int nq = S >> 2, lane = tid & 63, per = 64 / nq, sub = lane / nq, xq = lane - sub * nq;
+  const int x = xq * 4, xs = flip ? S - 4 - x : x;
+  for (int t = (tid >> 6) * per + sub; sub < per && t < nb * 3; t += (THREADS / 64) * per) {
+    const int c = t % 3, rr = t / 3, yy = r0 + rr;
+    const unsigned q = *(const unsigned*)&tile[c][rr][xs];
+    int u[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) u[j] = (int)((q >> (8 * (flip ? 3 - j : j))) & 255u);
+    if constexpr (U8) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) out8[(((size_t)b * S + yy) * S + x + j) * 3 + c] = (unsigned char)u[j];
+    } else {
+      finish_quad(fin, sp, b, c, yy, x, S, u, k0, k1, out);
+    }
+  }
+}
+
+template <bool U8>
+void launch_ragged(const unsigned char* arena, size_t arena_bytes, const devit_image_entry* entries, int n, const int* idx,
+                   const devit_augment_sample* table, int B, int S, int T, const int* ws, unsigned flags, Norm3 norm, unsigned long long seed,
+                   float* out, unsigned char* out8, hipStream_t stream) {
+  const int force = (flags & DEVIT_AUGMENT_FORCE_WIDE) != 0, wide_on = force || T > TAPS;
+  const unsigned k0 = (unsigned)(seed & 0xffffffffull), k1 = (unsigned)(seed >> 32);
+  if (!force)
+    hipLaunchKernelGGL(ragged_narrow_kernel<U8>, dim3((S + BAND - 1) / BAND, B), dim3(THREADS), 0, stream, arena, arena_bytes, entries, n, idx,
+                       table, S, T, ws, wide_on, norm, k0, k1, out, out8);
+  if (wide_on)
+    hipLaunchKernelGGL(ragged_wide_kernel<U8>, dim3((S + WBAND - 1) / WBAND, B), dim3(THREADS), 0, stream, arena, arena_bytes, entries, n, idx,
+                       table, S, T, ws, force, norm, k0, k1, out, out8);
+}
+
 }  // namespace
 
 extern "C" size_t devit_augment_workspace(int B, int S) {
@@ -739,4 +1079,47 @@ extern "C" int devit_augment_batch_ops(const unsigned char* src, int n, int H0, 
                      (const int*)workspace, window);
   DEVIT_LAUNCH_CHECK();
   return launch_image_ops<true>("devit_augment_batch_ops", window, ops, B, S, nullptr, table, norm, seed, out, stream);
+}
+
+extern "C" size_t devit_augment_ragged_workspace(int B, int S, int max_taps, int with_ops) {
+  if (B <= 0 || S <= 0 || max_taps < 1 || max_taps > TAPS_MAX) return 0;
+  const size_t coeffs = (size_t)B * 2 * (2 + max_taps) * S * sizeof(int);
+  return with_ops ? ((coeffs + 15) & ~(size_t)15) + (size_t)B * S * S * 3 : coeffs;
+}
+
+extern "C" int devit_augment_ragged(const unsigned char* arena, size_t arena_bytes, const devit_image_entry* entries, int n, const int* idx,
+                                    const devit_augment_sample* table, const devit_augment_ops* ops, int B, int S, const float* mean,
+                                    const float* std, unsigned long long seed, float* out, void* workspace, size_t workspace_bytes,
+                                    int max_taps, unsigned flags, void* stream) {
+  if (int rc = check_geometry("devit_augment_ragged", B, S)) return rc;
+  DEVIT_CHECK(arena && entries && idx && table && mean && std && out && workspace, DEVIT_ERR_ARG, "devit_augment_ragged: null pointer");
+  DEVIT_CHECK(n > 0 && arena_bytes >= 3, DEVIT_ERR_ARG, "devit_augment_ragged: a set of %d images in an arena of %zu bytes", n, arena_bytes);
+  DEVIT_CHECK(max_taps >= 1 && max_taps <= TAPS_MAX, DEVIT_ERR_ARG, "devit_augment_ragged: max_taps = %d, 1 .. %d", max_taps, TAPS_MAX);
+  DEVIT_CHECK((flags & ~DEVIT_AUGMENT_FORCE_WIDE) == 0, DEVIT_ERR_ARG, "devit_augment_ragged: unknown flags 0x%x", flags);
+  DEVIT_CHECK((((uintptr_t)out | (uintptr_t)workspace) & 15) == 0 && ((uintptr_t)entries & 7) == 0, DEVIT_ERR_ARG,
+              "devit_augment_ragged: out and the workspace must be 16-byte aligned, the directory 8-byte aligned");
+  const size_t need = devit_augment_ragged_workspace(B, S, max_taps, ops != nullptr);
+  DEVIT_CHECK(workspace_bytes >= need, DEVIT_ERR_ARG,
+              "devit_augment_ragged: the workspace holds %zu bytes, devit_augment_ragged_workspace(B, S, max_taps, with_ops) is %zu",
+              workspace_bytes, need);
+  Norm3 norm;
+  for (int c = 0; c < 3; ++c) {
+    DEVIT_CHECK(std[c] > 0.f, DEVIT_ERR_ARG, "devit_augment_ragged: std[%d] = %g must be positive", c, (double)std[c]);
+    norm.mean[c] = mean[c];
+    norm.std[c] = std[c];
+  }
+  hipLaunchKernelGGL(ragged_coeffs_kernel, dim3((B * 2 * S + 255) / 256), dim3(256), 0, (hipStream_t)stream, table, B, S, max_taps,
+                     (int*)workspace);
+  DEVIT_LAUNCH_CHECK();
+  if (!ops) {
+    launch_ragged<false>(arena, arena_bytes, entries, n, idx, table, B, S, max_taps, (const int*)workspace, flags, norm, seed, out, nullptr,
+                         (hipStream_t)stream);
+    DEVIT_LAUNCH_CHECK();
+    return DEVIT_OK;
+  }
+  unsigned char* window = (unsigned char*)workspace + ((devit_augment_ragged_workspace(B, S, max_taps, 0) + 15) & ~(size_t)15);
+  launch_ragged<true>(arena, arena_bytes, entries, n, idx, table, B, S, max_taps, (const int*)workspace, flags, norm, seed, nullptr, window,
+                      (hipStream_t)stream);
+  DEVIT_LAUNCH_CHECK();
+  return launch_image_ops<true>("devit_augment_ragged", window, ops, B, S, nullptr, table, norm, seed, out, stream);
 }

@@ -5,6 +5,9 @@ timm.data.transforms_factory.transforms_imagenet_train / the Resize + CenterCrop
 (or the padded crop at 32 pixels), horizontal flip, RandAugment's `rand-...-inc1` layers or ColorJitter without hue on the uint8 window
 (devit_augment_batch_ops; the header's "Image ops"), ToTensor, Normalize, RandomErasing.
 
+A set whose images differ in size is held packed (DeviceImageSet's `.ragged` form: one byte arena and a directory of offsets and sizes;
+devit_augment_ragged, the header's "Packed sets"): every sample is then drawn and resized on its own image's size, crops up to 128 taps.
+
 The draws are timm 0.5.4's own scalar formulas on a private random.Random; the arithmetic is the header's ("Input augmentation").
 Nothing here imports torchvision or timm; PIL only to read an image folder."""
 import math
@@ -30,6 +33,11 @@ AUG_OPS_DTYPE = np.dtype([("n_ops", "<i4"), ("reserved", "<i4"), ("op", "<i4", (
                           ("arg", "<i4", (4,)), ("fill", "<i4", (4, 4)), ("matrix", "<f8", (4, 6))])
 FILTERS = {"bilinear": L.AUG_BILINEAR, "bicubic": L.AUG_BICUBIC}
 ERASE_MODES = {"const": L.AUG_ERASE_CONST, "rand": L.AUG_ERASE_RAND, "pixel": L.AUG_ERASE_PIXEL}
+# host mirror of devit_image_entry (16 bytes, _lib.ImageEntry): one image of a packed set
+IMAGE_ENTRY_DTYPE = np.dtype([("offset", "<u8"), ("H", "<i4"), ("W", "<i4")])
+ARENA_ALIGN = 16                      # every image of a packed set starts at a multiple of this
+RESIDENT_RESERVE_BYTES = 8 << 30      # of the device's free memory left to the models, activations and workspaces when a folder is made resident
+DECODE_WORKERS = 16                   # threads that decode a folder's images, at most
 IMG_EXTENSIONS = ('.jpg', '.jpeg', '.png', '.ppm', '.bmp', '.pgm', '.tif', '.tiff', '.webp')      # torchvision's ImageFolder list
 
 
@@ -52,6 +60,25 @@ def _check_taps(length, R, filt, what):
         name = {v: k for k, v in FILTERS.items()}[filt]
         raise ValueError(f"{what}: resizing {length} source pixels to {R} with the {name} filter needs {n} taps per output pixel, the resampling "
                          f"kernel holds {L.AUGMENT_TAPS} (a crop side up to 3 x the output side for bicubic, 6 x for bilinear)")
+
+
+def taps_bound(length, R, filt):
+    """The header's closed-form bound on taps_needed ("Packed sets"), on numpy arrays: min(floor(2 * support) + 1, length), 1 for filter 0.
+    Never below the exact count and at most 1 above it; it is what the kernels decide a sample's kind with."""
+    length, R, filt = np.broadcast_arrays(np.asarray(length, np.int64), np.asarray(R, np.int64), np.asarray(filt, np.int64))
+    res = (filt != L.AUG_NONE) & (length > 0) & (R > 0)
+    scale = length.astype(np.float64) / np.where(res, R, 1).astype(np.float64)
+    support = np.where(filt == L.AUG_BICUBIC, 2.0, 1.0) * np.maximum(scale, 1.0)
+    return np.where(res, np.minimum(np.floor(2.0 * support) + 1.0, length.astype(np.float64)), 1.0).astype(np.int64)
+
+
+def _exact_where_over(bound, length, R, filt):
+    """bound with every entry above the wide kernel's limit replaced by the exact count (the bound may be 1 above it: only there does it matter)"""
+    bound = np.array(bound, dtype=np.int64)
+    length, R, filt = np.broadcast_arrays(length, R, filt)
+    for i in np.flatnonzero(bound > L.AUGMENT_TAPS_MAX):
+        bound[i] = taps_needed(int(length[i]), int(R[i]), int(filt[i]))
+    return bound
 
 
 def parse_auto_augment(config):
@@ -101,21 +128,93 @@ def rotate_matrix(deg, S):
 
 
 # ---- the resident set ------------------------------------------------------------------------------------------------------------------------
-class DeviceImageSet:
-    """images uint8 [n,H0,W0,3] and labels int64 [n] on the device, classes: the class names.  Every image has the same H0 x W0."""
+def pack_images(arrays):
+    """[uint8 [H,W,3]] -> (arena uint8 [bytes], IMAGE_ENTRY_DTYPE [n]): the images HWC one behind the other, each at a multiple of ARENA_ALIGN"""
+    entries = np.zeros(len(arrays), dtype=IMAGE_ENTRY_DTYPE)
+    at = 0
+    for i, a in enumerate(arrays):
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+            raise ValueError(f"DeviceImageSet: image {i} must be uint8 [H,W,3] with H, W >= 1, got {a.dtype} {tuple(a.shape)}")
+        entries[i] = (at, a.shape[0], a.shape[1])
+        at += (a.size + ARENA_ALIGN - 1) // ARENA_ALIGN * ARENA_ALIGN
+    arena = np.zeros(at, dtype=np.uint8)
+    for e, a in zip(entries, arrays):
+        arena[int(e["offset"]):int(e["offset"]) + a.size] = a.reshape(-1)
+    return arena, entries
 
-    def __init__(self, images, labels, classes):
+
+def check_directory(entries, arena_bytes):
+    """ValueError for a directory the kernels would read as zeros or that aliases images: H, W >= 1, offset + 3 H W <= arena_bytes, no overlap"""
+    if entries.dtype != IMAGE_ENTRY_DTYPE or entries.ndim != 1 or entries.shape[0] < 1:
+        raise ValueError("DeviceImageSet: the directory is a 1-d numpy array of IMAGE_ENTRY_DTYPE with at least one entry")
+    H, W, off = entries["H"].astype(np.int64), entries["W"].astype(np.int64), entries["offset"]
+    bad = np.flatnonzero((H < 1) | (W < 1))
+    if bad.size:
+        raise ValueError(f"DeviceImageSet: image {bad[0]} is {H[bad[0]]} x {W[bad[0]]}: H, W >= 1")
+    if (H > 1 << 20).any() or (W > 1 << 20).any():
+        raise ValueError("DeviceImageSet: an image side above 2^20 pixels")
+    end = off + (3 * H * W).astype(np.uint64)
+    bad = np.flatnonzero((off > np.uint64(arena_bytes)) | (end > np.uint64(arena_bytes)))
+    if bad.size:
+        raise ValueError(f"DeviceImageSet: image {bad[0]} ({H[bad[0]]} x {W[bad[0]]} at offset {off[bad[0]]}) reaches past the arena's {arena_bytes} bytes")
+    order = np.argsort(off, kind="stable")
+    over = np.flatnonzero(end[order][:-1] > off[order][1:])
+    if over.size:
+        raise ValueError(f"DeviceImageSet: images {order[over[0]]} and {order[over[0] + 1]} overlap in the arena")
+
+
+class DeviceImageSet:
+    """labels int64 [n] on the device, classes: the class names, and the images in one of two forms.
+    uniform: images uint8 [n,H0,W0,3] on the device, every image H0 x W0 (`.size`).
+    packed (`.ragged`; images of mixed sizes): arena uint8 [bytes] on the device, the images HWC one behind the other at multiples of 16;
+    entries: the device directory, one devit_image_entry per image, as uint8 [n * 16]; sizes int32 [n,2] (H, W) on the host."""
+
+    def __init__(self, images, labels, classes, arena=None, entries=None, sizes=None):
         self.images, self.labels, self.classes = images, labels, list(classes)
+        self.arena, self.entries, self.sizes = arena, entries, sizes
 
     def __len__(self):
-        return self.images.shape[0]
+        return self.labels.shape[0]
+
+    @property
+    def ragged(self):
+        return self.arena is not None
+
+    @property
+    def device(self):
+        return self.labels.device
 
     @property
     def size(self):
+        if self.ragged:
+            raise ValueError("DeviceImageSet.size: a packed set has one size per image (.sizes)")
         return int(self.images.shape[1]), int(self.images.shape[2])
 
     @classmethod
-    def from_arrays(cls, images, labels, classes=None, device="cuda"):
+    def from_packed(cls, arena, entries, labels, classes=None, device="cuda"):
+        """arena uint8 [bytes] and entries IMAGE_ENTRY_DTYPE [n] on the host: the directory is validated here, once, then both go to the device"""
+        arena, entries = np.asarray(arena), np.ascontiguousarray(entries)
+        if arena.dtype != np.uint8 or arena.ndim != 1:
+            raise ValueError(f"DeviceImageSet: the arena must be uint8 [bytes], got {arena.dtype} {tuple(arena.shape)}")
+        check_directory(entries, arena.shape[0])
+        labels = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.asarray(labels, dtype=np.int64))
+        if labels.dim() != 1 or labels.shape[0] != entries.shape[0]:
+            raise ValueError(f"DeviceImageSet: {entries.shape[0]} images, labels of shape {tuple(labels.shape)}")
+        if classes is None:
+            classes = [str(i) for i in range(int(labels.max()) + 1)]
+        sizes = np.stack([entries["H"], entries["W"]], axis=1).astype(np.int32)
+        return cls(None, labels.long().to(device), classes, arena=torch.from_numpy(arena).to(device),
+                   entries=torch.from_numpy(entries.view(np.uint8).reshape(-1).copy()).to(device), sizes=sizes)
+
+    @classmethod
+    def from_arrays(cls, images, labels, classes=None, device="cuda", ragged=False):
+        """ragged: False -- a uniform set, refusing images of differing shapes; True -- a packed set; "auto" -- uniform when every shape agrees"""
+        if ragged and isinstance(images, (list, tuple)):
+            arrays = [np.asarray(a) for a in images]
+            if ragged != "auto" or len({a.shape for a in arrays}) > 1:
+                return cls.from_packed(*pack_images(arrays), labels, classes, device)
+        elif ragged and ragged != "auto":
+            return cls.from_packed(*pack_images(list(np.asarray(images.cpu() if isinstance(images, torch.Tensor) else images))), labels, classes, device)
         if isinstance(images, (list, tuple)):
             shapes = sorted({tuple(np.shape(a)) for a in images})
             if len(shapes) > 1:
@@ -148,9 +247,11 @@ class DeviceImageSet:
         return cls.from_arrays(images, np.asarray(d["fine_labels"], dtype=np.int64), classes or [str(i) for i in range(100)], device)
 
     @classmethod
-    def from_folder(cls, root, device="cuda"):
+    def from_folder(cls, root, device="cuda", ragged=False, budget_bytes=None):
         """An ImageFolder tree root/<class>/<file>: classes are the sorted directory names, files sorted within a class, read with PIL
-        and convert('RGB')."""
+        and convert('RGB').  ragged (True or "auto", as from_arrays): a first pass reads the headers only, adds up the bytes and refuses
+        with SystemExit, before any image is decoded, a set above budget_bytes (None: the device's free memory less RESIDENT_RESERVE_BYTES);
+        then the images are decoded straight into the arena by at most DECODE_WORKERS threads."""
         try:
             from PIL import Image
         except ImportError as e:
@@ -158,6 +259,8 @@ class DeviceImageSet:
         if not os.path.isdir(root):
             raise SystemExit(f"--device-data: {root} is not a directory (an ImageFolder tree, as splite_dataset.py writes)")
         classes = sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d)))
+        if ragged:
+            return cls._from_folder_packed(Image, root, classes, device, ragged, budget_bytes)
         images, labels, size = [], [], None
         for ci, c in enumerate(classes):
             for dirpath, _, files in sorted(os.walk(os.path.join(root, c), followlinks=True)):
@@ -177,8 +280,102 @@ class DeviceImageSet:
             raise SystemExit(f"--device-data: no images under {root}")
         return cls.from_arrays(np.stack(images), np.asarray(labels, dtype=np.int64), classes, device)
 
+    @classmethod
+    def _from_folder_packed(cls, Image, root, classes, device, ragged, budget_bytes):
+        from concurrent.futures import ThreadPoolExecutor
+        paths, labels = [], []
+        for ci, c in enumerate(classes):
+            for dirpath, _, files in sorted(os.walk(os.path.join(root, c), followlinks=True)):
+                for fn in sorted(files):
+                    if fn.lower().endswith(IMG_EXTENSIONS):
+                        paths.append(os.path.join(dirpath, fn))
+                        labels.append(ci)
+        if not paths:
+            raise SystemExit(f"--device-data: no images under {root}")
+        entries = np.zeros(len(paths), dtype=IMAGE_ENTRY_DTYPE)
+        at = 0
+        for i, p in enumerate(paths):               # the headers only: nothing is decoded
+            with Image.open(p) as im:
+                W, H = im.size
+            entries[i] = (at, H, W)
+            at += (3 * H * W + ARENA_ALIGN - 1) // ARENA_ALIGN * ARENA_ALIGN
+        free = None
+        if budget_bytes is None and torch.device(device).type == "cuda":
+            free = torch.cuda.mem_get_info(device)[0]
+            budget_bytes = free - RESIDENT_RESERVE_BYTES
+        if budget_bytes is not None and at > budget_bytes:
+            big = int(np.argmax(entries["H"].astype(np.int64) * entries["W"]))
+            raise SystemExit(f"--device-data: the {len(paths)} images under {root} take {at} bytes as uint8, the budget for a resident set is {budget_bytes} bytes "
+                             + (f"(the device's {free} free bytes less a reserve of {RESIDENT_RESERVE_BYTES} for the models and activations)" if free is not None
+                                else "(budget_bytes)")
+                             + f"; the largest image is {paths[big]}, {entries['H'][big]} x {entries['W'][big]}")
+        uniform = ragged == "auto" and len(set(zip(entries["H"].tolist(), entries["W"].tolist()))) == 1
+        arena = np.zeros(at, dtype=np.uint8)
+
+        def decode(i):
+            with Image.open(paths[i]) as im:
+                a = np.asarray(im.convert('RGB'), dtype=np.uint8)
+            H, W = int(entries["H"][i]), int(entries["W"][i])
+            if a.shape != (H, W, 3):
+                raise ValueError(f"{paths[i]} decodes to {a.shape[0]} x {a.shape[1]}, its header says {H} x {W}")
+            arena[int(entries["offset"][i]):int(entries["offset"][i]) + a.size] = a.reshape(-1)
+        with ThreadPoolExecutor(max_workers=DECODE_WORKERS) as pool:
+            list(pool.map(decode, range(len(paths))))
+        labels = np.asarray(labels, dtype=np.int64)
+        if uniform:
+            H, W = int(entries["H"][0]), int(entries["W"][0])
+            step = (3 * H * W + ARENA_ALIGN - 1) // ARENA_ALIGN * ARENA_ALIGN
+            return cls.from_arrays(np.ascontiguousarray(arena.reshape(len(paths), step)[:, :3 * H * W]).reshape(len(paths), H, W, 3), labels, classes, device)
+        return cls.from_packed(arena, entries, labels, classes, device)
+
+    def save(self, path):
+        """The set as plain arrays under directory `path`: arena.npy + entries.npy (packed) or images.npy (uniform), labels.npy, classes.npy"""
+        os.makedirs(path, exist_ok=True)
+        if self.ragged:
+            np.save(os.path.join(path, "arena.npy"), self.arena.cpu().numpy())
+            np.save(os.path.join(path, "entries.npy"), self.entries.cpu().numpy().view(IMAGE_ENTRY_DTYPE))
+        else:
+            np.save(os.path.join(path, "images.npy"), self.images.cpu().numpy())
+        np.save(os.path.join(path, "labels.npy"), self.labels.cpu().numpy())
+        np.save(os.path.join(path, "classes.npy"), np.array([str(c) for c in self.classes], dtype=np.str_))
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        """What save() wrote; the image bytes are mapped (copy-on-write), so they are read once, by the copy to the device"""
+        labels = np.load(os.path.join(path, "labels.npy"))
+        classes = [str(c) for c in np.load(os.path.join(path, "classes.npy"))]
+        if os.path.exists(os.path.join(path, "arena.npy")):
+            return cls.from_packed(np.load(os.path.join(path, "arena.npy"), mmap_mode="c"), np.load(os.path.join(path, "entries.npy")), labels, classes, device)
+        return cls.from_arrays(torch.from_numpy(np.load(os.path.join(path, "images.npy"), mmap_mode="c")), labels, classes, device)
+
+    @staticmethod
+    def saved(path):
+        return os.path.exists(os.path.join(path, "labels.npy"))
+
 
 # ---- the per-sample draws --------------------------------------------------------------------------------------------------------------------
+def _per_sample(B, H0, W0):
+    """H0, W0 as ints (every sample's) or as int arrays of length B -> two lists of B python ints"""
+    out = []
+    for v in (H0, W0):
+        if np.ndim(v) == 0:
+            out.append([int(v)] * B)
+        else:
+            if len(v) != B:
+                raise ValueError(f"draw: {len(v)} image sizes for {B} samples")
+            out.append([int(x) for x in v])
+    return out
+
+
+def _refuse_over_wide(who, H, W, need):
+    """ValueError naming the images (index, size) whose `need` taps exceed the wide kernel's limit"""
+    bad = np.flatnonzero(need > L.AUGMENT_TAPS_MAX)
+    if bad.size:
+        some = ", ".join(f"image {i} ({H[i]} x {W[i]}: {need[i]} taps)" for i in bad[:5])
+        raise ValueError(f"{who}: {bad.size} image(s) of the set need more than {L.AUGMENT_TAPS_MAX} taps per output pixel (DEVIT_AUGMENT_TAPS_MAX), "
+                         f"the first: {some}")
+
+
 class TrainAugment:
     """One devit_augment_sample per sample, drawn as timm 0.5.4 draws (transforms_imagenet_train: RandomResizedCropAndInterpolation.get_params,
     the interpolation when 'random', RandomHorizontalFlip, RandomErasing._erase), in that order, on a private random.Random seeded by
@@ -210,7 +407,21 @@ class TrainAugment:
         return self.rand is not None or self.color_jitter > 0
 
     def check_set(self, H0, W0):
-        """Refuse a set this transform cannot serve (the tap limit of the resampling kernel), before anything is drawn."""
+        """Refuse a set this transform cannot serve (the tap limit of the resampling kernel), before anything is drawn.  H0, W0: ints (a
+        uniform set) or the int arrays of a packed set's sizes, which the wide kernel serves up to DEVIT_AUGMENT_TAPS_MAX taps."""
+        if np.ndim(H0):
+            H, W = np.asarray(H0, np.int64), np.asarray(W0, np.int64)
+            if self.S == 32:
+                bad = np.flatnonzero((H + 8 < self.S) | (W + 8 < self.S))
+                if bad.size:
+                    raise ValueError(f"TrainAugment: a padded {self.S} x {self.S} crop does not fit image {bad[0]} ({H[bad[0]]} x {W[bad[0]]})")
+                return
+            need = np.zeros(H.shape[0], np.int64)
+            for f in (FILTERS.values() if self.interpolation == 'random' else (FILTERS[self.interpolation],)):
+                for side in (H, W):                                  # the largest crop is the whole side
+                    need = np.maximum(need, _exact_where_over(taps_bound(side, self.S, f), side, self.S, f))
+            _refuse_over_wide(f"TrainAugment at {self.S} pixels", H, W, need)
+            return
         if self.S == 32:
             if H0 + 8 < self.S or W0 + 8 < self.S:
                 raise ValueError(f"TrainAugment: a padded {self.S} x {self.S} crop does not fit {H0} x {W0} images")
@@ -313,14 +524,17 @@ class TrainAugment:
         return self.draw_with_ops(B, H0, W0)[0]
 
     def draw_with_ops(self, B, H0, W0):
-        """-> (AUG_SAMPLE_DTYPE [B], AUG_OPS_DTYPE [B] or None): crop, interpolation if random, flip, the image-op layers, erasing per sample"""
+        """-> (AUG_SAMPLE_DTYPE [B], AUG_OPS_DTYPE [B] or None): crop, interpolation if random, flip, the image-op layers, erasing per sample.
+        H0, W0: ints, or int arrays of length B (a packed set): sample b is then drawn on its own size, by the same formulas in the same order."""
         S, rng = self.S, self.rng
+        Hs, Ws = _per_sample(B, H0, W0)
         layers = np.zeros(B, dtype=AUG_OPS_DTYPE) if self.has_ops else None
         if layers is not None:
             layers["matrix"][:, :, 0] = layers["matrix"][:, :, 4] = 1.
             layers["fill"][:, :, :3] = self.fill
         cols, erase = [], np.zeros((B, 4, 4), dtype=np.int32)      # (columns are filled at once: a field store per sample costs more than its draw)
         for b in range(B):
+            H0, W0 = Hs[b], Ws[b]
             if S == 32:
                 y0, x0, h, w, filt = rng.randint(0, H0 + 8 - S) - 4, rng.randint(0, W0 + 8 - S) - 4, S, S, L.AUG_NONE
             else:
@@ -375,6 +589,18 @@ class EvalTransform:
         return Rh, Rw, int(round((Rh - S) / 2.)), int(round((Rw - S) / 2.)), L.AUG_BICUBIC
 
     def check_set(self, H0, W0):
+        if np.ndim(H0):
+            H, W = np.asarray(H0, np.int64), np.asarray(W0, np.int64)
+            geo = np.asarray([self.geometry(int(h), int(w)) for h, w in zip(H, W)], dtype=np.int64)
+            if self.S == 32:
+                bad = np.flatnonzero((H != self.S) | (W != self.S))
+                if bad.size:
+                    raise ValueError(f"EvalTransform: at {self.S} pixels the images are used as they are, and image {bad[0]} is {H[bad[0]]} x {W[bad[0]]}")
+                return
+            need = np.maximum(_exact_where_over(taps_bound(H, geo[:, 0], geo[:, 4]), H, geo[:, 0], geo[:, 4]),
+                              _exact_where_over(taps_bound(W, geo[:, 1], geo[:, 4]), W, geo[:, 1], geo[:, 4]))
+            _refuse_over_wide(f"EvalTransform at {self.S} pixels", H, W, need)
+            return
         Rh, Rw, _, _, filt = self.geometry(H0, W0)
         if filt == L.AUG_NONE:
             if (H0, W0) != (self.S, self.S):
@@ -384,7 +610,16 @@ class EvalTransform:
         _check_taps(W0, Rw, filt, f"EvalTransform on {H0} x {W0} images")
 
     def draw(self, B, H0, W0):
+        """H0, W0: ints, or int arrays of length B (a packed set): the geometry is then each image's own"""
         tab = np.zeros(B, dtype=AUG_SAMPLE_DTYPE)
+        if np.ndim(H0) or np.ndim(W0):
+            Hs, Ws = _per_sample(B, H0, W0)
+            known = {}
+            geo = np.asarray([known.setdefault(hw, self.geometry(*hw)) for hw in zip(Hs, Ws)], dtype=np.int32)
+            tab["h"], tab["w"] = Hs, Ws
+            for k, name in enumerate(("Rh", "Rw", "oy", "ox", "filter")):
+                tab[name] = geo[:, k]
+            return tab
         tab["h"], tab["w"] = H0, W0
         tab["Rh"], tab["Rw"], tab["oy"], tab["ox"], tab["filter"] = self.geometry(H0, W0)
         return tab
@@ -419,7 +654,14 @@ def upload(host_bytes, device):
 
 
 def check_table(tab, H0, W0, S):
-    """ValueError for a table the header's definition does not cover (the kernels are memory-safe for any bytes; this is where values are checked)."""
+    """ValueError for a table the header's definition does not cover (the kernels are memory-safe for any bytes; this is where values are checked).
+    H0, W0 as int arrays, one size per row (a packed set): every row is held to its own image, the tap limit is the wide kernel's, and the
+    batch's max_taps for devit_augment_ragged is returned (the header's closed-form bound, in numpy: no loop per distinct length)."""
+    ragged = bool(np.ndim(H0) or np.ndim(W0))
+    if ragged:
+        H0, W0 = np.asarray(H0, np.int64), np.asarray(W0, np.int64)
+        if H0.shape != tab.shape or W0.shape != tab.shape:
+            raise ValueError(f"augment_batch: {H0.shape[0] if H0.ndim else 1} image sizes for a table of {tab.shape[0]} rows")
     if tab.dtype != AUG_SAMPLE_DTYPE or tab.ndim != 1 or tab.shape[0] < 1:
         raise ValueError("augment_batch: the table is a 1-d numpy array of AUG_SAMPLE_DTYPE")
     filt = tab["filter"]
@@ -433,9 +675,17 @@ def check_table(tab, H0, W0, S):
         raise ValueError(f"augment_batch: the {S} x {S} window must lie inside the virtual output")
     res = filt != 0
     if (res & ((tab["y0"] < 0) | (tab["x0"] < 0) | (tab["y0"] + tab["h"] > H0) | (tab["x0"] + tab["w"] > W0))).any():
-        raise ValueError(f"augment_batch: a resized box must lie inside the {H0} x {W0} image")
+        raise ValueError("augment_batch: a resized box must lie inside its image" if ragged else f"augment_batch: a resized box must lie inside the {H0} x {W0} image")
     if (~res & ((tab["h"] != tab["Rh"]) | (tab["w"] != tab["Rw"]))).any():
         raise ValueError("augment_batch: filter 0 is unit scale: the box has the virtual output's size")
+    if ragged:
+        need = np.maximum(_exact_where_over(taps_bound(tab["h"], tab["Rh"], filt), tab["h"], tab["Rh"], filt),
+                          _exact_where_over(taps_bound(tab["w"], tab["Rw"], filt), tab["w"], tab["Rw"], filt))
+        if (need > L.AUGMENT_TAPS_MAX).any():
+            b = int(np.argmax(need))
+            raise ValueError(f"augment_batch: row {b} resizes a {tab['h'][b]} x {tab['w'][b]} box to {tab['Rh'][b]} x {tab['Rw'][b]}, which needs {need[b]} taps "
+                             f"per output pixel; the wide resampling kernel holds {L.AUGMENT_TAPS_MAX}")
+        return int(need.max())
     for key in {(int(a), int(b), int(c)) for a, b, c in zip(tab["h"][res], tab["Rh"][res], filt[res])} | \
             {(int(a), int(b), int(c)) for a, b, c in zip(tab["w"][res], tab["Rw"][res], filt[res])}:
         _check_taps(*key, "augment_batch")
@@ -514,6 +764,41 @@ def augment_batch(src, idx, table, S, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_D
     return out
 
 
+def augment_ragged(ds, idx, table, S, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD, seed=0, out=None, table_dev=None, layers=None,
+                   layers_dev=None, max_taps=None, force_wide=False):
+    """augment_batch over a packed DeviceImageSet (devit_augment_ragged).  idx: int32 [B] on the device.  max_taps: what check_table returned
+    for this table on the samples' own sizes (None: validated here, which reads idx back); force_wide: every sample through the wide kernel."""
+    if not ds.ragged:
+        raise ValueError("augment_ragged: the set is uniform: augment_batch(ds.images, ...)")
+    L.require_device(ds.arena)
+    dev = ds.arena.device
+    if idx.dtype != torch.int32 or idx.dim() != 1 or idx.device != dev or not idx.is_contiguous():
+        raise ValueError("augment_batch: idx must be a contiguous int32 [B] tensor on the set's device")
+    S = ops.check_img_size(S, exc=ValueError)
+    B = idx.shape[0]
+    if table.shape[0] != B:
+        raise ValueError(f"augment_batch: the table has {table.shape[0]} rows, the batch {B} samples")
+    if max_taps is None:
+        sizes = ds.sizes[np.clip(idx.cpu().numpy(), 0, len(ds) - 1)]
+        max_taps = check_table(table, sizes[:, 0], sizes[:, 1], S)
+    if table_dev is None:
+        table_dev = upload(np.ascontiguousarray(table).view(np.uint8).reshape(-1), dev)
+    if out is None:
+        out = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.shape[1:] != (3, S, S) or out.shape[0] < B or not out.is_contiguous() or out.device != dev:
+        raise ValueError("augment_batch: out must be a contiguous fp32 [>=B,3,S,S] tensor on the set's device")
+    if layers is not None and layers_dev is None:
+        check_ops_table(layers, B)
+        layers_dev = upload(np.ascontiguousarray(layers).view(np.uint8).reshape(-1), dev)
+    m3, s3 = (L.C.c_float * 3)(*mean), (L.C.c_float * 3)(*std)
+    nbytes = L.load().devit_augment_ragged_workspace(B, S, int(max_taps), int(layers is not None))
+    ws = ops.workspace(dev, nbytes)
+    ops.call("devit_augment_ragged", ptr(ds.arena), ds.arena.shape[0], ptr(ds.entries), len(ds), ptr(idx), ptr(table_dev),
+             ptr(layers_dev) if layers is not None else None, B, S, m3, s3, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out), ptr(ws), nbytes,
+             int(max_taps), L.AUGMENT_FORCE_WIDE if force_wide else 0, stream_ptr())
+    return out
+
+
 class DeviceLoader:
     """Batches of a DeviceImageSet: (images fp32 [B,3,S,S], labels int64 [B]) device tensors, fresh per step as SyntheticLoader's and for its
     reason.  sampler: any iterable of indices with a length (RASampler, DistributedSampler, SequentialSampler); `.sampler` is what
@@ -521,7 +806,10 @@ class DeviceLoader:
 
     def __init__(self, dataset, sampler, batch_size, transform, drop_last):
         self.dataset, self.sampler, self.batch_size, self.transform, self.drop_last = dataset, sampler, int(batch_size), transform, drop_last
-        transform.check_set(*dataset.size)        # refuses a set that needs more taps than the kernel holds
+        if dataset.ragged:                        # a packed set: refuses it naming the images beyond the wide kernel's taps
+            transform.check_set(dataset.sizes[:, 0], dataset.sizes[:, 1])
+        else:
+            transform.check_set(*dataset.size)    # refuses a set that needs more taps than the kernel holds
 
     def __len__(self):
         n = len(self.sampler)
@@ -529,18 +817,23 @@ class DeviceLoader:
 
     def _batch(self, indices):
         ds, tf = self.dataset, self.transform
-        B, (H0, W0) = len(indices), ds.size
-        table, layers = tf.draw_with_ops(B, H0, W0) if getattr(tf, "has_ops", False) else (tf.draw(B, H0, W0), None)
+        B = len(indices)
         idx = np.asarray(indices, dtype=np.int32)
         if idx.min() < 0 or idx.max() >= len(ds):
             raise IndexError(f"DeviceLoader: the sampler yields indices outside 0 .. {len(ds) - 1}")
+        H0, W0 = (ds.sizes[idx, 0], ds.sizes[idx, 1]) if ds.ragged else ds.size
+        table, layers = tf.draw_with_ops(B, H0, W0) if getattr(tf, "has_ops", False) else (tf.draw(B, H0, W0), None)
         pad = (-idx.nbytes) % 8                   # the table's 64-bit field stays aligned behind the indices
         parts = [idx.view(np.uint8), np.zeros(pad, np.uint8), table.view(np.uint8).reshape(-1)]
         if layers is not None:
             check_ops_table(layers, B)
             parts.append(layers.view(np.uint8).reshape(-1))       # (120-byte rows: the layers' doubles stay 8-byte aligned behind them)
-        both = upload(np.concatenate(parts), ds.images.device)
+        both = upload(np.concatenate(parts), ds.device)
         idx_dev, at = both[:idx.nbytes].view(torch.int32), idx.nbytes + pad
+        if ds.ragged:
+            images = augment_ragged(ds, idx_dev, table, tf.S, tf.mean, tf.std, tf.seed, table_dev=both[at:at + table.nbytes], layers=layers,
+                                    layers_dev=both[at + table.nbytes:] if layers is not None else None, max_taps=check_table(table, H0, W0, tf.S))
+            return images, ds.labels.index_select(0, idx_dev.long())
         images = augment_batch(ds.images, idx_dev, table, tf.S, tf.mean, tf.std, tf.seed, table_dev=both[at:at + table.nbytes], layers=layers,
                                layers_dev=both[at + table.nbytes:] if layers is not None else None)
         return images, ds.labels.index_select(0, idx_dev.long())

@@ -85,6 +85,9 @@ def get_args_parser():
     a('--device-data', action='store_true', default=False,
       help='keep the uint8 dataset resident on the device and crop, resize, flip, normalize and erase there (devit_amd.data; DESIGN.md section 15): '
            'needs no torchvision / timm.  RandAugment and ColorJitter need --device-aug; without it give --aa none --color-jitter 0')
+    a('--device-data-cache', default='', type=str, metavar='DIR',
+      help='with --device-data: load the resident sets from DIR/{train,test} (plain .npy arrays) when they are there, else decode the folders once '
+           'and write them there')
     a('--device-aug', action='store_true', default=False,
       help='with --device-data: run --aa rand-m<M>-mstd<F>-inc1-n<N> (RandAugment) or --color-jitter (no hue), and --no_aug\'s stack, on the device too, '
            'on the uint8 image held in LDS between flip and ToTensor (DESIGN.md section 16)')
@@ -238,18 +241,35 @@ def build_device_loaders(args, num_classes, device, provider, plain_sampler_over
     """build_loaders with --device-data: the same samplers, drop_last and --no-repeated-aug quirk over devit_amd.data.DeviceImageSet."""
     from devit_amd import data
     check_device_data(args)
+    cache = getattr(args, 'device_data_cache', '') or ''
+
+    def folder_set(path, split):
+        """a folder tree made resident (uniform when its sizes agree, packed otherwise), by way of --device-data-cache DIR/<split> when given"""
+        saved = os.path.join(cache, split) if cache else ''
+        if saved and data.DeviceImageSet.saved(saved):
+            return data.DeviceImageSet.load(saved, device)
+        ds = data.DeviceImageSet.from_folder(path, device, ragged="auto")
+        if saved and utils.is_main_process():
+            ds.save(saved)
+        return ds
     if provider == "division":
         root = os.path.join(args.data_path, f"sub-dataset{args.start_division}")
-        train_ds = data.DeviceImageSet.from_folder(os.path.join(root, 'train_dataset'), device)
-        test_ds = data.DeviceImageSet.from_folder(os.path.join(root, 'test_dataset'), device)
+        train_ds = folder_set(os.path.join(root, 'train_dataset'), 'train')
+        test_ds = folder_set(os.path.join(root, 'test_dataset'), 'test')
+        num_classes = len(train_ds.classes)
+    elif args.dataset == 'IMNET':                  # torchvision's ImageFolder over <data-path>/train and /val (data/get_dataset.py)
+        train_ds = folder_set(os.path.join(args.data_path, 'train'), 'train')
+        test_ds = folder_set(os.path.join(args.data_path, 'val'), 'test')
         num_classes = len(train_ds.classes)
     elif args.dataset == 'cifar100':
         train_ds = data.DeviceImageSet.from_cifar100(args.data_path, True, device)
         test_ds = data.DeviceImageSet.from_cifar100(args.data_path, False, device)
         num_classes = 100
     else:
-        raise SystemExit(f"--device-data --dataset {args.dataset}: only cifar100 is read whole (its pickles under --data-path); the other sets "
-                         "have images of mixed sizes, and resident sets are uniform")
+        layout = {'flowers': "its .mat label and split files", 'cars': "its .mat annotation files", 'pets': "its annotation list files",
+                  'INAT': "its json annotation files", 'INAT19': "its json annotation files"}.get(args.dataset, "its file layout")
+        raise SystemExit(f"--device-data --dataset {args.dataset}: cifar100 (its pickles under --data-path), IMNET (<data-path>/train and /val as "
+                         f"folder trees) and the division folders are read; this set is not, for {layout}, which no reader here parses")
     world, rank = utils.get_world_size(), utils.get_rank()
     if args.repeated_aug:
         sampler_train = RASampler(train_ds, num_replicas=world, rank=rank, shuffle=True)

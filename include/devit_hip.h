@@ -837,6 +837,7 @@ DEVIT_API int devit_block_bwd_drop(const devit_block_weights* w, const devit_blo
  * devit_augment_coeffs fills it from the table; devit_augment_batch runs devit_augment_coeffs and then the resampling kernel, which is
  * integer arithmetic up to step 3.  mean / std are HOST arrays of 3 floats.  No address in either kernel depends on the table's or idx's contents
  * without a clamp, so both are memory-safe for any table bytes; rows of `out` beyond B and bytes outside `out` are never written.
+ * Sets whose images differ in size, and samples that need more than DEVIT_AUGMENT_TAPS taps: "Packed sets" below (devit_augment_ragged).
  * ---------------------------------------------------------------------------------------- */
 #define DEVIT_AUGMENT_TAPS 12
 #define DEVIT_AUGMENT_MAX_ERASE 4
@@ -928,6 +929,46 @@ DEVIT_API size_t devit_augment_ops_workspace(int B, int S);
 DEVIT_API int devit_augment_batch_ops(const unsigned char* src, int n, int H0, int W0, const int* idx, const devit_augment_sample* table,
                             const devit_augment_ops* ops, int B, int S, const float* mean /* host [3] */, const float* std /* host [3] */,
                             unsigned long long seed, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Packed sets: the "Input augmentation" stage over a set whose images differ in size.  The set is one byte arena on the device, the
+ * images HWC one behind the other, and a device directory of n devit_image_entry (struct id 16 of devit_abi_struct_size, 16 bytes): the image's byte offset in
+ * the arena (a multiple of 16 as devit_amd.data packs it; the kernels need no alignment) and its H and W.  out[b] is made from image
+ * clamp(idx[b], 0, n - 1) by steps 1 to 4 of that section, unchanged, with H0 and W0 that entry's; with ops != null the layers of "Image ops" above
+ * run between steps 2 and 3 as in devit_augment_batch_ops (with n_ops == 0 everywhere: the same bits as with ops == null).
+ *   max_taps  the caller's upper bound T, 1 .. DEVIT_AUGMENT_TAPS_MAX, on the taps any sample of the batch needs on either axis.
+ *             The coefficient workspace is int32 [B][2 axes][2 + T][S] (xmin, count, weights; counts are clamped to T);
+ *             devit_augment_ragged_workspace(B, S, max_taps, with_ops) bytes, with_ops != 0 adding the uint8 windows behind it.
+ *   A sample is WIDE when bound(h, Rh) or bound(w, Rw) exceeds DEVIT_AUGMENT_TAPS, with, in IEEE double,
+ *             bound(len, R) = min(floor(2 * support) + 1, len), support = (1 bilinear | 2 bicubic) * max(len / R, 1); filter 0: 1.
+ *             The bound is never below the exact tap count of the axis (and at most 1 above it), so a sample that is not wide fits the
+ *             narrow kernel.  max_taps is at least the largest bound of the batch's samples (or the exact count where the caller knows it).
+ * Two resampling kernels serve a batch, each launched over all B when max_taps > DEVIT_AUGMENT_TAPS; a workgroup leaves at once unless its
+ * sample is its kernel's kind, decided from the table row by the closed form above (no host decision per sample, no divergence in a wave).
+ *   narrow    devit_augment_batch's kernel with the image's base, H0 and W0 read from the directory: 12 weights in registers per column, the
+ *             uint8 intermediate of up to 24 source rows in LDS.
+ *   wide      13 .. DEVIT_AUGMENT_TAPS_MAX taps.  One workgroup per (sample, 16 output rows), thread x owning output column x: it walks the
+ *             band's source rows once, makes each row's horizontal result for its column (weights read [tap][x] from the workspace), clamps
+ *             it to uint8 -- PIL's intermediate, part of the definition -- and adds it, weighted, into the int32 accumulators of the output
+ *             rows whose vertical window holds that source row.  No intermediate image is kept, so a band may span any number of rows.
+ * Both compute the same integers: a sample gives identical bits through either (DEVIT_AUGMENT_FORCE_WIDE in flags sends every sample
+ * through the wide kernel; tests compare).  The pass order is horizontal first for every box (PIL itself makes the vertical pass first for
+ * boxes about 107 or more times as tall as wide).
+ * Memory safety: idx is clamped; every source address is clamped into the image's own extent, which is checked against [0, arena_bytes)
+ * per sample, and the value masked afterwards; an entry with H < 1, W < 1 or offset + 3 H W > arena_bytes reads as an image of zeros;
+ * counts and every LDS index are clamped; rows of `out` beyond B and bytes outside `out` are never written.
+ * ---------------------------------------------------------------------------------------- */
+#define DEVIT_AUGMENT_TAPS_MAX 128
+#define DEVIT_AUGMENT_FORCE_WIDE 1u /* flags: every sample through the wide kernel (tests) */
+typedef struct {
+  unsigned long long offset; /* of the image's first byte in the arena */
+  int H, W;
+} devit_image_entry;
+DEVIT_API size_t devit_augment_ragged_workspace(int B, int S, int max_taps, int with_ops);
+DEVIT_API int devit_augment_ragged(const unsigned char* arena, size_t arena_bytes, const devit_image_entry* entries /* device, n */, int n,
+                         const int* idx, const devit_augment_sample* table, const devit_augment_ops* ops /* may be null */, int B,
+                         int S, const float* mean /* host [3] */, const float* std /* host [3] */, unsigned long long seed, float* out,
+                         void* workspace, size_t workspace_bytes, int max_taps, unsigned flags, void* stream);
 
 #ifdef __cplusplus
 }
