@@ -233,6 +233,10 @@ SIGNATURES = {
     "devit_relation_grad": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
     "devit_relation_fused_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "devit_relation_fused_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
+    "devit_qkv_pair_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "devit_qkv_pair_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "devit_soft_ce_rows_fwd": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "devit_soft_ce_rows_bwd": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "devit_add_scale_cast_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "devit_hid_normalize": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "devit_hid_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),

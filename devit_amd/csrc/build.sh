@@ -28,7 +28,7 @@ case "$LIB" in /*) ;; *) LIB="$PWD/$LIB" ;; esac
 # -fvisibility=hidden: the library exports the C ABI of include/devit_hip.h (DEVIT_API) and nothing else
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -munsafe-fp-atomics -Wno-unused-result"
 # one object per unit, the slowest to compile first (all are started at once)
-UNITS="gemm_tile256 gemm_tile128 gemmfr gemm4 wgradfr attention elementwise optim dropout losses relation hid layernorm hsic gemm sgemm encoder shrink augment comm det api"
+UNITS="gemm_tile256 gemm_tile128 gemmfr gemm4 wgradfr attention elementwise optim dropout losses relation qkvce hid layernorm hsic gemm sgemm encoder shrink augment comm det api"
 
 # The asm K loops of the four-wave and full-row GEMM kernels are GENERATED (tools/gen_gemm4.py, tools/gen_gemmfr.py document the register
 # plans): made here, not committed (2 MB of text); tests/test_abi.py regenerates them and compares with what the library was built from.

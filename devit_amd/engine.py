@@ -64,17 +64,27 @@ def _side_forward(teacher_model, samples, main, side):
 
 
 def distill_forward(model, teacher_model, samples, targets, gama=(0.2, 0.1, 0.3), kind="hard", alpha=0.5, tau=1.0,
-                    criterion=None, dp_scales="draw", teacher_outputs=None, after_student=None, hid_gama=0.0):
+                    criterion=None, dp_scales="draw", teacher_outputs=None, after_student=None, hid_gama=0.0, qkv_ce_gama=0.0,
+                    qkv_cross_gama=0.0, qkv_layout="view"):
     """One DEKD forward.  Returns dict(loss, cls_loss, q_loss, k_loss, v_loss, logits, teacher_logits).
     teacher_outputs: the teacher's outputs for `samples` if they were computed ahead (TeacherLookahead).
     after_student: called once the student's forward is enqueued (TeacherLookahead.launch of the NEXT batch).
     hid_gama > 0: loss += hid_gama * cal_hid_relation_loss of the middle blocks' hidden states (utils/losses.py:295-304; the layer pair the q/k/v
     relation losses use), returned as `hid_loss`; student and teacher then hand out that one block's 'encoder' output (enc_layers).  0: the step as
-    it was, dict and all."""
+    it was, dict and all.
+    qkv_ce_gama / qkv_cross_gama > 0: loss += qkv_ce_gama * cal_qkv_loss([s_mid], [t_mid]) + qkv_cross_gama * cal_qkv_loss2([s_mid], [t_mid])
+    (utils/losses.py:247-292) on the same middle layer pair, rows per qkv_layout; returned as `qkv_ce_loss` / `qkv_cross_loss`.  Both 0: the step
+    as it was, dict and all."""
     vit = model.module if hasattr(model, "module") else model
     hid_gama = float(hid_gama)
     if not hid_gama >= 0.:
         raise ValueError(f"hid_gama must be >= 0, got {hid_gama}")
+    qkv_ce_gama, qkv_cross_gama = float(qkv_ce_gama), float(qkv_cross_gama)
+    for name, w in (("qkv_ce_gama", qkv_ce_gama), ("qkv_cross_gama", qkv_cross_gama)):
+        if not w >= 0.:
+            raise ValueError(f"{name} must be >= 0, got {w}")
+    if qkv_layout not in ops.QKV_LAYOUTS:
+        raise ValueError(f"qkv_layout must be one of {sorted(ops.QKV_LAYOUTS)}, got {qkv_layout!r}")
     hid = hid_gama > 0.
     vit._hid_request = hid
     if teacher_outputs is None:          # (a TeacherLookahead made its request when it was built)
@@ -127,6 +137,12 @@ def distill_forward(model, teacher_model, samples, targets, gama=(0.2, 0.1, 0.3)
                                "ahead must come from TeacherLookahead(teacher, hid=True)" % ("student's" if s_hid is None else "teacher's"))
         out['hid_loss'] = losses.cal_hid_relation_loss([s_hid], [t_hid], exact=getattr(vit, "precision", "bf16") == "f32")
         out['loss'] = loss + hid_gama * out['hid_loss']
+    if qkv_ce_gama > 0.:
+        out['qkv_ce_loss'] = losses.cal_qkv_loss([qkvs[sl // 2 - 1]], [teacher_qkvs[tl // 2 - 1]], layout=qkv_layout)
+        out['loss'] = out['loss'] + qkv_ce_gama * out['qkv_ce_loss']
+    if qkv_cross_gama > 0.:
+        out['qkv_cross_loss'] = losses.cal_qkv_loss2([qkvs[sl // 2 - 1]], [teacher_qkvs[tl // 2 - 1]], layout=qkv_layout)
+        out['loss'] = out['loss'] + qkv_cross_gama * out['qkv_cross_loss']
     return out
 
 
@@ -315,7 +331,11 @@ def train_1epoch_qkv(model, teacher_model, criterion, data_loader, optimizer, de
     model.train(True)
     metric_logger = MetricLogger(delimiter="  ")
     hid_gama = float(getattr(args, "hid_gama", 0.0) or 0.0)        # --hid-gama: the hidden-state relation term (0: the step and its log line as they were)
-    for name in ('lr', 'cls_loss', 'q_loss', 'k_loss', 'v_loss') + (('hid_loss',) if hid_gama > 0 else ()):
+    # --qkv-ce-gama / --qkv-cross-gama / --qkv-layout: the soft cross-entropy relation terms (0: the step and its log line as they were)
+    qkv_ce_gama, qkv_cross_gama = float(getattr(args, "qkv_ce_gama", 0.0) or 0.0), float(getattr(args, "qkv_cross_gama", 0.0) or 0.0)
+    qkv_layout = getattr(args, "qkv_layout", "view") or "view"
+    extra = [n for n, w in (('hid_loss', hid_gama), ('qkv_ce_loss', qkv_ce_gama), ('qkv_cross_loss', qkv_cross_gama)) if w > 0]
+    for name in ('lr', 'cls_loss', 'q_loss', 'k_loss', 'v_loss') + tuple(extra):
         metric_logger.add_meter(name, SmoothedValue(window_size=1, fmt='{value:.6f}'))
     header = 'Epoch: [{}]'.format(epoch)
     step = 0
@@ -324,7 +344,8 @@ def train_1epoch_qkv(model, teacher_model, criterion, data_loader, optimizer, de
                                row_dtypes=row_dtypes_for(model, teacher_model))
     for samples, targets, teacher_out in metric_logger.log_every(batches, print_freq, header):
         out = distill_forward(model, teacher_model, samples, targets, gama=args.gama, criterion=criterion,
-                              teacher_outputs=teacher_out, after_student=batches.launch_teacher, hid_gama=hid_gama)
+                              teacher_outputs=teacher_out, after_student=batches.launch_teacher, hid_gama=hid_gama,
+                              qkv_ce_gama=qkv_ce_gama, qkv_cross_gama=qkv_cross_gama, qkv_layout=qkv_layout)
         loss = out['loss']
         log_now = (step % print_freq == 0)
         if log_now:
@@ -334,8 +355,8 @@ def train_1epoch_qkv(model, teacher_model, criterion, data_loader, optimizer, de
                 sys.exit(1)
             metric_logger.update(cls_loss=out['cls_loss'].item(), q_loss=out['q_loss'].item(),
                                  k_loss=out['k_loss'].item(), v_loss=out['v_loss'].item(), loss=loss_value)
-            if hid_gama > 0:
-                metric_logger.update(hid_loss=out['hid_loss'].item())
+            for name in extra:
+                metric_logger.update(**{name: out[name].item()})
         optimizer.zero_grad()
         loss_scaler(loss, optimizer, clip_grad=max_norm, parameters=model.parameters())
         if model_ema is not None:

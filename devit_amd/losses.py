@@ -4,6 +4,7 @@
   feature_relation_loss(teacher_feature, student_feature)                                        :307-328
   relation_losses_packed(student_qkv, teacher_qkv)   -- the three q/k/v losses of engine.py:95 in one node
   cal_hid_relation_loss(stu_hid_list, tea_hid_list)                                              :295-304
+  cal_qkv_loss / cal_qkv_loss2(stu_qkv_list, tea_qkv_list), soft_cross_entropy(predicts, targets) :247-292, :37-41
 """
 import torch
 import torch.nn as nn
@@ -158,6 +159,83 @@ def cal_hid_relation_loss(stu_hid_list, tea_hid_list, exact=False):
         L.require_device(s)
         loss = loss + ops.HidRelationLossFn.apply(s, t.detach(), layers, bool(exact))
     return loss
+
+
+class _RepackQkvFn(torch.autograd.Function):
+    """Differentiable copy of three [B, H, N, hd] tensors (any strides, any float type) into one packed bf16 qkv buffer
+    [pad(B N) + ops.qkv_pad_rows(N), 3 H hd]: component j in columns [j D, (j + 1) D), head h of it at h hd."""
+
+    @staticmethod
+    def forward(ctx, q, k, v):
+        B, H, N, hd = q.shape
+        D = H * hd
+        buf = ops.rows_alloc(B * N, 3 * D, torch.bfloat16, q.device, extra=ops.qkv_pad_rows(N))
+        for j, x in enumerate((q, k, v)):
+            buf[: B * N, j * D:(j + 1) * D] = x.permute(0, 2, 1, 3).reshape(B * N, D).to(torch.bfloat16)
+        ctx.meta = (B, H, N, hd, D, tuple(x.dtype for x in (q, k, v)))
+        return buf
+
+    @staticmethod
+    def backward(ctx, g):
+        B, H, N, hd, D, dts = ctx.meta
+        return tuple(g[: B * N, j * D:(j + 1) * D].reshape(B, N, H, hd).permute(0, 2, 1, 3).to(dts[j]) for j in range(3))
+
+
+def _qkv_packed(qkv, student):
+    """(packed 16-bit buffer, B, N, head width) of one (q, k, v) tuple: the models' packed views in place, anything else repacked"""
+    q, k, v = qkv
+    L.require_device(q)
+    p = _packed_of(q)
+    if p is not None:
+        buf, B, N, H = p
+        hd = buf.shape[1] // (3 * H)
+        if buf.dtype == torch.float32:
+            if student:
+                raise NotImplementedError('cal_qkv_loss / cal_qkv_loss2: a precision="f32" student (an fp32 packed qkv buffer) is not built: '
+                                          'these losses run on the 16-bit MFMA path only (DESIGN.md)')
+            buf = buf.detach().to(torch.bfloat16)             # an fp32-path teacher under a 16-bit student
+        return (buf if student else buf.detach()), B, N, hd
+    if q.dim() != 4 or q.shape != k.shape or q.shape != v.shape:
+        raise L.DevitError(f"cal_qkv_loss: q, k, v are [B, H, N, 64] tensors of one shape, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    B, H, N, hd = q.shape
+    if student:
+        return _RepackQkvFn.apply(q, k, v), B, N, hd
+    with torch.no_grad():
+        return _RepackQkvFn.apply(q, k, v), B, N, hd
+
+
+def _cal_qkv(stu_qkv_list, tea_qkv_list, cross, layout, name):
+    layers = len(stu_qkv_list)
+    loss = 0.
+    for stu_qkv, tea_qkv in zip(stu_qkv_list, tea_qkv_list):
+        s_buf, B, N, hd_s = _qkv_packed(stu_qkv, True)
+        t_buf, Bt, Nt, hd_t = _qkv_packed(tea_qkv, False)
+        if (B, N) != (Bt, Nt):
+            raise L.DevitError(f"{name}: student [B={B}, N={N}] and teacher [B={Bt}, N={Nt}] differ in batch or tokens")
+        if hd_s != 64 or hd_t != 64:
+            raise L.DevitError(f"{name}: heads must be 64 wide (student {hd_s}, teacher {hd_t}): the view's chunk map is built on 64-wide heads")
+        loss = loss + ops.QkvPairLossFn.apply(s_buf, t_buf, B, N, cross, layout, layers)
+    return loss
+
+
+def cal_qkv_loss(stu_qkv_list, tea_qkv_list, layout="view"):
+    """utils/losses.py:247-268: for every (student, teacher) pair of (q, k, v) tuples of [B, H, N, 64] tensors (the lists are walked with zip) and
+    every component i, soft_cross_entropy(Z_s, Z_t) of the Grams Z = X_i X_i^T / 8 per image; the sum divided by 3 len(stu_qkv_list).  X_i are the
+    rows of the reference's `.contiguous().view(B, N, H * 64)`, a REINTERPRETATION of the [B, H, N, 64] memory (layout="view", each model with its
+    own H), or the head-concatenated token rows that feature_relation_loss uses (layout="tokens").  The models' packed qkv views are read in
+    place; the gradient goes to the student.  N <= 208, widths multiples of 64 up to 1024."""
+    return _cal_qkv(stu_qkv_list, tea_qkv_list, False, layout, "cal_qkv_loss")
+
+
+def cal_qkv_loss2(stu_qkv_list, tea_qkv_list, layout="view"):
+    """utils/losses.py:271-292: as cal_qkv_loss with the nine ordered cross pairs Z_ij = X_i X_j^T / 8; the sum divided by 9 len(stu_qkv_list)."""
+    return _cal_qkv(stu_qkv_list, tea_qkv_list, True, layout, "cal_qkv_loss2")
+
+
+def soft_cross_entropy(predicts, targets):
+    """utils/losses.py:37-41: mean over all rows of -sum_j softmax(targets)_j log_softmax(predicts)_j along the last dimension (fp32 kernels)."""
+    L.require_device(predicts)
+    return ops.SoftCrossEntropyFn.apply(predicts, targets)
 
 
 class DistillationLoss(nn.Module):

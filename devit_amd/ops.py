@@ -1483,6 +1483,80 @@ class RelationLossFn(torch.autograd.Function):
         return d, None, None, None, None, None
 
 
+# ---- cal_qkv_loss / cal_qkv_loss2 / soft_cross_entropy (utils/losses.py:37-41, 247-292) -- csrc/qkvce.hip ----
+QKV_LAYOUTS = {"view": 0, "tokens": 1}
+
+
+class QkvPairLossFn(torch.autograd.Function):
+    """One layer pair of cal_qkv_loss (cross=False: the three pairs (i, i)) or cal_qkv_loss2 (cross=True: all nine ordered pairs) on PACKED qkv
+    buffers: the mean soft cross-entropy of the pairs' Grams X_i X_j^T / 8, divided by `layers`.  s_qkv: bf16 [>= B N rows, 3 Ds], t_qkv bf16 or
+    f16 likewise with Dt; heads are 64 wide.  layout "view": rows as the reference's `.view(B, N, H * 64)` of [B, H, N, 64] reinterprets them;
+    "tokens": head-concatenated token rows.  Returns an fp32 scalar; the gradient goes to the student buffer.  The context keeps the bf16 S of the
+    three or nine slots and nothing else of the forward."""
+
+    @staticmethod
+    def forward(ctx, s_qkv, t_qkv, B, N, cross, layout, layers):
+        L.require_device(s_qkv)
+        if layout not in QKV_LAYOUTS:
+            raise ValueError(f"layout must be one of {sorted(QKV_LAYOUTS)}, got {layout!r}")
+        if s_qkv.dtype == F32:
+            raise NotImplementedError('cal_qkv_loss / cal_qkv_loss2: a precision="f32" student (an fp32 packed qkv buffer) is not built: these '
+                                      'losses run on the 16-bit MFMA path only (DESIGN.md)')
+        if s_qkv.dtype != BF16 or t_qkv.dtype not in (BF16, F16) or s_qkv.dim() != 2 or t_qkv.dim() != 2 or s_qkv.stride(1) != 1 \
+                or t_qkv.stride(1) != 1 or s_qkv.shape[0] < B * N or t_qkv.shape[0] < B * N or s_qkv.shape[1] % 3 or t_qkv.shape[1] % 3:
+            raise L.DevitError(f"QkvPairLossFn: a bf16 student and a bf16 / f16 teacher packed [>= B N, 3 D] buffer, got {tuple(s_qkv.shape)} "
+                               f"{s_qkv.dtype} and {tuple(t_qkv.shape)} {t_qkv.dtype} for B={B} N={N}")
+        dev = s_qkv.device
+        Ds, Dt = s_qkv.shape[1] // 3, t_qkv.shape[1] // 3
+        P = 9 if cross else 3
+        loss = torch.empty(1, dtype=F32, device=dev)
+        terms = torch.empty((P, B * N), dtype=F32, device=dev)            # dead after the reduce
+        S = torch.empty((P, B, 208, 224), dtype=BF16, device=dev)
+        call("devit_qkv_pair_fwd", ptr(s_qkv), ptr(t_qkv), B, N, Ds, Dt, s_qkv.stride(0), t_qkv.stride(0), 64, 64, int(t_qkv.dtype == F16),
+             int(bool(cross)), QKV_LAYOUTS[layout], int(layers), ptr(terms), ptr(S), ptr(loss), stream_ptr())
+        ctx.S, ctx.s_qkv = S, s_qkv
+        ctx.meta = (B, N, Ds, int(bool(cross)), QKV_LAYOUTS[layout])
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        B, N, Ds, cross, layout = ctx.meta
+        s_qkv = ctx.s_qkv
+        g = g.contiguous().float()
+        d = torch.empty_like(s_qkv)       # rows < B*N are all written below (every 64-wide chunk of the three components has one writer)
+        call("devit_qkv_pair_bwd", ptr(ctx.S), ptr(s_qkv), ptr(g), B, N, Ds, s_qkv.stride(0), 64, cross, layout, ptr(d), d.stride(0),
+             stream_ptr())
+        ctx.S = None
+        return d, None, None, None, None, None, None
+
+
+class SoftCrossEntropyFn(torch.autograd.Function):
+    """utils/losses.py:37-41 on fp32 rows: mean over the rows of -sum softmax(targets) log_softmax(predicts); the gradient goes to predicts."""
+
+    @staticmethod
+    def forward(ctx, predicts, targets):
+        L.require_device(predicts)
+        if predicts.shape != targets.shape or predicts.dim() < 1 or predicts.numel() == 0:
+            raise L.DevitError(f"soft_cross_entropy: predicts {tuple(predicts.shape)} and targets {tuple(targets.shape)} must agree and be non-empty")
+        C_ = predicts.shape[-1]
+        p = predicts.detach().reshape(-1, C_).contiguous().float()
+        t = targets.detach().reshape(-1, C_).contiguous().float()
+        R = p.shape[0]
+        row_loss = torch.empty(R, dtype=F32, device=p.device)
+        loss = torch.empty(1, dtype=F32, device=p.device)
+        call("devit_soft_ce_rows_fwd", ptr(p), ptr(t), R, C_, ptr(row_loss), ptr(loss), stream_ptr())
+        ctx.keep, ctx.shape, ctx.dtype = (p, t), predicts.shape, predicts.dtype
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        p, t = ctx.keep
+        ctx.keep = None
+        dp = torch.empty_like(p)
+        call("devit_soft_ce_rows_bwd", ptr(p), ptr(t), ptr(g.contiguous().float()), p.shape[0], p.shape[1], ptr(dp), stream_ptr())
+        return dp.reshape(ctx.shape).to(ctx.dtype), None
+
+
 # ---- hidden-state relation loss (utils/losses.py:295-304, cal_hid_relation_loss) -- csrc/hid.hip ----
 HID_EPS = 1e-12       # torch.nn.functional.normalize's default eps
 

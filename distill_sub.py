@@ -70,6 +70,12 @@ def get_args_parser():
     a('--hid-gama', type=_non_negative, default=0.0, metavar='G',
       help='weight of the hidden-state relation loss of the middle blocks (the reference\'s cal_hid_relation_loss, utils/losses.py:295-304); '
            '0: the DEKD step as it is')
+    a('--qkv-ce-gama', type=_non_negative, default=0.0, metavar='G',
+      help='weight of the q/k/v soft cross-entropy relation loss of the middle blocks (the reference\'s cal_qkv_loss, utils/losses.py:247-268)')
+    a('--qkv-cross-gama', type=_non_negative, default=0.0, metavar='G',
+      help='weight of the nine cross relations q k^T, q v^T, ... (the reference\'s cal_qkv_loss2, utils/losses.py:271-292)')
+    a('--qkv-layout', default='view', choices=['view', 'tokens'],
+      help='rows of the two losses above: the reference\'s reinterpreting .view(B, N, H * 64) (default) or head-concatenated token rows')
     a('--data-path', default=r'./datasets'); a('--dataset', default='cifar100', choices=['cifar100', 'IMNET', 'cars', 'pets', 'flowers'])
     a('--inat-category', default='name'); a('--num_division', metavar='N', type=int, default=4); a('--start-division', metavar='N', type=int, default=0)
     a('--device', default='cuda'); a('--seed', default=0, type=int); a('--resume', default=''); a('--start_epoch', default=0, type=int)

@@ -708,6 +708,39 @@ DEVIT_API int devit_relation_fused_bwd(const void* S, const void* s_qkv, const f
                              int ld_d, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * cal_qkv_loss / cal_qkv_loss2 / soft_cross_entropy (utils/losses.py:37-41, 247-292; csrc/qkvce.hip).
+ *
+ * One (student, teacher) layer pair of packed 16-bit qkv buffers, read in place as devit_relation_fused_fwd reads them.  X_i: the [N][D] rows of
+ * component i of an image under `layout`: 0 ("view") the reference's `.contiguous().view(B, N, H * 64)` of [B, H, N, 64], a reinterpretation --
+ * chunk m of row r is head (r H + m) / N, token (r H + m) % N, each model with its own H = D / 64; 1 ("tokens") head-concatenated token rows.
+ * Z_ij = X_i X_j^T / 8 for student and teacher; an ordered pair's term is mean over the B N rows of -sum_j softmax(Z_t)_rj log_softmax(Z_s)_rj.
+ * cross 0: the three pairs (i, i), P = 3; cross 1: all nine ordered pairs, P = 9 (six Grams: (j, i) is (i, j) with the softmax over columns).
+ *   fwd : terms: fp32 [P][B N] workspace, the rows' terms of ordered pair (i, j) in slot i (cross 0) or 3 i + j (cross 1);
+ *         loss[0] = sum(terms) / (P layers B N) in a fixed order;
+ *         S_out: bf16 [P][B][208][224], every element written: slot (i, j) holds
+ *             S_ij = (dP_rows(Z_ij) + dP_cols(Z_ij)) / (P layers B N 8),  dP = softmax(Z_s) - softmax(Z_t),
+ *         rounded once, zero outside N x N; slot (j, i) its transpose.
+ *   bwd : d_i = bf16(upstream[0] * sum_j S_ij X_j) (cross 0: j = i alone), fp32 sum, the device scalar applied in fp32, one rounding; the 64-wide
+ *         chunks are stored through the layout's map, one writer each.  Rows < B N of the three component column blocks of d are all written;
+ *         rows >= B N and columns >= 3 Ds are not touched.
+ * N <= 208, Ds and Dt multiples of 64 up to 1024, head_dim 64 for both models, ld multiples of 8 (ld_d: of 4) and >= 3 D: DEVIT_ERR_SHAPE otherwise.
+ * cross / layout outside {0, 1}, layers <= 0, a null or misaligned (16 bytes; d: 8) pointer: DEVIT_ERR_ARG.  Nothing is launched on a refusal.
+ *
+ * soft_cross_entropy on fp32 rows [R][C], R, C >= 1 (DEVIT_ERR_SHAPE otherwise):
+ *   fwd : row_loss: fp32 [R] workspace; loss[0] = mean over the rows of -sum_j softmax(targets)_j log_softmax(predicts)_j
+ *   bwd : d_predicts = (softmax(predicts) - softmax(targets)) upstream[0] / R
+ * No atomics: all four give the same bits on every run.
+ * ---------------------------------------------------------------------------------------- */
+DEVIT_API int devit_qkv_pair_fwd(const void* s_qkv, const void* t_qkv, int B, int N, int Ds, int Dt, int ld_s, int ld_t, int head_dim_s,
+                       int head_dim_t, int teacher_f16, int cross, int layout, int layers, float* terms, void* S_out, float* loss,
+                       void* stream);
+DEVIT_API int devit_qkv_pair_bwd(const void* S, const void* s_qkv, const float* upstream, int B, int N, int Ds, int ld_s, int head_dim_s,
+                       int cross, int layout, void* d, int ld_d, void* stream);
+DEVIT_API int devit_soft_ce_rows_fwd(const float* predicts, const float* targets, int R, int C, float* row_loss, float* loss, void* stream);
+DEVIT_API int devit_soft_ce_rows_bwd(const float* predicts, const float* targets, const float* upstream, int R, int C, float* d_predicts,
+                           void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hidden-state distillation (csrc/hid.hip).
  *
  * devit_add_scale_cast_bf16: a gradient that arrives for an exposed encoder output, injected between two devit_block_bwd calls:
