@@ -35,7 +35,20 @@ masked_in_place()); g1 and the caller's g2 are held bit for bit.  DROP_CASES (no
     compacted_drop   3 x 51, 384 / 4 / 640, block 11; default and DEVIT_WGRADFR=0; (0, 0.25): attention-only dropout on the plain sequence,
                      ceil4(51) = 52, and (0.1, 0.1)
     wide_drop        2 x 197, 256 / 4 / 512, block 5, (0.1, 0.1): split-K weight gradients on the side stream (and DEVIT_WGRAD_STREAM=0) reading
-                     buffers masked in place on the caller's stream"""
+                     buffers masked in place on the caller's stream
+
+The lean last block (devit_tail_fwd / devit_tail_bwd) is audited the same way at the end of this file: tail_forward_stages / tail_backward_stages /
+tail_audit / tail_emulate and TAIL_MUTATIONS.  Its branch half is the block's own code on the T = B ntok token rows, so both audits -- and both
+emulations -- call the same statements: branch_forward_stages / branch_backward_stages (_emu_branch_fwd / _emu_branch_bwd) take (rows, padded rows,
+rows per DropPath scale).  One bound is counted there: the token rows of dx_in, where a separate pass adds the stored fp32 dx1 to the stored fp32
+LayerNorm backward -- one fp32 rounding of the sum, U |reference| by the convention above, on top of ln_bwd_bounds without a residual.
+TAIL_CASES (B, N, ntok, D, heads, hidden), every M and T off the 256-row grid:
+    tail_student      3 x 198, 2, 384 / 6 / 1536: the all-rows product split-K; handed out as a job; offered a slot under DEVIT_WGRADFR=0 (not taken)
+    tail_one_token    2 x 197, 1, 256 / 4 / 512: D != 384, never a job even when a slot is offered
+    tail_compacted    3 x 51, 2, 384 / 4 (attn_width 256) / 640: every Da-versus-D offset and leading dimension differs
+    tail_short        4 x 6, 2, 384 / 6 / 768: fewer keys than one attention tile
+    tail_two_tiles    130 x 6, 2, 384 / 6 / 768: T = 260 crosses a row tile, Tp = 512
+    tail_wide_tokens  2 x 198, 40, 384 / 6 / 1536: several query rows per image in the rows-form backward"""
 import ctypes as C
 import math
 
@@ -372,9 +385,8 @@ def forward_stages(c, inp, bufs, drop=None):
     """yields (stage, got, float64 reference, bound) for what devit_encoder_fwd (with `drop`: devit_encoder_fwd_drop) left of one block, read off
     block_fwd"""
     d, w = dims(c), inp["w"]
-    B, N, H, M, D, Hd = d["B"], d["N"], d["H"], d["M"], d["D"], d["Hd"]
-    f16, save, att = bool(c["dtype16"]), bool(c["flags"] & SAVE), bool(c["flags"] & ATT)
-    dropped, _ = is_dropped(drop)
+    B, N, H, M = d["B"], d["N"], d["H"], d["M"]
+    f16, save = bool(c["dtype16"]), bool(c["flags"] & SAVE)
     x = bufs["x"]
     dev = x.device
     yield from _ln_fwd_stage("1", x, w["n1w"], w["n1b"], bufs["ln1"][:M], bufs.get("mean1"), bufs.get("rstd1"), f16, save)
@@ -385,6 +397,20 @@ def forward_stages(c, inp, bufs, drop=None):
     yield "attn_o", A.heads(bufs["attn_o"], B, N, H), r["O"], b["O"]
     if save:
         yield "lse", bufs["lse"].view(B, H, N), r["lse"], b["lse"]
+    yield from branch_forward_stages(c, inp, bufs, x, (M, d["Mp"], N), drop)
+
+
+def branch_forward_stages(c, inp, bufs, x, geo, drop=None):
+    """the branch half of the forward (branch_fwd in csrc/encoder.hip), from the proj GEMM on, on geo = (rows, padded rows, rows per DropPath scale) of
+    `x` and of the buffers: the block's own (dims(c)["M"], ["Mp"], ["N"]) with x = bufs["x"], the lean last block's (B ntok, pad_rows(B ntok), ntok)
+    with x = the gathered token rows.  The dropout passes are the block's alone."""
+    d, w = dims(c), inp["w"]
+    M, _, N = geo
+    D, Hd = d["D"], d["Hd"]
+    f16, save, att = bool(c["dtype16"]), bool(c["flags"] & SAVE), bool(c["flags"] & ATT)
+    dropped, _ = is_dropped(drop)
+    assert not dropped or (M, N) == (d["M"], d["N"])
+    dev = x.device
     if dropped:      # proj stores fp32 into the temporary fc2 then overwrites: its statement and the residual pass's (site 2) compose
         ref, bnd = G.statement(G.STORE_F32, _d(bufs["attn_o"][:M]), _d(w["proj_w16"]), bias=_d(w["proj_b"]))
         yield ("x1", bufs["x1"]) + residual_stage(c, drop, SITE_PROJ, bufs["x"], ref["out"], w["dp1"], site_keep(c, drop, SITE_PROJ, D, dev), bufs["x1"],
@@ -459,11 +485,51 @@ def backward_stages(c, inp, bufs, route, dln=None, drop=None):
     routes().  dln: {'dln2': .., 'dln1': ..} the LayerNorm backward's input where the fused launch kept it on chip (from a run of the two launches on
     bit-identical dh_pre / dqkv).  Under p > 0 bufs['g2'] is the caller's buffer as the call left it: masked (audit() holds it to the pre-mask value)."""
     d, w, a0 = dims(c), inp["w"], inp["acc0"]
-    B, N, H, M, Mp, Da, D, Hd = d["B"], d["N"], d["H"], d["M"], d["Mp"], d["Da"], d["D"], d["Hd"]
+    B, N, H, M, Mp, Da = d["B"], d["N"], d["H"], d["M"], d["Mp"], d["Da"]
+    tiles = Mp // 256
+    acc = bufs["acc"]
+    dev = bufs["dx"].device
+    yield from branch_backward_stages(c, inp, bufs, route, (M, Mp, N), dln, drop)
+    # 9
+    add = bufs.get("dqkv_add")
+    q, k, v, do, ad = A.split_packed(bufs["qkv"], B, N, H, bufs["dattn"], add)
+    r, b = A.bounds(q, k, v, w["head_gate"], 0.125, do, ad, **_attn_drop_kw(c, drop, dev))
+    got = torch.stack([A.heads(bufs["dqkv"], B, N, H, j * Da) for j in range(3)])
+    yield "dqkv", got, torch.stack([r["dQ"], r["dK"], r["dV"]]), torch.stack([b["dQ"], b["dK"], b["dV"]])
+    # 10
+    if not route["fused"][1]:
+        ref, bnd = G.statement(G.STORE_BF16, _d(bufs["dqkv"][:M]), _d(w["qkv_w16"]).t())
+        yield "dln1", bufs["dln1"][:M], ref["out"], bnd["out"]
+    # 11
+    for name, ref, bnd in _wgrad_stage("qkv_w", "qkv_b", bufs["dqkv"], bufs["ln1"], a0["qkv_w"], a0["qkv_b"], M, Mp, route):
+        yield name, acc[name], ref, bnd
+    # 12
+    dln1 = (dln or bufs)["dln1"] if route["fused"][1] else bufs["dln1"]
+    r, b = _ln_bwd_stage("1", bufs["x"], bufs["mean1"], bufs["rstd1"], w["n1w"], dln1[:M], bufs["dx1"], a0["n1w"], a0["n1b"], M, route["fused"][1], tiles)
+    yield "dx_in", bufs["dx_in"], r["dx"], b["dx"]
+    yield "n1w", acc["n1w"], r["dgamma"], b["dgamma"]
+    yield "n1b", acc["n1b"], r["dbeta"], b["dbeta"]
+    if route["prev"]:
+        ref = _rs(inp["prev_dp2"], N) * _d(bufs["dx_in"])
+        yield "g_prev", bufs["g_prev"][:M], ref, stored16(U * ref.abs(), ref)
+        if "prev_fc2_b" in acc:
+            ref, bnd = T.ln_colsum_bounds(bufs["g_prev"][:M], a0["prev_fc2_b"])
+            if route["fused"][1]:
+                bnd = bnd * max(T.ln_col_roundings(M), fused_chain(tiles)) / T.ln_col_roundings(M)
+            yield "prev_fc2_b", acc["prev_fc2_b"], ref, bnd
+
+
+def branch_backward_stages(c, inp, bufs, route, geo, dln=None, drop=None):
+    """the branch half of the backward (branch_bwd in csrc/encoder.hip: stages 1 to 8, up to proj's dgrad and weight gradient) on geo = (rows, padded
+    rows, rows per DropPath scale), as branch_forward_stages.  route: wmode / fc2_bias / fused[0] of the Ctx the half ran on."""
+    d, w, a0 = dims(c), inp["w"], inp["acc0"]
+    M, Mp, N = geo
+    D, Hd = d["D"], d["Hd"]
     tiles = Mp // 256
     acc = bufs["acc"]
     g2, dx = bufs["g2"], bufs["dx"]
     dropped, _ = is_dropped(drop)
+    assert not dropped or (M, N) == (d["M"], d["N"])
     dev = dx.device
     assert dropped == (route["fc2_bias"] == "masked")
     # 1, 2: fc2's weight gradient and who owns its bias gradient
@@ -520,33 +586,6 @@ def backward_stages(c, inp, bufs, route, dln=None, drop=None):
     # 8
     for name, ref, bnd in _wgrad_stage("proj_w", None, bufs["g1"], bufs["attn_o"], a0["proj_w"], None, M, Mp, route):
         yield name, acc[name], ref, bnd
-    # 9
-    add = bufs.get("dqkv_add")
-    q, k, v, do, ad = A.split_packed(bufs["qkv"], B, N, H, bufs["dattn"], add)
-    r, b = A.bounds(q, k, v, w["head_gate"], 0.125, do, ad, **_attn_drop_kw(c, drop, dev))
-    got = torch.stack([A.heads(bufs["dqkv"], B, N, H, j * Da) for j in range(3)])
-    yield "dqkv", got, torch.stack([r["dQ"], r["dK"], r["dV"]]), torch.stack([b["dQ"], b["dK"], b["dV"]])
-    # 10
-    if not route["fused"][1]:
-        ref, bnd = G.statement(G.STORE_BF16, _d(bufs["dqkv"][:M]), _d(w["qkv_w16"]).t())
-        yield "dln1", bufs["dln1"][:M], ref["out"], bnd["out"]
-    # 11
-    for name, ref, bnd in _wgrad_stage("qkv_w", "qkv_b", bufs["dqkv"], bufs["ln1"], a0["qkv_w"], a0["qkv_b"], M, Mp, route):
-        yield name, acc[name], ref, bnd
-    # 12
-    dln1 = (dln or bufs)["dln1"] if route["fused"][1] else bufs["dln1"]
-    r, b = _ln_bwd_stage("1", bufs["x"], bufs["mean1"], bufs["rstd1"], w["n1w"], dln1[:M], bufs["dx1"], a0["n1w"], a0["n1b"], M, route["fused"][1], tiles)
-    yield "dx_in", bufs["dx_in"], r["dx"], b["dx"]
-    yield "n1w", acc["n1w"], r["dgamma"], b["dgamma"]
-    yield "n1b", acc["n1b"], r["dbeta"], b["dbeta"]
-    if route["prev"]:
-        ref = _rs(inp["prev_dp2"], N) * _d(bufs["dx_in"])
-        yield "g_prev", bufs["g_prev"][:M], ref, stored16(U * ref.abs(), ref)
-        if "prev_fc2_b" in acc:
-            ref, bnd = T.ln_colsum_bounds(bufs["g_prev"][:M], a0["prev_fc2_b"])
-            if route["fused"][1]:
-                bnd = bnd * max(T.ln_col_roundings(M), fused_chain(tiles)) / T.ln_col_roundings(M)
-            yield "prev_fc2_b", acc["prev_fc2_b"], ref, bnd
 
 
 def audit(c, inp, bufs, route=None, dln=None, drop=None):
@@ -589,6 +628,115 @@ def _emu_residual(x, y, rs, keep, s):
     return torch.where(keep, (rs.to(F64) * t.to(F64) + x.to(F64)).to(F32), x)
 
 
+def _f32(t):
+    return t.to(F32)
+
+
+def _padded(v, M, Mp, t, extra=0):
+    """a buffer of Mp (+ extra) rows as the sequence leaves it: the live rows stored in `t`, zeros below"""
+    out = torch.zeros((Mp + extra, v.shape[1]), dtype=t)
+    out[:M] = v.to(t)
+    return out
+
+
+def _emu_drop_state(c, drop):
+    """what the emulated branch halves share of the dropped sequence: the masks of sites 2, 3, 4 and scale_keep (the forward half adds what the
+    mutations of the backward half read: proj's temporary, the unmasked h)"""
+    st = dict(dropped=is_dropped(drop)[0])
+    if st["dropped"]:
+        st["s_keep"] = DM.thr_s(drop["p"])[1]
+        st["keep2"], st["keep3"], st["keep4"] = (site_keep(c, drop, site, cols)
+                                                 for site, cols in ((SITE_PROJ, c["D"]), (SITE_HIDDEN, c["hidden"]), (SITE_FC2, c["D"])))
+    return st
+
+
+def _emu_branch_fwd(c, inp, bufs, x, geo, dp1, dp2, mutate, drop, st):
+    """branch_fwd emulated on geo = (rows, padded rows, rows per DropPath scale): from bufs['attn_o'] and the fp32 rows `x` to x1, ln2, mean2, rstd2,
+    h, h_pre, x2 (att, tmp).  dp1 / dp2: the scale of every row, [rows][1]."""
+    w = inp["w"]
+    M, Mp, _ = geo
+    f16, att = bool(c["dtype16"]), bool(c["flags"] & ATT)
+    dt = F16 if f16 else BF16
+    dropped = st["dropped"]
+    f = _f32
+    padded = lambda v: _padded(v, M, Mp, dt)                                                    # noqa: E731
+    pre = f(bufs["attn_o"][:M]) @ f(w["proj_w16"]).t() + w["proj_b"]
+    if mutate == "proj_bias_twice":
+        pre = pre + w["proj_b"]
+    if dropped:
+        s_keep, keep2, keep3, keep4 = st["s_keep"], st["keep2"], st["keep3"], st["keep4"]
+        st["tmp_proj"] = tmp_proj = pre
+        bufs["x1"] = _emu_residual(x, pre, dp1, keep2, DM.thr_s(drop["p_attn"])[1] if mutate == "attn_scale_at_site2" else s_keep)
+    else:
+        bufs["x1"] = x + dp1 * pre
+    if att:
+        bufs["att"] = pre.to(dt)
+    e = T.ln_fwd_emulate(x if mutate == "ln2_reads_x" else bufs["x1"], w["n2w"], w["n2b"], EPS)
+    bufs.update(ln2=padded(e["y"]), mean2=e["mean"], rstd2=e["rstd"])
+    pre = f(bufs["ln2"][:M]) @ f(w["fc1_w16"]).t() + w["fc1_b"]
+    bufs["h"] = padded(G.gelu_fit32(pre) * w["neuron_gate"])
+    bufs["h_pre"] = padded(pre * w["neuron_gate"] if mutate == "h_pre_after_gate" else pre)
+    if dropped:
+        st["h_unmasked"] = bufs["h"].clone()
+        bufs["h"][:M] = _emu_apply(bufs["h"][:M], keep3, s_keep)
+        if mutate == "h_pre_masked_too":
+            bufs["h_pre"][:M] = _emu_apply(bufs["h_pre"][:M], keep3, s_keep)
+        bufs["tmp"] = torch.full((Mp, c["D"]), math.nan, dtype=F32)      # (rows >= M are never written: whatever the arena held)
+        bufs["tmp"][:M] = f(bufs["h"][:M]) @ f(w["fc2_w16"]).t() + w["fc2_b"]
+        bufs["x2"] = _emu_residual(x if mutate == "x2_residual_from_x" else bufs["x1"], tmp_proj if mutate == "x2_from_proj_tmp" else bufs["tmp"][:M],
+                                   dp2, keep2 if mutate == "site2_mask_at_site4" else keep4, s_keep)
+    else:
+        bufs["x2"] = (x if mutate == "x2_residual_from_x" else bufs["x1"]) + dp2 * (f(bufs["h"][:M]) @ f(w["fc2_w16"]).t() + w["fc2_b"])
+
+
+def _emu_branch_bwd(c, inp, bufs, acc, geo, dp1, mutate, drop, st, route):
+    """branch_bwd emulated on geo, as _emu_branch_fwd: from dx and the caller's g2 (inp['dx'], inp['g2']: the live rows) to fc2 / fc1 / proj's
+    gradients, n2w / n2b, dh_pre, dln2, dx1, g1, dattn; bufs['dx'] and bufs['g2'] as the call leaves the caller's buffers' live rows"""
+    w, a0 = inp["w"], inp["acc0"]
+    M, Mp, _ = geo
+    D_ = c["D"]
+    dropped = st["dropped"]
+    f = _f32
+    padded = lambda v: _padded(v, M, Mp, BF16)                                                  # noqa: E731
+    dx, g2 = inp["dx"], padded(inp["g2"])
+    if dropped:      # site 4: the caller's g2 masked in place, its column sums are fc2's bias gradient
+        assert route["fc2_bias"] == "masked", "routes(..., drop=...)"
+        s_keep, keep2, keep3, keep4 = st["s_keep"], st["keep2"], st["keep3"], st["keep4"]
+        g2_unmasked = g2
+        g2 = padded(_emu_apply(inp["g2"], keep4, s_keep))
+    bufs.update(dx=dx.clone(), g2=inp["g2"].clone() if (not dropped or mutate == "g2_masked_out_of_place") else g2[:M].clone())
+    if mutate == "pad_rows_left":
+        bufs["h"][Mp - 2] = 0.375
+    if route["fc2_bias"] == "handed":
+        acc["fc2_b"] = a0["fc2_b"].clone()
+    elif mutate == "fc2_b_from_unmasked_g2":
+        acc["fc2_b"] = a0["fc2_b"] + f(g2_unmasked).sum(0)
+    else:
+        acc["fc2_b"] = a0["fc2_b"] + f(g2).sum(0) * (2 if mutate == "fc2_bias_twice" else 1)
+    acc["fc2_w"] = a0["fc2_w"] + f(g2).t() @ f(st["h_unmasked"] if mutate == "fc2_w_reads_unmasked_h" else bufs["h"])
+    dh = (f(g2[:M]) @ f(w["fc2_w16"])) * w["neuron_gate"] * G.dgelu_fit32(f(bufs["h_pre"][:M]))
+    bufs["dh_pre"] = padded(dh)
+    if dropped and mutate != "bwd_site3_left_out":
+        bufs["dh_pre"][:M] = _emu_apply(bufs["dh_pre"][:M], keep3, s_keep)
+    bufs["dln2"] = padded(f(bufs["dh_pre"][:M]) @ f(w["fc1_w16"]))
+    acc["fc1_w"] = a0["fc1_w"] + f(bufs["dh_pre"]).t() @ f(bufs["ln2"])
+    acc["fc1_b"] = a0["fc1_b"] + f(bufs["dh_pre"]).sum(0)
+    e = T.ln_bwd_emulate(bufs["x1"], bufs["mean2"], bufs["rstd2"], w["n2w"], bufs["dln2"][:M], dx, a0["n2w"], a0["n2b"])
+    bufs["dx1"], acc["n2w"], acc["n2b"] = e["dx"], e["dgamma"], e["dbeta"]
+    bufs["g1"] = padded(dp1 * bufs["dx1"])
+    ln_sums = f(bufs["g1"][:M]).sum(0)       # what the LayerNorm backward would add, given a column-sum pointer
+    if dropped:      # site 2
+        kb = site_keep(c, drop, SITE_PROJ, D_, block=drop["block"] + 1) if mutate == "bwd_mask_of_next_block" else keep2
+        bufs["g1"][:M] = _emu_apply(bufs["g1"][:M], kb, s_keep)
+    acc["proj_b"] = a0["proj_b"] + (bufs["dx1"] if mutate == "proj_b_from_dx1" else f(bufs["g1"][:M])).sum(0)
+    if mutate == "proj_b_by_layernorm_too":
+        acc["proj_b"] = acc["proj_b"] + ln_sums
+    if mutate == "pad_rows_left":
+        bufs["g1"][M] = -0.75
+    bufs["dattn"] = padded(f(bufs["g1"][:M]) @ f(w["proj_w16"]))
+    acc["proj_w"] = a0["proj_w"] + f(bufs["g1"]).t() @ f(bufs["attn_o"])
+
+
 def emulate(c, inp, mutate=None, route=None, drop=None):
     """One block forward (and, with DEVIT_BLK_SAVE, backward) in fp32 torch, every buffer of the sequence as it would be left -> bufs as audit()
     takes them.  The GEMMs are plain fp32 products (another order than the kernels'), LayerNorm and attention are the sibling models' emulations,
@@ -596,15 +744,11 @@ def emulate(c, inp, mutate=None, route=None, drop=None):
     sequence, with bufs['tmp'] as fc2 leaves it and bufs['g2'] masked in place."""
     assert mutate is None or mutate in MUTATIONS
     assert mutate not in DROP_MUTATIONS or drop is not None
-    dropped, dropped_attn = is_dropped(drop)
-    D_, Hd_ = c["D"], c["hidden"]
-    if dropped:
-        s_keep = DM.thr_s(drop["p"])[1]
-        keep2, keep3, keep4 = (site_keep(c, drop, site, cols) for site, cols in ((SITE_PROJ, D_), (SITE_HIDDEN, Hd_), (SITE_FC2, D_)))
+    st = _emu_drop_state(c, drop)
     akw = _attn_drop_kw(c, drop, "cpu", pitch=c["N"] if mutate == "attn_pitch_N" else None)
     d, w, a0 = dims(c), inp["w"], inp["acc0"]
     B, N, H, M, Mp, Da = d["B"], d["N"], d["H"], d["M"], d["Mp"], d["Da"]
-    f16, save, att = bool(c["dtype16"]), bool(c["flags"] & SAVE), bool(c["flags"] & ATT)
+    f16, save = bool(c["dtype16"]), bool(c["flags"] & SAVE)
     dt = F16 if f16 else BF16
     route = route or default_routes(c)
     f = lambda t: t.to(F32)                                                                     # noqa: E731
@@ -628,74 +772,15 @@ def emulate(c, inp, mutate=None, route=None, drop=None):
     if mutate == "lse_not_saved_per_head":
         lse = lse[:, :1].expand(B, H, N).contiguous()
     bufs["lse"] = lse
-    pre = f(bufs["attn_o"][:M]) @ f(w["proj_w16"]).t() + w["proj_b"]
-    if mutate == "proj_bias_twice":
-        pre = pre + w["proj_b"]
-    if dropped:
-        tmp_proj = pre
-        bufs["x1"] = _emu_residual(x, pre, dp1, keep2, DM.thr_s(drop["p_attn"])[1] if mutate == "attn_scale_at_site2" else s_keep)
-    else:
-        bufs["x1"] = x + dp1 * pre
-    if att:
-        bufs["att"] = pre.to(dt)
-    e = T.ln_fwd_emulate(x if mutate == "ln2_reads_x" else bufs["x1"], w["n2w"], w["n2b"], EPS)
-    bufs.update(ln2=padded(e["y"]), mean2=e["mean"], rstd2=e["rstd"])
-    pre = f(bufs["ln2"][:M]) @ f(w["fc1_w16"]).t() + w["fc1_b"]
-    bufs["h"] = padded(G.gelu_fit32(pre) * w["neuron_gate"])
-    bufs["h_pre"] = padded(pre * w["neuron_gate"] if mutate == "h_pre_after_gate" else pre)
-    if dropped:
-        h_unmasked = bufs["h"].clone()
-        bufs["h"][:M] = _emu_apply(bufs["h"][:M], keep3, s_keep)
-        if mutate == "h_pre_masked_too":
-            bufs["h_pre"][:M] = _emu_apply(bufs["h_pre"][:M], keep3, s_keep)
-        bufs["tmp"] = torch.full((Mp, D_), math.nan, dtype=F32)      # (rows >= M are never written: whatever the arena held)
-        bufs["tmp"][:M] = f(bufs["h"][:M]) @ f(w["fc2_w16"]).t() + w["fc2_b"]
-        bufs["x2"] = _emu_residual(x if mutate == "x2_residual_from_x" else bufs["x1"], tmp_proj if mutate == "x2_from_proj_tmp" else bufs["tmp"][:M],
-                                   dp2, keep2 if mutate == "site2_mask_at_site4" else keep4, s_keep)
-    else:
-        bufs["x2"] = (x if mutate == "x2_residual_from_x" else bufs["x1"]) + dp2 * (f(bufs["h"][:M]) @ f(w["fc2_w16"]).t() + w["fc2_b"])
+    _emu_branch_fwd(c, inp, bufs, x, (M, Mp, N), dp1, dp2, mutate, drop, st)
     if not save:
         for k_ in ("mean1", "rstd1", "lse", "mean2", "rstd2", "h_pre"):
             del bufs[k_]
         return bufs
     # ---- backward
-    dx, g2 = inp["dx"], padded(inp["g2"], t=BF16)
-    if dropped:      # site 4: the caller's g2 masked in place, its column sums are fc2's bias gradient
-        assert route["fc2_bias"] == "masked", "routes(..., drop=...)"
-        g2_unmasked = g2
-        g2 = padded(_emu_apply(inp["g2"], keep4, s_keep), t=BF16)
-    bufs.update(dx=dx.clone(), g2=inp["g2"].clone() if (not dropped or mutate == "g2_masked_out_of_place") else g2[:M].clone(), dqkv_add=inp["dqkv_add"])
     acc = {}
-    if mutate == "pad_rows_left":
-        bufs["h"][Mp - 2] = 0.375
-    if route["fc2_bias"] == "handed":
-        acc["fc2_b"] = a0["fc2_b"].clone()
-    elif mutate == "fc2_b_from_unmasked_g2":
-        acc["fc2_b"] = a0["fc2_b"] + f(g2_unmasked).sum(0)
-    else:
-        acc["fc2_b"] = a0["fc2_b"] + f(g2).sum(0) * (2 if mutate == "fc2_bias_twice" else 1)
-    acc["fc2_w"] = a0["fc2_w"] + f(g2).t() @ f(h_unmasked if mutate == "fc2_w_reads_unmasked_h" else bufs["h"])
-    dh = (f(g2[:M]) @ f(w["fc2_w16"])) * w["neuron_gate"] * G.dgelu_fit32(f(bufs["h_pre"][:M]))
-    bufs["dh_pre"] = padded(dh, t=BF16)
-    if dropped and mutate != "bwd_site3_left_out":
-        bufs["dh_pre"][:M] = _emu_apply(bufs["dh_pre"][:M], keep3, s_keep)
-    bufs["dln2"] = padded(f(bufs["dh_pre"][:M]) @ f(w["fc1_w16"]), t=BF16)
-    acc["fc1_w"] = a0["fc1_w"] + f(bufs["dh_pre"]).t() @ f(bufs["ln2"])
-    acc["fc1_b"] = a0["fc1_b"] + f(bufs["dh_pre"]).sum(0)
-    e = T.ln_bwd_emulate(bufs["x1"], bufs["mean2"], bufs["rstd2"], w["n2w"], bufs["dln2"][:M], dx, a0["n2w"], a0["n2b"])
-    bufs["dx1"], acc["n2w"], acc["n2b"] = e["dx"], e["dgamma"], e["dbeta"]
-    bufs["g1"] = padded(dp1 * bufs["dx1"], t=BF16)
-    ln_sums = f(bufs["g1"][:M]).sum(0)       # what the LayerNorm backward would add, given a column-sum pointer
-    if dropped:      # site 2
-        kb = site_keep(c, drop, SITE_PROJ, D_, block=drop["block"] + 1) if mutate == "bwd_mask_of_next_block" else keep2
-        bufs["g1"][:M] = _emu_apply(bufs["g1"][:M], kb, s_keep)
-    acc["proj_b"] = a0["proj_b"] + (bufs["dx1"] if mutate == "proj_b_from_dx1" else f(bufs["g1"][:M])).sum(0)
-    if mutate == "proj_b_by_layernorm_too":
-        acc["proj_b"] = acc["proj_b"] + ln_sums
-    if mutate == "pad_rows_left":
-        bufs["g1"][M] = -0.75
-    bufs["dattn"] = padded(f(bufs["g1"][:M]) @ f(w["proj_w16"]), t=BF16)
-    acc["proj_w"] = a0["proj_w"] + f(bufs["g1"]).t() @ f(bufs["attn_o"])
+    _emu_branch_bwd(c, inp, bufs, acc, (M, Mp, N), dp1, mutate, drop, st, route)
+    bufs["dqkv_add"] = inp["dqkv_add"]
     add = None if (inp["dqkv_add"] is None or mutate == "dqkv_add_dropped") else inp["dqkv_add"]
     q, k, v, do, ad = A.split_packed(bufs["qkv"], B, N, H, bufs["dattn"], add)
     ae = A.emulate(q, k, v, w["head_gate"], 0.125, do, ad, **akw)
@@ -989,3 +1074,330 @@ def library_sizes(c):
     L.call("devit_block_acts_sizes", d["B"], d["N"], d["D"], d["Da"], d["Hd"], c["flags"], sa)
     L.call("devit_block_bwd_sizes", d["B"], d["N"], d["D"], d["Da"], d["Hd"], sb)
     return dict(zip(ACT_NAMES, sa)), dict(zip(BWD_NAMES, sb))
+
+
+# ============================================================================================ the lean last block, stage by stage
+# devit_tail_fwd / devit_tail_bwd read line by line.  The branch half is the block's own code on a Ctx of T = B ntok rows with ntok rows per DropPath
+# scale: branch_forward_stages / branch_backward_stages with geo = (T, pad_rows(T), ntok), route wmode = 0 (Wgrads wg(ct, nullptr, 0, ...): split-K
+# launches on the caller's stream) and fc2's bias from fc2's own launch (g2_bias_done = false and no grouped launch, so no column-sum pass).
+# A case is a block case (flags = DEVIT_BLK_SAVE) + ntok + its runs: (tag, environment, is a defer_jobs slot offered).
+def _tail_case(name, B, N, ntok, D, heads, hidden, runs=(("", {}, False),)):
+    return dict(_case(name, B, N, D, heads, hidden, SAVE), ntok=ntok, runs=runs)
+
+
+TAIL_CASES = [
+    # split-K for the all-rows product; the product handed out as a job (the test runs it); a slot offered under DEVIT_WGRADFR=0: not taken
+    _tail_case("tail_student", 3, 198, 2, 384, 6, 1536,
+               runs=(("split_k", {}, False), ("deferred", {}, True), ("wgradfr0", {"DEVIT_WGRADFR": "0"}, True))),
+    _tail_case("tail_one_token", 2, 197, 1, 256, 4, 512, runs=(("", {}, True),)),      # D != 384: never deferred, even when a slot is offered
+    _tail_case("tail_compacted", 3, 51, 2, 384, 4, 640),                               # attn_width 256: every Da-versus-D offset and ld differs
+    _tail_case("tail_short", 4, 6, 2, 384, 6, 768),                                    # the 32-pixel geometry: fewer keys than one attention tile
+    _tail_case("tail_two_tiles", 130, 6, 2, 384, 6, 768),                              # T = 260 crosses a row tile; Tp = 512; pad rows 260 .. 511
+    _tail_case("tail_wide_tokens", 2, 198, 40, 384, 6, 1536),                          # several query rows per image in the rows-form backward
+]
+TAIL_FWD_STAGES = ("ln1", "mean1", "rstd1", "kv", "ln1_tok", "q", "attn_o", "lse", "x_tok", "x1", "ln2", "mean2", "rstd2", "h", "h_pre", "x2")
+TAIL_BWD_STAGES = ("fc2_b", "fc2_w", "dh_pre", "dln2", "fc1_w", "fc1_b", "dx1", "g1", "n2w", "n2b", "proj_b", "dattn", "proj_w", "dq", "dkv", "dqkv_kv",
+                   "dln1_tok", "dln1", "dln1/tok", "qkv_w/kv", "qkv_b/kv", "qkv_w/q", "qkv_b/q", "dx_in", "dx_in/tok", "n1w", "n1b")
+# 16-bit buffers whose rows beyond the live ones the two calls zero: T-row buffers (the caller's g2 among them), M-row buffers
+TAIL_PADDED_T = ("ln1_tok", "q", "attn_o", "ln2", "h", "h_pre", "dh_pre", "dln2", "g1", "dattn", "dqkv", "dln1_tok", "g2")
+TAIL_PADDED_M = ("ln1", "kv", "dkv", "dln1")
+# planted wiring bug of tail_emulate -> the stage, or the untouched-bytes statement, that must see it
+TAIL_MUTATIONS = {
+    "kv_weight_at_q": "dln1",                    # the K/V dgrad reads qkv_w16 without the Da * D offset
+    "kv_weight_at_q_fwd": "kv",                  # the K/V forward product likewise
+    "kv_bias_grad_at_q": "qkv_b/kv",             # g.qkv_b without + Da
+    "dkv_token_rows_not_copied": "dqkv_kv",
+    "dq_ld_Da": "qkv_w/q",                       # the Q weight gradient reads dQ at ld = Da instead of 3 Da
+    "dln1_tok_not_scattered": "dln1/tok",
+    "dx1_not_added": "dx_in/tok",
+    "dx1_added_at_packed_rows": "dx_in",         # at rows b * ntok + t of dx_in instead of b * N + t
+    "droppath_per_N_rows": "x1",                 # the scale of row r taken as r / N instead of r / ntok
+    "pad_rows_left": "pad_rows/dkv",
+    "g2_pad_not_zeroed": "pad_rows/g2",
+    "token_q_wgrad_over_kv_too": "qkv_w/kv",     # the T-row weight gradient launched with 3 Da columns: the K/V token rows counted twice
+    "deferred_and_launched": "qkv_w/kv",         # the all-rows product both handed out as a job and launched
+}
+
+
+def tail_case_named(name):
+    return next(c for c in TAIL_CASES if c["name"] == name)
+
+
+def tail_variants():
+    """(id, case, environment, slot offered) of every run of the tail table"""
+    return [(c["name"] + ("/" + tag if tag else ""), c, env, offered) for c in TAIL_CASES for tag, env, offered in c["runs"]]
+
+
+def tail_dims(c, ntok):
+    d = dims(c)
+    Tr = d["B"] * ntok
+    return dict(d, ntok=ntok, T=Tr, Tp=pad_rows(Tr))
+
+
+def tail_routes(c, ntok, env=None, offered=False, fused=False):
+    """the decisions of devit_tail_bwd: `branch` is routes() of the token-row Ctx (wmode 0, fc2's bias from its own launch; fused: what
+    devit_dgrad_layernorm_bwd_fused(pad_rows(T), D, hidden) answers); kv_job: the all-rows product (dK | dV)^T ln1 is handed to the caller as a
+    job of the grouped launch -- a slot offered, wgrad_mode of the ALL-rows Ctx (D == 384, three K-steps, DEVIT_WGRADFR != 0), and 2 Da a multiple of 128"""
+    d = tail_dims(c, ntok)
+    wmode_all = d["D"] == 384 and d["Mp"] // 64 >= 3 and (env or {}).get("DEVIT_WGRADFR", "1") != "0"
+    return dict(branch=dict(wmode=False, fc2_bias="launch", fused=(bool(fused), False), prev=False),
+                kv_job=bool(offered and wmode_all and (2 * d["Da"]) % 128 == 0))
+
+
+def tok_rows(B, N, ntok, dev="cpu"):
+    """the rows b * N + t, t < ntok, of an all-rows buffer, in the order of the packed token rows b * ntok + t"""
+    return (torch.arange(B, device=dev)[:, None] * N + torch.arange(ntok, device=dev)[None, :]).reshape(-1)
+
+
+def tail_inputs(c, ntok, key=0):
+    """as inputs(), for the lean block: x on all M rows; dx and g2 = bf16(dp2 dx) on the T token rows (ntok rows per scale); no dqkv_add, no block
+    below; acc0: what every gradient accumulator holds before the call"""
+    d = tail_dims(c, ntok)
+    M, Tr, D, Da, Hd = d["M"], d["T"], d["D"], d["Da"], d["Hd"]
+    g = gen("tail", c["name"], "x", key)
+    w = block_weights(c, key)
+    x = T.randn(g, M, D) + 2 * T.randn(g, M, 1)
+    dx = T.randn(g, Tr, D)
+    inp = dict(w=w, x=x, dx=dx, g2=(dx * w["dp2"].repeat_interleave(ntok)[:, None]).to(BF16))
+    shapes = dict(n1w=(D,), n1b=(D,), qkv_w=(3 * Da, D), qkv_b=(3 * Da,), proj_w=(D, Da), proj_b=(D,), n2w=(D,), n2b=(D,), fc1_w=(Hd, D),
+                  fc1_b=(Hd,), fc2_w=(D, Hd), fc2_b=(D,))
+    inp["acc0"] = {k: 3 * T.randn(g, *s) for k, s in shapes.items()}
+    return inp
+
+
+def tail_buffer_shapes(c, ntok):
+    """name -> (rows, cols, 16-bit?) of every buffer devit_tail_fwd / devit_tail_bwd write, as the sequence addresses them ('kv' is the qkv slot)"""
+    d = tail_dims(c, ntok)
+    M, Mp, Tr, Tp, D, Da, Hd = d["M"], d["Mp"], d["T"], d["Tp"], d["D"], d["Da"], d["Hd"]
+    return dict(ln1=(Mp, D, 1), mean1=(1, M, 0), rstd1=(1, M, 0), kv=(Mp, 2 * Da, 1), attn_o=(Tp, Da, 1), lse=(d["B"] * d["H"], ntok, 0), x1=(Tr, D, 0),
+                ln2=(Tp, D, 1), mean2=(1, Tr, 0), rstd2=(1, Tr, 0), h=(Tp, Hd, 1), h_pre=(Tp, Hd, 1), x2=(Tr, D, 0), ln1_tok=(Tp, D, 1), q=(Tp, Da, 1),
+                x_tok=(Tr, D, 0), dh_pre=(Tp, Hd, 1), dln2=(Tp, D, 1), dx1=(Tr, D, 0), g1=(Tp, D, 1), dattn=(Tp, Da, 1), dqkv=(Tp, 3 * Da, 1),
+                dln1=(Mp, D, 1), dkv=(Mp, 2 * Da, 1), dln1_tok=(Tp, D, 1))
+
+
+def _exact(name, got, want):
+    """a stage that is a copy: the reference is the source's value, the bound 0 -- any difference is an infinite ratio"""
+    want = want.to(F64)
+    return name, got, want, torch.zeros_like(want)
+
+
+def tail_forward_stages(c, ntok, inp, bufs):
+    """yields (stage, got, float64 reference, bound) for what devit_tail_fwd left, read off it line by line: LN1 on all rows, (K | V) on all rows
+    from the K/V rows of the weight and bias, the token rows of ln1 gathered, Q on them, the rows-form attention, the token rows of x gathered,
+    then the block's branch half on the T token rows"""
+    d, w = tail_dims(c, ntok), inp["w"]
+    B, N, H, M, Tr, Tp, Da = d["B"], d["N"], d["H"], d["M"], d["T"], d["Tp"], d["Da"]
+    x = bufs["x"]
+    tok = tok_rows(B, N, ntok, x.device)
+    yield from _ln_fwd_stage("1", x, w["n1w"], w["n1b"], bufs["ln1"][:M], bufs["mean1"], bufs["rstd1"], False, True)
+    ref, bnd = G.statement(G.STORE_BF16, _d(bufs["ln1"][:M]), _d(w["qkv_w16"][Da:]), bias=_d(w["qkv_b"][Da:]))
+    yield "kv", bufs["kv"][:M], ref["out"], bnd["out"]
+    yield _exact("ln1_tok", bufs["ln1_tok"][:Tr], bufs["ln1"][tok])
+    ref, bnd = G.statement(G.STORE_BF16, _d(bufs["ln1_tok"][:Tr]), _d(w["qkv_w16"][:Da]), bias=_d(w["qkv_b"][:Da]))
+    yield "q", bufs["q"][:Tr], ref["out"], bnd["out"]
+    q, k, v = A.heads(bufs["q"], B, ntok, H), A.heads(bufs["kv"], B, N, H, 0), A.heads(bufs["kv"], B, N, H, Da)
+    r, b = A.bounds(q, k, v, w["head_gate"], 0.125)
+    yield "attn_o", A.heads(bufs["attn_o"], B, ntok, H), r["O"], b["O"]
+    yield "lse", bufs["lse"].view(B, H, ntok), r["lse"], b["lse"]
+    yield _exact("x_tok", bufs["x_tok"], x[tok])
+    yield from branch_forward_stages(c, inp, bufs, bufs["x_tok"], (Tr, Tp, ntok))
+
+
+def tail_backward_stages(c, ntok, inp, bufs, route):
+    """yields (stage, got, float64 reference, bound) for what devit_tail_bwd left, read off it line by line.  route: tail_routes().  The branch half
+    on the token rows, then the lean block's own wiring, every stage stated on its inputs as they lie in memory:
+        dq          columns [0, Da) of the [Tp][3 Da] buffer;  dkv [Mp][2 Da]: _attn_model.bounds in rows form, NQ = ntok
+        dqkv_kv     columns [Da, 3 Da) of the token rows: the token rows of dkv, bit for bit
+        dln1_tok    the K = 3 Da product of dqkv against qkv_w16;  dln1 off the token rows: the K = 2 Da product of dkv against qkv_w16[Da:];
+        dln1/tok    the token rows of dln1: dln1_tok, bit for bit
+        qkv_w/kv, qkv_b/kv   dkv^T ln1 over Mp rows into rows [Da, 3 Da): a job of the grouped launch (route['kv_job']) or split-K
+        qkv_w/q, qkv_b/q     dQ^T ln1_tok over Tp rows into rows [0, Da): split-K, dQ read at ld = 3 Da
+        dx_in, n1w, n1b      _tail_model.ln_bwd_bounds without a residual on the stored dln1; dx_in/tok: the token rows, where the reference is that
+                             statement + the stored dx1 and the bound the statement's + U |reference| -- the add is a separate pass over a stored
+                             fp32 value (devit_token_rows_copy with add = 1): one fp32 rounding of the sum, the one term that is new here"""
+    d, w, a0 = tail_dims(c, ntok), inp["w"], inp["acc0"]
+    B, N, H, M, Mp, Tr, Tp, Da = d["B"], d["N"], d["H"], d["M"], d["Mp"], d["T"], d["Tp"], d["Da"]
+    acc = bufs["acc"]
+    dev = bufs["dx"].device
+    tok = tok_rows(B, N, ntok, dev)
+    off = torch.ones(M, dtype=torch.bool, device=dev)
+    off[tok] = False
+    yield from branch_backward_stages(c, inp, bufs, route["branch"], (Tr, Tp, ntok))
+    q, k, v = A.heads(bufs["q"], B, ntok, H), A.heads(bufs["kv"], B, N, H, 0), A.heads(bufs["kv"], B, N, H, Da)
+    r, b = A.bounds(q, k, v, w["head_gate"], 0.125, A.heads(bufs["dattn"], B, ntok, H))
+    yield "dq", A.heads(bufs["dqkv"], B, ntok, H, 0), r["dQ"], b["dQ"]
+    got = torch.stack([A.heads(bufs["dkv"], B, N, H, j * Da) for j in range(2)])
+    yield "dkv", got, torch.stack([r["dK"], r["dV"]]), torch.stack([b["dK"], b["dV"]])
+    yield _exact("dqkv_kv", bufs["dqkv"][:Tr, Da:], bufs["dkv"][tok])
+    ref, bnd = G.statement(G.STORE_BF16, _d(bufs["dqkv"][:Tr]), _d(w["qkv_w16"]).t())
+    yield "dln1_tok", bufs["dln1_tok"][:Tr], ref["out"], bnd["out"]
+    ref, bnd = G.statement(G.STORE_BF16, _d(bufs["dkv"][:M][off]), _d(w["qkv_w16"][Da:]).t())
+    yield "dln1", bufs["dln1"][:M][off], ref["out"], bnd["out"]
+    yield _exact("dln1/tok", bufs["dln1"][tok], bufs["dln1_tok"][:Tr])
+    names = {"qkv_w": "qkv_w/kv", "qkv_b": "qkv_b/kv"}
+    for name, ref, bnd in _wgrad_stage("qkv_w", "qkv_b", bufs["dkv"], bufs["ln1"], a0["qkv_w"][Da:], a0["qkv_b"][Da:], M, Mp, dict(wmode=route["kv_job"])):
+        yield names[name], acc[name][Da:], ref, bnd
+    names = {"qkv_w": "qkv_w/q", "qkv_b": "qkv_b/q"}
+    for name, ref, bnd in _wgrad_stage("qkv_w", "qkv_b", bufs["dqkv"][:, :Da], bufs["ln1_tok"], a0["qkv_w"][:Da], a0["qkv_b"][:Da], Tr, Tp, dict(wmode=False)):
+        yield names[name], acc[name][:Da], ref, bnd
+    r, b = T.ln_bwd_bounds(bufs["x"], bufs["mean1"], bufs["rstd1"], w["n1w"], bufs["dln1"][:M], None, a0["n1w"], a0["n1b"])
+    yield "dx_in", bufs["dx_in"][off], r["dx"][off], b["dx"][off]
+    ref = r["dx"][tok] + _d(bufs["dx1"])
+    yield "dx_in/tok", bufs["dx_in"][tok], ref, b["dx"][tok] + U * ref.abs()
+    yield "n1w", acc["n1w"], r["dgamma"], b["dgamma"]
+    yield "n1b", acc["n1b"], r["dbeta"], b["dbeta"]
+
+
+def tail_audit(c, ntok, inp, bufs, route=None, arena=None):
+    """-> ({stage: worst |err| / bound over EVERY live element}, problems).  route None: the forward alone.  problems names every untouched-bytes
+    statement that does not hold: 'pad_rows/<buffer>' (rows >= T of a Tp-row 16-bit buffer, the caller's g2 among them, or rows >= M of ln1, kv,
+    dkv, dln1, not zero), 'inputs/<name>' (x, dx or the first T rows of g2 did not come back bit for bit), and, with the TailArena the buffers
+    were carved from, 'extent/<slot>' / 'guard/...' (a byte beyond a slot's stated extent, or of a guard slot, is no longer the prefill)"""
+    d = tail_dims(c, ntok)
+    M, Tr = d["M"], d["T"]
+    rt = {}
+    for name, got, ref, bnd in tail_forward_stages(c, ntok, inp, bufs):
+        rt[name] = ratio(got, ref, bnd)
+    if route is not None:
+        for name, got, ref, bnd in tail_backward_stages(c, ntok, inp, bufs, route):
+            rt[name] = ratio(got, ref, bnd)
+    problems = []
+    for names, live in ((TAIL_PADDED_T, Tr), (TAIL_PADDED_M, M)):
+        for name in names:
+            t = bufs.get(name)
+            if t is not None and bool((t[live:].view(torch.int16) != 0).any()):
+                problems.append("pad_rows/" + name)
+    for name in ("x", "dx", "g2"):
+        if bufs.get(name) is not None and not torch.equal(bufs[name][:inp[name].shape[0]].cpu(), inp[name].cpu()):
+            problems.append("inputs/" + name)
+    if arena is not None:
+        problems += arena.written_outside()
+    return rt, problems
+
+
+ARENA_FILL, ARENA_GUARD = 0x55, 4096
+
+
+class TailArena:
+    """Every buffer of the two calls carved back to back out of ONE allocation at exactly the sizes devit_tail_acts_sizes / devit_tail_bwd_sizes
+    report (and, 256-aligned, dx_in, the caller's g2 and the twelve accumulators), a guard slot in front and behind, every byte 0x55 before the
+    call: in bf16 and in fp32 a finite 1.5e13, so a pad row left alone, an element never written and a read of junk all show.  `extents`: the bytes
+    of each slot the calls may write (tail_extents(); the whole of lnws, which is the library's scratch)."""
+
+    def __init__(self, dev, sizes, extents):
+        self.sizes, self.extents, self.off, off = dict(sizes), dict(extents), {}, ARENA_GUARD
+        for name, n in self.sizes.items():
+            assert n % 256 == 0 and self.extents[name] <= n, (name, n, self.extents[name])
+            self.off[name] = off
+            off += n
+        self.end = off
+        self.mem = torch.full((off + ARENA_GUARD,), ARENA_FILL, dtype=torch.uint8, device=dev)
+
+    def adr(self, name):
+        return self.mem.data_ptr() + self.off[name] if self.sizes[name] else None
+
+    def view(self, name, rows, cols, dtype):
+        o = self.off[name]
+        assert rows * cols * dtype.itemsize <= self.sizes[name], name
+        return self.mem[o:o + rows * cols * dtype.itemsize].view(dtype).view(rows, cols)
+
+    def refill(self, names, byte):
+        for n in names:
+            self.mem[self.off[n]:self.off[n] + self.sizes[n]] = byte
+
+    def written_outside(self, fill=None):
+        """-> 'extent/<slot>' for every slot with a changed byte beyond its extent, 'guard/front', 'guard/back'.  fill: {slot: byte} where a slot was
+        refilled with another byte than 0x55"""
+        fill = fill or {}
+        bad = ["extent/" + n for n, e in self.extents.items()
+               if not bool((self.mem[self.off[n] + e:self.off[n] + self.sizes[n]] == fill.get(n, ARENA_FILL)).all())]
+        bad += ["guard/front"] if not bool((self.mem[:ARENA_GUARD] == ARENA_FILL).all()) else []
+        return bad + (["guard/back"] if not bool((self.mem[self.end:] == ARENA_FILL).all()) else [])
+
+
+def tail_arena(dev, c, ntok):
+    """the TailArena of a case: the library's sizes for the 17 + 10 buffers ('kv' is the qkv slot), dx_in [M][D] fp32, g2 [Tp][D] bf16 and 'g_<name>'
+    per accumulator"""
+    d = tail_dims(c, ntok)
+    al = lambda n: (n + 255) // 256 * 256                                                       # noqa: E731
+    sa, sb = tail_library_sizes(d["B"], d["N"], ntok, d["D"], d["Da"], d["Hd"], SAVE)
+    ea, eb = tail_extents(d["B"], d["N"], ntok, d["D"], d["Da"], d["Hd"], 1)
+    sizes, ext = {}, {}
+    for s, e in ((sa, ea), (sb, eb)):
+        for n in s:
+            sizes["kv" if n == "qkv" else n], ext["kv" if n == "qkv" else n] = s[n], e[n]
+    ext["lnws"] = sizes["lnws"]
+    acc = {"g_" + n: t.numel() * 4 for n, t in tail_inputs(c, ntok)["acc0"].items()}
+    for n, e in dict(acc, dx_in=d["M"] * d["D"] * 4, g2=d["Tp"] * d["D"] * 2).items():
+        sizes[n], ext[n] = al(e), e
+    return TailArena(dev, sizes, ext)
+
+
+def tail_emulate(c, ntok, inp, mutate=None, route=None):
+    """devit_tail_fwd + devit_tail_bwd in fp32 torch, in the project's rounding (as emulate(), whose branch halves it runs on the token rows), every
+    buffer as the two calls would leave it -> bufs as tail_audit() takes them.  `mutate`: one of TAIL_MUTATIONS, a planted WIRING bug of the lean
+    block's own wiring -- every kernel stays correct.  route: tail_routes() (only deferred_and_launched reads it: it needs the job handed out)."""
+    assert mutate is None or mutate in TAIL_MUTATIONS
+    d, w, a0 = tail_dims(c, ntok), inp["w"], inp["acc0"]
+    B, N, H, M, Mp, Tr, Tp, Da = d["B"], d["N"], d["H"], d["M"], d["Mp"], d["T"], d["Tp"], d["Da"]
+    route = route or tail_routes(c, ntok)
+    f = _f32
+    pm = lambda v: _padded(v, M, Mp, BF16)                                                      # noqa: E731
+    pt = lambda v: _padded(v, Tr, Tp, BF16)                                                     # noqa: E731
+    st = _emu_drop_state(c, None)
+    tok = tok_rows(B, N, ntok)
+    x = inp["x"]
+    per = N if mutate == "droppath_per_N_rows" else ntok
+    dp1, dp2 = (w[n][torch.arange(Tr) // per][:, None] for n in ("dp1", "dp2"))
+    bufs = dict(x=x.clone())
+    e = T.ln_fwd_emulate(x, w["n1w"], w["n1b"], EPS)
+    bufs.update(ln1=pm(e["y"]), mean1=e["mean"], rstd1=e["rstd"])
+    kv_w = w["qkv_w16"][:2 * Da] if mutate == "kv_weight_at_q_fwd" else w["qkv_w16"][Da:]
+    bufs["kv"] = pm(f(bufs["ln1"][:M]) @ f(kv_w).t() + w["qkv_b"][Da:])
+    bufs["ln1_tok"] = pt(bufs["ln1"][tok])
+    bufs["q"] = pt(f(bufs["ln1_tok"][:Tr]) @ f(w["qkv_w16"][:Da]).t() + w["qkv_b"][:Da])
+    q, k, v = A.heads(bufs["q"], B, ntok, H), A.heads(bufs["kv"], B, N, H, 0), A.heads(bufs["kv"], B, N, H, Da)
+    ae = A.emulate(q, k, v, w["head_gate"], 0.125)
+    bufs["attn_o"], bufs["lse"] = pt(A.rows(ae["O"])), ae["lse"].to(F32)
+    bufs["x_tok"] = x[tok].clone()
+    _emu_branch_fwd(c, inp, bufs, bufs["x_tok"], (Tr, Tp, ntok), dp1, dp2, mutate, None, st)
+    # ---- backward
+    acc = {}
+    _emu_branch_bwd(c, inp, bufs, acc, (Tr, Tp, ntok), dp1, mutate, None, st, route["branch"])
+    bufs["g2"] = pt(inp["g2"])                   # the caller's buffer, pad rows and all: the call zeroes them
+    if mutate == "g2_pad_not_zeroed":
+        bufs["g2"][Tp - 1] = 1.5
+    ae = A.emulate(q, k, v, w["head_gate"], 0.125, A.heads(bufs["dattn"], B, ntok, H))
+    bufs["dkv"] = pm(torch.cat([A.rows(ae["dK"]), A.rows(ae["dV"])], 1))
+    if mutate == "pad_rows_left":
+        bufs["dkv"][M] = -0.75
+    dqkv = torch.zeros((Tp, 3 * Da), dtype=BF16)
+    dqkv[:Tr, :Da] = A.rows(ae["dQ"]).to(BF16)
+    if mutate != "dkv_token_rows_not_copied":
+        dqkv[:Tr, Da:] = bufs["dkv"][tok]
+    bufs["dqkv"] = dqkv
+    kv_w = w["qkv_w16"][:2 * Da] if mutate == "kv_weight_at_q" else w["qkv_w16"][Da:]
+    bufs["dln1"] = pm(f(bufs["dkv"][:M]) @ f(kv_w))
+    bufs["dln1_tok"] = pt(f(dqkv[:Tr]) @ f(w["qkv_w16"]))
+    if mutate != "dln1_tok_not_scattered":
+        bufs["dln1"][tok] = bufs["dln1_tok"][:Tr]
+    acc["qkv_w"], acc["qkv_b"] = a0["qkv_w"].clone(), a0["qkv_b"].clone()
+    times = 2 if (mutate == "deferred_and_launched" and route["kv_job"]) else 1
+    acc["qkv_w"][Da:] += times * (f(bufs["dkv"]).t() @ f(bufs["ln1"]))
+    b0 = 0 if mutate == "kv_bias_grad_at_q" else Da
+    acc["qkv_b"][b0:b0 + 2 * Da] += times * f(bufs["dkv"]).sum(0)
+    if mutate == "token_q_wgrad_over_kv_too":
+        acc["qkv_w"] += f(dqkv).t() @ f(bufs["ln1_tok"])
+        acc["qkv_b"] += f(dqkv).sum(0)
+    else:
+        dq = dqkv.reshape(-1)[:Tp * Da].view(Tp, Da) if mutate == "dq_ld_Da" else dqkv[:, :Da]
+        acc["qkv_w"][:Da] += f(dq).t() @ f(bufs["ln1_tok"])
+        acc["qkv_b"][:Da] += f(dq).sum(0)
+    e = T.ln_bwd_emulate(x, bufs["mean1"], bufs["rstd1"], w["n1w"], bufs["dln1"][:M], None, a0["n1w"], a0["n1b"])
+    bufs["dx_in"], acc["n1w"], acc["n1b"] = e["dx"], e["dgamma"], e["dbeta"]
+    if mutate == "dx1_added_at_packed_rows":
+        bufs["dx_in"][:Tr] += bufs["dx1"]
+    elif mutate != "dx1_not_added":
+        bufs["dx_in"][tok] += bufs["dx1"]
+    bufs["acc"] = acc
+    return bufs

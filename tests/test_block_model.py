@@ -1,7 +1,9 @@
 """tests/_block_model.py under test, without a GPU: the fp32 emulation of one encoder block passes the stage audit, every planted wiring bug is seen
 on the stage it is named for (or by the untouched-bytes statement it breaks), the buffer extents include/devit_hip.h words are what
 devit_block_acts_sizes / devit_block_bwd_sizes report, and the entry points' refusals -- argument checks in front of the first launch, so they
-need no device -- return their DEVIT_ERR_* with the cause in the message.  tests/test_gpu_block.py runs the same audit on the sequence itself."""
+need no device -- return their DEVIT_ERR_* with the cause in the message.  tests/test_gpu_block.py runs the same audit on the sequence itself.
+The lean last block (devit_tail_fwd / devit_tail_bwd) likewise: tail_emulate under tail_audit on the six cases of the tail table, and every entry
+of TAIL_MUTATIONS seen where it is named; tests/test_gpu_tail_call.py runs that audit on the two calls."""
 import functools
 
 import pytest
@@ -144,6 +146,97 @@ def test_without_dqkv_add_and_without_a_block_below(c):
         assert r < 1.0 if name in STORES16 else r <= 0.5, (c["name"], name, r)
     rt, _ = K.audit(c, inp, K.emulate(c, inp, route=K.default_routes(c, prev=False)), route)
     assert rt["fc2_b"] == float("inf"), "a bias gradient formed twice (handed down AND taken here) is seen"
+
+
+# ---- the lean last block (devit_tail_fwd / devit_tail_bwd): tail_emulate under tail_audit
+TAIL_STORES16 = STORES16 | {"kv", "ln1_tok", "q", "dq", "dkv", "dqkv_kv", "dln1_tok", "dln1/tok"}
+TAIL_PLANT_CASES = ("tail_compacted", "tail_short", "tail_one_token")      # Da != D; N below a key tile; D != 384 (never a job)
+
+
+@functools.lru_cache(maxsize=None)
+def clean_tail(name):
+    """(inputs, unmutated emulation, its audit) of a tail case: computed once, shared, left unchanged"""
+    c = K.tail_case_named(name)
+    inp = K.tail_inputs(c, c["ntok"])
+    route = K.tail_routes(c, c["ntok"])
+    bufs = K.tail_emulate(c, c["ntok"], inp)
+    return inp, bufs, K.tail_audit(c, c["ntok"], inp, bufs, route)
+
+
+@pytest.mark.parametrize("c", K.TAIL_CASES, ids=[c["name"] for c in K.TAIL_CASES])
+def test_tail_emulation_passes_the_stage_audit(c):
+    _, bufs, (rt, problems) = clean_tail(c["name"])
+    print(" ".join(f"{k} {v:.3f}" for k, v in rt.items()))
+    assert not problems, problems
+    for name, r in rt.items():
+        assert r < 1.0 if name in TAIL_STORES16 else r <= 0.5, (c["name"], name, r)
+    # the whole list of the two calls, and every buffer they write is one the audit reads: nothing the lean block leaves in memory is unaudited
+    assert list(rt) == list(K.TAIL_FWD_STAGES + K.TAIL_BWD_STAGES)
+    assert set(K.tail_buffer_shapes(c, c["ntok"])) | {"x", "dx", "g2", "dx_in", "acc"} == set(bufs)
+    assert set(bufs["acc"]) == set(K.ACC_NAMES)
+    d = K.tail_dims(c, c["ntok"])
+    for name, (rows, cols, is16) in K.tail_buffer_shapes(c, c["ntok"]).items():
+        assert bufs[name].numel() == rows * cols and (bufs[name].dtype == K.BF16) == bool(is16), name
+    assert d["M"] % 256 and d["T"] % 256, "every M and T is off the 256-row grid"
+
+
+@pytest.mark.parametrize("mutate", sorted(K.TAIL_MUTATIONS))
+def test_planted_tail_wiring_bug_is_seen(mutate):
+    where = K.TAIL_MUTATIONS[mutate]
+    for name in TAIL_PLANT_CASES:
+        c = K.tail_case_named(name)
+        nt = c["ntok"]
+        inp = clean_tail(name)[0]
+        route = K.tail_routes(c, nt, offered=mutate == "deferred_and_launched")
+        rt, problems = K.tail_audit(c, nt, inp, K.tail_emulate(c, nt, inp, mutate=mutate, route=route), route)
+        if mutate == "deferred_and_launched" and not route["kv_job"]:
+            assert c["D"] != 384 and not problems and max(rt.values()) < 1.0, "no job is handed out: nothing to launch twice"
+        elif where.startswith("pad_rows/"):
+            assert where in problems, (name, mutate, problems)
+        else:
+            assert rt[where] >= 1.0, (name, mutate, where, rt[where])
+
+
+def test_tail_mutation_table_lists_what_the_emulation_implements():
+    import inspect
+    import re
+    src = inspect.getsource(K.tail_emulate)
+    assert set(re.findall(r'mutate [!=]= "(\w+)"', src)) == set(K.TAIL_MUTATIONS)
+    stages = set(K.TAIL_FWD_STAGES + K.TAIL_BWD_STAGES) | {"pad_rows/" + n for n in K.TAIL_PADDED_T + K.TAIL_PADDED_M}
+    assert set(K.TAIL_MUTATIONS.values()) <= stages
+
+
+def test_tail_routes_and_inputs_of_the_table():
+    by = {v[0]: K.tail_routes(v[1], v[1]["ntok"], v[2], v[3]) for v in K.tail_variants()}
+    assert [k for k, r in by.items() if r["kv_job"]] == ["tail_student/deferred"]
+    assert all(r["branch"] == dict(wmode=False, fc2_bias="launch", fused=(False, False), prev=False) for r in by.values())
+    assert K.tail_variants()[3][3], "tail_one_token is offered a slot and must not take it"
+    shapes = {c["name"]: (c["B"], c["N"], c["ntok"], c["D"], c["heads"], c["hidden"]) for c in K.TAIL_CASES}
+    assert shapes == {"tail_student": (3, 198, 2, 384, 6, 1536), "tail_one_token": (2, 197, 1, 256, 4, 512), "tail_compacted": (3, 51, 2, 384, 4, 640),
+                      "tail_short": (4, 6, 2, 384, 6, 768), "tail_two_tiles": (130, 6, 2, 384, 6, 768), "tail_wide_tokens": (2, 198, 40, 384, 6, 1536)}
+    for c in K.TAIL_CASES:
+        inp = clean_tail(c["name"])[0]
+        assert all(bool((v != 0).all()) for v in inp["acc0"].values()), "every accumulator is preloaded"
+        assert inp["g2"].shape[0] == c["B"] * c["ntok"] and not torch.equal(inp["w"]["dp1"], inp["w"]["dp2"])
+        assert bool((inp["w"]["head_gate"] == 0).any()) and bool((inp["w"]["neuron_gate"] == 0).any())
+
+
+def test_tail_arena_sees_a_write_outside_an_extent():
+    """the arena of the GPU test, on the host: slots at the library's sizes, clean when only the stated extents are written, and a byte behind an
+    extent, or in a guard, is named"""
+    c = K.tail_case_named("tail_compacted")
+    ar = K.tail_arena("cpu", c, c["ntok"])
+    acts, bwd = K.tail_library_sizes(3, 51, 2, 384, 256, 640, K.SAVE)
+    assert ar.sizes["kv"] == acts["qkv"] and ar.sizes["dkv"] == bwd["dkv"] and ar.adr("att") is None
+    for name, e in ar.extents.items():
+        ar.mem[ar.off[name]:ar.off[name] + e] = 0
+    assert ar.written_outside() == []
+    slack = [n for n, e in ar.extents.items() if e < ar.sizes[n]]
+    assert slack, "a slot with bytes beyond its extent"
+    ar.mem[ar.off[slack[0]] + ar.extents[slack[0]]] = 0
+    ar.mem[0] = 0
+    ar.mem[-1] = 0
+    assert ar.written_outside() == ["extent/" + slack[0], "guard/front", "guard/back"]
 
 
 # ---- host-only statements about the library

@@ -1,14 +1,24 @@
 """The lean last block's entry points on the device, at the C-ABI level (no model): devit_token_rows_copy against indexing, bit for bit and with
-everything around the addressed elements untouched, and devit_tail_fwd against devit_encoder_fwd on identical inputs -- the token rows of the
-block's output are the lean block's output, torch.equal.  (The backward is held through the model: tests/test_gpu_lean.py, and launch for launch
-in tests/test_gpu_tail_launches.py.)"""
+everything around the addressed elements untouched; devit_tail_fwd against devit_encoder_fwd on identical inputs -- every buffer the lean block
+saves on its token rows is the block's, torch.equal; and devit_tail_fwd + devit_tail_bwd audited STAGE BY STAGE on their own buffers
+(tests/_block_model.py: tail_audit; tests/test_block_model.py holds that model to its planted wiring bugs without a GPU).
+
+The audit's memory is ONE arena (K.TailArena): every buffer at exactly the size devit_tail_acts_sizes / devit_tail_bwd_sizes report, dx_in, the
+caller's g2 and the accumulators behind them, a guard slot in front and behind, every byte 0x55 before the calls -- except the accumulators, whose
+non-zero preload is part of the statement.  After the calls every stage holds chk(worst |err| / bound, 1.0, name="tail/<case>/<stage>") against
+the float64 statement of that ONE operation on the stage's stored inputs, every pad row is zero (the caller's g2 included), x, dx and the live
+rows of g2 come back bit for bit, and no byte beyond a buffer's stated extent has changed.  Every bar is 1.0 against a bound of the sibling
+models, or torch.equal.  (The launch list is held in tests/test_gpu_tail_launches.py, the whole step in tests/test_gpu_lean.py.)"""
+import contextlib
 import ctypes as C
+import os
 
 import pytest
 import torch
 
 import _block_model as K
 from _block_model import BF16, F16, F32
+from conftest import chk
 
 pytestmark = pytest.mark.gpu
 GUARD = 16          # sentinel rows in front of and behind every matrix
@@ -125,7 +135,185 @@ def test_tail_fwd_equals_the_token_rows_of_the_block(dev, c, ntok):
     assert torch.equal(bits(tail.view("qkv", d["Mp"], 2 * Da, dt)), bits(blk.view("qkv", d["Mp"], 3 * Da, dt)[:, Da:]))
     for name, cols in (("ln1_tok", D), ("q", Da), ("attn_o", Da), ("ln2", D), ("h", Hd)) + ((("h_pre", Hd),) if c["flags"] & K.SAVE else ()):
         assert not bool(bits(tail.view(name, Tp, cols, dt))[T:].any()), (name, "pad rows")
-    if c["flags"] & K.SAVE:
+    # every buffer the backward later reads on the token rows is the block's, bit for bit
+    tok = K.tok_rows(B, N, ntok, dev)
+    save = bool(c["flags"] & K.SAVE)
+    same = [("ln1_tok", "ln1", D, dt, slice(0, D)), ("q", "qkv", 3 * Da, dt, slice(0, Da)), ("attn_o", "attn_o", Da, dt, slice(0, Da)),
+            ("x_tok", None, D, F32, slice(0, D)), ("x1", "x1", D, F32, slice(0, D)), ("ln2", "ln2", D, dt, slice(0, D)), ("h", "h", Hd, dt, slice(0, Hd))]
+    same += [("h_pre", "h_pre", Hd, dt, slice(0, Hd))] if save else []
+    for name, src, ld, ty, cols in same:
+        want = inp["x"][tok] if src is None else blk.view(src, M, ld, ty)[tok][:, cols]
+        got = tail.view(name, T, cols.stop, ty)
+        assert torch.equal(bits(got), bits(want.contiguous())), (name, "token rows")
+    if save:
         assert torch.equal(tail.view("mean1", 1, M, F32), blk.view("mean1", 1, M, F32))
+        assert torch.equal(tail.view("rstd1", 1, M, F32), blk.view("rstd1", 1, M, F32))
+        for name in ("mean2", "rstd2"):
+            assert torch.equal(tail.view(name, 1, T, F32)[0], blk.view(name, 1, M, F32)[0][tok]), name
         lse_b, lse_t = blk.view("lse", B * d["H"], N, F32).view(B, d["H"], N), tail.view("lse", B * d["H"], ntok, F32).view(B, d["H"], ntok)
         assert torch.equal(lse_t, lse_b[:, :, :ntok])
+
+
+# ============================================================================================ the two calls, stage by stage
+@contextlib.contextmanager
+def environment(env):
+    """the per-call switches of the sequence: all cleared, the run's set; put back afterwards"""
+    old = {k: os.environ.get(k) for k in K.ENV_SWITCHES}
+    try:
+        for k in K.ENV_SWITCHES:
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        yield
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+
+
+JUNK = 0x7f         # the second prefill of the transients: 3.4e38 in bf16 and in fp32, finite
+BWD_SLOTS = K.TAIL_BWD_NAMES + ("dx_in", "g2")
+
+
+class TailRun:
+    """one case's memory -- the arena, the inputs on the device -- and the two calls"""
+
+    def __init__(self, dev, c, env, offered):
+        from devit_amd import _lib as L
+        self.c, self.ntok, self.env, self.offered = c, c["ntok"], env, offered
+        self.d = K.tail_dims(c, self.ntok)
+        self.inp = K.to_device(K.tail_inputs(c, self.ntok), dev)
+        self.x, self.dx = self.inp["x"].clone(), self.inp["dx"].clone()
+        self.ar = K.tail_arena(dev, c, self.ntok)
+        self.fill = {}
+        self.load()
+        self.jobs, self.count = (L.WgradJob * 4)(), C.c_int(-1)
+        with environment(env):
+            fused = bool(L.load().devit_dgrad_layernorm_bwd_fused(self.d["Tp"], self.d["D"], self.d["Hd"]))
+        assert not fused, "the LN2 site of the token rows runs as two launches under the default switches: dln2 is in memory"
+        self.route = K.tail_routes(c, self.ntok, env, offered, fused)
+
+    def load(self):
+        """the caller's part of the arena: the live rows of g2 (its pad rows keep the prefill: the call zeroes them), every accumulator's preload"""
+        d = self.d
+        self.ar.view("g2", d["Tp"], d["D"], BF16)[:d["T"]] = self.inp["g2"]
+        for n, t in self.inp["acc0"].items():
+            self.ar.view("g_" + n, 1, t.numel(), F32)[0] = t.reshape(-1)
+
+    def adr(self, name):
+        name = "kv" if name == "qkv" else name
+        if name in self.ar.sizes:
+            return self.ar.adr(name)
+        t = {"x": self.x, "dx": self.dx}.get(name, self.inp["w"].get(name))
+        return None if t is None else t.data_ptr()
+
+    def structs(self):
+        w, t, g, io = K.tail_structs(self.c, self.adr, self.ntok)
+        io.lnws_bytes = self.ar.sizes["lnws"]
+        if self.offered:
+            io.defer_jobs, io.defer_count = C.addressof(self.jobs), C.addressof(self.count)
+        return w, t, g, io
+
+    def forward(self):
+        from devit_amd import _lib as L
+        w, t, _, _ = self.structs()
+        with environment(self.env):
+            L.call("devit_tail_fwd", C.byref(w), C.byref(t), self.d["B"], self.d["N"], self.d["D"], K.EPS, L.stream_ptr())
+
+    def backward(self):
+        """devit_tail_bwd, then -- as the caller of a deferred product must -- the one job through devit_wgrad_grouped over K = Mp rows"""
+        from devit_amd import _lib as L
+        w, t, g, io = self.structs()
+        self.count.value = -1
+        with environment(self.env):
+            L.call("devit_tail_bwd", C.byref(w), C.byref(t), C.byref(g), C.byref(io), self.d["B"], self.d["N"], self.d["D"], K.EPS, L.stream_ptr())
+            if self.offered:
+                assert self.count.value == int(self.route["kv_job"]), (self.count.value, self.route)
+                if self.count.value == 1:
+                    L.call("devit_wgrad_grouped", self.jobs, 1, self.d["Mp"], 0, L.stream_ptr())
+        torch.cuda.synchronize()
+
+    def bufs(self):
+        """the logical views tail_audit() takes, of whatever the calls left"""
+        d = self.d
+        out = dict(x=self.x, dx=self.dx, g2=self.ar.view("g2", d["Tp"], d["D"], BF16), dx_in=self.ar.view("dx_in", d["M"], d["D"], F32))
+        for name, (rows, cols, is16) in K.tail_buffer_shapes(self.c, self.ntok).items():
+            v = self.ar.view(name, rows, cols, BF16 if is16 else F32)
+            out[name] = v[0] if name.startswith(("mean", "rstd")) else v
+        out["acc"] = {n: self.ar.view("g_" + n, 1, t.numel(), F32)[0].view(t.shape) for n, t in self.inp["acc0"].items()}
+        return out
+
+    def audit(self):
+        rt, problems = K.tail_audit(self.c, self.ntok, self.inp, self.bufs(), self.route)
+        return rt, problems + self.ar.written_outside(self.fill)
+
+
+_RUNS = {}
+
+
+def the_run(dev, c, env, offered):
+    """one forward + backward per (case, environment, slot offered), shared by the tests that need it and left unchanged"""
+    key = (c["name"], tuple(sorted(env.items())), offered)
+    if key not in _RUNS:
+        run = TailRun(dev, c, env, offered)
+        run.forward()
+        run.backward()
+        _RUNS[key] = run
+    return _RUNS[key]
+
+
+def hold_all(tag, rt, problems):
+    print(f"tail/{tag}", " ".join(f"{k} {v:.3f}" for k, v in rt.items()))
+    assert problems == [], f"tail/{tag}: {problems}"
+    assert list(rt) == list(K.TAIL_FWD_STAGES + K.TAIL_BWD_STAGES), "no stage is left out"
+    bad = [k for k, v in rt.items() if not chk(v, 1.0, name=f"tail/{tag}/{k}")]
+    assert not bad, f"tail/{tag}: worst |err| / bound {({k: rt[k] for k in bad})}"
+
+
+TAIL_VARIANTS = K.tail_variants()
+
+
+@pytest.mark.parametrize("tag,c,env,offered", TAIL_VARIANTS, ids=[v[0] for v in TAIL_VARIANTS])
+def test_tail_stages(dev, tag, c, env, offered):
+    """Worst |err| / bound per stage, MI355X (profiles/tail_bwd_parity_margins.json): the 16-bit stores sit just under 1, the copies at 0 (bit for
+    bit), the fp32 stages and the accumulators far below."""
+    run = the_run(dev, c, env, offered)
+    want = {"tail_student/split_k": -1, "tail_student/deferred": 1, "tail_student/wgradfr0": 0, "tail_one_token": 0}.get(tag, -1)
+    assert run.count.value == want, "*defer_count: 1 where the all-rows product is handed out, 0 where a slot is offered and not taken"
+    if want == 0:
+        assert run.jobs[0].a is None and run.jobs[0].out is None, "no job written"
+    hold_all(tag, *run.audit())
+
+
+@pytest.mark.parametrize("c", K.TAIL_CASES, ids=[c["name"] for c in K.TAIL_CASES])
+def test_tail_bwd_again_on_junk_transients(dev, c):
+    """the backward a second time, on fresh accumulators, with every transient, dx_in and the pad rows of g2 prefilled with other junk: the same
+    audit holds, because the call zeroes what it needs and reads nothing it has not written"""
+    _, env, offered = c["runs"][0]
+    run = TailRun(dev, c, env, offered)
+    run.forward()
+    run.backward()
+    first, problems = run.audit()
+    assert problems == [], problems
+    run.ar.refill(BWD_SLOTS, JUNK)
+    run.fill = {n: JUNK for n in BWD_SLOTS}
+    run.load()
+    run.backward()
+    again, problems = run.audit()
+    hold_all(c["name"] + "/again", again, problems)
+    exact = [k for k, v in first.items() if v == 0.0]
+    assert {"ln1_tok", "x_tok", "dqkv_kv", "dln1/tok"} <= set(exact) and all(again[k] == 0.0 for k in exact)
+
+
+REFUSAL_CASE = K._tail_case("student", 2, 198, 2, 384, 6, 1536)      # the shape the TAIL_REFUSALS rows are worded for
+
+
+@pytest.mark.parametrize("name,case,change,entry,code,words", K.TAIL_REFUSALS, ids=[r[0] for r in K.TAIL_REFUSALS])
+def test_tail_entry_points_refuse(dev, name, case, change, entry, code, words):
+    """the DEVIT_ERR_* with the cause in the message and nothing launched: every byte of the arena, and the inputs, come back as they were"""
+    run = TailRun(dev, REFUSAL_CASE, {}, False)
+    before = [run.ar.mem.clone(), run.x.clone(), run.dx.clone()]
+    rc, msg = K.refused(case, change, entry, run.adr)
+    assert rc == code and words in msg, (name, rc, msg)
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(before, [run.ar.mem, run.x, run.dx])), f"{name}: a refused call wrote"
