@@ -7,6 +7,7 @@ The five `.item()` host syncs + `cuda.synchronize()` per step of the reference (
 kept for logging parity in train_1epoch_qkv, but only every `print_freq` steps.
 """
 import math
+import operator
 import os
 import sys
 
@@ -30,23 +31,83 @@ def _hand_over(out, main):
             continue                      # tagged by the composite path: lives in the main stream's pool already
         if packed.untyped_storage().nbytes() <= packed.numel() * packed.element_size():    # its own allocation
             packed.record_stream(main)
-    for t in out.get('encoder') or ():    # (hid_gama > 0: one block's hidden states -- a view of its arena on the 16-bit path, as the qkv buffers)
+    for t in out.get('encoder') or ():    # (hid_gama > 0: the selected blocks' hidden states -- views of their arenas on the 16-bit path, as the qkv buffers; a last block's is a clone)
         if t is not None and t.untyped_storage().nbytes() <= t.numel() * t.element_size():
             t.record_stream(main)
 
 
-def _hid_layer(m):
-    """The block whose output enters the hidden-state relation loss: the one whose q/k/v enter the relation losses (engine.py:91-92)."""
-    return len(m.blocks) // 2 - 1
+RELATION_WORDS = ("mid", "last", "all")
+
+
+def resolve_relation_layers(spec, student_depth, teacher_depth):
+    """The layer pairs ((s, t), ...) whose q/k/v (and, with the other families on, hidden states) the step compares -- --relation-layers.
+    spec: None or "mid" (the reference's one pair, engine.py:91-92: block depth // 2 - 1 of each model), "last", "all", or an iterable of 0-based
+    student block indices (sorted, deduplicated).  The teacher's block of student block s is t(s) = (s + 1) * (tl // sl) - 1: the last block of
+    the s-th of sl equal groups of teacher blocks, which is the reference's pair for "mid" at every depth ratio.  ValueError names the offender."""
+    sl, tl = int(student_depth), int(teacher_depth)
+    if sl < 1 or tl < 1 or tl % sl != 0:
+        raise ValueError(f"relation layers: the teacher's depth {tl} is not a multiple of the student's depth {sl}: the layers cannot be paired")
+    if isinstance(spec, (list, tuple)) and len(spec) == 1 and isinstance(spec[0], str) and not spec[0].lstrip("+-").isdigit():
+        spec = spec[0]                             # (the command line's one word)
+    if spec is None:
+        spec = "mid"
+    if isinstance(spec, str):
+        if spec not in RELATION_WORDS:
+            raise ValueError(f"relation layers: unknown selection {spec!r}: one of {', '.join(RELATION_WORDS)}, or 0-based student block indices")
+        if spec == "mid" and sl < 2:
+            raise ValueError(f"relation layers: 'mid' is block depth // 2 - 1: a student of depth {sl} has none")
+        layers = {"mid": [sl // 2 - 1], "last": [sl - 1], "all": list(range(sl))}[spec]
+    else:
+        layers = []
+        for v in spec:
+            try:                                   # (the command line hands the indices over as strings)
+                i = int(v, 10) if isinstance(v, str) else operator.index(v)
+            except (ValueError, TypeError):
+                raise ValueError(f"relation layers: {v!r} is not a 0-based student block index"
+                                 + (f": {v!r} stands alone, not among indices" if v in RELATION_WORDS else "")) from None
+            if i < 0 or i >= sl:
+                raise ValueError(f"relation layers: block index {i} is outside the student's blocks 0 .. {sl - 1}")
+            layers.append(i)
+        if not layers:
+            raise ValueError("relation layers: the selection [] is empty: name at least one student block")
+        layers = sorted(set(layers))
+    r = tl // sl
+    return tuple((s, (s + 1) * r - 1) for s in layers)
+
+
+def _unwrapped(m):
+    return m.module if hasattr(m, "module") else m
+
+
+def _depth(m):
+    m = _unwrapped(m)
+    return len(m.blocks) if hasattr(m, "blocks") else None
+
+
+def _request(m, layers, hid):
+    """What the next forwards of `m` hand out beside the logits: the q/k/v of `layers` with the zeroed overhang rows the relation kernels read
+    (qkv_pad_layers) and, with `hid`, those blocks' 'encoder' outputs.  Set on every call: the request follows the step's selection, it does not
+    stick to the model.  A selection that holds the last block makes the model run it in full (de_vit.run_blocks drops the lean tail)."""
+    vit = _unwrapped(m)
+    vit._rel_request = frozenset(layers)
+    vit._hid_request = bool(hid)
+    if hasattr(vit, "blocks"):
+        vit.qkv_pad_layers = set(layers)
+
+
+def _hid_layers(vit):
+    """The blocks whose output enters the hidden-state relation loss: those whose q/k/v enter the relation losses (engine.py:91-92: the middle one)."""
+    return set(getattr(vit, "_rel_request", None) or {len(vit.blocks) // 2 - 1})
 
 
 def _forward_outputs(m, samples):
     """m(samples) with the outputs the step reads: q/k/v, and -- when the step asked for it (m._hid_request, set by distill_forward /
-    TeacherLookahead for hid_gama > 0) -- the 'encoder' output of the middle block alone (enc_layers), which keeps the lean tail."""
-    vit = m.module if hasattr(m, "module") else m
+    TeacherLookahead for hid_gama > 0) -- the 'encoder' outputs of the selected blocks alone (enc_layers), which keeps the lean tail unless the
+    last block is one of them."""
+    vit = _unwrapped(m)
     if not getattr(vit, "_hid_request", False):
         return m(samples, output_qkv=True)
-    prev, vit.enc_layers = getattr(vit, "enc_layers", None), {_hid_layer(vit)}
+    prev, vit.enc_layers = getattr(vit, "enc_layers", None), _hid_layers(vit)
     try:
         return m(samples, output_qkv=True, output_encoders=True)
     finally:
@@ -65,7 +126,7 @@ def _side_forward(teacher_model, samples, main, side):
 
 def distill_forward(model, teacher_model, samples, targets, gama=(0.2, 0.1, 0.3), kind="hard", alpha=0.5, tau=1.0,
                     criterion=None, dp_scales="draw", teacher_outputs=None, after_student=None, hid_gama=0.0, qkv_ce_gama=0.0,
-                    qkv_cross_gama=0.0, qkv_layout="view"):
+                    qkv_cross_gama=0.0, qkv_layout="view", relation_layers=None):
     """One DEKD forward.  Returns dict(loss, cls_loss, q_loss, k_loss, v_loss, logits, teacher_logits).
     teacher_outputs: the teacher's outputs for `samples` if they were computed ahead (TeacherLookahead).
     after_student: called once the student's forward is enqueued (TeacherLookahead.launch of the NEXT batch).
@@ -74,7 +135,13 @@ def distill_forward(model, teacher_model, samples, targets, gama=(0.2, 0.1, 0.3)
     it was, dict and all.
     qkv_ce_gama / qkv_cross_gama > 0: loss += qkv_ce_gama * cal_qkv_loss([s_mid], [t_mid]) + qkv_cross_gama * cal_qkv_loss2([s_mid], [t_mid])
     (utils/losses.py:247-292) on the same middle layer pair, rows per qkv_layout; returned as `qkv_ce_loss` / `qkv_cross_loss`.  Both 0: the step
-    as it was, dict and all."""
+    as it was, dict and all.
+    relation_layers: the layer pairs all of the above compare (resolve_relation_layers: None or "mid", "last", "all", student block indices) in
+    place of "the middle pair": loss = cls + sum over the pairs of sum_j gama_j * relation_loss_j(s, t) / depth_s + the list losses over the pairs'
+    lists, each with the reference's own normalisation (/ len, / 3 len, / 9 len).  q_loss / k_loss / v_loss are the sums over the pairs / depth_s;
+    `rel_layers` is the [len(pairs), 3] tensor of the unscaled per-pair losses.  None: the step as it was, dict and all (no `rel_layers`); its
+    numbers are those of "mid".  The models' requests (qkv_pad_layers, the hidden states handed out, the lean tail) follow the selection on
+    every call; teacher outputs computed ahead for another selection are a RuntimeError."""
     vit = model.module if hasattr(model, "module") else model
     hid_gama = float(hid_gama)
     if not hid_gama >= 0.:
@@ -86,18 +153,29 @@ def distill_forward(model, teacher_model, samples, targets, gama=(0.2, 0.1, 0.3)
     if qkv_layout not in ops.QKV_LAYOUTS:
         raise ValueError(f"qkv_layout must be one of {sorted(ops.QKV_LAYOUTS)}, got {qkv_layout!r}")
     hid = hid_gama > 0.
-    vit._hid_request = hid
-    if teacher_outputs is None:          # (a TeacherLookahead made its request when it was built)
-        (teacher_model.module if hasattr(teacher_model, "module") else teacher_model)._hid_request = hid
-    # only the middle block's q/k/v enter the relation loss (engine.py:91-100): the other blocks' packed qkv buffers
-    # need no zeroed overhang rows
-    for m in (vit, teacher_model):
-        if getattr(m, "qkv_pad_layers", None) is None and hasattr(m, "blocks"):
-            m.qkv_pad_layers = {len(m.blocks) // 2 - 1}
+    tvit = _unwrapped(teacher_model)
+    # the selection, resolved before the forwards when both depths are known from the models (else from the outputs, below)
+    pairs = None
+    if _depth(vit) is not None and _depth(tvit) is not None:
+        pairs = resolve_relation_layers(relation_layers, _depth(vit), _depth(tvit))
+    if pairs is not None and teacher_outputs is not None:
+        _check_teacher_outputs(teacher_outputs, pairs)
+    # only the selected blocks' q/k/v enter the relation loss (engine.py:91-100: the middle one): the other blocks' packed qkv buffers need no
+    # zeroed overhang rows.  The request is made on every call -- a selection does not stick to the model object.
+    if pairs is not None:
+        _check_compacted(vit, pairs)
+        _request(vit, [s for s, _ in pairs], hid)
+        if teacher_outputs is None:      # (a TeacherLookahead makes its request when it launches)
+            _request(tvit, [t for _, t in pairs], hid)
+    else:
+        vit._hid_request = hid
+        if teacher_outputs is None:
+            tvit._hid_request = hid
     pre_teacher = None
     if teacher_outputs is None and os.environ.get("DEVIT_TEACHER_STREAM", "1") == "1" and samples.is_cuda:
         pre_teacher = _teacher_forward_async(teacher_model, samples)
-    # only the logits and the middle block's q/k/v are read below: the last block runs on its two token rows (de_vit.lean_tail)
+    # only the logits and the selected blocks' q/k/v are read below: unless the last block is one of them it runs on its two token rows
+    # (de_vit.lean_tail)
     with de_vit.lean_tail(vit):
         if dp_scales != "draw":   # explicit DropPath masks (parity tests)
             outputs = _forward_with_dp(vit, samples, dp_scales, hid)
@@ -113,37 +191,92 @@ def distill_forward(model, teacher_model, samples, targets, gama=(0.2, 0.1, 0.3)
         criterion = losses.DistillLoss(losses.SoftTargetCrossEntropy(), kind, alpha, tau)
     cls_loss = criterion(outputs=logits, teacher_outputs=teacher_logits, labels=targets)   # :79
     tl, sl = len(teacher_qkvs), len(qkvs)
-    assert tl % sl == 0, 'The number of student layer can not be divisible by the number of teacher layer'
-    rel3 = losses.relation_losses_vector(qkvs[sl // 2 - 1], teacher_qkvs[tl // 2 - 1])     # :91-100, as one [q, k, v] tensor
+    if pairs is None:
+        pairs = resolve_relation_layers(relation_layers, sl, tl)
+    _check_outputs(outputs, teacher_outputs, pairs, hid)
+    s_qkvs, t_qkvs = [qkvs[s] for s, _ in pairs], [teacher_qkvs[t] for _, t in pairs]
+    rel3 = losses.relation_losses_vector(s_qkvs[0], t_qkvs[0])                             # :91-100, as one [q, k, v] tensor
     if rel3 is not None:
         # :102-106 on the vector: total = cls + sum_j (gama_j / sl) loss_j (one multiply-sum + one add; backward one multiply) and the
         # three logged values as views of loss / sl -- the scalar form costs ~25 tiny kernels per step around the same numbers
-        scaled = rel3 / sl
+        if len(pairs) == 1:
+            rel, summed = rel3, rel3
+        else:            # one [L, 3] tensor of the pairs' losses: the weights broadcast over its rows, the logged values are its column sums
+            rel = torch.stack([rel3] + [losses.relation_losses_vector(sq, tq) for sq, tq in zip(s_qkvs[1:], t_qkvs[1:])])
+            summed = rel.sum(0)
+        scaled = summed / sl
         q_loss, k_loss, v_loss = scaled[0], scaled[1], scaled[2]
         # (an elementwise product + sum, not torch.dot: on ROCm torch.dot is a rocBLAS call, and no vendor BLAS runs on this path)
-        loss = cls_loss + (rel3 * _relation_weights(gama, sl, rel3.device)).sum()
+        loss = cls_loss + (rel * _relation_weights(gama, sl, rel.device)).sum()
+        rel_layers = rel.detach().view(len(pairs), 3)
     else:
-        q_loss, k_loss, v_loss = losses.relation_losses_packed(qkvs[sl // 2 - 1], teacher_qkvs[tl // 2 - 1])
-        q_loss, k_loss, v_loss = q_loss / sl, k_loss / sl, v_loss / sl                  # :102-104
+        per = [losses.relation_losses_packed(sq, tq) for sq, tq in zip(s_qkvs, t_qkvs)]
+        q_loss, k_loss, v_loss = (sum(p[j] for p in per) / sl for j in range(3))        # :102-104
         loss = cls_loss + float(gama[0]) * q_loss + float(gama[1]) * k_loss + float(gama[2]) * v_loss   # :105-106
+        rel_layers = torch.stack([torch.stack([x.detach() for x in p]) for p in per])
     out = dict(loss=loss, cls_loss=cls_loss, q_loss=q_loss, k_loss=k_loss, v_loss=v_loss, logits=logits,
                teacher_logits=teacher_logits)
+    if relation_layers is not None:      # (None: the step as it was, dict and all)
+        out['rel_layers'] = rel_layers
     if hid:
-        s_enc, t_enc = outputs.get('encoder'), teacher_outputs.get('encoder')
-        s_hid = s_enc[sl // 2 - 1] if s_enc else None
-        t_hid = t_enc[tl // 2 - 1] if t_enc else None
-        if s_hid is None or t_hid is None:
-            raise RuntimeError("distill_forward(hid_gama > 0): the %s outputs hold no hidden states of the middle block -- teacher outputs computed "
-                               "ahead must come from TeacherLookahead(teacher, hid=True)" % ("student's" if s_hid is None else "teacher's"))
-        out['hid_loss'] = losses.cal_hid_relation_loss([s_hid], [t_hid], exact=getattr(vit, "precision", "bf16") == "f32")
+        s_enc, t_enc = outputs['encoder'], teacher_outputs['encoder']
+        out['hid_loss'] = losses.cal_hid_relation_loss([s_enc[s] for s, _ in pairs], [t_enc[t] for _, t in pairs],
+                                                       exact=getattr(vit, "precision", "bf16") == "f32")
         out['loss'] = loss + hid_gama * out['hid_loss']
     if qkv_ce_gama > 0.:
-        out['qkv_ce_loss'] = losses.cal_qkv_loss([qkvs[sl // 2 - 1]], [teacher_qkvs[tl // 2 - 1]], layout=qkv_layout)
+        out['qkv_ce_loss'] = losses.cal_qkv_loss(s_qkvs, t_qkvs, layout=qkv_layout)
         out['loss'] = out['loss'] + qkv_ce_gama * out['qkv_ce_loss']
     if qkv_cross_gama > 0.:
-        out['qkv_cross_loss'] = losses.cal_qkv_loss2([qkvs[sl // 2 - 1]], [teacher_qkvs[tl // 2 - 1]], layout=qkv_layout)
+        out['qkv_cross_loss'] = losses.cal_qkv_loss2(s_qkvs, t_qkvs, layout=qkv_layout)
         out['loss'] = out['loss'] + qkv_cross_gama * out['qkv_cross_loss']
     return out
+
+
+def _check_compacted(vit, pairs):
+    """A student compacted for training keeps every head in the GEMMs of the blocks whose q/k/v enter the relation losses (a masked head's q/k/v
+    still do, shrink.compact): refuse a selection whose block has lost them instead of comparing fewer heads in silence."""
+    for s, _ in pairs:
+        blk = vit.blocks[s]
+        c = getattr(blk, "_compact", None)
+        if c is not None and c.get("heads_compacted") and c["num_heads"] < blk.attn.num_heads:
+            raise RuntimeError(f"distill_forward: block {s} of the student is one of this step's relation layers {[p[0] for p in pairs]}, but it was "
+                               f"compacted to {c['num_heads']} of its {blk.attn.num_heads} heads: the q/k/v of its masked heads enter the relation "
+                               "losses -- compact with shrink.compact(model, trainable=True, relation_layers=...) for the step's selection")
+
+
+def _selection_text(pairs):
+    return "student blocks %s / teacher blocks %s" % ([s for s, _ in pairs], [t for _, t in pairs])
+
+
+def _check_teacher_outputs(teacher_outputs, pairs):
+    """Teacher outputs computed ahead carry the teacher blocks they were prepared for (TeacherLookahead.take): refuse another selection's."""
+    made = teacher_outputs.get('relation_layers') if isinstance(teacher_outputs, dict) else None
+    want = tuple(t for _, t in pairs)
+    if made is not None and tuple(made) != want:
+        raise RuntimeError(f"distill_forward: this step's relation layers are {_selection_text(pairs)}, the teacher outputs handed in were computed "
+                           f"ahead for teacher blocks {list(made)}: build the look-ahead for the step's selection, "
+                           "TeacherLookahead(teacher, relation_layers=..., student_depth=...)")
+
+
+def _check_outputs(outputs, teacher_outputs, pairs, hid):
+    """Every entry the losses read is there -- a RuntimeError here, not a failure inside a loss."""
+    _check_teacher_outputs(teacher_outputs, pairs)
+    made = teacher_outputs.get('relation_layers') if isinstance(teacher_outputs, dict) else None
+    made = "" if made is None else f" (computed ahead for teacher blocks {list(made)})"
+    for who, o, idx in (("student's", outputs, [s for s, _ in pairs]), ("teacher's", teacher_outputs, [t for _, t in pairs])):
+        qk = o['qkv']
+        gone = [i for i in idx if i >= len(qk) or qk[i] is None]
+        if gone:
+            raise RuntimeError(f"distill_forward: this step's relation layers are {_selection_text(pairs)}, but the {who} outputs"
+                               f"{made if who[0] == 't' else ''} hold no q/k/v of block(s) {gone} -- a forward inside de_vit.lean_tail hands out "
+                               "none of its last block unless that block was requested")
+        if hid:
+            enc = o.get('encoder')
+            gone = [i for i in idx if not enc or i >= len(enc) or enc[i] is None]
+            if gone:
+                raise RuntimeError(f"distill_forward(hid_gama > 0): this step's relation layers are {_selection_text(pairs)}, but the {who} outputs"
+                                   f"{made if who[0] == 't' else ''} hold no hidden states of block(s) {gone} -- teacher outputs computed ahead "
+                                   "must come from TeacherLookahead(teacher, hid=True, relation_layers=...)")
 
 
 _side_stream = {}
@@ -214,13 +347,34 @@ class TeacherLookahead:
         for k: t_out = look.take(batch_k); look.submit(batch_k+1); distill_forward(..., batch_k, teacher_outputs=t_out)
     """
 
-    def __init__(self, teacher_model, hid=False):
-        """hid: the forwards also hand out the middle block's hidden states (distill_forward(hid_gama > 0) reads them)"""
+    layers, hid = None, None     # (an object made without __init__ prepares nothing and stamps nothing)
+
+    def __init__(self, teacher_model, hid=False, relation_layers=None, student_depth=None):
+        """hid: the forwards also hand out the selected blocks' hidden states (distill_forward(hid_gama > 0) reads them).
+        relation_layers, student_depth: the step's selection (resolve_relation_layers) and the depth of the student it is paired with (None: the
+        teacher's own depth); the forwards are prepared for the teacher side of the pairs, and the outputs carry it ('relation_layers') so that a
+        step with another selection refuses them.  None: the middle block."""
         self.teacher = teacher_model
-        if getattr(teacher_model, "qkv_pad_layers", None) is None and hasattr(teacher_model, "blocks"):
-            teacher_model.qkv_pad_layers = {len(teacher_model.blocks) // 2 - 1}
-        (teacher_model.module if hasattr(teacher_model, "module") else teacher_model)._hid_request = bool(hid)
+        self.hid = bool(hid)
+        depth = _depth(teacher_model)
+        if depth is not None:
+            pairs = resolve_relation_layers(relation_layers, depth if student_depth is None else student_depth, depth)
+            self.layers = tuple(t for _, t in pairs)
+        elif relation_layers is None:
+            self.layers = None
+        else:
+            raise ValueError("TeacherLookahead(relation_layers=...): the teacher has no `blocks` to select from")
+        self._prepare()
         self._pending = None
+
+    def _prepare(self):
+        """the teacher's request, made again at every launch: a step run in between with another selection (or none ahead) leaves its own behind"""
+        if self.hid is None:
+            return
+        if self.layers is not None:
+            _request(self.teacher, self.layers, self.hid)
+        else:
+            _unwrapped(self.teacher)._hid_request = self.hid
 
     def submit(self, samples, defer=False):
         """defer: record the batch, enqueue its forward at launch() (or at take(), at the latest).  Round 6: the loop launches the NEXT batch's
@@ -236,6 +390,7 @@ class TeacherLookahead:
 
     def launch(self):
         if self._pending is not None and self._pending[1] is None:
+            self._prepare()
             self._pending[1] = _teacher_forward_async(self.teacher, self._pending[0])
 
     def take(self, samples):
@@ -243,7 +398,10 @@ class TeacherLookahead:
             raise RuntimeError("TeacherLookahead.take: not the batch that was submitted")
         self.launch()
         join, self._pending = self._pending[1], None
-        return join()
+        out = join()
+        if self.layers is not None and isinstance(out, dict):
+            out['relation_layers'] = self.layers
+        return out
 
 
 class _PreparedBatches:
@@ -318,7 +476,7 @@ def _forward_with_dp(vit, samples, dp_scales, hid=False):
                                           grad_ready=vit.grad_ready, dp_scales=dp_scales, precision=vit.precision,
                                           qkv_pad_layers=getattr(vit, "qkv_pad_layers", None),
                                           lean_tokens=vit.num_tokens if getattr(vit, "_lean_tail", False) else 0,
-                                          enc_layers={_hid_layer(vit)} if hid else None)
+                                          enc_layers=_hid_layers(vit) if hid else None)
     heads = vit._tokens_and_logits(xo, True)
     return {'output': (heads[1], heads[2]) if vit.training else (heads[1] + heads[2]) / 2, 'qkv': qkvs, 'encoder': encs}
 
@@ -340,12 +498,13 @@ def train_1epoch_qkv(model, teacher_model, criterion, data_loader, optimizer, de
     header = 'Epoch: [{}]'.format(epoch)
     step = 0
     lookahead = bool(getattr(args, "teacher_lookahead", True)) and device is not None and str(device).startswith("cuda")
-    batches = _PreparedBatches(data_loader, device, mixup_fn, TeacherLookahead(teacher_model, hid=hid_gama > 0) if lookahead else None,
-                               row_dtypes=row_dtypes_for(model, teacher_model))
+    relation_layers = getattr(args, "relation_layers", None)       # --relation-layers: the layer pairs of all relation terms (None: the middle pair)
+    look = TeacherLookahead(teacher_model, hid=hid_gama > 0, relation_layers=relation_layers, student_depth=_depth(model)) if lookahead else None
+    batches = _PreparedBatches(data_loader, device, mixup_fn, look, row_dtypes=row_dtypes_for(model, teacher_model))
     for samples, targets, teacher_out in metric_logger.log_every(batches, print_freq, header):
         out = distill_forward(model, teacher_model, samples, targets, gama=args.gama, criterion=criterion,
                               teacher_outputs=teacher_out, after_student=batches.launch_teacher, hid_gama=hid_gama,
-                              qkv_ce_gama=qkv_ce_gama, qkv_cross_gama=qkv_cross_gama, qkv_layout=qkv_layout)
+                              qkv_ce_gama=qkv_ce_gama, qkv_cross_gama=qkv_cross_gama, qkv_layout=qkv_layout, relation_layers=relation_layers)
         loss = out['loss']
         log_now = (step % print_freq == 0)
         if log_now:

@@ -72,7 +72,7 @@ _serial = [0]          # stamps every compaction (cache keys use it, never id())
 
 
 @torch.no_grad()
-def compact(model, trainable=False):
+def compact(model, trainable=False, relation_layers=None):
     """Build the compacted weights of every block of `model` (a devit_amd VisionTransformer, MultiViT sub-models
     included) from its current gates.  Returns [(kept heads, heads run, kept neurons, neurons run)] per block.
 
@@ -81,17 +81,19 @@ def compact(model, trainable=False):
     core/imp_rank.py:50-71,132-153).  The fp32 masters stay the parameters: every training forward re-gathers the kept
     rows / columns from their current bf16 copies (refresh_compact), the backward's weight-gradient GEMMs run at the
     compact shapes and their results are added into the kept rows / columns of the masters' gradients; masked units get
-    exact-zero gradients, as in the masked model (their activations are multiplied by a zero gate there)."""
+    exact-zero gradients, as in the masked model (their activations are multiplied by a zero gate there).
+    relation_layers (with trainable=True): the step's selection of student blocks (engine.resolve_relation_layers; None: the middle block)."""
     report = []
     _serial[0] += 1
-    # DEKD reads q/k/v of ALL heads of the middle block (engine.py:91-92; the gate of models/de_vit.py:77-79 acts on the head
-    # OUTPUTS, so a masked head's q/k/v still enter -- and get gradients from -- the relation loss): when training, that
-    # block keeps every head in its GEMMs and masks at run time
+    # DEKD reads q/k/v of ALL heads of the blocks of its relation layers (engine.py:91-92: the middle one; the gate of models/de_vit.py:77-79
+    # acts on the head OUTPUTS, so a masked head's q/k/v still enter -- and get gradients from -- the relation loss): when training, those
+    # blocks keep every head in their GEMMs and mask at run time
     keep_heads = set()
     if trainable:
+        from .engine import resolve_relation_layers
         for m in model.modules():
             if type(m).__name__ == "VisionTransformer" and len(m.blocks) >= 2:
-                keep_heads.add(id(m.blocks[len(m.blocks) // 2 - 1]))
+                keep_heads.update(id(m.blocks[s]) for s, _ in resolve_relation_layers(relation_layers, len(m.blocks), len(m.blocks)))
     for blk in _blocks(model):
         if trainable:
             for g in (blk.attn.gate, blk.mlp.gate):

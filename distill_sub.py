@@ -76,6 +76,10 @@ def get_args_parser():
       help='weight of the nine cross relations q k^T, q v^T, ... (the reference\'s cal_qkv_loss2, utils/losses.py:271-292)')
     a('--qkv-layout', default='view', choices=['view', 'tokens'],
       help='rows of the two losses above: the reference\'s reinterpreting .view(B, N, H * 64) (default) or head-concatenated token rows')
+    a('--relation-layers', nargs='+', default=['mid'], metavar='L',
+      help='the student blocks whose q/k/v relations (and the terms of --hid-gama, --qkv-ce-gama, --qkv-cross-gama) are distilled: mid (the '
+           'reference\'s block depth // 2 - 1, the default), last, all, or 0-based block indices; student block s is paired with teacher block '
+           '(s + 1) * (teacher depth // student depth) - 1')
     a('--data-path', default=r'./datasets'); a('--dataset', default='cifar100', choices=['cifar100', 'IMNET', 'cars', 'pets', 'flowers'])
     a('--inat-category', default='name'); a('--num_division', metavar='N', type=int, default=4); a('--start-division', metavar='N', type=int, default=0)
     a('--device', default='cuda'); a('--seed', default=0, type=int); a('--resume', default=''); a('--start_epoch', default=0, type=int)
@@ -502,12 +506,35 @@ class StepRunner:
         pass
 
 
+DEKD_ONLY_FLAGS = ('--relation-layers',)
+
+
+def without_dekd_flags(parser):
+    """get_args_parser() without the flags that belong to the DEKD stage alone: train_subdata.py and ensemble.py build their parsers on this one"""
+    for act in [x for x in parser._actions if set(x.option_strings) & set(DEKD_ONLY_FLAGS)]:
+        parser._optionals._remove_action(act)
+        for opt in act.option_strings:
+            parser._option_string_actions.pop(opt, None)
+    return parser
+
+
 def check_input_size(args):
     """--input-size: the square sides the patch-embed kernels are built for (devit_amd.ops.IMG_SIZES); SystemExit with the list otherwise."""
     from devit_amd.ops import IMG_SIZES
     if getattr(args, 'input_size', 224) not in IMG_SIZES:
         raise SystemExit(f"--input-size {args.input_size}: the patch-embed kernels are built for square images of side {list(IMG_SIZES)} "
                          "(multiples of the 16-pixel patch; 224 is the ceiling: 240 pixels are 227 tokens, over the attention kernels' 208)")
+
+
+def check_relation_layers(args, model, teacher):
+    """--relation-layers against the built models: SystemExit with engine.resolve_relation_layers' message for a word or an index it refuses, or
+    for depths that cannot be paired.  Leaves the student's block indices in args.relation_layers."""
+    try:
+        pairs = engine.resolve_relation_layers(getattr(args, 'relation_layers', None), len(model.blocks), len(teacher.blocks))
+    except ValueError as e:
+        raise SystemExit(f"--relation-layers {' '.join(str(v) for v in args.relation_layers)}: {e}")
+    args.relation_layers = tuple(s for s, _ in pairs)
+    return pairs
 
 
 def load_weights_any_size(model, state_dict):
@@ -589,6 +616,7 @@ def main(args):
         for p_ in teacher.parameters():
             p_.requires_grad_(False)
         teacher.request_precision(args.teacher_precision)
+        check_relation_layers(args, model, teacher)
         if mixup_fn is not None:                    # Mixup's fused im2row emits the patch rows in every 16-bit type a model reads
             mixup_fn.set_precisions(model.precision, teacher.precision)
 
@@ -630,7 +658,7 @@ def main(args):
             print("shrink: heads kept per block", [int(h.sum()) for h, _ in policy],
                   "neurons kept per block", [int(n.sum()) for _, n in policy])
             if args.physical_shrink:     # train at the shrunk model's FLOPs (the reference trains the masked model at the dense cost)
-                rep = shrink.compact(model, trainable=True)
+                rep = shrink.compact(model, trainable=True, relation_layers=getattr(args, 'relation_layers', None))
                 print("shrink: compacted for training, (heads run, neurons run) per block", [(r[1], r[3]) for r in rep],
                       f"-> {shrink.compacted_gflops(model, num_classes=num_classes):.3f} GFLOP per image forward")
 

@@ -28,7 +28,7 @@ from devit_amd.ensemble_models import EnsMLP, MultiViT, load_sub_checkpoints
 
 
 def get_args_parser():
-    base = ds.get_args_parser()
+    base = ds.without_dekd_flags(ds.get_args_parser())
     p = argparse.ArgumentParser('DeViT Ensemble script (MI355X)', add_help=False, parents=[base], conflict_handler='resolve')
     # defaults where ensemble.py differs from distill_sub.py (ensemble.py:39-41,47,68,72,77)
     p.add_argument('--lr', type=float, default=1e-5, metavar='LR')

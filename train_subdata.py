@@ -22,7 +22,7 @@ from devit_amd import ddp, engine, losses, optim, utils
 
 
 def get_args_parser():
-    p = argparse.ArgumentParser('DeViT sub-dataset training (MI355X)', add_help=False, parents=[ds.get_args_parser()],
+    p = argparse.ArgumentParser('DeViT sub-dataset training (MI355X)', add_help=False, parents=[ds.without_dekd_flags(ds.get_args_parser())],
                                 conflict_handler='resolve')
     p.add_argument('--model', default='deit_base_distilled_patch16_224', type=str, metavar='MODEL')
     p.add_argument('--distillation-type', default='none', choices=['none', 'soft', 'hard'], type=str)
