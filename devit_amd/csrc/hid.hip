@@ -5,6 +5,7 @@
 //     S = coef (G_s - G_t) the gradient GEMM reads, and the backward of the row normalisation.  The Grams h h^T and dh^ = S h^ run on the
 //     batched devit_gemm_bf16 (exact mode: devit_gemm_f32), as the q/k/v relation loss does.
 #include "devit_common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -82,28 +83,7 @@ __global__ __launch_bounds__(256) void hid_stats_kernel(const float* gs, const f
   s = wave_sum(s);
   if (lane == 0) row_sq[row] = s;
 }
-// loss = scale * sum(row_sq): one block, fixed summation order (run-to-run deterministic), as losses.hip's rel_reduce_kernel
-__global__ __launch_bounds__(1024) void hid_reduce_kernel(const float* row_sq, int n, float scale, float* loss) {
-  __shared__ float red[16];
-  float p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int i0 = threadIdx.x; i0 < n; i0 += 8 * 1024) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int i = i0 + u * 1024;
-      p[u] += i < n ? row_sq[i] : 0.f;
-    }
-  }
-  float s = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) t += red[w];
-    loss[0] = t * scale;
-  }
-}
+// loss = scale * sum(row_sq): reduce.h's one block, fixed summation order (run-to-run deterministic)
 
 // ---- (c) gradient: S = (coef * upstream) (G_s - G_t), bf16 (or fp32) [B][256][256], zero outside N x N; one wave per row
 struct HidGradArgs {
@@ -211,7 +191,7 @@ extern "C" int devit_hid_stats(const float* gram_s, const float* gram_t, int B, 
   hipLaunchKernelGGL(hid_stats_kernel, dim3((B * N + 3) / 4), dim3(256), 0, (hipStream_t)stream, gram_s, gram_t, B, N, row_sq);
   DEVIT_LAUNCH_CHECK();
   const float scale = (float)(1.0 / ((double)B * N * N * layers));
-  hipLaunchKernelGGL(hid_reduce_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const float*)row_sq, B * N, scale, loss);
+  hipLaunchKernelGGL(fixed_order_reduce_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const float*)row_sq, (long long)B * N, scale, loss);
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
 }

@@ -4,6 +4,7 @@
 //   relation   : utils/losses.py:307-328 (feature_relation_loss), closed form in SURVEY.md App. A
 #include "det.h"
 #include "devit_common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -99,30 +100,7 @@ __global__ __launch_bounds__(256) void rel_stats_kernel(const RelStatArgs a) {
     a.row_kl[row] = kl;
   }
 }
-// loss = sum(row_kl) / B   (KLDivLoss batchmean, utils/losses.py:309)
-// One block of 1024 threads, 8 independent partial sums per thread (50688 values: six 16-byte-strided trips instead
-// of 198 dependent ones); fixed summation order, so the result is run-to-run deterministic.
-__global__ __launch_bounds__(1024) void rel_reduce_kernel(const float* row_kl, int n, float inv_b, float* loss) {
-  __shared__ float red[16];
-  float p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int i0 = threadIdx.x; i0 < n; i0 += 8 * 1024) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int i = i0 + u * 1024;
-      p[u] += i < n ? row_kl[i] : 0.f;
-    }
-  }
-  float s = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) t += red[w];
-    loss[0] = t * inv_b;
-  }
-}
+// loss = sum(row_kl) / B   (KLDivLoss batchmean, utils/losses.py:309): reduce.h's one block, fixed summation order
 // stage 2 (backward): S = G + G^T with G = (softmax(R_s) - softmax(R_t)) * upstream / (B sqrt(hd_s)); the Gram
 // is symmetric, so S_ij = e^{rs_ij}(e^{-ls_i} + e^{-ls_j}) - e^{rt_ij}(e^{-lt_i} + e^{-lt_j}).  bf16 [B][ldr][ldr],
 // zero outside N x N; dF_student = S F_student runs on the MFMA GEMM.
@@ -259,7 +237,7 @@ extern "C" int devit_relation_stats(const float* gram_t, const float* gram_s, in
                 1.0f / sqrtf((float)head_dim_s)};
   hipLaunchKernelGGL(rel_stats_kernel, dim3((B * N + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
   DEVIT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rel_reduce_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const float*)row_kl, B * N,
+  hipLaunchKernelGGL(fixed_order_reduce_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const float*)row_kl, (long long)B * N,
                      1.0f / (float)B, loss);
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;

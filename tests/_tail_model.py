@@ -593,7 +593,7 @@ def rel_stats_bounds(gram_t, gram_s, hd_t, hd_s):
     lse:     as _lse_err with n_lane = 4 and the scaling roundings above
     a = t - lse (:189): e_a = sr u |t| + e_lse + u |a|
     row_kl = sum_j expf(a_t) (a_t - a_s) (:190): per term pt ((e_at + 2 u + 1 u) |diff| + e_at + e_as + u |diff|), 4 adds per lane + 6 shuffle adds
-    loss (rel_reduce_kernel :202-221): ceil(n / 8192) adds per slot, 3 tree adds, 6 shuffle adds, 16 waves, 1 / B and the product 3"""
+    loss (fixed_order_reduce_kernel, reduce.h): ceil(n / 8192) adds per slot, 3 tree adds, 6 shuffle adds, 16 waves, 1 / B and the product 3"""
     B, N, _ = gram_t.shape
     t, srt, _ = _rel_scaled(gram_t, hd_t)
     s, srs, _ = _rel_scaled(gram_s, hd_s)
