@@ -115,6 +115,41 @@ def save_on_master(*args, **kwargs):
         torch.save(*args, **kwargs)
 
 
+def _device_generator(device):
+    """the torch.device whose default generator a training step on `device` draws from, None without one"""
+    device = torch.device('cuda' if device is None else device)
+    return device if device.type == 'cuda' and torch.cuda.is_available() else None
+
+
+def rng_state(device=None):
+    """The global random streams a training step draws from, for a checkpoint: torch's CPU generator (the dropout seed of every forward),
+    the default generator of `device` (stochastic depth; None: the current device, no entry without one), numpy's (Mixup / CutMix) and
+    Python's."""
+    import random
+    import numpy as np
+    state = {'torch': torch.get_rng_state(), 'numpy': np.random.get_state(), 'python': random.getstate()}
+    dev = _device_generator(device)
+    if dev is not None:
+        state['device'] = torch.cuda.get_rng_state(dev)
+    return state
+
+
+def load_rng_state(state, device=None):
+    """Put rng_state()'s streams back; the device's only where the state holds one and `device` has a generator.  False, with every stream
+    left as it is, for None: a checkpoint written before the streams were kept."""
+    import random
+    import numpy as np
+    if state is None:
+        return False
+    torch.set_rng_state(state['torch'])
+    np.random.set_state(state['numpy'])
+    random.setstate(state['python'])
+    dev = _device_generator(device)
+    if dev is not None and state.get('device') is not None:
+        torch.cuda.set_rng_state(state['device'], dev)
+    return True
+
+
 def init_distributed_mode(args):
     """env:// rendezvous from RANK / WORLD_SIZE / LOCAL_RANK (utils/dist_utils.py:215-237)."""
     if 'RANK' in os.environ and 'WORLD_SIZE' in os.environ:

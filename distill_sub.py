@@ -14,7 +14,8 @@ reference's dataset package must be importable as `data.get_dataset` (its `build
 samplers and loaders are then built as the reference builds them (`build_loaders`); `--device-data` reads the division's image folders (or the
 CIFAR-100 pickles) itself, keeps them on the device as uint8 and runs the reference's crop / flip / normalize / erase stack in one HIP stage;
 (2) bf16 needs no loss scaling: `scaler` in checkpoints is an empty dict; (3) Mixup/CutMix run as device-side
-tensor ops (SURVEY §8f-4 "next").
+tensor ops (SURVEY §8f-4 "next"); (4) `checkpoint_temp.pth` is written after the epoch's evaluation and also holds the global
+random streams (`rng`) and the best accuracy so far (`max_accuracy`), which `--resume` restores.
 """
 import argparse
 import datetime
@@ -576,6 +577,23 @@ def check_supported(args):
         raise SystemExit("--distillation-token (resize_dim models, models/de_vit.py:198-201) is outside the DEKD path")
 
 
+def check_no_resume(args, script):
+    """train_subdata.py and ensemble.py inherit --resume from the shared parser and restore nothing from it: refuse it instead of training or
+    evaluating freshly initialised weights without a word."""
+    if getattr(args, 'resume', ''):
+        raise SystemExit(f"--resume {args.resume}: implemented by distill_sub.py only; {script} restores no checkpoint "
+                         "(its models load from --model-path / --teacher-path)")
+
+
+def load_run_state(ck, device):
+    """What --resume restores beside the model, the optimizer and the schedule: the random streams the step draws from (utils.rng_state)
+    and the best accuracy so far, which is returned.  A checkpoint from before they were kept resumes as it always did."""
+    rng = ck.get('rng') if utils.is_main_process() else None      # the file is rank 0's: the other ranks restart from --seed + rank, as before
+    if not utils.load_rng_state(rng, device):
+        print("--resume: the checkpoint holds no random streams: Mixup, dropout and stochastic depth restart from --seed")
+    return float(ck.get('max_accuracy', 0.0))
+
+
 def main(args):
     utils.init_distributed_mode(args)
     check_supported(args)
@@ -636,6 +654,7 @@ def main(args):
     criterion = losses.DistillLoss(base, args.distillation_type, args.distillation_alpha, args.distillation_tau)
     n_parameters = sum(p_.numel() for p_ in model.parameters() if p_.requires_grad)
 
+    max_accuracy = 0.0
     if args.resume:
         ck = torch.load(args.resume, map_location='cpu', weights_only=False)   # holds the argparse Namespace, like the reference's
         model.load_state_dict(ck['model'])
@@ -645,6 +664,7 @@ def main(args):
             lr_scheduler.load_state_dict(ck['lr_scheduler'])
             args.start_epoch = ck['epoch'] + 1
             load_loader_state(train_loader, ck.get('data'))
+            max_accuracy = load_run_state(ck, device)       # after the models are built: their initialisation draws from torch's generator
     if args.eval:
         print(engine.evaluate(val_loader, model, device))
         return
@@ -664,7 +684,7 @@ def main(args):
 
     # distill_sub.py:403-404: everything of this division goes under sub-dataset{start_division}/ -- where ensemble.py
     # (:228) looks for `{model-path}/sub-dataset{i}/checkpoint.pth`
-    output_dir, max_accuracy, start = Path(args.output_dir) / f'sub-dataset{args.start_division}', 0.0, time.time()
+    output_dir, start = Path(args.output_dir) / f'sub-dataset{args.start_division}', time.time()
     output_dir.mkdir(parents=True, exist_ok=True)
     for epoch in range(args.start_epoch, args.epochs):
         if args.distributed:
@@ -673,11 +693,6 @@ def main(args):
                                               data_loader=train_loader, optimizer=optimizer, device=device, epoch=epoch,
                                               loss_scaler=loss_scaler, log=None, max_norm=args.clip_grad, mixup_fn=mixup_fn)
         lr_scheduler.step(epoch)
-        utils.save_on_master({'model': model.state_dict(), 'optimizer': optimizer.state_dict(),
-                              'lr_scheduler': lr_scheduler.state_dict(), 'epoch': epoch,
-                              'model_ema': optimizer.ema_state_dict(model), 'scaler': loss_scaler.state_dict(),
-                              'args': args, **({'data': loader_state(train_loader)} if loader_state(train_loader) else {})},   # (--device-data only)
-                             output_dir / 'checkpoint_temp.pth')
         test_stats = engine.evaluate(val_loader, model, device)
         print(f"Epoch: {epoch}/{args.epochs}  [Train] Loss: {train_stats.get('loss', float('nan')):.4f}  "
               f"[Eval] Top-1: {test_stats['acc1']:.4f} Top-5: {test_stats['acc5']:.4f} Loss: {test_stats['loss']:.4f}")
@@ -690,6 +705,14 @@ def main(args):
                 if args.shrink_checkpoint:       # the gates are not in state_dict(): side-car file
                     from devit_amd import shrink
                     shrink.save_gates(model, output_dir / 'gates.pt')
+        # the epoch's checkpoint, after its evaluation (the reference writes it before): max_accuracy then counts this epoch, so a run
+        # resumed into the same directory replaces the best model only with a better one; rng: the global streams the next step draws from
+        utils.save_on_master({'model': model.state_dict(), 'optimizer': optimizer.state_dict(),
+                              'lr_scheduler': lr_scheduler.state_dict(), 'epoch': epoch,
+                              'model_ema': optimizer.ema_state_dict(model), 'scaler': loss_scaler.state_dict(),
+                              'args': args, 'rng': utils.rng_state(device), 'max_accuracy': max_accuracy,
+                              **({'data': loader_state(train_loader)} if loader_state(train_loader) else {})},   # (--device-data only)
+                             output_dir / 'checkpoint_temp.pth')
         if utils.is_main_process():
             with (output_dir / "log.txt").open("a") as f:
                 f.write(json.dumps({**{f'train_{k}': v for k, v in train_stats.items()},

@@ -114,6 +114,7 @@ def param_groups(module, weight_decay):
 
 def main(args):
     utils.init_distributed_mode(args)
+    ds.check_no_resume(args, 'ensemble.py')
     ds.check_supported(args)
     device = torch.device(args.device)
     torch.manual_seed(args.seed + utils.get_rank())

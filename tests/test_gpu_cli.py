@@ -22,7 +22,7 @@ def test_distill_sub_cli(tmp_path):
     out = os.path.join(args.output_dir, "sub-dataset0")          # distill_sub.py:403-404
     assert os.path.exists(os.path.join(out, "checkpoint_temp.pth")) and os.path.exists(os.path.join(out, "log.txt"))
     ck = torch.load(os.path.join(out, "checkpoint_temp.pth"), map_location="cpu", weights_only=False)
-    assert set(ck) == {"model", "optimizer", "lr_scheduler", "epoch", "model_ema", "scaler", "args"}
+    assert set(ck) == {"model", "optimizer", "lr_scheduler", "epoch", "model_ema", "scaler", "args", "rng", "max_accuracy"}
     assert len(ck["model"]) == 155 and len(ck["model_ema"]) == 155
     import json
     line = json.loads(open(os.path.join(out, "log.txt")).read().splitlines()[-1])

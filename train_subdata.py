@@ -34,6 +34,7 @@ def get_args_parser():
 
 def main(args):
     utils.init_distributed_mode(args)
+    ds.check_no_resume(args, 'train_subdata.py')
     ds.check_supported(args)
     device = torch.device(args.device)
     seed = args.seed + utils.get_rank()
