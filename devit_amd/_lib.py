@@ -226,6 +226,11 @@ SIGNATURES = {
     "devit_adam_l2_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _F, _F, _P]),
     "devit_lamb_workspace": (_Z, [_I, _I]),
     "devit_lamb_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P, _Z, _P]),
+    # the same four with a learning rate per granule: the sibling's arguments, lr_group4 and lr_scales (256 floats) in front of the stream
+    "devit_adamw_step_lrs": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
+    "devit_sgd_step_lrs": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _Z, _F, _I, _F, _F, _F, _F, _P, _P, _P]),
+    "devit_adam_l2_step_lrs": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
+    "devit_lamb_step_lrs": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P, _Z, _P, _P, _P]),
     "devit_cls_distill_loss": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
     "devit_token_mse": (_I, [_P, _P, _Z, _P, _P, _I, _P]),
     "devit_token_kldiv": (_I, [_P, _P, _Z, _I, _P, _P, _I, _P]),

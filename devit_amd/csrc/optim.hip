@@ -4,7 +4,7 @@
 // (OptArgs), the global-norm clip folded into the gradient load (tail_clip), the per-granule weight decay exemption, the EMA and the bf16
 // re-cast of the new weights (model_tail), and on the host one validation + fill (fill_args) and one launch (launch_tail).  A tail adds its
 // update rule between the two.  All of them are HBM-bound streams: one thread owns a 16-byte granule of every buffer, loads and stores are 16
-// bytes wide.
+// bytes wide.  Every tail has a sibling with a learning rate per granule (the *_lrs kernels, LrScale): lr = dyn[0] * lr_scales[lr_group4[granule]].
 #include "devit_common.h"
 
 namespace {
@@ -91,6 +91,77 @@ __global__ __launch_bounds__(256) void adam_l2_kernel(const OptArgs a) {
   const float lr = a.dyn[0], bc1 = a.dyn[1], bc2 = a.dyn[2];
   const size_t n4 = a.n / 4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    f32x4 p = *(const f32x4*)(a.p + i * 4);
+    const f32x4 g = *(const f32x4*)(a.g + i * 4) * clip;
+    f32x4 m = *(const f32x4*)(a.m + i * 4), v = *(const f32x4*)(a.v + i * 4);
+    const float wd = (a.no_decay4 && a.no_decay4[i]) ? 0.0f : a.wd;
+    const f32x4 d = g + wd * p;
+    m = a.beta1 * m + (1.0f - a.beta1) * d;
+    v = a.beta2 * v + (1.0f - a.beta2) * d * d;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) p[e] -= (lr / bc1) * m[e] / (sqrtf(v[e]) / sqrtf(bc2) + a.eps);
+    *(f32x4*)(a.p + i * 4) = p;
+    *(f32x4*)(a.m + i * 4) = m;
+    *(f32x4*)(a.v + i * 4) = v;
+    model_tail(a.ema, a.p_bf16, i, p, a.ema_decay);
+  }
+}
+
+// ---- the three tails above with a learning rate per granule (layer-wise lr decay): lr = dyn[0] * scales[group4[i]], one fp32 multiply, used
+// wherever the sibling uses lr.  scales has 256 entries, so the byte needs no check: no address depends on what the array holds.  The byte is
+// a 64-byte load per wave like no_decay4's; the table is a gather of one dword per lane through the vector cache, where its 1 KB (eight
+// 128-byte lines, re-read by every wave) stays; a wave's 64 granules lie in one tensor or two, so a gather touches one or two lines.
+struct LrScale {
+  const unsigned char* group4;      // one byte per granule: the index of its scale
+  const float* scales;              // [256]
+};
+
+__global__ __launch_bounds__(256) void adamw_lrs_kernel(const OptArgs a, const LrScale s) {
+  const float clip = tail_clip(a.gnorm_sq, a.max_norm, a.grad_scale);
+  const float lr0 = a.dyn[0], bc1 = a.dyn[1], bc2 = a.dyn[2];
+  const size_t n4 = a.n / 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const float lr = lr0 * s.scales[s.group4[i]];
+    f32x4 p = *(const f32x4*)(a.p + i * 4);
+    const f32x4 g = *(const f32x4*)(a.g + i * 4) * clip;
+    f32x4 m = *(const f32x4*)(a.m + i * 4), v = *(const f32x4*)(a.v + i * 4);
+    if (!(a.no_decay4 && a.no_decay4[i])) p *= (1.0f - lr * a.wd);
+    m = a.beta1 * m + (1.0f - a.beta1) * g;
+    v = a.beta2 * v + (1.0f - a.beta2) * g * g;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) p[e] -= (lr / bc1) * m[e] / (sqrtf(v[e]) / sqrtf(bc2) + a.eps);
+    *(f32x4*)(a.p + i * 4) = p;
+    *(f32x4*)(a.m + i * 4) = m;
+    *(f32x4*)(a.v + i * 4) = v;
+    model_tail(a.ema, a.p_bf16, i, p, a.ema_decay);
+  }
+}
+
+__global__ __launch_bounds__(256) void sgd_lrs_kernel(const OptArgs a, const LrScale s) {
+  const float clip = tail_clip(a.gnorm_sq, a.max_norm, a.grad_scale);
+  const float lr0 = a.dyn[0], mu = a.beta1;
+  const size_t n4 = a.n / 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const float lr = lr0 * s.scales[s.group4[i]];
+    f32x4 p = *(const f32x4*)(a.p + i * 4);
+    const f32x4 g = *(const f32x4*)(a.g + i * 4) * clip;
+    f32x4 buf = *(const f32x4*)(a.m + i * 4);
+    const float wd = (a.no_decay4 && a.no_decay4[i]) ? 0.0f : a.wd;
+    const f32x4 d = g + wd * p;
+    buf = mu * buf + d;
+    p -= lr * (a.nesterov ? d + mu * buf : buf);
+    *(f32x4*)(a.p + i * 4) = p;
+    *(f32x4*)(a.m + i * 4) = buf;
+    model_tail(a.ema, a.p_bf16, i, p, a.ema_decay);
+  }
+}
+
+__global__ __launch_bounds__(256) void adam_l2_lrs_kernel(const OptArgs a, const LrScale s) {
+  const float clip = tail_clip(a.gnorm_sq, a.max_norm, a.grad_scale);
+  const float lr0 = a.dyn[0], bc1 = a.dyn[1], bc2 = a.dyn[2];
+  const size_t n4 = a.n / 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const float lr = lr0 * s.scales[s.group4[i]];
     f32x4 p = *(const f32x4*)(a.p + i * 4);
     const f32x4 g = *(const f32x4*)(a.g + i * 4) * clip;
     f32x4 m = *(const f32x4*)(a.m + i * 4), v = *(const f32x4*)(a.v + i * 4);
@@ -229,6 +300,24 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(const LambArgs a) {
   }
 }
 
+// lamb_apply_kernel with the learning rate per granule: p' = p - (lr scale) trust u.  The moments and the trust ratio do not see the scale.
+__global__ __launch_bounds__(256) void lamb_apply_lrs_kernel(const LambArgs a, const LrScale s) {
+  const devit_opt_chunk c = a.chunks[blockIdx.x];
+  if (!chunk_ok(c, a.o.n / 4, a.nsegments)) return;
+  const float lr0 = a.o.dyn[0], bc1 = a.o.dyn[1], sqrt_bc2 = sqrtf(a.o.dyn[2]);
+  const float wd = (c.flags & CHUNK_NO_DECAY) ? 0.0f : a.o.wd;
+  const float trust = a.trust[c.segment];
+  for (unsigned t = threadIdx.x; t < c.count4; t += 256) {
+    const size_t i = (size_t)c.first4 + t;
+    const float step = (lr0 * s.scales[s.group4[i]]) * trust;
+    f32x4 p = *(const f32x4*)(a.o.p + i * 4);
+    const f32x4 m = *(const f32x4*)(a.o.m + i * 4), v = *(const f32x4*)(a.o.v + i * 4);
+    p -= step * lamb_update(p, m, v, bc1, sqrt_bc2, a.o.eps, wd);
+    *(f32x4*)(a.o.p + i * 4) = p;
+    model_tail(a.o.ema, a.o.p_bf16, i, p, a.o.ema_decay);
+  }
+}
+
 // ---- sum of squares of a flat f32 buffer -> out[0] (two-stage, deterministic): the norm tail_clip reads
 __global__ __launch_bounds__(256) void sumsq_stage1(const float* g, size_t n, float* partial) {
   __shared__ float red[4];
@@ -273,6 +362,16 @@ int fill_args(OptArgs& a, const char* who, bool two_moments, float* p, const flo
 // a grid-stride tail: one thread per granule up to 4096 workgroups
 int launch_tail(void (*kernel)(const OptArgs), const OptArgs& a, void* stream) {
   hipLaunchKernelGGL(kernel, dim3(grid_for(a.n / 4, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  DEVIT_LAUNCH_CHECK();
+  return DEVIT_OK;
+}
+
+// the same launch for a tail with a learning rate per granule: both arrays are required (a caller without scales has the sibling entry point)
+int launch_tail(void (*kernel)(const OptArgs, const LrScale), const OptArgs& a, const char* who, const unsigned char* lr_group4,
+                const float* lr_scales, void* stream) {
+  DEVIT_CHECK(lr_group4 && lr_scales, DEVIT_ERR_ARG, "%s: lr_group4 (n / 4 bytes) and lr_scales (256 floats) are required", who);
+  const LrScale s = {lr_group4, lr_scales};
+  hipLaunchKernelGGL(kernel, dim3(grid_for(a.n / 4, 4096)), dim3(256), 0, (hipStream_t)stream, a, s);
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
 }
@@ -329,20 +428,23 @@ extern "C" size_t devit_lamb_workspace(int nchunks, int nsegments) {
   return ((size_t)nchunks * 2 + (size_t)nsegments) * sizeof(float);
 }
 
-extern "C" int devit_lamb_step(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16, const float* gnorm_sq,
-                               const float* dyn, size_t n, const devit_opt_chunk* chunks, int nchunks, int nsegments,
-                               int trust_clip, float beta1, float beta2, float eps, float weight_decay, float max_norm,
-                               float ema_decay, float grad_scale, void* workspace, size_t workspace_bytes, void* stream) {
+// devit_lamb_step and devit_lamb_step_lrs (`scaled`: the last launch is lamb_apply_lrs_kernel over lr_group4 / lr_scales, both required)
+static int lamb_step(const char* who, bool scaled, float* p, const float* g, float* m, float* v, float* ema, void* p_bf16,
+                     const float* gnorm_sq, const float* dyn, size_t n, const devit_opt_chunk* chunks, int nchunks, int nsegments,
+                     int trust_clip, float beta1, float beta2, float eps, float weight_decay, float max_norm, float ema_decay,
+                     float grad_scale, void* workspace, size_t workspace_bytes, const unsigned char* lr_group4, const float* lr_scales,
+                     void* stream) {
   DEVIT_CHECK(p && g && m && v && dyn && gnorm_sq && chunks && workspace, DEVIT_ERR_ARG,
-              "devit_lamb_step: bad argument (gnorm_sq is required: LAMB clips the gradient to norm 1 itself)");
+              "%s: bad argument (gnorm_sq is required: LAMB clips the gradient to norm 1 itself)", who);
+  DEVIT_CHECK(!scaled || (lr_group4 && lr_scales), DEVIT_ERR_ARG, "%s: lr_group4 (n / 4 bytes) and lr_scales (256 floats) are required", who);
   LambArgs a;
-  if (int rc = fill_args(a.o, "devit_lamb_step", true, p, g, m, v, ema, p_bf16, nullptr, gnorm_sq, dyn, n, beta1, beta2, eps, weight_decay,
+  if (int rc = fill_args(a.o, who, true, p, g, m, v, ema, p_bf16, nullptr, gnorm_sq, dyn, n, beta1, beta2, eps, weight_decay,
                          max_norm, ema_decay, grad_scale, 0))
     return rc;
   DEVIT_CHECK(nchunks > 0 && nsegments > 0 && n / 4 <= 0xffffffffu, DEVIT_ERR_SHAPE,
-              "devit_lamb_step: nchunks = %d, nsegments = %d must be positive, n / 4 must fit 32 bits", nchunks, nsegments);
+              "%s: nchunks = %d, nsegments = %d must be positive, n / 4 must fit 32 bits", who, nchunks, nsegments);
   DEVIT_CHECK(workspace_bytes >= devit_lamb_workspace(nchunks, nsegments) && ((size_t)workspace & 7) == 0, DEVIT_ERR_ARG,
-              "devit_lamb_step: workspace of %zu bytes, devit_lamb_workspace(%d, %d) = %zu (8-byte aligned)", workspace_bytes,
+              "%s: workspace of %zu bytes, devit_lamb_workspace(%d, %d) = %zu (8-byte aligned)", who, workspace_bytes,
               nchunks, nsegments, devit_lamb_workspace(nchunks, nsegments));
   a.chunks = chunks; a.nchunks = nchunks; a.nsegments = nsegments; a.trust_clip = trust_clip != 0;
   a.partials = (float*)workspace;
@@ -351,7 +453,63 @@ extern "C" int devit_lamb_step(float* p, const float* g, float* m, float* v, flo
   DEVIT_LAUNCH_CHECK();
   hipLaunchKernelGGL(lamb_trust_kernel, dim3(nsegments), dim3(64), 0, (hipStream_t)stream, a);
   DEVIT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(lamb_apply_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, a);
+  if (scaled) {
+    const LrScale s = {lr_group4, lr_scales};
+    hipLaunchKernelGGL(lamb_apply_lrs_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, a, s);
+  } else {
+    hipLaunchKernelGGL(lamb_apply_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, a);
+  }
   DEVIT_LAUNCH_CHECK();
   return DEVIT_OK;
+}
+
+extern "C" int devit_lamb_step(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16, const float* gnorm_sq,
+                               const float* dyn, size_t n, const devit_opt_chunk* chunks, int nchunks, int nsegments,
+                               int trust_clip, float beta1, float beta2, float eps, float weight_decay, float max_norm,
+                               float ema_decay, float grad_scale, void* workspace, size_t workspace_bytes, void* stream) {
+  return lamb_step("devit_lamb_step", false, p, g, m, v, ema, p_bf16, gnorm_sq, dyn, n, chunks, nchunks, nsegments, trust_clip, beta1, beta2,
+                   eps, weight_decay, max_norm, ema_decay, grad_scale, workspace, workspace_bytes, nullptr, nullptr, stream);
+}
+
+// ---- the four tails with a learning rate per granule: the sibling's arguments, then lr_group4 and lr_scales in front of the stream
+extern "C" int devit_adamw_step_lrs(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16,
+                                    const unsigned char* no_decay4, const float* gnorm_sq, const float* dyn, size_t n,
+                                    float beta1, float beta2, float eps, float weight_decay, float max_norm, float ema_decay,
+                                    float grad_scale, const unsigned char* lr_group4, const float* lr_scales, void* stream) {
+  OptArgs a;
+  if (int rc = fill_args(a, "devit_adamw_step_lrs", true, p, g, m, v, ema, p_bf16, no_decay4, gnorm_sq, dyn, n, beta1, beta2, eps,
+                         weight_decay, max_norm, ema_decay, grad_scale, 0))
+    return rc;
+  return launch_tail(adamw_lrs_kernel, a, "devit_adamw_step_lrs", lr_group4, lr_scales, stream);
+}
+
+extern "C" int devit_sgd_step_lrs(float* p, const float* g, float* buf, float* ema, void* p_bf16, const unsigned char* no_decay4,
+                                  const float* gnorm_sq, const float* dyn, size_t n, float momentum, int nesterov,
+                                  float weight_decay, float max_norm, float ema_decay, float grad_scale,
+                                  const unsigned char* lr_group4, const float* lr_scales, void* stream) {
+  OptArgs a;
+  if (int rc = fill_args(a, "devit_sgd_step_lrs", false, p, g, buf, nullptr, ema, p_bf16, no_decay4, gnorm_sq, dyn, n, momentum, 0.0f, 0.0f,
+                         weight_decay, max_norm, ema_decay, grad_scale, nesterov))
+    return rc;
+  return launch_tail(sgd_lrs_kernel, a, "devit_sgd_step_lrs", lr_group4, lr_scales, stream);
+}
+
+extern "C" int devit_adam_l2_step_lrs(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16,
+                                      const unsigned char* no_decay4, const float* gnorm_sq, const float* dyn, size_t n,
+                                      float beta1, float beta2, float eps, float weight_decay, float max_norm, float ema_decay,
+                                      float grad_scale, const unsigned char* lr_group4, const float* lr_scales, void* stream) {
+  OptArgs a;
+  if (int rc = fill_args(a, "devit_adam_l2_step_lrs", true, p, g, m, v, ema, p_bf16, no_decay4, gnorm_sq, dyn, n, beta1, beta2, eps,
+                         weight_decay, max_norm, ema_decay, grad_scale, 0))
+    return rc;
+  return launch_tail(adam_l2_lrs_kernel, a, "devit_adam_l2_step_lrs", lr_group4, lr_scales, stream);
+}
+
+extern "C" int devit_lamb_step_lrs(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16, const float* gnorm_sq,
+                                   const float* dyn, size_t n, const devit_opt_chunk* chunks, int nchunks, int nsegments,
+                                   int trust_clip, float beta1, float beta2, float eps, float weight_decay, float max_norm,
+                                   float ema_decay, float grad_scale, void* workspace, size_t workspace_bytes,
+                                   const unsigned char* lr_group4, const float* lr_scales, void* stream) {
+  return lamb_step("devit_lamb_step_lrs", true, p, g, m, v, ema, p_bf16, gnorm_sq, dyn, n, chunks, nchunks, nsegments, trust_clip, beta1,
+                   beta2, eps, weight_decay, max_norm, ema_decay, grad_scale, workspace, workspace_bytes, lr_group4, lr_scales, stream);
 }

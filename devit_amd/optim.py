@@ -6,6 +6,9 @@ Five tails on one frame (_FlatTail: the buffers, the scalar ring, the step's beg
 reference's `--opt` reaches through timm's create_optimizer: FlatAdamW (`adamw`), FlatSGD (`momentum`, `nesterov`), FlatAdam (`adam`: L2 decay
 coupled into the gradient) and FlatLamb (`lamb`, `lambc`: per-tensor trust ratios over a chunk table, three launches).  A class adds its
 hyper-parameters and its one C call; create_flat_optimizer maps the command line to one of them."""
+import math
+import re
+
 import torch
 
 from . import _lib as L
@@ -22,13 +25,80 @@ def no_decay_names(model):
             if p.requires_grad and (p.ndim <= 1 or n.endswith(".bias") or n in skip)}
 
 
+_STEM_NAMES = ("cls_token", "dist_token", "pos_embed")
+LR_TABLE = 256          # entries of the kernels' lr_scales table: one for every value of a byte (include/devit_hip.h)
+
+
+def layer_ids(names, depth):
+    """{name: layer id} of layer-wise lr decay over a ViT of `depth` blocks (`--layer-decay`): cls_token, dist_token,
+    pos_embed and patch_embed.* 0, blocks.<i>.* i + 1, everything else (norm, head, head_dist, resize_*) depth + 1.  A prefix in front of the
+    name (`backbones.<k>.` of MultiViT, `module.`) changes nothing: blocks.<i>. is matched at any dot, the bare names at the path's end."""
+    ids = {}
+    for name in names:
+        m = re.search(r"(^|\.)blocks\.(\d+)\.", name)
+        if m:
+            i = int(m.group(2))
+            if i >= depth:
+                raise ValueError(f"{name}: block {i} of a model of depth {depth}")
+            ids[name] = i + 1
+        elif name.split(".")[-1] in _STEM_NAMES or re.search(r"(^|\.)patch_embed\.", name):
+            ids[name] = 0
+        else:
+            ids[name] = depth + 1
+    return ids
+
+
+def layer_decay_scales(names, depth, decay):
+    """{name: scale}: scale(id) = decay^(depth + 1 - id), formed in float64 and rounded to fp32 -- the head and the final norm train at the
+    scheduled lr, the last block at decay times it, the stem at decay^(depth + 1) times it"""
+    return {n: float(torch.tensor(float(decay) ** (depth + 1 - i), dtype=torch.float64).to(torch.float32)) for n, i in layer_ids(names, depth).items()}
+
+
+def model_depth(model):
+    """len(model.blocks), or the common depth of a MultiViT's backbones"""
+    if hasattr(model, "blocks"):
+        return len(model.blocks)
+    depths = {len(b.blocks) for b in getattr(model, "backbones", []) if hasattr(b, "blocks")}
+    if len(depths) != 1:
+        raise ValueError(f"--layer-decay: {type(model).__name__} has no blocks, or backbones of different depths {sorted(depths)}")
+    return depths.pop()
+
+
+def lr_scale_table(names, sizes, offsets, numel, lr_scales):
+    """{name: scale} over a flat buffer -> (group bytes [numel / 4] uint8, table [256] fp32), both on the CPU: what the *_lrs entry points read.
+    The distinct scales, as fp32, are numbered in ascending order behind group 0, which is scale 1: padding between tensors and tensors the dict
+    does not name are in it, and so is every table entry no group uses.  Every granule of a tensor, its last partial one too, carries the
+    tensor's group.  ValueError: a name the buffer does not hold, a negative or non-finite scale, more than 256 distinct scales."""
+    unknown = sorted(set(lr_scales) - set(names))
+    if unknown:
+        raise ValueError(f"lr_scales: {unknown[0]} is not a tensor of the flat buffer")
+    f32 = {}
+    for n, s in lr_scales.items():
+        s = float(s)
+        if not math.isfinite(s) or s < 0:
+            raise ValueError(f"lr_scales: {n} has scale {s}; a scale is finite and >= 0")
+        f32[n] = float(torch.tensor(s, dtype=torch.float32))
+    values = [1.0] + sorted(set(f32.values()) - {1.0})
+    if len(values) > LR_TABLE:
+        raise ValueError(f"lr_scales: {len(values)} distinct scales (1.0 included); the table has {LR_TABLE} entries")
+    group_of = {v: g for g, v in enumerate(values)}
+    table = torch.ones(LR_TABLE, dtype=torch.float32)
+    table[:len(values)] = torch.tensor(values, dtype=torch.float32)
+    group4 = torch.zeros(numel // 4, dtype=torch.uint8)
+    for name, size, o in zip(names, sizes, offsets):
+        if name in f32:
+            group4[o // 4:(o + size + 3) // 4] = group_of[f32[name]]
+    return group4, table
+
+
 class _FlatTail:
     """What every optimizer over ddp.FlatParams shares: the buffers and the scalar ring (_setup), the surface the training loops use
     (param_groups[0]["lr"], zero_grad, max_norm, ema_state_dict), the step's frame and the state dict."""
     opt_name = "adamw"
     state_keys = ("m", "v")
+    layer_decay = None      # what --layer-decay gave when the scales came from it (create_flat_optimizer): kept in the state dict
 
-    def _setup(self, flat, lr, weight_decay, max_norm, ema_decay, no_decay, dyn_len):
+    def _setup(self, flat, lr, weight_decay, max_norm, ema_decay, no_decay, dyn_len, lr_scales=None):
         self.flat, self.weight_decay, self.max_norm, self.ema_decay = flat, weight_decay, max_norm, ema_decay
         dev = flat.flat.device
         self.no_decay4 = None
@@ -38,6 +108,11 @@ class _FlatTail:
                 if name in no_decay:
                     mask[o // 4:(o + p.numel() + 3) // 4] = 1
             self.no_decay4 = mask.to(dev)
+        # a learning rate per tensor, {name: scale}: one byte per granule into a table of 256 scales, and the step calls the *_lrs entry point
+        self.lr_group4 = self.lr_scales = None
+        if lr_scales is not None:
+            group4, table = lr_scale_table(flat.names, [p.numel() for p in flat.params], flat.offsets, flat.numel, lr_scales)
+            self.lr_group4, self.lr_scales = group4.to(dev), table.to(dev)
         for k in self.state_keys:
             setattr(self, k, torch.zeros_like(flat.flat))
         self.ema = flat.flat.clone() if ema_decay is not None else None
@@ -95,10 +170,14 @@ class _FlatTail:
     def state_dict(self):
         sd = {"opt": self.opt_name, "ema": self.ema, "step": self.step_count, "lr": self.param_groups[0]["lr"]}
         sd.update({k: getattr(self, k) for k in self.state_keys})
+        if self.layer_decay is not None:        # the flag, not the scales: they are rebuilt from it
+            sd["layer_decay"] = self.layer_decay
         return sd
 
     def load_state_dict(self, sd):
         self._check_kind(sd)
+        if sd.get("layer_decay") != self.layer_decay:
+            raise ValueError(f"optimizer state of --layer-decay {sd.get('layer_decay')} cannot be loaded into --layer-decay {self.layer_decay}")
         for k in self.state_keys:
             getattr(self, k).copy_(sd[k])
         if self.ema is not None and sd.get("ema") is not None:
@@ -112,18 +191,24 @@ class FlatAdamW(_FlatTail):
     tensor starts on a 4-element granule of the flat buffer, so the exemption is one byte per granule)."""
 
     def __init__(self, flat, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None, ema_decay=None,
-                 no_decay=None):
+                 no_decay=None, lr_scales=None):
         self.betas, self.eps = betas, eps
-        self._setup(flat, lr, weight_decay, max_norm, ema_decay, no_decay, 3)
+        self._setup(flat, lr, weight_decay, max_norm, ema_decay, no_decay, 3, lr_scales)
 
     def step(self):
         clip = self._begin_step(self._scalars)
         f = self.flat
         # f.grad_scale: 1 / world after the summing bucket all-reduce (ddp.BucketedGradReducer.finish) -- the mean of DDP
-        call("devit_adamw_step", ptr(f.flat), ptr(f.flat_grad), ptr(self.m), ptr(self.v), ptr(self.ema), ptr(f.flat16),
-             ptr(self.no_decay4), ptr(self.gnorm_sq) if clip else None, ptr(self._dyn), f.numel, self.betas[0], self.betas[1], self.eps,
-             self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0), float(f.grad_scale),
-             stream_ptr())
+        if self.lr_scales is None:
+            call("devit_adamw_step", ptr(f.flat), ptr(f.flat_grad), ptr(self.m), ptr(self.v), ptr(self.ema), ptr(f.flat16),
+                 ptr(self.no_decay4), ptr(self.gnorm_sq) if clip else None, ptr(self._dyn), f.numel, self.betas[0], self.betas[1], self.eps,
+                 self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0), float(f.grad_scale),
+                 stream_ptr())
+        else:
+            call("devit_adamw_step_lrs", ptr(f.flat), ptr(f.flat_grad), ptr(self.m), ptr(self.v), ptr(self.ema), ptr(f.flat16),
+                 ptr(self.no_decay4), ptr(self.gnorm_sq) if clip else None, ptr(self._dyn), f.numel, self.betas[0], self.betas[1], self.eps,
+                 self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0), float(f.grad_scale),
+                 ptr(self.lr_group4), ptr(self.lr_scales), stream_ptr())
         self._end_step()
 
     def state_dict(self):
@@ -137,17 +222,24 @@ class FlatSGD(_FlatTail):
     `--opt nesterov` (devit_sgd_step)."""
     state_keys = ("buf",)
 
-    def __init__(self, flat, lr=5e-4, momentum=0.9, nesterov=False, weight_decay=0.0, max_norm=None, ema_decay=None, no_decay=None):
+    def __init__(self, flat, lr=5e-4, momentum=0.9, nesterov=False, weight_decay=0.0, max_norm=None, ema_decay=None, no_decay=None,
+                 lr_scales=None):
         self.momentum, self.nesterov = momentum, bool(nesterov)
         self.opt_name = "nesterov" if nesterov else "momentum"
-        self._setup(flat, lr, weight_decay, max_norm, ema_decay, no_decay, 1)
+        self._setup(flat, lr, weight_decay, max_norm, ema_decay, no_decay, 1, lr_scales)
 
     def step(self):
         clip = self._begin_step(lambda t: (self.param_groups[0]["lr"],))
         f = self.flat
-        call("devit_sgd_step", ptr(f.flat), ptr(f.flat_grad), ptr(self.buf), ptr(self.ema), ptr(f.flat16), ptr(self.no_decay4),
-             ptr(self.gnorm_sq) if clip else None, ptr(self._dyn), f.numel, self.momentum, int(self.nesterov),
-             self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0), float(f.grad_scale), stream_ptr())
+        if self.lr_scales is None:
+            call("devit_sgd_step", ptr(f.flat), ptr(f.flat_grad), ptr(self.buf), ptr(self.ema), ptr(f.flat16), ptr(self.no_decay4),
+                 ptr(self.gnorm_sq) if clip else None, ptr(self._dyn), f.numel, self.momentum, int(self.nesterov),
+                 self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0), float(f.grad_scale), stream_ptr())
+        else:
+            call("devit_sgd_step_lrs", ptr(f.flat), ptr(f.flat_grad), ptr(self.buf), ptr(self.ema), ptr(f.flat16), ptr(self.no_decay4),
+                 ptr(self.gnorm_sq) if clip else None, ptr(self._dyn), f.numel, self.momentum, int(self.nesterov),
+                 self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0), float(f.grad_scale),
+                 ptr(self.lr_group4), ptr(self.lr_scales), stream_ptr())
         self._end_step()
 
 
@@ -156,17 +248,24 @@ class FlatAdam(_FlatTail):
     devit_adam_l2_step)."""
     opt_name = "adam"
 
-    def __init__(self, flat, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None, ema_decay=None, no_decay=None):
+    def __init__(self, flat, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None, ema_decay=None, no_decay=None,
+                 lr_scales=None):
         self.betas, self.eps = betas, eps
-        self._setup(flat, lr, weight_decay, max_norm, ema_decay, no_decay, 3)
+        self._setup(flat, lr, weight_decay, max_norm, ema_decay, no_decay, 3, lr_scales)
 
     def step(self):
         clip = self._begin_step(self._scalars)
         f = self.flat
-        call("devit_adam_l2_step", ptr(f.flat), ptr(f.flat_grad), ptr(self.m), ptr(self.v), ptr(self.ema), ptr(f.flat16),
-             ptr(self.no_decay4), ptr(self.gnorm_sq) if clip else None, ptr(self._dyn), f.numel, self.betas[0], self.betas[1],
-             self.eps, self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0), float(f.grad_scale),
-             stream_ptr())
+        if self.lr_scales is None:
+            call("devit_adam_l2_step", ptr(f.flat), ptr(f.flat_grad), ptr(self.m), ptr(self.v), ptr(self.ema), ptr(f.flat16),
+                 ptr(self.no_decay4), ptr(self.gnorm_sq) if clip else None, ptr(self._dyn), f.numel, self.betas[0], self.betas[1],
+                 self.eps, self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0), float(f.grad_scale),
+                 stream_ptr())
+        else:
+            call("devit_adam_l2_step_lrs", ptr(f.flat), ptr(f.flat_grad), ptr(self.m), ptr(self.v), ptr(self.ema), ptr(f.flat16),
+                 ptr(self.no_decay4), ptr(self.gnorm_sq) if clip else None, ptr(self._dyn), f.numel, self.betas[0], self.betas[1],
+                 self.eps, self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0), float(f.grad_scale),
+                 ptr(self.lr_group4), ptr(self.lr_scales), stream_ptr())
         self._end_step()
 
 
@@ -225,10 +324,10 @@ class FlatLamb(_FlatTail):
     (and validated) here once.  Tensors of the no-decay group -- all of them when weight_decay is 0 -- take trust 1, as in timm."""
 
     def __init__(self, flat, lr=5e-4, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, max_norm=None, ema_decay=None, no_decay=None,
-                 trust_clip=False):
+                 trust_clip=False, lr_scales=None):
         self.betas, self.eps, self.trust_clip = betas, eps, bool(trust_clip)
         self.opt_name = "lambc" if trust_clip else "lamb"
-        self._setup(flat, lr, weight_decay, max_norm, ema_decay, no_decay, 3)
+        self._setup(flat, lr, weight_decay, max_norm, ema_decay, no_decay, 3, lr_scales)
         sizes = [p.numel() for p in flat.params]
         exempt = set(flat.names) if not weight_decay else set(no_decay or ())
         self.chunks_host = validate_chunk_table(lamb_chunk_table(flat.names, sizes, flat.offsets, exempt), sizes, flat.offsets, flat.numel)
@@ -244,27 +343,52 @@ class FlatLamb(_FlatTail):
     def step(self):
         self._begin_step(self._scalars, need_norm=True)
         f = self.flat
-        call("devit_lamb_step", ptr(f.flat), ptr(f.flat_grad), ptr(self.m), ptr(self.v), ptr(self.ema), ptr(f.flat16),
-             ptr(self.gnorm_sq), ptr(self._dyn), f.numel, ptr(self.chunks), self.nchunks, self.nsegments, int(self.trust_clip),
-             self.betas[0], self.betas[1], self.eps, self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0),
-             float(f.grad_scale), ptr(self._lamb_ws), self._lamb_ws.numel(), stream_ptr())
+        if self.lr_scales is None:
+            call("devit_lamb_step", ptr(f.flat), ptr(f.flat_grad), ptr(self.m), ptr(self.v), ptr(self.ema), ptr(f.flat16),
+                 ptr(self.gnorm_sq), ptr(self._dyn), f.numel, ptr(self.chunks), self.nchunks, self.nsegments, int(self.trust_clip),
+                 self.betas[0], self.betas[1], self.eps, self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0),
+                 float(f.grad_scale), ptr(self._lamb_ws), self._lamb_ws.numel(), stream_ptr())
+        else:
+            call("devit_lamb_step_lrs", ptr(f.flat), ptr(f.flat_grad), ptr(self.m), ptr(self.v), ptr(self.ema), ptr(f.flat16),
+                 ptr(self.gnorm_sq), ptr(self._dyn), f.numel, ptr(self.chunks), self.nchunks, self.nsegments, int(self.trust_clip),
+                 self.betas[0], self.betas[1], self.eps, self.weight_decay, float(self.max_norm or 0.0), float(self.ema_decay or 0.0),
+                 float(f.grad_scale), ptr(self._lamb_ws), self._lamb_ws.numel(), ptr(self.lr_group4), ptr(self.lr_scales), stream_ptr())
         self._end_step()
 
 
-def create_flat_optimizer(args, flat, model):
+def check_layer_decay(decay):
+    """`--layer-decay D`: None (absent) or a number in (0, 1]; SystemExit otherwise"""
+    if decay is not None and not (math.isfinite(decay) and 0.0 < decay <= 1.0):
+        raise SystemExit(f"--layer-decay {decay}: the decay per layer lies in (0, 1] (1 trains every layer at the scheduled lr)")
+
+
+def create_flat_optimizer(args, flat, model, layer_decay=True):
     """timm create_optimizer(args, model) for the fused tails: `--opt` (adamw, adam, momentum, nesterov, lamb, lambc), `--momentum`,
     `--opt-eps`, `--opt-betas`, `--weight-decay`, `--clip-grad`, `--model-ema` / `--model-ema-decay` -> the optimizer over `flat`, with
-    timm's two weight-decay groups of `model`."""
+    timm's two weight-decay groups of `model`.  `--layer-decay D` below 1 gives every tensor the learning rate of its depth (layer_decay_scales
+    over model_depth(model); one line per layer id is printed); layer_decay=False: this optimizer ignores the flag (the ensemble's fusion head)."""
     name = args.opt.lower()
+    if name not in OPT_NAMES:
+        raise ValueError(f"--opt {args.opt}: not one of {', '.join(OPT_NAMES)}")
     kw = dict(lr=args.lr, weight_decay=args.weight_decay, max_norm=args.clip_grad,
               ema_decay=args.model_ema_decay if getattr(args, "model_ema", False) else None, no_decay=no_decay_names(model))
-    if name in ("momentum", "nesterov"):
-        return FlatSGD(flat, momentum=args.momentum, nesterov=name == "nesterov", **kw)
+    decay = getattr(args, "layer_decay", None) if layer_decay else None
+    check_layer_decay(decay)
+    if decay is not None and decay != 1.0:      # 1.0 is the unscaled path: the old entry points, their bits
+        depth = model_depth(model)
+        kw["lr_scales"] = layer_decay_scales(flat.names, depth, decay)
+        ids = layer_ids(flat.names, depth)
+        for i in range(depth + 2):
+            print(f"--layer-decay {decay}: layer {i:2d}  lr x {float(decay) ** (depth + 1 - i):.6g}  {sum(1 for v in ids.values() if v == i)} tensors")
     adam = dict(eps=args.opt_eps, betas=tuple(args.opt_betas or (0.9, 0.999)), **kw)
-    if name == "adamw":
-        return FlatAdamW(flat, **adam)
-    if name == "adam":
-        return FlatAdam(flat, **adam)
-    if name in ("lamb", "lambc"):
-        return FlatLamb(flat, trust_clip=name == "lambc", **adam)
-    raise ValueError(f"--opt {args.opt}: not one of {', '.join(OPT_NAMES)}")
+    if name in ("momentum", "nesterov"):
+        opt = FlatSGD(flat, momentum=args.momentum, nesterov=name == "nesterov", **kw)
+    elif name == "adamw":
+        opt = FlatAdamW(flat, **adam)
+    elif name == "adam":
+        opt = FlatAdam(flat, **adam)
+    else:
+        opt = FlatLamb(flat, trust_clip=name == "lambc", **adam)
+    if "lr_scales" in kw:
+        opt.layer_decay = float(decay)
+    return opt

@@ -153,7 +153,7 @@ def main(args):
         flat, ens_flat = ddp.FlatParams(model).attach_bf16(model), ddp.FlatParams(ens_model)
         runner = EnsStepRunner(ddp.BucketedGradReducer(flat).attach(model), ddp.BucketedGradReducer(ens_flat))
         optimizer = optim.create_flat_optimizer(args, flat, model)
-        ens_optimizer = optim.create_flat_optimizer(args, ens_flat, ens_model)
+        ens_optimizer = optim.create_flat_optimizer(args, ens_flat, ens_model, layer_decay=False)     # --layer-decay: the backbones' alone
         if args.gates and args.physical_shrink:     # train at the shrunk models' FLOPs (the reference trains the masked models at the dense cost)
             from devit_amd import shrink
             rep = shrink.compact(model, trainable=True)

@@ -654,6 +654,32 @@ DEVIT_API int devit_lamb_step(float* p, const float* g, float* m, float* v, floa
                     float beta1, float beta2, float eps, float weight_decay, float max_norm, float ema_decay, float grad_scale,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* The four tails with a learning rate per granule (layer-wise lr decay: lr x decay^(distance from the head)).  Each takes its sibling's
+ * arguments and, in front of the stream, two more, both required:
+ *   lr_group4   one byte per 4-element granule of the flat buffer, n / 4 bytes, laid out like no_decay4: the index of the granule's scale
+ *   lr_scales   a device table of EXACTLY 256 floats.  Every value a byte can hold indexes inside it, so the kernels check nothing and no
+ *               address depends on the contents of lr_group4; entries that no granule uses should hold 1.
+ * The granule's learning rate is fp32(dyn[0]) * lr_scales[lr_group4[granule]], one fp32 multiply, and stands wherever the sibling uses lr:
+ * AdamW in p *= 1 - lr wd and in the update, SGD and Adam in the update, LAMB in p' = p - lr trust u (the moments and the trust ratio do not
+ * see the scale).  A table of ones gives the sibling's bits.  A scale of 0 freezes its granules' learning rate (moments and EMA still move). */
+DEVIT_API int devit_adamw_step_lrs(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16,
+                         const unsigned char* no_decay4, const float* gnorm_sq, const float* dyn, size_t n, float beta1,
+                         float beta2, float eps, float weight_decay, float max_norm, float ema_decay, float grad_scale,
+                         const unsigned char* lr_group4, const float* lr_scales, void* stream);
+DEVIT_API int devit_sgd_step_lrs(float* p, const float* g, float* buf, float* ema, void* p_bf16, const unsigned char* no_decay4,
+                       const float* gnorm_sq, const float* dyn, size_t n, float momentum, int nesterov, float weight_decay,
+                       float max_norm, float ema_decay, float grad_scale, const unsigned char* lr_group4,
+                       const float* lr_scales, void* stream);
+DEVIT_API int devit_adam_l2_step_lrs(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16,
+                           const unsigned char* no_decay4, const float* gnorm_sq, const float* dyn, size_t n, float beta1,
+                           float beta2, float eps, float weight_decay, float max_norm, float ema_decay, float grad_scale,
+                           const unsigned char* lr_group4, const float* lr_scales, void* stream);
+DEVIT_API int devit_lamb_step_lrs(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16, const float* gnorm_sq,
+                        const float* dyn, size_t n, const devit_opt_chunk* chunks, int nchunks, int nsegments, int trust_clip,
+                        float beta1, float beta2, float eps, float weight_decay, float max_norm, float ema_decay,
+                        float grad_scale, void* workspace, size_t workspace_bytes, const unsigned char* lr_group4,
+                        const float* lr_scales, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * DEKD logit loss + gradient in one launch.  Replaces DistillLoss.forward (utils/losses.py:156-177)
  * with a timm SoftTargetCrossEntropy base criterion (distill_sub.py:348) and its backward.
